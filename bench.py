@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- ensemble-member simulated years per second, SSP2-4.5 1745-2300.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run times the headline workload only: set-up, W warm-up steps, K timed steps, the result
+line.  --full adds everything else the line can hold (other_configs, workload_variants,
+safe_build, sustained, cpu_baseline below; at N > 1 the 131 072-member workload); the --no-* and
+--sustain switches trim a --full run.  --dump-outputs DIR writes what the last timed step
+computed, as .npy files (float64): ensemble_stats.npy -- the per-year {count, sum, sumsq, min,
+max} of CO2 and Tgav the step hands its caller, [2, 556, 5] -- and CO2_concentration.npy /
+global_tas.npy, the trajectories [556, 2048] of a fixed, seeded sample of this rank's members.
 
 --gpus N > 1 always drives N GPUs: under torch.distributed.run (WORLD_SIZE set) this process is
 one of N ranks; started as plain `python bench.py --gpus N` it launches those N ranks itself
@@ -497,9 +505,14 @@ def runtime_versions():
     return v
 
 
-def run_workload(args, ctx, n, steps, warmup, sustain=0):
+DUMP_SAMPLE = 2048   # members whose trajectories --dump-outputs writes (a fixed, seeded sample)
+DUMP_SEED = 20300
+
+
+def run_workload(args, ctx, n, steps, warmup, sustain=0, dump=False):
     """One weak-scaling workload: n members on every GPU, `steps` timed steps between barriers.
-    -> dict of this rank's view (elapsed and kernel time already the maximum over ranks)."""
+    -> dict of this rank's view (elapsed and kernel time already the maximum over ranks).
+    dump: also return what the last timed step computed (r["outputs"]: name -> float64 array)."""
     import numpy as np
     import torch
     from hector_amd.distributed import allreduce_stats
@@ -571,6 +584,14 @@ def run_workload(args, ctx, n, steps, warmup, sustain=0):
     if use_dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    outputs = None
+    if dump:   # the last timed step's results, fetched after the clock stopped
+        members = core.n_members
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(members, min(DUMP_SAMPLE, members),
+                                                                 replace=False))
+        outputs = {"ensemble_stats": stats.cpu().numpy().astype(np.float64)}
+        for v in STAT_VARS:
+            outputs[v] = np.ascontiguousarray(core.fetchvars(v, (start, end))[:, pick], dtype=np.float64)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     km = torch.tensor([float(np.mean(kern_ms)), first_ms], dtype=torch.float64, device=dev)
     if use_dist:
@@ -606,7 +627,8 @@ def run_workload(args, ctx, n, steps, warmup, sustain=0):
          "which_kernel": core.last_run_kernel(),
          "calibrated": core.lanes_calibrated(), "lanes_by": core.lane_order_source(), "first_run_lanes_by": first_by,
          "wave_time": wave_time(core),   # (this rank's first shard, the last timed launch)
-         "spin_ms": spin_ms, "collective": collective, "native_fallback": fallback}
+         "spin_ms": spin_ms, "collective": collective, "native_fallback": fallback,
+         "outputs": outputs}
     r["comm_world"], _, r["comm_backend"] = core.comm_info()
     core.shutdown()
     return r
@@ -650,7 +672,7 @@ def main():
     ap.add_argument("--biomes", type=int, default=1, choices=[1, 4])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sustain", type=int, default=300,
-                    help="N = 1: steps of the sustained leg behind the timed region (0 = none)")
+                    help="--full, N = 1: steps of the sustained leg behind the timed region (0 = none)")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="target wall time of the bounded CPU-baseline sample")
@@ -666,6 +688,11 @@ def main():
     ap.add_argument("--force-collective", action="store_true",
                     help="with one rank: still create the communicator and run the collective "
                          "(world size 1) -- the RCCL path on a one-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the other configurations, workload variants, safe build, "
+                         "sustained leg and CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -715,9 +742,15 @@ def main():
     # timed after it in the same job (N > 1: other_configs[0]; N = 1: among other_configs), and
     # both are at the top level of every line: value_per_gpu_workload, first_run_kernel_ms.
     n = args.members if args.members else 65536
-    r = run_workload(args, ctx, n, args.steps, args.warmup, sustain=(args.sustain if n_gpus == 1 and not args.members else 0))
+    r = run_workload(args, ctx, n, args.steps, args.warmup,
+                     sustain=(args.sustain if args.full and n_gpus == 1 and not args.members else 0),
+                     dump=bool(args.dump_outputs) and rank == 0)
+    if r["outputs"] is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in r["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     second = None
-    if n_gpus > 1 and not args.members and not args.no_other_configs:
+    if args.full and n_gpus > 1 and not args.members and not args.no_other_configs:
         # (timed like the headline -- the same steps and warmup -- so that the two
         # workloads of a multi-GPU line are of equal standing)
         second = run_workload(args, ctx, 131072, args.steps, args.warmup)
@@ -821,7 +854,7 @@ def main():
             out["first_run_over_steady"][k2] = second["first_run_kernel_ms"] / second["kernel_ms"]
             out["first_run_prewarmed"][k2] = second["first_run_prewarmed"]
             out["kernel_ms"][k2] = second["kernel_ms"]
-        if n_gpus == 1 and not args.no_other_configs:
+        if args.full and n_gpus == 1 and not args.no_other_configs:
             others = []
             for (m2, b2) in ((1024, 1), (32768, 1), (131072, 1), (65536, 4)):
                 if (m2, b2) == (n, args.biomes):
@@ -853,7 +886,7 @@ def main():
                     out["safe_build"] = {"error": str(e)[:200]}
             else:
                 out["safe_build"] = {"error": "hector_amd/lib/libhector_amd_safe.so not built (make -C hector_amd/csrc safe)"}
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             v, dt, ns, cores = cpu_baseline(args.cpu_seconds)
             out["cpu_baseline"] = {
                 "value": v, "unit": "member-years/s", "cores": cores, "kind": "port",

@@ -12,6 +12,7 @@ SCENARIO = os.path.join(ROOT, "hector_amd", "data", "ssp245.hxs")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "hector_comp_ssp245.txt")
 EMUL_LIB = os.path.join(ROOT, "tests", "emul", "libhector_amd_emul.so")
 HIP_LIB = os.path.join(ROOT, "hector_amd", "lib", "libhector_amd.so")
+REFERENCE_INPUT = os.path.join(ROOT, "tests", "golden", "reference_input.tar.xz")
 
 
 def pytest_configure(config):
@@ -47,6 +48,17 @@ def golden():
             p = line.split()
             g[p[0]] = np.array([float(x) for x in p[3:]])
     return g
+
+
+@pytest.fixture(scope="session")
+def reference_input(tmp_path_factory):
+    """The reference's own inst/input data, verbatim: hector_{ssp119,ssp245,ssp585,picontrol}.ini
+    and the csv tables they name, unpacked from tests/golden/reference_input.tar.xz -> its folder."""
+    import tarfile
+    d = tmp_path_factory.mktemp("reference")
+    with tarfile.open(REFERENCE_INPUT) as t:
+        t.extractall(d, **({"filter": "data"} if hasattr(tarfile, "data_filter") else {}))
+    return os.path.join(str(d), "reference_input")
 
 
 @pytest.fixture(scope="session")

@@ -70,11 +70,9 @@ def test_shard_ranges_partition_exactly():
             assert o0 + c0 == o1
 
 
-def test_scenario_pack_matches_reference_inputs_when_available(tmp_path):
+def test_scenario_pack_matches_reference_inputs_when_available(tmp_path, reference_input):
     """The committed pack is regenerated from the reference INI/CSV and must be identical."""
-    ini = "/root/reference/inst/input/hector_ssp245.ini"
-    if not os.path.exists(ini):
-        pytest.skip("reference not present on this box")
+    ini = os.path.join(reference_input, "hector_ssp245.ini")
     import subprocess, sys
     out = tmp_path / "x.hxs"
     subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "import_scenario.py"),
@@ -82,12 +80,10 @@ def test_scenario_pack_matches_reference_inputs_when_available(tmp_path):
     assert open(out).read() == open(SCENARIO).read()
 
 
-def test_ini_reader_equals_pack(emul_lib):
+def test_ini_reader_equals_pack(emul_lib, reference_input):
     """The C++ INI/CSV front end (hx_scenario.cpp) on the reference's own INI gives
     the same core as the committed dense pack."""
-    ini = "/root/reference/inst/input/hector_ssp245.ini"
-    if not os.path.exists(ini):
-        pytest.skip("reference not present on this box")
+    ini = os.path.join(reference_input, "hector_ssp245.ini")
     import hector_amd
     a = hector_amd.Core(SCENARIO, 1, lib_path=emul_lib, allow_emulation=True).run(1800)
     b = hector_amd.Core(ini, 1, lib_path=emul_lib, allow_emulation=True).run(1800)

@@ -13,7 +13,6 @@ REL_CO2 = 2e-8
 ABS_T = 2e-8
 SCENARIOS = ["picontrol", "ssp119", "ssp126", "ssp245", "ssp370", "ssp434", "ssp460",
              "ssp534-over", "ssp585"]
-REF_INPUT = "/root/reference/inst/input"
 
 
 def pack(name):
@@ -49,13 +48,12 @@ def test_shipped_scenarios_vs_oracle(emul_lib, oracle, name):
                              np.array([2.2, 1.3, 2.9]), allow_emulation=True)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INPUT), reason="needs the reference's input files")
 @pytest.mark.parametrize("name", ["ssp119", "ssp585", "picontrol"])
-def test_ini_reader_equals_pack(emul_lib, name):
+def test_ini_reader_equals_pack(emul_lib, reference_input, name):
     """The C++ INI + csv: reader (hx_scenario.cpp; ini_to_core_reader.cpp:100-180,
     csv_table_reader.cpp:115-198) gives the core the same inputs as the imported pack."""
     out = []
-    for path in (os.path.join(REF_INPUT, "hector_%s.ini" % name), pack(name)):
+    for path in (os.path.join(reference_input, "hector_%s.ini" % name), pack(name)):
         c = hector_amd.Core(path, 1, lib_path=emul_lib, allow_emulation=True)
         c.set_outputs(["CO2_concentration", "global_tas", "RF_tot", "CH4_concentration"])
         c.run(2300)
