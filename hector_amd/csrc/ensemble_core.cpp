@@ -55,6 +55,11 @@ struct ParamDef {
   const char *name; int row; bool per_biome; const char *units; bool spinup;
 };
 // capability strings: inst/include/component_data.hpp; units: src/unitval.cpp
+// `spinup`: the spinup sees the parameter.  It zeroes the emissions and holds co2fert, tempfert and
+// f_frozen at 1 (simpleNbox-runtime.cpp:952-1000; simpleNbox.cpp:733,802), so beta, q10_rh,
+// warmingfactor, rh_ch4_frac, pf_mu, pf_sigma, fpf_static and the temperature side do not reach it:
+// those rows may differ between members under one shared spinup (prepare()).
+// tests/test_one_factor.py varies each row alone against the uniform ensemble.
 const ParamDef kParams[] = {
     {"S", HXP_S, false, "degC", false},
     {"diff", HXP_DIFF, false, "cm2/s", false},
