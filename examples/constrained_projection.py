@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""A constrained projection: run a perturbed-parameter ensemble, score every member against an
+observed record, weight the members by their likelihood and report the weighted median and 5-95 %
+band -- without a trajectory leaving the GPU (Core.score, Core.quantiles).  The "observations"
+here are pseudo-observations: one held-out member plus seeded noise.
+Needs an MI355X:  python examples/constrained_projection.py [n_members]"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import hector_amd                                    # noqa: E402
+from hector_amd.capabilities import ECS, Q10_RH, BETA, CONCENTRATIONS_CO2, GLOBAL_TAS  # noqa: E402
+
+PROBS = (0.05, 0.5, 0.95)
+SIGMA_CO2, SIGMA_TAS = 2.0, 0.12          # ppmv, K: the noise of the pseudo-observations
+
+
+def main(n=20000, truth=0, **core_kwargs):
+    rng = np.random.default_rng(1)
+    core = hector_amd.newcore(None, n_members=n, **core_kwargs)   # packaged SSP2-4.5
+    hector_amd.setvar(core, None, ECS(), rng.uniform(1.5, 6.0, n), "degC")
+    hector_amd.setvar(core, None, Q10_RH(), rng.uniform(1.0, 3.0, n), "(unitless)")
+    hector_amd.setvar(core, None, BETA(), rng.uniform(0.1, 0.9, n), "(unitless)")
+    hector_amd.run(core, 2100)
+
+    # pseudo-observations: the held-out member's record 1850-2014 plus noise; its temperature as
+    # an anomaly relative to 1850-1900, the way observed records come
+    years = np.arange(1850, 2015)
+    co2 = core.fetchvars(CONCENTRATIONS_CO2(), (1850, 2014))[:, truth]
+    tas = core.fetchvars(GLOBAL_TAS(), (1850, 2014))[:, truth]
+    obs_co2 = co2 + rng.normal(0.0, SIGMA_CO2, years.size)
+    obs_tas = tas - tas[:51].mean() + rng.normal(0.0, SIGMA_TAS, years.size)
+
+    # chi-square of every member, on the device; n_members doubles come back per call
+    chi2 = core.score(CONCENTRATIONS_CO2(), years, obs_co2, sigma=SIGMA_CO2)
+    chi2 += core.score(GLOBAL_TAS(), years, obs_tas, sigma=SIGMA_TAS, baseline=(1850, 1900))
+    ok = core.status() == 0
+    ok[truth] = False                                  # held out
+    weights = np.where(ok, np.exp(-0.5 * (chi2 - chi2[ok].min())), 0.0)
+    n_eff = weights.sum() ** 2 / (weights ** 2).sum()
+
+    for var, unit in ((GLOBAL_TAS(), "K"), (CONCENTRATIONS_CO2(), "ppmv")):
+        prior = core.quantiles(var, PROBS, (2100, 2100))[0]
+        post = core.quantiles(var, PROBS, (2100, 2100), weights=weights)[0]
+        actual = core.fetchvars(var, (2100, 2100))[0, truth]
+        print("%-18s 2100  prior %.2f (%.2f-%.2f) %s   constrained %.2f (%.2f-%.2f) %s   held-out member %.2f"
+              % (var, prior[1], prior[0], prior[2], unit, post[1], post[0], post[2], unit, actual))
+    print("%d members, %d with a model error, effective sample size %.1f, %.1f ms on the GPU"
+          % (n, int((core.status() != 0).sum()), n_eff, core.last_run_ms()))
+    band = core.quantiles(GLOBAL_TAS(), PROBS, (1850, 2100), weights=weights)   # [251, 3]: the plot
+    hector_amd.shutdown(core)
+    return band, weights
+
+
+if __name__ == "__main__":
+    main(int(sys.argv[1]) if len(sys.argv) > 1 else 20000)

@@ -328,6 +328,51 @@ class Core:
         self._ck(self._lib.hx_stats_device(self._h, var.encode(), int(year0), int(year1),
                                            ctypes.c_void_p(d_ptr)))
 
+    def score(self, var, years, obs, sigma=None, baseline=None, return_used=False):
+        """chi2 of every member against an observed record, on the device (hx_member_score):
+        sum over i of (((x(years[i]) - base) - obs[i]) / sigma[i])**2 -> ndarray [n_members].
+        obs NaN: that year is skipped; sigma None: no division; baseline = (year0, year1): base is
+        the member's own mean of x over those years, None: nothing is subtracted.  The evaluation
+        order is fixed (include/hector_amd.h): numpy reproduces the result bit for bit."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        yr = np.ascontiguousarray(np.atleast_1d(np.asarray(years)).astype(np.int32))
+        ob = np.ascontiguousarray(np.atleast_1d(np.asarray(obs, dtype=np.float64)))
+        if ob.shape != yr.shape or yr.ndim != 1:
+            raise HectorAmdError("score: years and obs must be one-dimensional and of equal length")
+        sg = None
+        if sigma is not None:
+            sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), yr.shape))
+        b0, b1 = (1, 0) if baseline is None else (int(baseline[0]), int(baseline[1]))
+        out = np.empty(self.n_members)
+        used = ctypes.c_int()
+        self._ck(self._lib.hx_member_score(
+            self._h, var.encode(), yr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ob.ctypes.data_as(dp),
+            sg.ctypes.data_as(dp) if sg is not None else None, int(yr.size), b0, b1,
+            out.ctypes.data_as(dp), ctypes.byref(used)))
+        return (out, used.value) if return_used else out
+
+    def quantiles(self, var, probs, dates=None, weights=None, counts=False):
+        """Per-year weighted quantiles over every member, on the device (hx_ensemble_quantiles:
+        exact inverted-CDF quantiles, numpy's method="inverted_cdf") -> ndarray [n_years, n_probs];
+        counts=True: also the members that took part in every year [n_years]."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
+            (int(min(dates)), int(max(dates)))
+        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+            if w.shape != (self.n_members,):
+                raise HectorAmdError("quantiles: weights must have n_members entries")
+        ny = max(y1 - y0 + 1, 0)
+        out = np.empty((ny, pr.size))
+        npart = np.zeros(ny, dtype=np.int64)
+        self._ck(self._lib.hx_ensemble_quantiles(
+            self._h, var.encode(), y0, y1, w.ctypes.data_as(dp) if w is not None else None,
+            pr.ctypes.data_as(dp), int(pr.size), out.ctypes.data_as(dp),
+            npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return (out, npart) if counts else out
+
     def status(self):
         out = np.zeros(self.n_members, dtype=np.uint32)
         self._ck(self._lib.hx_status(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint))))

@@ -47,6 +47,23 @@ hipError_t hx_launch_derive(const double *params, double *derived, const double 
                             int ker_per_member, int ns, int nbiome, int npad, hipStream_t st);
 hipError_t hx_launch_doeclim_kernel(const double *diff_row, double *ker, int ns, int count,
                                     int stride, hipStream_t st);
+// the post-processing kernels (hx_dev_post.h): compiled into hx_post.hip's object for the GPU; the
+// host-emulation build takes the score kernel and its launcher in here
+#ifdef HX_HOST_EMULATION
+#include "hx_dev_post.h"
+#else
+hipError_t hx_launch_score(const double *var, int n, int npad, const int *iy, const double *obs,
+                           const double *sigma, int nobs, int b0, int b1, double *out, hipStream_t st);
+hipError_t hx_launch_q_minmax(const double *var, int n, int npad, int iy0, int ny,
+                              const unsigned long long *q, void *st, hipStream_t stream);
+hipError_t hx_launch_q_init(const void *st, int ny, const double *probs, int np, int skip, int *lo,
+                            unsigned long long *prefix, unsigned long long *rem, hipStream_t stream);
+hipError_t hx_launch_q_hist(const double *var, int n, int npad, int iy0, int ny,
+                            const unsigned long long *q, const int *lo, const unsigned long long *prefix,
+                            int np, int aggregate, unsigned long long *hist, hipStream_t stream);
+hipError_t hx_launch_q_pick(int ny, int *lo, unsigned long long *prefix, unsigned long long *rem, int np,
+                            unsigned long long *hist, hipStream_t stream);
+#endif
 
 namespace hx {
 namespace {
@@ -525,6 +542,9 @@ void EnsembleCore::free_device() {
   fr(d_wave_clk_); d_wave_clk_ = nullptr;
   fr(d_bscratch_); d_bscratch_ = nullptr;
   fr(d_spin_rec_); d_spin_rec_ = nullptr;
+  fr(d_score_); fr(d_q_); fr(d_qstate_); fr(d_qhist_);
+  d_score_ = nullptr; d_q_ = d_qstate_ = d_qhist_ = nullptr;
+  score_cap_ = qstate_cap_ = qhist_cap_ = 0; q_v_ = -1;
   d_hist_ = nullptr; d_hist_status_ = nullptr;
   for (int k = 0; k < HXM_N; ++k) { fr(d_mseries_[k]); d_mseries_[k] = nullptr; if (!member_series_[k].empty()) mseries_dirty_ = true; }
   fr(d_diag_); fr(d_slr_); d_diag_ = d_slr_ = nullptr; diag_cap_ = 0; slr_valid_to_ = -1;
@@ -2718,6 +2738,214 @@ int EnsembleCore::spinup_steps(int member) {
   check(hipMemcpy(&v, d_spin_steps_ + lane_of_member_[(size_t)member], sizeof(int),
                   hipMemcpyDeviceToHost), "steps");
   return v;
+}
+
+// ---- post-processing: member scores and weighted quantiles (hx_dev_post.h) -----------------------
+
+int EnsembleCore::member_score(const std::string &capability, const int *years, const double *obs,
+                               const double *sigma, int n, int base_year0, int base_year1,
+                               double *out_host) {
+  if (n < 1 || !years || !obs || !out_host)
+    throw std::runtime_error("hx_member_score: n < 1 or a null argument");
+  const int v = out_index(capability);
+  if (!d_out_[v])
+    throw std::runtime_error("variable " + capability + " was not enabled with set_outputs()");
+  const int last = last_date();
+  const bool has_base = base_year0 <= base_year1;
+  std::vector<int> iy((size_t)n);
+  int used = 0;
+  for (int i = 0; i < n; ++i) {
+    if (years[i] < scen_.start || years[i] > last)
+      throw std::runtime_error("hx_member_score: dates must lie between startDate and the current date");
+    iy[(size_t)i] = years[i] - scen_.start;
+    if (obs[i] == obs[i]) ++used;
+  }
+  if (has_base && (base_year0 < scen_.start || base_year1 > last))
+    throw std::runtime_error("hx_member_score: the reference period must lie between startDate and the current date");
+  if (!d_lane_of_member_) throw std::runtime_error("hx_member_score: run the core first");
+  sync();
+  const size_t nn = (size_t)n, doubles = 2 * nn + (size_t)npad_ + (size_t)n_;
+  const size_t bytes = sizeof(double) * doubles + sizeof(int) * nn;
+  if (bytes > score_cap_) {
+    if (d_score_) (void)hipFree(d_score_);
+    d_score_ = nullptr; score_cap_ = 0;
+    check(hipMalloc(&d_score_, bytes), "hipMalloc score");
+    score_cap_ = bytes;
+  }
+  double *d_obs = d_score_, *d_sig = d_obs + nn, *d_lane = d_sig + nn, *d_mem = d_lane + npad_;
+  int *d_iy = reinterpret_cast<int *>(d_mem + n_);
+  check(hipMemcpyAsync(d_obs, obs, sizeof(double) * nn, hipMemcpyHostToDevice, stream_), "score obs");
+  if (sigma)
+    check(hipMemcpyAsync(d_sig, sigma, sizeof(double) * nn, hipMemcpyHostToDevice, stream_), "score sigma");
+  check(hipMemcpyAsync(d_iy, iy.data(), sizeof(int) * nn, hipMemcpyHostToDevice, stream_), "score years");
+  check(hx_launch_score(d_out_[v], n_, npad_, d_iy, d_obs, sigma ? d_sig : nullptr, n,
+                        has_base ? base_year0 - scen_.start : 1, has_base ? base_year1 - scen_.start : 0,
+                        d_lane, stream_), "score kernel");
+  check(hx_launch_gather(d_lane, d_lane_of_member_, d_mem, n_, npad_, 1, stream_), "score gather");
+  check(hipMemcpyAsync(out_host, d_mem, sizeof(double) * (size_t)n_, hipMemcpyDeviceToHost, stream_), "score fetch");
+  check(hipStreamSynchronize(stream_), "score sync");
+  return used;
+}
+
+int hxq_host_start(const unsigned long long *st, unsigned long long *pre) {
+  *pre = 0;
+  if (st[3] == 0) return 0;
+  const unsigned long long kmin = ~st[0], diff = kmin ^ st[1];
+  if (!diff) { *pre = kmin; return 0; }
+  int lo = 0;
+  while (lo < 64 && (diff >> lo)) ++lo;
+  if (lo < 64) *pre = (kmin >> lo) << lo;
+  return lo;
+}
+unsigned long long hxq_host_target(double p, unsigned long long W) {
+  const double t = std::ceil(p * (double)W);
+  return t < 1.0 ? 1ull : (unsigned long long)t;
+}
+void hxq_host_pick(int lo, const unsigned long long *hist, unsigned long long *prefix,
+                   unsigned long long *rem) {
+  const int shift = lo >= 8 ? lo - 8 : 0;
+  unsigned long long cum = 0, bin = 255;
+  for (unsigned long long b = 0; b < 256; ++b) {
+    if (cum + hist[b] >= *rem) { bin = b; break; }
+    cum += hist[b];
+  }
+  *prefix = (*prefix & ~(255ull << shift)) | (bin << shift);
+  *rem -= cum;
+}
+double hxq_key_to_double(unsigned long long key) {
+  const unsigned long long b = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
+  double x;
+  std::memcpy(&x, &b, sizeof x);
+  return x;
+}
+
+int EnsembleCore::q_check(const std::string &capability, int year0, int year1, int nprobs) {
+  if (nprobs < 1 || nprobs > 16)
+    throw std::runtime_error("hx_ensemble_quantiles: nprobs must lie in 1..16");
+  const int v = out_index(capability);
+  if (!d_out_[v])
+    throw std::runtime_error("variable " + capability + " was not enabled with set_outputs()");
+  if (year0 < scen_.start || year1 > last_date() || year1 < year0)
+    throw std::runtime_error("hx_ensemble_quantiles: dates must lie between startDate and the current date");
+  if (!d_lane_of_member_) throw std::runtime_error("hx_ensemble_quantiles: run the core first");
+  if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
+  return v;
+}
+
+namespace {
+// d_qstate_ in 8-byte words: [ny][4] year records, [ny][np] prefix, [ny][np] rem, [16] probs, [ny] lo (int)
+struct QState {
+  unsigned long long *st, *prefix, *rem;
+  double *probs;
+  int *lo;
+  size_t words;
+  QState(unsigned long long *base, int ny, int np) {
+    const size_t y = (size_t)ny, yp = y * (size_t)np;
+    st = base; prefix = st + 4 * y; rem = prefix + yp;
+    probs = reinterpret_cast<double *>(rem + yp);
+    lo = reinterpret_cast<int *>(rem + yp + 16);
+    words = 4 * y + 2 * yp + 16 + (y + 1) / 2;
+  }
+};
+}  // namespace
+
+// scratch for ny years x np probabilities; the weights into lane order (padding lanes: 0)
+void EnsembleCore::q_upload(const unsigned long long *q, int ny, int np) {
+  const size_t words = QState(nullptr, ny, np).words, hwords = (size_t)ny * (size_t)np * 256;
+  if (words > qstate_cap_) {
+    if (d_qstate_) (void)hipFree(d_qstate_);
+    d_qstate_ = nullptr; qstate_cap_ = 0;
+    check(hipMalloc(&d_qstate_, 8 * words), "hipMalloc quantile state");
+    qstate_cap_ = words;
+  }
+  if (hwords > qhist_cap_) {
+    if (d_qhist_) (void)hipFree(d_qhist_);
+    d_qhist_ = nullptr; qhist_cap_ = 0;
+    check(hipMalloc(&d_qhist_, 8 * hwords), "hipMalloc quantile histograms");
+    qhist_cap_ = hwords;
+  }
+  if (!q) return;
+  if (!d_q_) check(hipMalloc(&d_q_, 8 * (size_t)npad_), "hipMalloc quantile weights");
+  std::vector<unsigned long long> ql((size_t)npad_, 0ull);
+  for (int m = 0; m < n_; ++m) ql[(size_t)lane_of_member_[(size_t)m]] = q[m];
+  check(hipMemcpy(d_q_, ql.data(), 8 * (size_t)npad_, hipMemcpyHostToDevice), "quantile weights");
+}
+
+void EnsembleCore::quantiles(const std::string &capability, int year0, int year1,
+                             const unsigned long long *q, const double *probs, int nprobs,
+                             double *out_host, long long *n_part) {
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)year0; (void)year1; (void)q; (void)probs; (void)nprobs; (void)out_host; (void)n_part;
+  throw std::runtime_error("hx_ensemble_quantiles is not available in the host-emulation build (its "
+                           "kernels are cooperative: LDS atomics and cross-lane operations)");
+#else
+  const int v = q_check(capability, year0, year1, nprobs);
+  const int ny = year1 - year0 + 1, iy0 = year0 - scen_.start, np = nprobs;
+  sync();
+  q_upload(q, ny, np);
+  QState s(d_qstate_, ny, np);
+  const size_t yp = (size_t)ny * (size_t)np;
+  check(hipMemsetAsync(s.st, 0, 8 * 4 * (size_t)ny, stream_), "quantile state");
+  check(hipMemsetAsync(d_qhist_, 0, 8 * yp * 256, stream_), "quantile histograms");
+  check(hipMemcpyAsync(s.probs, probs, sizeof(double) * (size_t)np, hipMemcpyHostToDevice, stream_), "quantile probs");
+  const unsigned long long *dq = q ? d_q_ : nullptr;
+  check(hx_launch_q_minmax(d_out_[v], n_, npad_, iy0, ny, dq, s.st, stream_), "quantile min/max kernel");
+  check(hx_launch_q_init(s.st, ny, s.probs, np, (post_flags_ & 1) ? 0 : 1, s.lo, s.prefix, s.rem, stream_),
+        "quantile init kernel");
+  // eight 8-bit digits at most; a year whose select has finished makes its workgroups return at once
+  for (int pass = 0; pass < 8; ++pass) {
+    check(hx_launch_q_hist(d_out_[v], n_, npad_, iy0, ny, dq, s.lo, s.prefix, np, (post_flags_ & 2) ? 1 : 0,
+                           d_qhist_, stream_), "quantile histogram kernel");
+    check(hx_launch_q_pick(ny, s.lo, s.prefix, s.rem, np, d_qhist_, stream_), "quantile pick kernel");
+  }
+  std::vector<unsigned long long> h((size_t)4 * ny + yp);   // year records, then prefixes: adjacent
+  check(hipMemcpyAsync(h.data(), s.st, 8 * h.size(), hipMemcpyDeviceToHost, stream_), "quantile fetch");
+  check(hipStreamSynchronize(stream_), "quantile sync");
+  for (int y = 0; y < ny; ++y) {
+    const unsigned long long cnt = h[(size_t)4 * y + 3];
+    if (n_part) n_part[y] = (long long)cnt;
+    for (int j = 0; j < np; ++j)
+      out_host[(size_t)y * np + j] = cnt ? hxq_key_to_double(h[(size_t)4 * ny + (size_t)y * np + j]) : std::nan("");
+  }
+#endif
+}
+
+void EnsembleCore::q_begin(const std::string &capability, int year0, int year1,
+                           const unsigned long long *q, int nprobs, unsigned long long *st_host) {
+#ifdef HX_HOST_EMULATION
+  quantiles(capability, year0, year1, q, nullptr, nprobs, nullptr, nullptr);
+  (void)st_host;
+#else
+  const int v = q_check(capability, year0, year1, nprobs);
+  const int ny = year1 - year0 + 1;
+  sync();
+  q_upload(q, ny, nprobs);
+  QState s(d_qstate_, ny, nprobs);
+  check(hipMemsetAsync(s.st, 0, 8 * 4 * (size_t)ny, stream_), "quantile state");
+  check(hx_launch_q_minmax(d_out_[v], n_, npad_, year0 - scen_.start, ny, q ? d_q_ : nullptr, s.st, stream_),
+        "quantile min/max kernel");
+  check(hipMemcpyAsync(st_host, s.st, 8 * 4 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "quantile fetch");
+  check(hipStreamSynchronize(stream_), "quantile sync");
+  q_v_ = v; q_iy0_ = year0 - scen_.start; q_ny_ = ny; q_np_ = nprobs; q_weighted_ = q != nullptr;
+#endif
+}
+
+void EnsembleCore::q_pass(const int *lo, const unsigned long long *prefix, unsigned long long *hist_host) {
+#ifdef HX_HOST_EMULATION
+  (void)lo; (void)prefix; (void)hist_host;
+  throw std::runtime_error("hx_ensemble_quantiles is not available in the host-emulation build");
+#else
+  if (q_v_ < 0 || !d_out_[q_v_]) throw std::runtime_error("quantile pass without q_begin");
+  QState s(d_qstate_, q_ny_, q_np_);
+  const size_t yp = (size_t)q_ny_ * (size_t)q_np_;
+  check(hipMemcpyAsync(s.lo, lo, sizeof(int) * (size_t)q_ny_, hipMemcpyHostToDevice, stream_), "quantile lo");
+  check(hipMemcpyAsync(s.prefix, prefix, 8 * yp, hipMemcpyHostToDevice, stream_), "quantile prefix");
+  check(hipMemsetAsync(d_qhist_, 0, 8 * yp * 256, stream_), "quantile histograms");
+  check(hx_launch_q_hist(d_out_[q_v_], n_, npad_, q_iy0_, q_ny_, q_weighted_ ? d_q_ : nullptr, s.lo, s.prefix,
+                         q_np_, (post_flags_ & 2) ? 1 : 0, d_qhist_, stream_), "quantile histogram kernel");
+  check(hipMemcpyAsync(hist_host, d_qhist_, 8 * yp * 256, hipMemcpyDeviceToHost, stream_), "quantile fetch");
+  check(hipStreamSynchronize(stream_), "quantile sync");
+#endif
 }
 
 }  // namespace hx

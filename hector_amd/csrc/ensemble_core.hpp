@@ -140,6 +140,23 @@ class EnsembleCore {
   void stats_device(const std::string &capability, int year0, int year1, double *d_stats);
   // the same, queued on the core's stream without waiting (the fleet's collective follows it)
   void stats_async(const std::string &capability, int year0, int year1, double *d_stats);
+  // ---- post-processing on the device (hx_dev_post.h); both read results only: no prepare(), no
+  // prewarm loop, no spinup, the core is not dirtied.  Scratch is allocated on first use.
+  // chi2[member] of a recorded output against obs (hx_member_score in hector_amd.h): out_host[n_]
+  // in member order; -> the number of observations that counted
+  int member_score(const std::string &capability, const int *years, const double *obs,
+                   const double *sigma, int n, int base_year0, int base_year1, double *out_host);
+  // weighted quantiles (hx_ensemble_quantiles): q[n_] integer weights in member order (nullptr:
+  // every member 1), out_host[(year - year0) * nprobs + j], n_part[year - year0] (may be nullptr)
+  void quantiles(const std::string &capability, int year0, int year1, const unsigned long long *q,
+                 const double *probs, int nprobs, double *out_host, long long *n_part);
+  // ... and its steps for a core of several shards (hx_fleet.cpp adds the shards' integer
+  // histograms): q_begin validates, uploads q and reduces {~min key, max key, sum q, count} of
+  // every year into st_host[ny][4]; q_pass fills hist_host[ny][nprobs][256] for the select state
+  // lo[ny], prefix[ny][nprobs] (hxq_* below)
+  void q_begin(const std::string &capability, int year0, int year1, const unsigned long long *q,
+               int nprobs, unsigned long long *st_host);
+  void q_pass(const int *lo, const unsigned long long *prefix, unsigned long long *hist_host);
   int device() const { return device_; }
   void status(unsigned *out_host);
   void state_row(int row, double *out_host);
@@ -256,6 +273,18 @@ class EnsembleCore {
   void check_parameters() const;
   bool fetch_host(const std::string &capability, int year0, int year1, double *out_host);
   void compute_derived(const std::string &capability, int iy0, int ny);
+  // scratch of member_score / quantiles
+  double *d_score_ = nullptr;                 // [obs n][sigma n][chi2 npad][chi2 in member order n_] + years
+  size_t score_cap_ = 0;
+  unsigned long long *d_q_ = nullptr;         // integer weights in lane order [npad]
+  unsigned long long *d_qstate_ = nullptr;    // per year {HxQYear, lo}, per (year, prob) {prefix, rem}, probs
+  unsigned long long *d_qhist_ = nullptr;     // [ny][nprobs][256]
+  size_t qstate_cap_ = 0, qhist_cap_ = 0;
+  int q_v_ = -1, q_iy0_ = 0, q_ny_ = 0, q_np_ = 0;   // what q_begin prepared for q_pass
+  bool q_weighted_ = false;
+  int post_flags_ = 0;                        // HECTOR_AMD_POST_AB (measurements): 1 no prefix skip, 2 with wave aggregation
+  int q_check(const std::string &capability, int year0, int year1, int nprobs);
+  void q_upload(const unsigned long long *q, int ny, int np);
   hipStream_t stream_ = nullptr;
   hipStream_t aux_stream_ = nullptr;          // the prewarm loop's (non-blocking)
   unsigned char *d_prewarm_ = nullptr;        // its stop flag (+ a sink)
@@ -277,5 +306,14 @@ class EnsembleCore {
   int simds_ = 1024;              // SIMDs of this core's device (4 per compute unit)
   mutable double run_ms_ = 0, spin_ms_ = 0;
 };
+
+// the select state of hx_ensemble_quantiles on the host (the same arithmetic as the device's
+// hx_q_init_kernel / hx_q_pick_kernel): st[4] = {~min key, max key, sum q, count}
+int hxq_host_start(const unsigned long long *st, unsigned long long *pre);
+unsigned long long hxq_host_target(double p, unsigned long long W);
+// one probability of one year: hist[256] -> prefix and remaining rank updated for the digit below lo
+void hxq_host_pick(int lo, const unsigned long long *hist, unsigned long long *prefix,
+                   unsigned long long *rem);
+double hxq_key_to_double(unsigned long long key);
 
 }  // namespace hx

@@ -358,6 +358,21 @@ int hx_stats_device(hx_core *core, const char *capability, int year0, int year1,
   if (!capability || !d_stats) return fail("hx_stats_device: null argument");
   HX_TRY(core->core->stats_device(capability, year0, year1, d_stats))
 }
+int hx_member_score(hx_core *core, const char *capability, const int *years, const double *obs,
+                    const double *sigma, int n, int base_year0, int base_year1, double *out,
+                    int *n_used) {
+  if (!capability || !years || !obs || !out) return fail("hx_member_score: null argument");
+  if (n < 1) return fail("hx_member_score: n < 1");
+  HX_TRY(const int used = core->core->member_score(capability, years, obs, sigma, n, base_year0,
+                                                   base_year1, out);
+         if (n_used) *n_used = used)
+}
+int hx_ensemble_quantiles(hx_core *core, const char *capability, int year0, int year1,
+                          const double *weights, const double *probs, int nprobs, double *out,
+                          long long *n_part) {
+  if (!capability || !probs || !out) return fail("hx_ensemble_quantiles: null argument");
+  HX_TRY(core->core->quantiles(capability, year0, year1, weights, probs, nprobs, out, n_part))
+}
 int hx_status(hx_core *core, unsigned *out) {
   if (!out) return fail("hx_status: null argument");
   HX_TRY(core->core->status(out))

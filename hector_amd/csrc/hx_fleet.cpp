@@ -2,6 +2,7 @@
 #include "hx_fleet.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -337,6 +338,111 @@ void Fleet::stats_device(const std::string &cap, int year0, int year1, double *d
 }
 
 void Fleet::status(unsigned *out) { for (Shard &s : shards_) { use(s); s.core->status(out + s.offset); } }
+
+int Fleet::member_score(const std::string &cap, const int *years, const double *obs, const double *sigma,
+                        int n, int base_year0, int base_year1, double *out) {
+  check_poison();
+  int used = 0;
+  for (Shard &s : shards_) {
+    use(s);
+    used = s.core->member_score(cap, years, obs, sigma, n, base_year0, base_year1, out + s.offset);
+  }
+  return used;
+}
+
+void Fleet::quantiles(const std::string &cap, int year0, int year1, const double *weights,
+                      const double *probs, int nprobs, double *out, long long *n_part) {
+  check_poison();
+  if (nprobs < 1 || nprobs > 16 || !probs)
+    throw std::runtime_error("hx_ensemble_quantiles: nprobs must lie in 1..16");
+  for (int j = 0; j < nprobs; ++j)
+    if (!(probs[j] >= 0.0 && probs[j] <= 1.0))
+      throw std::runtime_error("hx_ensemble_quantiles: a probability outside [0, 1]");
+  if (comm_ready_ && world_ > n_shards())
+    throw std::runtime_error("hx_ensemble_quantiles: this core joined a communicator of several "
+                             "processes (hx_comm_init_rank with n_procs > 1); quantiles over "
+                             "processes are not supported");
+  // integer weights: q = rint(w / wmax * 2^32), wmax over ALL shards
+  std::vector<unsigned long long> q;
+  if (weights) {
+    double wmax = 0.0;
+    for (int m = 0; m < n_; ++m) {
+      const double w = weights[m];
+      if (!(w >= 0.0) || std::isinf(w))
+        throw std::runtime_error("hx_ensemble_quantiles: a weight is negative, NaN or infinite");
+      wmax = std::max(wmax, w);
+    }
+    if (!(wmax > 0.0)) throw std::runtime_error("hx_ensemble_quantiles: the weights are all zero");
+    q.resize((size_t)n_);
+    unsigned long long total = 0;
+    for (int m = 0; m < n_; ++m) {
+      q[(size_t)m] = (unsigned long long)std::rint(weights[m] / wmax * 4294967296.0);
+      total += q[(size_t)m];
+    }
+    if (total > (1ull << 52))
+      throw std::runtime_error("hx_ensemble_quantiles: more than 2^20 weighted members");
+  }
+  const unsigned long long *qp = weights ? q.data() : nullptr;
+  if (shards_.size() == 1) {
+    use(shards_[0]);
+    shards_[0].core->quantiles(cap, year0, year1, qp, probs, nprobs, out, n_part);
+    return;
+  }
+  const int ny = year1 - year0 + 1, np = nprobs;
+  if (ny < 1) throw std::runtime_error("hx_ensemble_quantiles: year1 < year0");
+  const size_t Y = (size_t)ny, YP = Y * (size_t)np;
+  std::vector<unsigned long long> st(4 * Y, 0ull), part(4 * Y);
+  for (Shard &s : shards_) {
+    use(s);
+    s.core->q_begin(cap, year0, year1, qp ? qp + s.offset : nullptr, np, part.data());
+    for (size_t y = 0; y < Y; ++y) {
+      if (!part[4 * y + 3]) continue;
+      st[4 * y] = std::max(st[4 * y], part[4 * y]);
+      st[4 * y + 1] = std::max(st[4 * y + 1], part[4 * y + 1]);
+      st[4 * y + 2] += part[4 * y + 2];
+      st[4 * y + 3] += part[4 * y + 3];
+    }
+  }
+  std::vector<int> lo(Y);
+  std::vector<unsigned long long> prefix(YP), rem(YP), hist(YP * 256), hpart(YP * 256);
+  bool open = false;
+  for (size_t y = 0; y < Y; ++y) {
+    unsigned long long pre;
+    lo[y] = hxq_host_start(&st[4 * y], &pre);
+    open = open || lo[y] > 0;
+    for (int j = 0; j < np; ++j) {
+      prefix[y * np + j] = pre;
+      rem[y * np + j] = hxq_host_target(probs[j], st[4 * y + 2]);
+    }
+  }
+  while (open) {
+    std::fill(hist.begin(), hist.end(), 0ull);
+    for (Shard &s : shards_) {
+      use(s);
+      s.core->q_pass(lo.data(), prefix.data(), hpart.data());
+      for (size_t i = 0; i < hist.size(); ++i) hist[i] += hpart[i];
+    }
+    open = false;
+    for (size_t y = 0; y < Y; ++y) {
+      if (lo[y] == 0) continue;
+      int owner[16];   // the first probability with the same prefix holds the histogram
+      for (int j = 0; j < np; ++j) {
+        owner[j] = j;
+        for (int k = 0; k < j; ++k) if (prefix[y * np + k] == prefix[y * np + j]) { owner[j] = k; break; }
+      }
+      for (int j = 0; j < np; ++j)
+        hxq_host_pick(lo[y], &hist[(y * np + (size_t)owner[j]) * 256], &prefix[y * np + j], &rem[y * np + j]);
+      lo[y] = lo[y] >= 8 ? lo[y] - 8 : 0;
+      open = open || lo[y] > 0;
+    }
+  }
+  for (size_t y = 0; y < Y; ++y) {
+    if (n_part) n_part[y] = (long long)st[4 * y + 3];
+    for (int j = 0; j < np; ++j)
+      out[y * np + j] = st[4 * y + 3] ? hxq_key_to_double(prefix[y * np + j]) : std::nan("");
+  }
+}
+
 void Fleet::state_row(int row, double *out) {
   for (Shard &s : shards_) { use(s); s.core->state_row(row, out + s.offset); }
 }

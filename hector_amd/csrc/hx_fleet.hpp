@@ -86,6 +86,14 @@ class Fleet {
   const double *device_var(const std::string &capability, int *npad, int shard_index = -1);
   void stats_device(const std::string &capability, int year0, int year1, double *d_stats);
   void status(unsigned *out_host);
+  // hx_member_score: every shard scores its block (routed like status()); -> observations that counted
+  int member_score(const std::string &capability, const int *years, const double *obs,
+                   const double *sigma, int n, int base_year0, int base_year1, double *out_host);
+  // hx_ensemble_quantiles: weights checked and quantised against the largest of the WHOLE ensemble;
+  // one shard runs the select on its GPU, several shards fill integer histograms that are added
+  // and searched here, pass by pass (exact: the same bits as one core)
+  void quantiles(const std::string &capability, int year0, int year1, const double *weights,
+                 const double *probs, int nprobs, double *out_host, long long *n_part);
   void state_row(int row, double *out_host);
   int spinup_steps(int member);
   void tracking_data(int member, int year0, int year1, double *values, double *fractions,

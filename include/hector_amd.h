@@ -257,6 +257,52 @@ int hx_device_var_shard(hx_core *core, int shard, const char *capability, const 
 int hx_stats_device(hx_core *core, const char *capability, int year0, int year1,
                     double *d_stats);
 
+/* Misfit of every member against an observed record, on the device; no counterpart in the
+ * reference (its hosts score fetchvars() data frames in R).
+ *   chi2[member] = sum_i r_i^2,  r_i = ((x(years[i], member) - base(member)) - obs[i]) / sigma[i]
+ * x: a RECORDED output (hx_set_outputs), years inside startDate..current date, in any order.
+ * obs[i] NaN: that year is skipped.  sigma NULL: no division.
+ * base_year0 <= base_year1: base = the member's own mean of x over those years (an anomaly relative
+ * to a reference period); base_year0 > base_year1: base is not subtracted.
+ * Evaluated per member in exactly this order, in IEEE double, without fused multiply-add:
+ *   s = 0.0; for y = base_year0..base_year1: s = s + x_y;  base = s / count;
+ *   chi = 0.0; for i = 0..n-1 with obs_i not NaN: r = ((x_i - base) - obs_i) / sigma_i;
+ *   chi = chi + (r * r)  -- the product rounded before the sum
+ * (no baseline: r = (x_i - obs_i) / sigma_i), so numpy reproduces it bit for bit and the result
+ * does not depend on lane order, kernel flavour or shard layout.
+ * out[n_members] in the caller's member order; *n_used (may be NULL) = years that counted.
+ * Cost: one kernel, one lane per member, n (+ reference period) coalesced row reads, and
+ * n_members doubles back to the host; returns when they are there.  The core is not prepared, spun
+ * up or dirtied.  Errors: an unrecorded capability, dates outside startDate..current date, n < 1. */
+int hx_member_score(hx_core *core, const char *capability, const int *years, const double *obs,
+                    const double *sigma, int n, int base_year0, int base_year1,
+                    double *out, int *n_used);
+
+/* Per-year weighted quantiles over the whole ensemble, on the device; no counterpart in the
+ * reference.  out[(year - year0) * nprobs + j] = the probs[j]-quantile of x(year, .) over the members
+ * that take part, weighted by weights[n_members] (member order; NULL = every member weight 1);
+ * n_part[year - year0] (may be NULL) = members that took part.  1 <= nprobs <= 16, 0 <= probs <= 1.
+ * Definition: the weighted inverted CDF (Hyndman-Fan type 1, numpy's method="inverted_cdf").  The
+ * weights are made integers once, q_m = (uint64) rint(w_m / wmax * 2^32) with wmax the largest
+ * weight of the WHOLE ensemble (NULL weights: q_m = 1); a member takes part in a year if q_m > 0 and
+ * its value that year is not NaN; with the participating values sorted ascending and W = sum q, the
+ * answer for p is the value of the first member in that order whose running sum of q reaches
+ * t = max(1, ceil(p * (double) W)).  Every sum is an exact integer, the result is a value some
+ * member has, bit-identical under any lane order or shard split; a year in which nobody takes
+ * part gives NaN and n_part = 0.
+ * Cost: an exact most-significant-digit radix select on the order-preserving 64-bit image of the
+ * doubles, begun at the highest bit in which the year's min and max differ: one read of the
+ * year's row for min / max and one per 8-bit digit (at most 8) for ALL probabilities together;
+ * nprobs (+ 4) x n_years values back to the host; returns when they are there.  A core of several
+ * shards adds the shards' integer histograms on the host after every digit (the same bits as one
+ * core); a core that joined a communicator of several processes is refused.  The core is not
+ * prepared, spun up or dirtied.  Errors: an unrecorded capability, dates outside startDate..current
+ * date, nprobs outside 1..16, a probability outside [0, 1], a negative, NaN or infinite weight,
+ * weights that are all zero.  Not available in the host-emulation build of the test suite. */
+int hx_ensemble_quantiles(hx_core *core, const char *capability, int year0, int year1,
+                          const double *weights, const double *probs, int nprobs,
+                          double *out, long long *n_part);
+
 /* per-member model-error bitmask (HX_ERR_* below), host array of n_members */
 int hx_status(hx_core *core, unsigned *out);
 int hx_spinup_steps(hx_core *core, int member, int *steps);
