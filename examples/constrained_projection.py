@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """A constrained projection: run a perturbed-parameter ensemble, score every member against an
 observed record, weight the members by their likelihood and report the weighted median and 5-95 %
-band -- without a trajectory leaving the GPU (Core.score, Core.quantiles).  The "observations"
-here are pseudo-observations: one held-out member plus seeded noise.
+band -- without a trajectory leaving the GPU (Core.score, Core.quantiles) -- and then what a user
+reports: the constrained 2081-2100 warming relative to 1850-1900, the distribution of the
+peak-warming year and the probability of the warming classes in 2100 (Core.metric_quantiles,
+Core.metric_probabilities).  The "observations" here are pseudo-observations: one held-out member
+plus seeded noise.
 Needs an MI355X:  python examples/constrained_projection.py [n_members]"""
 import os
 import sys
@@ -11,6 +14,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import hector_amd                                    # noqa: E402
+from hector_amd import Metric                        # noqa: E402
 from hector_amd.capabilities import ECS, Q10_RH, BETA, CONCENTRATIONS_CO2, GLOBAL_TAS  # noqa: E402
 
 PROBS = (0.05, 0.5, 0.95)
@@ -50,6 +54,17 @@ def main(n=20000, truth=0, **core_kwargs):
     print("%d members, %d with a model error, effective sample size %.1f, %.1f ms on the GPU"
           % (n, int((core.status() != 0).sum()), n_eff, core.last_run_ms()))
     band = core.quantiles(GLOBAL_TAS(), PROBS, (1850, 2100), weights=weights)   # [251, 3]: the plot
+
+    # a number per member, reduced on the device; only the weighted summaries come back
+    base = (1850, 1900)
+    specs = [Metric("mean", (2081, 2100), baseline=base), Metric("year_of_max", (1850, 2100), baseline=base)]
+    for name, wts in (("prior", None), ("constrained", weights)):
+        warm, peak = core.metric_quantiles(GLOBAL_TAS(), specs, PROBS, weights=wts)
+        print("%-12s 2081-2100 warming rel. 1850-1900: %.2f (%.2f-%.2f) K   peak-warming year: %d (%d-%d)"
+              % (name, warm[1], warm[0], warm[2], peak[1], peak[0], peak[2]))
+    classes = core.metric_probabilities(GLOBAL_TAS(), [Metric("mean", 2100, baseline=base)], (1.5, 2.0, 3.0),
+                                        weights=weights)[0]
+    print("constrained 2100 warming: P(< 1.5 K) %.3f  P(1.5-2 K) %.3f  P(2-3 K) %.3f  P(>= 3 K) %.3f" % tuple(classes))
     hector_amd.shutdown(core)
     return band, weights
 

@@ -15,6 +15,41 @@ from ._lib import HectorAmdError, DEFAULT_SCENARIO
 # (the R-style capability accessors -- ECS(), BETA(biome) ... -- live in hector_amd.capabilities)
 
 
+METRIC_OPS = {"mean": 0, "min": 1, "max": 2, "year_of_min": 3, "year_of_max": 4, "first_ge": 5,
+              "count_ge": 6, "slope": 7}    # HX_MET_* of include/hector_amd.h
+
+
+class _HxMetric(ctypes.Structure):   # hx_metric
+    _fields_ = [("op", ctypes.c_int), ("year0", ctypes.c_int), ("year1", ctypes.c_int),
+                ("base_year0", ctypes.c_int), ("base_year1", ctypes.c_int), ("reserved", ctypes.c_int),
+                ("threshold", ctypes.c_double)]
+
+
+class Metric:
+    """One number per member from a window of a recorded output (hx_metric in include/hector_amd.h).
+    op: "mean", "min", "max", "year_of_min", "year_of_max", "first_ge", "count_ge" or "slope";
+    years = (year0, year1) or one year; baseline = (year0, year1): the member's own mean over those
+    years is subtracted first; threshold: for "first_ge" and "count_ge"."""
+
+    def __init__(self, op, years, baseline=None, threshold=float("nan")):
+        if op not in METRIC_OPS:
+            raise HectorAmdError("Metric: unknown op %r (one of %s)" % (op, ", ".join(METRIC_OPS)))
+        y = np.atleast_1d(np.asarray(years)).astype(np.int64)
+        if y.size < 1:
+            raise HectorAmdError("Metric: years must be a year or (year0, year1)")
+        self.op = op
+        self.years = (int(y.min()), int(y.max()))
+        self.baseline = None if baseline is None else (int(baseline[0]), int(baseline[1]))
+        self.threshold = float(threshold)
+
+    def __repr__(self):
+        return "Metric(%r, %r, baseline=%r, threshold=%r)" % (self.op, self.years, self.baseline, self.threshold)
+
+    def _c(self):
+        b0, b1 = (1, 0) if self.baseline is None else self.baseline
+        return _HxMetric(METRIC_OPS[self.op], self.years[0], self.years[1], b0, b1, 0, self.threshold)
+
+
 class Core:
     """An N-member ensemble core bound to one GPU (device=) or sharded over a list of GPUs
     (devices=[...]: contiguous member blocks, hx_newcore_devices)."""
@@ -372,6 +407,90 @@ class Core:
             pr.ctypes.data_as(dp), int(pr.size), out.ctypes.data_as(dp),
             npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         return (out, npart) if counts else out
+
+    @staticmethod
+    def _metric_array(specs, what):
+        if isinstance(specs, Metric):
+            specs = [specs]
+        specs = list(specs)
+        if not all(isinstance(m, Metric) for m in specs):
+            raise HectorAmdError("%s: specs must be hector_amd.Metric objects" % what)
+        arr = (_HxMetric * max(len(specs), 1))(*[m._c() for m in specs])
+        return arr, len(specs)
+
+    def _weights(self, weights, what):
+        if weights is None:
+            return None
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+        if w.shape != (self.n_members,):
+            raise HectorAmdError("%s: weights must have n_members entries" % what)
+        return w
+
+    def metrics(self, var, specs):
+        """One number per member and specification, on the device (hx_member_metrics): windowed
+        mean / min / max / year of min or max / first year at or above a threshold / years at or
+        above it / least-squares trend of a recorded output, optionally relative to the member's
+        own reference-period mean -> ndarray [n_specs, n_members].  The evaluation order is fixed
+        (include/hector_amd.h): numpy reproduces the result bit for bit."""
+        arr, ns = self._metric_array(specs, "metrics")
+        out = np.empty((ns, self.n_members))
+        self._ck(self._lib.hx_member_metrics(self._h, var.encode(), ctypes.byref(arr), ns,
+                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return out
+
+    def metric_quantiles(self, var, specs, probs, weights=None, counts=False):
+        """Weighted quantiles of every metric over the ensemble (hx_metric_quantiles: the metrics
+        are computed and selected on the device, definition as quantiles()) -> ndarray
+        [n_specs, n_probs]; counts=True: also the members that took part [n_specs]."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        arr, ns = self._metric_array(specs, "metric_quantiles")
+        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if pr.ndim != 1:
+            raise HectorAmdError("metric_quantiles: probs must be one-dimensional")
+        w = self._weights(weights, "metric_quantiles")
+        out = np.empty((ns, pr.size))
+        npart = np.zeros(ns, dtype=np.int64)
+        self._ck(self._lib.hx_metric_quantiles(
+            self._h, var.encode(), ctypes.byref(arr), ns, w.ctypes.data_as(dp) if w is not None else None,
+            pr.ctypes.data_as(dp), int(pr.size), out.ctypes.data_as(dp),
+            npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return (out, npart) if counts else out
+
+    def _probabilities(self, what, call, nrows, edges, weights, counts, sums):
+        dp = ctypes.POINTER(ctypes.c_double)
+        ed = np.ascontiguousarray(np.atleast_1d(np.asarray(edges, dtype=np.float64)))
+        if ed.ndim != 1:
+            raise HectorAmdError("%s: edges must be one-dimensional" % what)
+        w = self._weights(weights, what)
+        prob = np.empty((nrows, ed.size + 1))
+        qs = np.zeros((nrows, ed.size + 1), dtype=np.uint64)
+        npart = np.zeros(nrows, dtype=np.int64)
+        self._ck(call(w.ctypes.data_as(dp) if w is not None else None, ed.ctypes.data_as(dp), int(ed.size),
+                      prob.ctypes.data_as(dp), qs.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
+                      npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        res = (prob,) + ((npart,) if counts else ()) + ((qs,) if sums else ())
+        return res if len(res) > 1 else prob
+
+    def probabilities(self, var, edges, dates=None, weights=None, counts=False, sums=False):
+        """Per-year weighted probabilities of the classes x < edges[0], edges[0] <= x < edges[1],
+        ..., x >= edges[-1] over every member, on the device (hx_ensemble_probabilities: one pass
+        over the rows, exact integer sums) -> ndarray [n_years, n_edges + 1]; counts=True: also
+        the members that took part [n_years]; sums=True: also the integer sums (uint64)."""
+        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
+            (int(min(dates)), int(max(dates)))
+        return self._probabilities(
+            "probabilities",
+            lambda *a: self._lib.hx_ensemble_probabilities(self._h, var.encode(), y0, y1, *a),
+            max(y1 - y0 + 1, 0), edges, weights, counts, sums)
+
+    def metric_probabilities(self, var, specs, edges, weights=None, counts=False, sums=False):
+        """The same classes over metrics (hx_metric_probabilities) -> ndarray
+        [n_specs, n_edges + 1] (+ counts [n_specs], + sums)."""
+        arr, ns = self._metric_array(specs, "metric_probabilities")
+        return self._probabilities(
+            "metric_probabilities",
+            lambda *a: self._lib.hx_metric_probabilities(self._h, var.encode(), ctypes.byref(arr), ns, *a),
+            ns, edges, weights, counts, sums)
 
     def status(self):
         out = np.zeros(self.n_members, dtype=np.uint32)

@@ -54,6 +54,10 @@ hipError_t hx_launch_doeclim_kernel(const double *diff_row, double *ker, int ns,
 #else
 hipError_t hx_launch_score(const double *var, int n, int npad, const int *iy, const double *obs,
                            const double *sigma, int nobs, int b0, int b1, double *out, hipStream_t st);
+hipError_t hx_launch_metric(const double *var, int n, int npad, const void *groups, int ngroups,
+                            const int *rows, int year_start, double *out, hipStream_t st);
+hipError_t hx_launch_bin(const double *var, int n, int npad, int iy0, int nrows, const unsigned long long *q,
+                         const double *edges, int K, unsigned long long *sums, hipStream_t stream);
 hipError_t hx_launch_q_minmax(const double *var, int n, int npad, int iy0, int ny,
                               const unsigned long long *q, void *st, hipStream_t stream);
 hipError_t hx_launch_q_init(const void *st, int ny, const double *probs, int np, int skip, int *lo,
@@ -542,9 +546,10 @@ void EnsembleCore::free_device() {
   fr(d_wave_clk_); d_wave_clk_ = nullptr;
   fr(d_bscratch_); d_bscratch_ = nullptr;
   fr(d_spin_rec_); d_spin_rec_ = nullptr;
-  fr(d_score_); fr(d_q_); fr(d_qstate_); fr(d_qhist_);
+  fr(d_score_); fr(d_q_); fr(d_qstate_); fr(d_qhist_); fr(d_metplan_); fr(d_met_); fr(d_bin_);
   d_score_ = nullptr; d_q_ = d_qstate_ = d_qhist_ = nullptr;
-  score_cap_ = qstate_cap_ = qhist_cap_ = 0; q_v_ = -1;
+  d_metplan_ = nullptr; d_met_ = nullptr; d_bin_ = nullptr;
+  score_cap_ = qstate_cap_ = qhist_cap_ = metplan_cap_ = met_cap_ = bin_cap_ = 0; q_src_ = nullptr;
   d_hist_ = nullptr; d_hist_status_ = nullptr;
   for (int k = 0; k < HXM_N; ++k) { fr(d_mseries_[k]); d_mseries_[k] = nullptr; if (!member_series_[k].empty()) mseries_dirty_ = true; }
   fr(d_diag_); fr(d_slr_); d_diag_ = d_slr_ = nullptr; diag_cap_ = 0; slr_valid_to_ = -1;
@@ -2819,15 +2824,18 @@ double hxq_key_to_double(unsigned long long key) {
   return x;
 }
 
-int EnsembleCore::q_check(const std::string &capability, int year0, int year1, int nprobs) {
+int EnsembleCore::q_check(const std::string &capability, int year0, int year1, int nprobs, const char *fn) {
+  const std::string f(fn);
   if (nprobs < 1 || nprobs > 16)
-    throw std::runtime_error("hx_ensemble_quantiles: nprobs must lie in 1..16");
+    throw std::runtime_error(f + ": nprobs must lie in 1..16");
   const int v = out_index(capability);
-  if (!d_out_[v])
-    throw std::runtime_error("variable " + capability + " was not enabled with set_outputs()");
+  const bool is_q = f == "hx_ensemble_quantiles";   // (its messages stay as they were)
+  if (is_q ? !d_out_[v] : !out_enabled_[v])
+    throw std::runtime_error((is_q ? std::string() : f + ": ") + "variable " + capability +
+                             " was not enabled with set_outputs()");
   if (year0 < scen_.start || year1 > last_date() || year1 < year0)
-    throw std::runtime_error("hx_ensemble_quantiles: dates must lie between startDate and the current date");
-  if (!d_lane_of_member_) throw std::runtime_error("hx_ensemble_quantiles: run the core first");
+    throw std::runtime_error(f + ": dates must lie between startDate and the current date");
+  if (!d_lane_of_member_ || !d_out_[v]) throw std::runtime_error(f + ": run the core first");
   if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
   return v;
 }
@@ -2871,17 +2879,17 @@ void EnsembleCore::q_upload(const unsigned long long *q, int ny, int np) {
   check(hipMemcpy(d_q_, ql.data(), 8 * (size_t)npad_, hipMemcpyHostToDevice), "quantile weights");
 }
 
-void EnsembleCore::quantiles(const std::string &capability, int year0, int year1,
-                             const unsigned long long *q, const double *probs, int nprobs,
-                             double *out_host, long long *n_part) {
 #ifdef HX_HOST_EMULATION
-  (void)capability; (void)year0; (void)year1; (void)q; (void)probs; (void)nprobs; (void)out_host; (void)n_part;
-  throw std::runtime_error("hx_ensemble_quantiles is not available in the host-emulation build (its "
-                           "kernels are cooperative: LDS atomics and cross-lane operations)");
+static const char *const kEmulRefusal =
+    " is not available in the host-emulation build (its kernels are cooperative: LDS atomics and "
+    "cross-lane operations)";
+#endif
+
+void EnsembleCore::q_select(const double *src, int iy0, int ny, const unsigned long long *q,
+                            const double *probs, int np, double *out_host, long long *n_part) {
+#ifdef HX_HOST_EMULATION
+  (void)src; (void)iy0; (void)ny; (void)q; (void)probs; (void)np; (void)out_host; (void)n_part;
 #else
-  const int v = q_check(capability, year0, year1, nprobs);
-  const int ny = year1 - year0 + 1, iy0 = year0 - scen_.start, np = nprobs;
-  sync();
   q_upload(q, ny, np);
   QState s(d_qstate_, ny, np);
   const size_t yp = (size_t)ny * (size_t)np;
@@ -2889,12 +2897,12 @@ void EnsembleCore::quantiles(const std::string &capability, int year0, int year1
   check(hipMemsetAsync(d_qhist_, 0, 8 * yp * 256, stream_), "quantile histograms");
   check(hipMemcpyAsync(s.probs, probs, sizeof(double) * (size_t)np, hipMemcpyHostToDevice, stream_), "quantile probs");
   const unsigned long long *dq = q ? d_q_ : nullptr;
-  check(hx_launch_q_minmax(d_out_[v], n_, npad_, iy0, ny, dq, s.st, stream_), "quantile min/max kernel");
+  check(hx_launch_q_minmax(src, n_, npad_, iy0, ny, dq, s.st, stream_), "quantile min/max kernel");
   check(hx_launch_q_init(s.st, ny, s.probs, np, (post_flags_ & 1) ? 0 : 1, s.lo, s.prefix, s.rem, stream_),
         "quantile init kernel");
   // eight 8-bit digits at most; a year whose select has finished makes its workgroups return at once
   for (int pass = 0; pass < 8; ++pass) {
-    check(hx_launch_q_hist(d_out_[v], n_, npad_, iy0, ny, dq, s.lo, s.prefix, np, (post_flags_ & 2) ? 1 : 0,
+    check(hx_launch_q_hist(src, n_, npad_, iy0, ny, dq, s.lo, s.prefix, np, (post_flags_ & 2) ? 1 : 0,
                            d_qhist_, stream_), "quantile histogram kernel");
     check(hx_launch_q_pick(ny, s.lo, s.prefix, s.rem, np, d_qhist_, stream_), "quantile pick kernel");
   }
@@ -2910,6 +2918,34 @@ void EnsembleCore::quantiles(const std::string &capability, int year0, int year1
 #endif
 }
 
+void EnsembleCore::q_begin_block(const double *src, int iy0, int ny, const unsigned long long *q, int np,
+                                 unsigned long long *st_host) {
+#ifdef HX_HOST_EMULATION
+  (void)src; (void)iy0; (void)ny; (void)q; (void)np; (void)st_host;
+#else
+  q_upload(q, ny, np);
+  QState s(d_qstate_, ny, np);
+  check(hipMemsetAsync(s.st, 0, 8 * 4 * (size_t)ny, stream_), "quantile state");
+  check(hx_launch_q_minmax(src, n_, npad_, iy0, ny, q ? d_q_ : nullptr, s.st, stream_), "quantile min/max kernel");
+  check(hipMemcpyAsync(st_host, s.st, 8 * 4 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "quantile fetch");
+  check(hipStreamSynchronize(stream_), "quantile sync");
+  q_src_ = src; q_iy0_ = iy0; q_ny_ = ny; q_np_ = np; q_weighted_ = q != nullptr;
+#endif
+}
+
+void EnsembleCore::quantiles(const std::string &capability, int year0, int year1,
+                             const unsigned long long *q, const double *probs, int nprobs,
+                             double *out_host, long long *n_part) {
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)year0; (void)year1; (void)q; (void)probs; (void)nprobs; (void)out_host; (void)n_part;
+  throw std::runtime_error(std::string("hx_ensemble_quantiles") + kEmulRefusal);
+#else
+  const int v = q_check(capability, year0, year1, nprobs);
+  sync();
+  q_select(d_out_[v], year0 - scen_.start, year1 - year0 + 1, q, probs, nprobs, out_host, n_part);
+#endif
+}
+
 void EnsembleCore::q_begin(const std::string &capability, int year0, int year1,
                            const unsigned long long *q, int nprobs, unsigned long long *st_host) {
 #ifdef HX_HOST_EMULATION
@@ -2917,16 +2953,8 @@ void EnsembleCore::q_begin(const std::string &capability, int year0, int year1,
   (void)st_host;
 #else
   const int v = q_check(capability, year0, year1, nprobs);
-  const int ny = year1 - year0 + 1;
   sync();
-  q_upload(q, ny, nprobs);
-  QState s(d_qstate_, ny, nprobs);
-  check(hipMemsetAsync(s.st, 0, 8 * 4 * (size_t)ny, stream_), "quantile state");
-  check(hx_launch_q_minmax(d_out_[v], n_, npad_, year0 - scen_.start, ny, q ? d_q_ : nullptr, s.st, stream_),
-        "quantile min/max kernel");
-  check(hipMemcpyAsync(st_host, s.st, 8 * 4 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "quantile fetch");
-  check(hipStreamSynchronize(stream_), "quantile sync");
-  q_v_ = v; q_iy0_ = year0 - scen_.start; q_ny_ = ny; q_np_ = nprobs; q_weighted_ = q != nullptr;
+  q_begin_block(d_out_[v], year0 - scen_.start, year1 - year0 + 1, q, nprobs, st_host);
 #endif
 }
 
@@ -2935,16 +2963,215 @@ void EnsembleCore::q_pass(const int *lo, const unsigned long long *prefix, unsig
   (void)lo; (void)prefix; (void)hist_host;
   throw std::runtime_error("hx_ensemble_quantiles is not available in the host-emulation build");
 #else
-  if (q_v_ < 0 || !d_out_[q_v_]) throw std::runtime_error("quantile pass without q_begin");
+  if (!q_src_) throw std::runtime_error("quantile pass without q_begin");
   QState s(d_qstate_, q_ny_, q_np_);
   const size_t yp = (size_t)q_ny_ * (size_t)q_np_;
   check(hipMemcpyAsync(s.lo, lo, sizeof(int) * (size_t)q_ny_, hipMemcpyHostToDevice, stream_), "quantile lo");
   check(hipMemcpyAsync(s.prefix, prefix, 8 * yp, hipMemcpyHostToDevice, stream_), "quantile prefix");
   check(hipMemsetAsync(d_qhist_, 0, 8 * yp * 256, stream_), "quantile histograms");
-  check(hx_launch_q_hist(d_out_[q_v_], n_, npad_, q_iy0_, q_ny_, q_weighted_ ? d_q_ : nullptr, s.lo, s.prefix,
+  check(hx_launch_q_hist(q_src_, n_, npad_, q_iy0_, q_ny_, q_weighted_ ? d_q_ : nullptr, s.lo, s.prefix,
                          q_np_, (post_flags_ & 2) ? 1 : 0, d_qhist_, stream_), "quantile histogram kernel");
   check(hipMemcpyAsync(hist_host, d_qhist_, 8 * yp * 256, hipMemcpyDeviceToHost, stream_), "quantile fetch");
   check(hipStreamSynchronize(stream_), "quantile sync");
+#endif
+}
+
+// ---- per-member metrics, their quantiles, and bin probabilities ----------------------------------
+
+int EnsembleCore::metric_check(const std::string &capability, const hx_metric *specs, int nspecs,
+                               const char *fn) {
+  const std::string f(fn);
+  if (nspecs < 1 || nspecs > HX_MET_MAX_SPECS || !specs)
+    throw std::runtime_error(f + ": nspecs must lie in 1..32");
+  const int v = out_index(capability);
+  if (!out_enabled_[v])
+    throw std::runtime_error(f + ": variable " + capability + " was not enabled with set_outputs()");
+  const int last = last_date();
+  for (int i = 0; i < nspecs; ++i) {
+    const hx_metric &m = specs[i];
+    const std::string which = " (specification " + std::to_string(i) + ")";
+    if (m.op < 0 || m.op >= HX_MET_NOPS) throw std::runtime_error(f + ": unknown op" + which);
+    if (m.year1 < m.year0) throw std::runtime_error(f + ": year1 < year0" + which);
+    if (m.year0 < scen_.start || m.year1 > last)
+      throw std::runtime_error(f + ": the window must lie between startDate and the current date" + which);
+    if (m.base_year0 <= m.base_year1 && (m.base_year0 < scen_.start || m.base_year1 > last))
+      throw std::runtime_error(f + ": the reference period must lie between startDate and the current date" + which);
+    if ((m.op == HX_MET_FIRST_GE || m.op == HX_MET_COUNT_GE) && !(m.threshold == m.threshold))
+      throw std::runtime_error(f + ": the threshold is NaN" + which);
+  }
+  if (!d_lane_of_member_ || !d_out_[v]) throw std::runtime_error(f + ": run the core first");
+  return v;
+}
+
+namespace {
+// the device's records (hx_dev_post.h)
+constexpr int kMetGroup = 4, kMetBatch = 16, kMetPad = 0x40000000;
+struct MetSpec { int op, iy0, iy1, base; double thr, mid; };
+struct MetGroup {
+  int nspec, nbase, brow0, nbrow, wrow0, nwrow, pad0, pad1;
+  int b0[kMetGroup], b1[kMetGroup];
+  MetSpec s[kMetGroup];
+};
+// the ascending union of [lo, hi] ranges, padded to a multiple of kMetBatch, appended to rows
+void append_rows(const std::vector<std::pair<int, int>> &ranges, std::vector<int> &rows, int *first, int *count) {
+  std::vector<int> u;
+  for (const auto &r : ranges) for (int y = r.first; y <= r.second; ++y) u.push_back(y);
+  std::sort(u.begin(), u.end());
+  u.erase(std::unique(u.begin(), u.end()), u.end());
+  while (!u.empty() && u.size() % kMetBatch) u.push_back(u.back() | kMetPad);
+  for (size_t i = 0; i < u.size(); ++i) if (i && (u[i] & kMetPad)) u[i] = (u[i - 1] & (kMetPad - 1)) | kMetPad;
+  *first = (int)rows.size(); *count = (int)u.size();
+  rows.insert(rows.end(), u.begin(), u.end());
+}
+}  // namespace
+
+// the specifications, four to a group in the caller's order, into the device's records and row
+// lists; the kernel is queued on stream_ and d_met_ [nspecs rounded up to groups][npad_] returned
+const double *EnsembleCore::metric_block(int v, const hx_metric *specs, int nspecs) {
+  const int ngroups = (nspecs + kMetGroup - 1) / kMetGroup;
+  std::vector<MetGroup> groups((size_t)ngroups);
+  std::vector<int> rows;
+  for (int gi = 0; gi < ngroups; ++gi) {
+    MetGroup &g = groups[(size_t)gi];
+    std::memset(&g, 0, sizeof g);
+    std::vector<std::pair<int, int>> bases, windows;
+    for (int j = 0; j < kMetGroup && gi * kMetGroup + j < nspecs; ++j) {
+      const hx_metric &m = specs[gi * kMetGroup + j];
+      MetSpec &d = g.s[g.nspec++];
+      d.op = m.op; d.iy0 = m.year0 - scen_.start; d.iy1 = m.year1 - scen_.start; d.base = -1;
+      d.thr = m.threshold; d.mid = 0.5 * (double)(m.year0 + m.year1);
+      windows.emplace_back(d.iy0, d.iy1);
+      if (m.base_year0 <= m.base_year1) {
+        const std::pair<int, int> b(m.base_year0 - scen_.start, m.base_year1 - scen_.start);
+        size_t k = 0;
+        while (k < bases.size() && bases[k] != b) ++k;
+        if (k == bases.size()) { bases.push_back(b); g.b0[k] = b.first; g.b1[k] = b.second; }
+        d.base = (int)k;
+      }
+    }
+    g.nbase = (int)bases.size();
+    append_rows(bases, rows, &g.brow0, &g.nbrow);
+    append_rows(windows, rows, &g.wrow0, &g.nwrow);
+  }
+  const size_t gbytes = sizeof(MetGroup) * groups.size(), rbytes = sizeof(int) * rows.size();
+  if (gbytes + rbytes > metplan_cap_) {
+    if (d_metplan_) (void)hipFree(d_metplan_);
+    d_metplan_ = nullptr; metplan_cap_ = 0;
+    check(hipMalloc(&d_metplan_, gbytes + rbytes), "hipMalloc metric plan");
+    metplan_cap_ = gbytes + rbytes;
+  }
+  const size_t words = (size_t)ngroups * kMetGroup * (size_t)npad_;
+  if (words > met_cap_) {
+    if (d_met_) (void)hipFree(d_met_);
+    d_met_ = nullptr; met_cap_ = 0;
+    check(hipMalloc(&d_met_, sizeof(double) * words), "hipMalloc metric block");
+    met_cap_ = words;
+  }
+  // (stream order: an earlier call's kernel has finished with the plan before this copy lands)
+  check(hipMemcpyAsync(d_metplan_, groups.data(), gbytes, hipMemcpyHostToDevice, stream_), "metric groups");
+  check(hipMemcpyAsync(d_metplan_ + gbytes, rows.data(), rbytes, hipMemcpyHostToDevice, stream_), "metric rows");
+  check(hipStreamSynchronize(stream_), "metric plan");   // groups / rows are this call's locals
+  check(hx_launch_metric(d_out_[v], n_, npad_, d_metplan_, ngroups,
+                         reinterpret_cast<const int *>(d_metplan_ + gbytes), scen_.start, d_met_, stream_),
+        "metric kernel");
+  return d_met_;
+}
+
+void EnsembleCore::member_metrics(const std::string &capability, const hx_metric *specs, int nspecs,
+                                  double *out_host, const char *fn) {
+  const int v = metric_check(capability, specs, nspecs, fn);
+  if (!out_host) throw std::runtime_error(std::string(fn) + ": null argument");
+  sync();
+  const double *blk = metric_block(v, specs, nspecs);
+  // member order through the score scratch: [nspecs][n_]
+  const size_t bytes = sizeof(double) * (size_t)nspecs * (size_t)n_;
+  if (bytes > score_cap_) {
+    if (d_score_) (void)hipFree(d_score_);
+    d_score_ = nullptr; score_cap_ = 0;
+    check(hipMalloc(&d_score_, bytes), "hipMalloc score");
+    score_cap_ = bytes;
+  }
+  check(hx_launch_gather(blk, d_lane_of_member_, d_score_, n_, npad_, nspecs, stream_), "metric gather");
+  check(hipMemcpyAsync(out_host, d_score_, bytes, hipMemcpyDeviceToHost, stream_), "metric fetch");
+  check(hipStreamSynchronize(stream_), "metric sync");
+}
+
+void EnsembleCore::metric_quantiles(const std::string &capability, const hx_metric *specs, int nspecs,
+                                    const unsigned long long *q, const double *probs, int nprobs,
+                                    double *out_host, long long *n_part) {
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)specs; (void)nspecs; (void)q; (void)probs; (void)nprobs; (void)out_host; (void)n_part;
+  throw std::runtime_error(std::string("hx_metric_quantiles") + kEmulRefusal);
+#else
+  const int v = metric_check(capability, specs, nspecs, "hx_metric_quantiles");
+  if (nprobs < 1 || nprobs > 16) throw std::runtime_error("hx_metric_quantiles: nprobs must lie in 1..16");
+  if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
+  sync();
+  q_select(metric_block(v, specs, nspecs), 0, nspecs, q, probs, nprobs, out_host, n_part);
+#endif
+}
+
+void EnsembleCore::mq_begin(const std::string &capability, const hx_metric *specs, int nspecs,
+                            const unsigned long long *q, int nprobs, unsigned long long *st_host) {
+#ifdef HX_HOST_EMULATION
+  (void)st_host;
+  metric_quantiles(capability, specs, nspecs, q, nullptr, nprobs, nullptr, nullptr);
+#else
+  const int v = metric_check(capability, specs, nspecs, "hx_metric_quantiles");
+  if (nprobs < 1 || nprobs > 16) throw std::runtime_error("hx_metric_quantiles: nprobs must lie in 1..16");
+  if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
+  sync();
+  q_begin_block(metric_block(v, specs, nspecs), 0, nspecs, q, nprobs, st_host);
+#endif
+}
+
+// edges checked by the fleet (1..31, finite, strictly ascending)
+void EnsembleCore::bin_block(const double *src, int iy0, int nrows, const unsigned long long *q,
+                             const double *edges, int nedges, unsigned long long *sums_host) {
+#ifdef HX_HOST_EMULATION
+  (void)src; (void)iy0; (void)nrows; (void)q; (void)edges; (void)nedges; (void)sums_host;
+#else
+  q_upload(q, 1, 1);   // (the weights into lane order; the select's scratch at its smallest)
+  const size_t words = 32 + (size_t)nrows * (size_t)(nedges + 2);
+  if (words > bin_cap_) {
+    if (d_bin_) (void)hipFree(d_bin_);
+    d_bin_ = nullptr; bin_cap_ = 0;
+    check(hipMalloc(&d_bin_, 8 * words), "hipMalloc bin sums");
+    bin_cap_ = words;
+  }
+  double *d_edges = reinterpret_cast<double *>(d_bin_);
+  unsigned long long *d_sums = d_bin_ + 32;
+  check(hipMemcpyAsync(d_edges, edges, sizeof(double) * (size_t)nedges, hipMemcpyHostToDevice, stream_), "bin edges");
+  check(hipMemsetAsync(d_sums, 0, 8 * (words - 32), stream_), "bin sums");
+  check(hx_launch_bin(src, n_, npad_, iy0, nrows, q ? d_q_ : nullptr, d_edges, nedges, d_sums, stream_),
+        "bin kernel");
+  check(hipMemcpyAsync(sums_host, d_sums, 8 * (words - 32), hipMemcpyDeviceToHost, stream_), "bin fetch");
+  check(hipStreamSynchronize(stream_), "bin sync");
+#endif
+}
+
+void EnsembleCore::bin_sums(const std::string &capability, int year0, int year1, const unsigned long long *q,
+                            const double *edges, int nedges, unsigned long long *sums_host) {
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)year0; (void)year1; (void)q; (void)edges; (void)nedges; (void)sums_host;
+  throw std::runtime_error(std::string("hx_ensemble_probabilities") + kEmulRefusal);
+#else
+  const int v = q_check(capability, year0, year1, 1, "hx_ensemble_probabilities");
+  sync();
+  bin_block(d_out_[v], year0 - scen_.start, year1 - year0 + 1, q, edges, nedges, sums_host);
+#endif
+}
+
+void EnsembleCore::metric_bin_sums(const std::string &capability, const hx_metric *specs, int nspecs,
+                                   const unsigned long long *q, const double *edges, int nedges,
+                                   unsigned long long *sums_host) {
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)specs; (void)nspecs; (void)q; (void)edges; (void)nedges; (void)sums_host;
+  throw std::runtime_error(std::string("hx_metric_probabilities") + kEmulRefusal);
+#else
+  const int v = metric_check(capability, specs, nspecs, "hx_metric_probabilities");
+  sync();
+  bin_block(metric_block(v, specs, nspecs), 0, nspecs, q, edges, nedges, sums_host);
 #endif
 }
 

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/hector_amd.h"   // hx_metric
 #include "hx_layout.h"
 #include "hx_scenario.hpp"
 
@@ -157,6 +158,24 @@ class EnsembleCore {
   void q_begin(const std::string &capability, int year0, int year1, const unsigned long long *q,
                int nprobs, unsigned long long *st_host);
   void q_pass(const int *lo, const unsigned long long *prefix, unsigned long long *hist_host);
+  // per-member metrics (hx_member_metrics): out_host[nspecs][n_] in member order.  fn: the ABI
+  // function on whose behalf the specifications are checked (it is named in every message)
+  void member_metrics(const std::string &capability, const hx_metric *specs, int nspecs,
+                      double *out_host, const char *fn = "hx_member_metrics");
+  // hx_metric_quantiles: the metric block [nspecs][npad] is computed in lane order on the device and
+  // handed to the same select as a block of year rows; mq_begin is q_begin for it (q_pass follows)
+  void metric_quantiles(const std::string &capability, const hx_metric *specs, int nspecs,
+                        const unsigned long long *q, const double *probs, int nprobs, double *out_host,
+                        long long *n_part);
+  void mq_begin(const std::string &capability, const hx_metric *specs, int nspecs,
+                const unsigned long long *q, int nprobs, unsigned long long *st_host);
+  // weighted bin sums (hx_ensemble_probabilities / hx_metric_probabilities): this core's integer
+  // sums_host[row][nedges + 2] = the nedges + 1 bins, then the members that took part
+  void bin_sums(const std::string &capability, int year0, int year1, const unsigned long long *q,
+                const double *edges, int nedges, unsigned long long *sums_host);
+  void metric_bin_sums(const std::string &capability, const hx_metric *specs, int nspecs,
+                       const unsigned long long *q, const double *edges, int nedges,
+                       unsigned long long *sums_host);
   int device() const { return device_; }
   void status(unsigned *out_host);
   void state_row(int row, double *out_host);
@@ -280,11 +299,28 @@ class EnsembleCore {
   unsigned long long *d_qstate_ = nullptr;    // per year {HxQYear, lo}, per (year, prob) {prefix, rem}, probs
   unsigned long long *d_qhist_ = nullptr;     // [ny][nprobs][256]
   size_t qstate_cap_ = 0, qhist_cap_ = 0;
-  int q_v_ = -1, q_iy0_ = 0, q_ny_ = 0, q_np_ = 0;   // what q_begin prepared for q_pass
+  const double *q_src_ = nullptr;             // the block q_begin / mq_begin prepared for q_pass: d_out_[v] or d_met_
+  int q_iy0_ = 0, q_ny_ = 0, q_np_ = 0;
   bool q_weighted_ = false;
   int post_flags_ = 0;                        // HECTOR_AMD_POST_AB (measurements): 1 no prefix skip, 2 with wave aggregation
-  int q_check(const std::string &capability, int year0, int year1, int nprobs);
+  int q_check(const std::string &capability, int year0, int year1, int nprobs,
+              const char *fn = "hx_ensemble_quantiles");
   void q_upload(const unsigned long long *q, int ny, int np);
+  // the select over the rows iy0 .. iy0 + ny - 1 of a [rows][npad_] block in lane order
+  void q_select(const double *src, int iy0, int ny, const unsigned long long *q, const double *probs,
+                int np, double *out_host, long long *n_part);
+  void q_begin_block(const double *src, int iy0, int ny, const unsigned long long *q, int np,
+                     unsigned long long *st_host);
+  void bin_block(const double *src, int iy0, int nrows, const unsigned long long *q, const double *edges,
+                 int nedges, unsigned long long *sums_host);
+  // scratch of the metric kernel: group records + row lists, and the block [nspecs][npad_] (lane order)
+  unsigned char *d_metplan_ = nullptr;
+  double *d_met_ = nullptr;
+  size_t metplan_cap_ = 0, met_cap_ = 0;
+  unsigned long long *d_bin_ = nullptr;       // [32 edges as doubles][rows][nedges + 2]
+  size_t bin_cap_ = 0;
+  int metric_check(const std::string &capability, const hx_metric *specs, int nspecs, const char *fn);
+  const double *metric_block(int v, const hx_metric *specs, int nspecs);   // -> d_met_, queued on stream_
   hipStream_t stream_ = nullptr;
   hipStream_t aux_stream_ = nullptr;          // the prewarm loop's (non-blocking)
   unsigned char *d_prewarm_ = nullptr;        // its stop flag (+ a sink)

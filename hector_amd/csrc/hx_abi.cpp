@@ -373,6 +373,31 @@ int hx_ensemble_quantiles(hx_core *core, const char *capability, int year0, int 
   if (!capability || !probs || !out) return fail("hx_ensemble_quantiles: null argument");
   HX_TRY(core->core->quantiles(capability, year0, year1, weights, probs, nprobs, out, n_part))
 }
+int hx_member_metrics(hx_core *core, const char *capability, const hx_metric *specs, int nspecs,
+                      double *out) {
+  if (!capability || !specs || !out) return fail("hx_member_metrics: null argument");
+  HX_TRY(core->core->member_metrics(capability, specs, nspecs, out))
+}
+int hx_metric_quantiles(hx_core *core, const char *capability, const hx_metric *specs, int nspecs,
+                        const double *weights, const double *probs, int nprobs, double *out,
+                        long long *n_part) {
+  if (!capability || !specs || !probs || !out) return fail("hx_metric_quantiles: null argument");
+  HX_TRY(core->core->metric_quantiles(capability, specs, nspecs, weights, probs, nprobs, out, n_part))
+}
+int hx_ensemble_probabilities(hx_core *core, const char *capability, int year0, int year1,
+                              const double *weights, const double *edges, int nedges, double *prob,
+                              unsigned long long *sums, long long *n_part) {
+  if (!capability || !prob) return fail("hx_ensemble_probabilities: null argument");
+  HX_TRY(core->core->probabilities(capability, year0, year1, nullptr, 0, weights, edges, nedges, prob,
+                                   sums, n_part))
+}
+int hx_metric_probabilities(hx_core *core, const char *capability, const hx_metric *specs,
+                            int nspecs, const double *weights, const double *edges, int nedges,
+                            double *prob, unsigned long long *sums, long long *n_part) {
+  if (!capability || !specs || !prob) return fail("hx_metric_probabilities: null argument");
+  HX_TRY(core->core->probabilities(capability, 0, 0, specs, nspecs, weights, edges, nedges, prob, sums,
+                                   n_part))
+}
 int hx_status(hx_core *core, unsigned *out) {
   if (!out) return fail("hx_status: null argument");
   HX_TRY(core->core->status(out))

@@ -1,13 +1,17 @@
 // hx_dev_post.h -- what a user does with a finished ensemble, on the device: a per-member misfit
-// of a recorded output against an observation series (hx_score_kernel) and exact per-year
-// weighted quantiles over the members (hx_q_* kernels).  The reference has no counterpart: its
+// of a recorded output against an observation series (hx_score_kernel), per-member metrics of a
+// window (hx_metric_kernel), exact weighted quantiles over the members (hx_q_* kernels) and
+// weighted bin sums against fixed edges (hx_bin_kernel).  The reference has no counterpart: its
 // hosts aggregate fetchvars() data frames in R.  Compiled for the GPU through hx_post.hip -- a
 // translation unit of its own, so the year-loop kernels' code generation does not see it -- and
-// for the host-emulation build through ensemble_core.cpp (score kernel only: the quantile kernels
-// are cooperative -- LDS atomics, cross-lane -- and one lane at a time cannot run them).
+// for the host-emulation build through ensemble_core.cpp (score and metric kernels only: the
+// quantile and bin kernels are cooperative -- LDS atomics, cross-lane -- and one lane at a time
+// cannot run them).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../include/hector_amd.h"   // hx_metric, HX_MET_*
 
 // ===========================================================================
 // Score: chi2[lane] = sum_i r_i^2, r_i = ((x(iy[i], lane) - base) - obs[i]) / sigma[i], evaluated
@@ -54,6 +58,216 @@ hipError_t hx_launch_score(const double *var, int n, int npad, const int *iy, co
                            hipStream_t st) {
   hipLaunchKernelGGL(hx_score_kernel, dim3((n + 255) / 256), dim3(256), 0, st, var, n, npad, iy, obs,
                      sigma, nobs, b0, b1, out);
+  return hipGetLastError();
+}
+
+// ===========================================================================
+// Metrics: one double per member from a window of a recorded output (hx_member_metrics in
+// hector_amd.h defines every operation and its order; contraction is off as in the score kernel).
+// One lane per member, nothing exchanged between lanes; blockIdx.y picks a GROUP of up to
+// HXM_GROUP specifications whose state lives in registers.  The host (EnsembleCore::metric_block)
+// hands every group two ascending row lists -- the union of its reference periods, the union of
+// its windows -- so that the specifications of a group read a row they share once, and the
+// reference means are complete before the windows are consumed.  The score kernel has one dependent
+// load of a lane in flight; here a lane takes HXM_BATCH rows into registers, all loads in flight,
+// and the next batch is issued before the current one is consumed in the defined order.  The group
+// record and the row lists are wave-uniform reads of constant memory (scalar loads).
+// ===========================================================================
+#define HXM_GROUP 4
+#define HXM_BATCH 16
+#define HXM_PAD 0x40000000   // a list is padded to a multiple of HXM_BATCH with (last row | HXM_PAD): loaded, never consumed
+struct HxMetSpec { int op, iy0, iy1, base; double thr, mid; };   // base: which of the group's reference periods, -1 none
+struct HxMetGroup {
+  int nspec, nbase, brow0, nbrow, wrow0, nwrow, pad0, pad1;   // rows[brow0 .. brow0 + nbrow), rows[wrow0 .. wrow0 + nwrow)
+  int b0[HXM_GROUP], b1[HXM_GROUP];
+  HxMetSpec s[HXM_GROUP];
+};
+
+// (the row numbers are read again from the list when the batch is consumed -- scalar loads that hit
+//  the scalar cache -- instead of being held in 2 x HXM_BATCH scalar registers across the loop)
+__device__ __forceinline__ void hxm_load(const double *col, int npad, const int *r, double (&x)[HXM_BATCH]) {
+#pragma unroll
+  for (int e = 0; e < HXM_BATCH; ++e)
+    x[e] = col[(size_t)(r[e] & (HXM_PAD - 1)) * (size_t)npad];
+}
+
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__device__ __forceinline__ void hxm_base_batch(const HxMetGroup &g, const int *__restrict__ iy,
+                                               const double (&x)[HXM_BATCH], double (&bs)[HXM_GROUP],
+                                               unsigned (&bbad)[HXM_GROUP]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+#pragma unroll
+  for (int k = 0; k < HXM_GROUP; ++k) {
+    if (k >= g.nbase) continue;
+    const int b0 = g.b0[k], b1 = g.b1[k];
+#pragma unroll
+    for (int e = 0; e < HXM_BATCH; ++e)
+      if (iy[e] >= b0 && iy[e] <= b1) {
+        bs[k] = bs[k] + x[e];
+        bbad[k] |= x[e] != x[e] ? 1u : 0u;
+      }
+  }
+}
+
+// one specification over one batch of rows, in row order.  sb = +0.0 without a reference period
+// (x - 0.0 is x, bit for bit).  Four code paths: MEAN; MIN / MAX and their years (MAX as the MIN of
+// the negated values: negation is exact and strict > becomes strict <); the two _GE operations
+// (count in acc, first year in aux); SLOPE.
+#define HXM_PATH_MEAN 0
+#define HXM_PATH_EXT 1
+#define HXM_PATH_GE 2
+#define HXM_PATH_SLOPE 3
+template <int PATH>
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__device__ __forceinline__ void hxm_spec_batch(int iy0, int iy1, bool negate, double thr, double mid,
+                                               const int *__restrict__ iy, const double (&x)[HXM_BATCH],
+                                               double sb, int year_start, double &acc, double &aux,
+                                               double &den, unsigned &bad) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+#pragma unroll
+  for (int e = 0; e < HXM_BATCH; ++e) {
+    if (iy[e] < iy0 || iy[e] > iy1) continue;   // wave-uniform
+    const double xv = x[e];
+    bad |= xv != xv ? 1u : 0u;   // (a lane flag in a vector register, not a mask in scalar ones)
+    const double a = xv - sb;
+    const double yd = (double)(year_start + iy[e]);
+    if (PATH == HXM_PATH_MEAN) {
+      acc = acc + a;
+    } else if (PATH == HXM_PATH_EXT) {
+      const double c = negate ? -a : a;
+      if (iy[e] == iy0 || c < acc) { acc = c; aux = yd; }
+    } else if (PATH == HXM_PATH_GE) {
+      const bool ge = a >= thr;
+      acc = acc + (ge ? 1.0 : 0.0);
+      if (ge && aux != aux) aux = yd;
+    } else {
+      const double t = yd - mid;
+      const double p = t * a;
+      acc = acc + p;
+      const double tt = t * t;
+      den = den + tt;
+    }
+  }
+}
+
+__device__ __forceinline__ int hxm_path(int op) {
+  return op == HX_MET_MEAN ? HXM_PATH_MEAN
+         : op == HX_MET_SLOPE ? HXM_PATH_SLOPE
+         : (op == HX_MET_FIRST_GE || op == HX_MET_COUNT_GE) ? HXM_PATH_GE : HXM_PATH_EXT;
+}
+
+// out[(group * HXM_GROUP + j)][npad] in lane order; lanes >= n are not written
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__global__ __launch_bounds__(256) void hx_metric_kernel(const double *__restrict__ var, int n, int npad,
+                                                        const HxMetGroup *__restrict__ groups,
+                                                        const int *__restrict__ rows, int year_start,
+                                                        double *__restrict__ out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= n) return;
+  const HxMetGroup &g = groups[blockIdx.y];
+  const double *col = var + lane;
+  const int nspec = g.nspec, nbase = g.nbase;
+  double xa[HXM_BATCH], xb[HXM_BATCH];
+  // the reference means of the group
+  double bs[HXM_GROUP];
+  unsigned bbad[HXM_GROUP];
+#pragma unroll
+  for (int k = 0; k < HXM_GROUP; ++k) { bs[k] = 0.0; bbad[k] = 0u; }
+  if (g.nbrow > 0) {
+    const int *r = rows + g.brow0;
+    const int nrow = g.nbrow;
+    hxm_load(col, npad, r, xa);
+    for (int i = 0; i < nrow; i += HXM_BATCH) {
+      const bool more = i + HXM_BATCH < nrow;
+      if (more) hxm_load(col, npad, r + i + HXM_BATCH, xb);   // in flight while this batch is consumed
+      hxm_base_batch(g, r + i, xa, bs, bbad);
+      if (more) {
+#pragma unroll
+        for (int e = 0; e < HXM_BATCH; ++e) xa[e] = xb[e];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < HXM_GROUP; ++k)
+    if (k < nbase) bs[k] = bs[k] / (double)(g.b1[k] - g.b0[k] + 1);
+  int op[HXM_GROUP], iy0[HXM_GROUP], iy1[HXM_GROUP];
+  double thr[HXM_GROUP], mid[HXM_GROUP];
+  double acc[HXM_GROUP], aux[HXM_GROUP], den[HXM_GROUP], sb[HXM_GROUP];
+  unsigned bad[HXM_GROUP];
+#pragma unroll
+  for (int j = 0; j < HXM_GROUP; ++j) {
+    acc[j] = 0.0; den[j] = 0.0; aux[j] = __builtin_nan(""); sb[j] = 0.0; bad[j] = 0u;
+    op[j] = g.s[j].op; iy0[j] = g.s[j].iy0; iy1[j] = g.s[j].iy1; thr[j] = g.s[j].thr; mid[j] = g.s[j].mid;
+    const int b = g.s[j].base;
+#pragma unroll
+    for (int k = 0; k < HXM_GROUP; ++k)
+      if (b == k) { sb[j] = bs[k]; bad[j] = bbad[k]; }
+  }
+  {
+    const int *r = rows + g.wrow0;
+    const int nrow = g.nwrow;
+    hxm_load(col, npad, r, xa);
+    for (int i = 0; i < nrow; i += HXM_BATCH) {
+      const bool more = i + HXM_BATCH < nrow;
+      if (more) hxm_load(col, npad, r + i + HXM_BATCH, xb);
+#pragma unroll
+      for (int j = 0; j < HXM_GROUP; ++j) {
+        if (j >= nspec) continue;
+        const bool neg = op[j] == HX_MET_MAX || op[j] == HX_MET_YEAR_OF_MAX;
+        switch (hxm_path(op[j])) {   // wave-uniform
+          case HXM_PATH_MEAN:
+            hxm_spec_batch<HXM_PATH_MEAN>(iy0[j], iy1[j], neg, thr[j], mid[j], r + i, xa, sb[j], year_start,
+                                          acc[j], aux[j], den[j], bad[j]); break;
+          case HXM_PATH_EXT:
+            hxm_spec_batch<HXM_PATH_EXT>(iy0[j], iy1[j], neg, thr[j], mid[j], r + i, xa, sb[j], year_start,
+                                         acc[j], aux[j], den[j], bad[j]); break;
+          case HXM_PATH_GE:
+            hxm_spec_batch<HXM_PATH_GE>(iy0[j], iy1[j], neg, thr[j], mid[j], r + i, xa, sb[j], year_start,
+                                        acc[j], aux[j], den[j], bad[j]); break;
+          default:
+            hxm_spec_batch<HXM_PATH_SLOPE>(iy0[j], iy1[j], neg, thr[j], mid[j], r + i, xa, sb[j], year_start,
+                                           acc[j], aux[j], den[j], bad[j]); break;
+        }
+      }
+      if (more) {
+#pragma unroll
+        for (int e = 0; e < HXM_BATCH; ++e) xa[e] = xb[e];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < HXM_GROUP; ++j) {
+    if (j >= nspec) continue;
+    const int o = op[j];
+    double v = acc[j];                                   // MIN, COUNT_GE
+    if (o == HX_MET_MAX) v = -acc[j];
+    if (o == HX_MET_YEAR_OF_MIN || o == HX_MET_YEAR_OF_MAX || o == HX_MET_FIRST_GE) v = aux[j];
+    if (o == HX_MET_MEAN || o == HX_MET_SLOPE) {
+      const double d = o == HX_MET_MEAN ? (double)(iy1[j] - iy0[j] + 1) : den[j];
+      v = acc[j] / d;
+    }
+    if (bad[j]) v = __builtin_nan("");
+    out[((size_t)blockIdx.y * HXM_GROUP + (size_t)j) * (size_t)npad + (size_t)lane] = v;
+  }
+}
+
+hipError_t hx_launch_metric(const double *var, int n, int npad, const void *groups, int ngroups,
+                            const int *rows, int year_start, double *out, hipStream_t st) {
+  hipLaunchKernelGGL(hx_metric_kernel, dim3((n + 255) / 256, ngroups), dim3(256), 0, st, var, n, npad,
+                     (const HxMetGroup *)groups, rows, year_start, out);
   return hipGetLastError();
 }
 
@@ -305,6 +519,79 @@ hipError_t hx_launch_q_hist(const double *var, int n, int npad, int iy0, int ny,
 hipError_t hx_launch_q_pick(int ny, int *lo, unsigned long long *prefix, unsigned long long *rem, int np,
                             unsigned long long *hist, hipStream_t stream) {
   hipLaunchKernelGGL(hx_q_pick_kernel, dim3(ny), dim3(64 * np), 0, stream, lo, prefix, rem, np, hist);
+  return hipGetLastError();
+}
+
+// ===========================================================================
+// Weighted bin sums of rows against fixed edges (hx_ensemble_probabilities, hx_metric_probabilities).
+// grid (row chunks, rows) like hx_q_hist_kernel; a lane takes its HXQ_PER values of the chunk into
+// registers first.  bin(x) = the number of edges <= x: a branch-free binary search over the edges in
+// LDS (32 slots, the unused ones NaN: `edge <= x` is false for them, also for x = +inf).  There are
+// at most 32 bins, so one histogram would put a wavefront's adds on a handful of addresses: the
+// workgroup keeps HXB_COPIES histograms, h[bin][copy] with copy = thread & 31 -- the copies of a bin
+// lie in different banks, an address is shared by eight threads -- adds with 64-bit ds_add, then
+// sums the copies (rotated: conflict-free) and flushes each bin once.  sums[row][K + 2]: the K + 1
+// bins, then the number of members that took part; zero on entry.
+// ===========================================================================
+#define HXB_COPIES 32
+template <bool WEIGHTED>
+__global__ __launch_bounds__(HXQ_BLOCK) void hx_bin_kernel(const double *var, int n, int npad, int iy0,
+                                                           const hxq_u64 *q, const double *edges, int K,
+                                                           hxq_u64 *sums) {
+  __shared__ hxq_u64 h[32 * HXB_COPIES];
+  __shared__ double ed[32];
+  __shared__ hxq_u64 hcnt;
+  const int tid = (int)threadIdx.x;
+  const double *row = var + (size_t)(iy0 + (int)blockIdx.y) * npad;
+  const int beg = (int)blockIdx.x * HXQ_CHUNK, end = min(beg + HXQ_CHUNK, n);
+  double x[HXQ_PER];
+  hxq_u64 w[WEIGHTED ? HXQ_PER : 1];
+#pragma unroll
+  for (int e = 0; e < HXQ_PER; ++e) {
+    const int i = beg + e * HXQ_BLOCK + tid;
+    x[e] = __builtin_nan("");
+    if (i < end) x[e] = row[i];
+    if (WEIGHTED) w[e] = i < end ? q[i] : 0ull;
+  }
+  if (tid < 32) ed[tid] = tid < K ? edges[tid] : __builtin_nan("");
+  for (int i = tid; i < 32 * HXB_COPIES; i += HXQ_BLOCK) h[i] = 0;
+  if (tid == 0) hcnt = 0;
+  __syncthreads();
+  const int copy = tid & (HXB_COPIES - 1);
+  hxq_u64 cnt = 0;
+#pragma unroll
+  for (int e = 0; e < HXQ_PER; ++e) {
+    const double v = x[e];
+    const hxq_u64 we = WEIGHTED ? w[e] : 1ull;
+    int pos = 0;   // -> the number of edges <= v, 0..31 (slot 31 is never read)
+#pragma unroll
+    for (int step = 16; step > 0; step >>= 1)
+      if (ed[pos + step - 1] <= v) pos += step;
+    if (v == v && we) {
+      atomicAdd(h + pos * HXB_COPIES + copy, we);
+      ++cnt;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+  if ((tid & 63) == 0 && cnt) atomicAdd(&hcnt, cnt);
+  __syncthreads();
+  hxq_u64 *g = sums + (size_t)blockIdx.y * (size_t)(K + 2);
+  if (tid <= K) {
+    hxq_u64 s = 0;
+    for (int c = 0; c < HXB_COPIES; ++c) s += h[tid * HXB_COPIES + ((c + tid) & (HXB_COPIES - 1))];
+    if (s) atomicAdd(g + tid, s);
+  }
+  if (tid == 0 && hcnt) atomicAdd(g + K + 1, hcnt);
+}
+
+hipError_t hx_launch_bin(const double *var, int n, int npad, int iy0, int nrows, const unsigned long long *q,
+                         const double *edges, int K, unsigned long long *sums, hipStream_t stream) {
+  const dim3 grid((n + HXQ_CHUNK - 1) / HXQ_CHUNK, nrows);
+  if (q)
+    hipLaunchKernelGGL(hx_bin_kernel<true>, grid, dim3(HXQ_BLOCK), 0, stream, var, n, npad, iy0, q, edges, K, sums);
+  else
+    hipLaunchKernelGGL(hx_bin_kernel<false>, grid, dim3(HXQ_BLOCK), 0, stream, var, n, npad, iy0, q, edges, K, sums);
   return hipGetLastError();
 }
 #endif  // !HX_HOST_EMULATION

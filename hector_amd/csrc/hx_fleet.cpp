@@ -350,51 +350,96 @@ int Fleet::member_score(const std::string &cap, const int *years, const double *
   return used;
 }
 
+void Fleet::quantise_weights(const double *weights, const char *fn, std::vector<unsigned long long> &q) const {
+  // integer weights: q = rint(w / wmax * 2^32), wmax over ALL shards
+  q.clear();
+  if (!weights) return;
+  const std::string f(fn);
+  double wmax = 0.0;
+  for (int m = 0; m < n_; ++m) {
+    const double w = weights[m];
+    if (!(w >= 0.0) || std::isinf(w))
+      throw std::runtime_error(f + ": a weight is negative, NaN or infinite");
+    wmax = std::max(wmax, w);
+  }
+  if (!(wmax > 0.0)) throw std::runtime_error(f + ": the weights are all zero");
+  q.resize((size_t)n_);
+  unsigned long long total = 0;
+  for (int m = 0; m < n_; ++m) {
+    q[(size_t)m] = (unsigned long long)std::rint(weights[m] / wmax * 4294967296.0);
+    total += q[(size_t)m];
+  }
+  if (total > (1ull << 52))
+    throw std::runtime_error(f + ": more than 2^20 weighted members");
+}
+
+void Fleet::refuse_processes(const char *fn, const char *what) const {
+  if (comm_ready_ && world_ > n_shards())
+    throw std::runtime_error(std::string(fn) + ": this core joined a communicator of several "
+                             "processes (hx_comm_init_rank with n_procs > 1); " + what +
+                             " over processes are not supported");
+}
+
+static void check_probs(const double *probs, int nprobs, const char *fn) {
+  const std::string f(fn);
+  if (nprobs < 1 || nprobs > 16 || !probs)
+    throw std::runtime_error(f + ": nprobs must lie in 1..16");
+  for (int j = 0; j < nprobs; ++j)
+    if (!(probs[j] >= 0.0 && probs[j] <= 1.0))
+      throw std::runtime_error(f + ": a probability outside [0, 1]");
+}
+
 void Fleet::quantiles(const std::string &cap, int year0, int year1, const double *weights,
                       const double *probs, int nprobs, double *out, long long *n_part) {
   check_poison();
-  if (nprobs < 1 || nprobs > 16 || !probs)
-    throw std::runtime_error("hx_ensemble_quantiles: nprobs must lie in 1..16");
-  for (int j = 0; j < nprobs; ++j)
-    if (!(probs[j] >= 0.0 && probs[j] <= 1.0))
-      throw std::runtime_error("hx_ensemble_quantiles: a probability outside [0, 1]");
-  if (comm_ready_ && world_ > n_shards())
-    throw std::runtime_error("hx_ensemble_quantiles: this core joined a communicator of several "
-                             "processes (hx_comm_init_rank with n_procs > 1); quantiles over "
-                             "processes are not supported");
-  // integer weights: q = rint(w / wmax * 2^32), wmax over ALL shards
+  check_probs(probs, nprobs, "hx_ensemble_quantiles");
+  refuse_processes("hx_ensemble_quantiles", "quantiles");
   std::vector<unsigned long long> q;
-  if (weights) {
-    double wmax = 0.0;
-    for (int m = 0; m < n_; ++m) {
-      const double w = weights[m];
-      if (!(w >= 0.0) || std::isinf(w))
-        throw std::runtime_error("hx_ensemble_quantiles: a weight is negative, NaN or infinite");
-      wmax = std::max(wmax, w);
-    }
-    if (!(wmax > 0.0)) throw std::runtime_error("hx_ensemble_quantiles: the weights are all zero");
-    q.resize((size_t)n_);
-    unsigned long long total = 0;
-    for (int m = 0; m < n_; ++m) {
-      q[(size_t)m] = (unsigned long long)std::rint(weights[m] / wmax * 4294967296.0);
-      total += q[(size_t)m];
-    }
-    if (total > (1ull << 52))
-      throw std::runtime_error("hx_ensemble_quantiles: more than 2^20 weighted members");
-  }
+  quantise_weights(weights, "hx_ensemble_quantiles", q);
   const unsigned long long *qp = weights ? q.data() : nullptr;
   if (shards_.size() == 1) {
     use(shards_[0]);
     shards_[0].core->quantiles(cap, year0, year1, qp, probs, nprobs, out, n_part);
     return;
   }
-  const int ny = year1 - year0 + 1, np = nprobs;
+  const int ny = year1 - year0 + 1;
   if (ny < 1) throw std::runtime_error("hx_ensemble_quantiles: year1 < year0");
+  select_rows(ny, qp, probs, nprobs, out, n_part,
+              [&](Shard &s, const unsigned long long *qs, unsigned long long *part) {
+                s.core->q_begin(cap, year0, year1, qs, nprobs, part);
+              });
+}
+
+void Fleet::metric_quantiles(const std::string &cap, const hx_metric *specs, int nspecs,
+                             const double *weights, const double *probs, int nprobs, double *out,
+                             long long *n_part) {
+  check_poison();
+  if (nspecs < 1 || nspecs > HX_MET_MAX_SPECS || !specs)
+    throw std::runtime_error("hx_metric_quantiles: nspecs must lie in 1..32");
+  check_probs(probs, nprobs, "hx_metric_quantiles");
+  refuse_processes("hx_metric_quantiles", "quantiles");
+  std::vector<unsigned long long> q;
+  quantise_weights(weights, "hx_metric_quantiles", q);
+  const unsigned long long *qp = weights ? q.data() : nullptr;
+  if (shards_.size() == 1) {
+    use(shards_[0]);
+    shards_[0].core->metric_quantiles(cap, specs, nspecs, qp, probs, nprobs, out, n_part);
+    return;
+  }
+  select_rows(nspecs, qp, probs, nprobs, out, n_part,
+              [&](Shard &s, const unsigned long long *qs, unsigned long long *part) {
+                s.core->mq_begin(cap, specs, nspecs, qs, nprobs, part);
+              });
+}
+
+void Fleet::select_rows(int ny, const unsigned long long *qp, const double *probs, int np, double *out,
+                        long long *n_part,
+                        const std::function<void(Shard &, const unsigned long long *, unsigned long long *)> &begin) {
   const size_t Y = (size_t)ny, YP = Y * (size_t)np;
   std::vector<unsigned long long> st(4 * Y, 0ull), part(4 * Y);
   for (Shard &s : shards_) {
     use(s);
-    s.core->q_begin(cap, year0, year1, qp ? qp + s.offset : nullptr, np, part.data());
+    begin(s, qp ? qp + s.offset : nullptr, part.data());
     for (size_t y = 0; y < Y; ++y) {
       if (!part[4 * y + 3]) continue;
       st[4 * y] = std::max(st[4 * y], part[4 * y]);
@@ -440,6 +485,68 @@ void Fleet::quantiles(const std::string &cap, int year0, int year1, const double
     if (n_part) n_part[y] = (long long)st[4 * y + 3];
     for (int j = 0; j < np; ++j)
       out[y * np + j] = st[4 * y + 3] ? hxq_key_to_double(prefix[y * np + j]) : std::nan("");
+  }
+}
+
+void Fleet::member_metrics(const std::string &cap, const hx_metric *specs, int nspecs, double *out) {
+  check_poison();
+  if (shards_.size() == 1) {
+    use(shards_[0]);
+    shards_[0].core->member_metrics(cap, specs, nspecs, out);
+    return;
+  }
+  if (nspecs < 1 || nspecs > HX_MET_MAX_SPECS || !specs)
+    throw std::runtime_error("hx_member_metrics: nspecs must lie in 1..32");
+  std::vector<double> part;
+  for (Shard &s : shards_) {   // a shard returns [nspecs][its members]; out is [nspecs][n_]
+    use(s);
+    part.resize((size_t)nspecs * (size_t)s.count);
+    s.core->member_metrics(cap, specs, nspecs, part.data());
+    for (int k = 0; k < nspecs; ++k)
+      std::copy(part.begin() + (size_t)k * s.count, part.begin() + (size_t)(k + 1) * s.count,
+                out + (size_t)k * n_ + s.offset);
+  }
+}
+
+void Fleet::probabilities(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
+                          const double *weights, const double *edges, int nedges, double *prob,
+                          unsigned long long *sums, long long *n_part) {
+  check_poison();
+  const char *fn = specs ? "hx_metric_probabilities" : "hx_ensemble_probabilities";
+  const std::string f(fn);
+  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
+    throw std::runtime_error(f + ": nspecs must lie in 1..32");
+  if (nedges < 1 || nedges > HX_BIN_MAX_EDGES || !edges)
+    throw std::runtime_error(f + ": nedges must lie in 1..31");
+  for (int k = 0; k < nedges; ++k) {
+    if (!std::isfinite(edges[k])) throw std::runtime_error(f + ": an edge is not finite");
+    if (k && !(edges[k] > edges[k - 1])) throw std::runtime_error(f + ": the edges are not strictly ascending");
+  }
+  refuse_processes(fn, "probabilities");
+  std::vector<unsigned long long> q;
+  quantise_weights(weights, fn, q);
+  const unsigned long long *qp = weights ? q.data() : nullptr;
+  const int nrows = specs ? nspecs : year1 - year0 + 1;
+  if (nrows < 1) throw std::runtime_error(f + ": year1 < year0");
+  const size_t stride = (size_t)nedges + 2, R = (size_t)nrows;
+  std::vector<unsigned long long> tot(R * stride, 0ull), part(R * stride);
+  for (Shard &s : shards_) {
+    use(s);
+    const unsigned long long *qs = qp ? qp + s.offset : nullptr;
+    if (specs) s.core->metric_bin_sums(cap, specs, nspecs, qs, edges, nedges, part.data());
+    else s.core->bin_sums(cap, year0, year1, qs, edges, nedges, part.data());
+    for (size_t i = 0; i < tot.size(); ++i) tot[i] += part[i];
+  }
+  const size_t B = (size_t)nedges + 1;
+  for (size_t r = 0; r < R; ++r) {
+    const unsigned long long *t = &tot[r * stride];
+    unsigned long long W = 0;
+    for (size_t b = 0; b < B; ++b) W += t[b];
+    if (n_part) n_part[r] = (long long)t[B];
+    for (size_t b = 0; b < B; ++b) {
+      if (sums) sums[r * B + b] = t[b];
+      prob[r * B + b] = t[B] ? (double)t[b] / (double)W : std::nan("");
+    }
   }
 }
 

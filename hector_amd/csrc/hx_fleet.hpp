@@ -17,6 +17,7 @@
 // (dlopen of librccl.so.1: the copy already in the process if there is one, e.g. PyTorch's), so
 // single-GPU hosts never touch it.
 #pragma once
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -94,6 +95,17 @@ class Fleet {
   // and searched here, pass by pass (exact: the same bits as one core)
   void quantiles(const std::string &capability, int year0, int year1, const double *weights,
                  const double *probs, int nprobs, double *out_host, long long *n_part);
+  // hx_member_metrics: routed per shard like member_score
+  void member_metrics(const std::string &capability, const hx_metric *specs, int nspecs, double *out_host);
+  // hx_metric_quantiles: quantiles() over the metric block every shard computes on its GPU
+  void metric_quantiles(const std::string &capability, const hx_metric *specs, int nspecs,
+                        const double *weights, const double *probs, int nprobs, double *out_host,
+                        long long *n_part);
+  // hx_ensemble_probabilities (specs == nullptr: the rows year0..year1) and hx_metric_probabilities
+  // (the rows are the nspecs metrics): the shards' integer bin sums added here
+  void probabilities(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                     const double *weights, const double *edges, int nedges, double *prob,
+                     unsigned long long *sums, long long *n_part);
   void state_row(int row, double *out_host);
   int spinup_steps(int member);
   void tracking_data(int member, int year0, int year1, double *values, double *fractions,
@@ -134,6 +146,14 @@ class Fleet {
   void ensure_comm();
   void ensure_stats_buffers(size_t block_doubles);
   void free_stats_buffers();
+  // integer weights of hx_ensemble_quantiles for fn (named in the messages): q empty = every member 1
+  void quantise_weights(const double *weights, const char *fn, std::vector<unsigned long long> &q) const;
+  void refuse_processes(const char *fn, const char *what) const;
+  // the select over ny rows, one shard on its GPU or the shards' histograms added per pass; begin /
+  // one: what to call on a shard
+  void select_rows(int ny, const unsigned long long *qp, const double *probs, int np, double *out,
+                   long long *n_part,
+                   const std::function<void(Shard &, const unsigned long long *, unsigned long long *)> &begin);
   std::vector<Shard> shards_;
   int n_ = 0;
   bool duplicates_ = false;  // a device appears twice: rehearsal on a smaller box, copies instead of RCCL

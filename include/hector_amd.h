@@ -303,6 +303,90 @@ int hx_ensemble_quantiles(hx_core *core, const char *capability, int year0, int 
                           const double *weights, const double *probs, int nprobs,
                           double *out, long long *n_part);
 
+/* ---- A number per member, its weighted distribution, and outcome classes ----------------------
+ * The metric_calc / prob_calc step of a perturbed-parameter workflow, on the device; no counterpart
+ * in the reference (its hosts do this in R on fetchvars() data frames).
+ *
+ * A metric specification reduces the window year0..year1 of ONE recorded output to one double per
+ * member.  base_year0 <= base_year1: the member's own mean over that reference period is subtracted
+ * first; base_year0 > base_year1: nothing is subtracted.  threshold: the two _GE operations only. */
+typedef struct {
+  int op, year0, year1, base_year0, base_year1, reserved;
+  double threshold;
+} hx_metric;
+#define HX_MET_MEAN 0        /* mean of a over the window */
+#define HX_MET_MIN 1         /* smallest a */
+#define HX_MET_MAX 2         /* largest a */
+#define HX_MET_YEAR_OF_MIN 3 /* the first year that holds the smallest a */
+#define HX_MET_YEAR_OF_MAX 4 /* the first year that holds the largest a */
+#define HX_MET_FIRST_GE 5    /* the first year with a >= threshold; NaN if there is none */
+#define HX_MET_COUNT_GE 6    /* the number of years with a >= threshold */
+#define HX_MET_SLOPE 7       /* ordinary least-squares trend of a, per year */
+#define HX_MET_NOPS 8
+#define HX_MET_MAX_SPECS 32
+#define HX_BIN_MAX_EDGES 31
+
+/* out[s * n_members + member] = metric s of every member, in the caller's member order;
+ * 1 <= nspecs <= 32, all on the one recorded output `capability`.
+ * Evaluated per member in exactly this order, in IEEE double, without fused multiply-add, so that
+ * numpy reproduces it bit for bit under any lane order, kernel flavour or shard layout:
+ *   base:  s = 0.0; for y = base_year0..base_year1: s = s + x_y;  base = s / count
+ *   a_y = x_y - base (with a reference period), a_y = x_y (without); y ascends from year0 to year1
+ *   MEAN:  s = 0.0; s = s + a_y;  result s / count
+ *   MIN / MAX:  m = a_year0; a later a_y replaces m on strict < / > (the first occurrence is kept)
+ *   YEAR_OF_MIN / YEAR_OF_MAX:  the year of that first occurrence, as a double
+ *   FIRST_GE:  the first year with a_y >= threshold, as a double; NaN if there is none
+ *   COUNT_GE:  the number of years with a_y >= threshold, as a double
+ *   SLOPE:  t_y = (double) y - 0.5 * (double) (year0 + year1)  (exact);
+ *           num = 0.0; num = num + (t_y * a_y)  -- the product rounded before the sum;
+ *           den = 0.0; den = den + (t_y * t_y);  result num / den  (a one-year window: NaN)
+ *   NaN rule: if any x_y of the window or of the reference period is NaN, the result is NaN.
+ * Cost: one kernel, one lane per member; specifications are handled four at a time, and the four
+ * of a group read every row of the union of their reference periods once and every row of the
+ * union of their windows once (sixteen rows of a lane in flight at a time); nspecs x n_members
+ * doubles back to the host; returns when they are there.  A core of several shards routes the call
+ * to every shard.  The core is not prepared, spun up or dirtied.
+ * Errors (every message names the function): an unrecorded capability ("not enabled"), nspecs
+ * outside 1..32, an unknown op, year1 < year0, a window or reference period outside
+ * startDate..current date, a NaN threshold for FIRST_GE / COUNT_GE, a core that has not run. */
+int hx_member_metrics(hx_core *core, const char *capability, const hx_metric *specs, int nspecs,
+                      double *out);
+
+/* The weighted quantiles of every metric over the ensemble: out[s * nprobs + j], n_part[s] (may be
+ * NULL) = members that took part.  Definition, weights, limits and errors of hx_ensemble_quantiles,
+ * with the members' metric values (as hx_member_metrics defines them) in place of a year's row; a
+ * member whose metric is NaN does not take part.  The metric block is computed on the device and
+ * selected there: it never reaches the host.  A core of several shards adds the shards' integer
+ * histograms on the host; a communicator of several processes is refused.  Not available in the
+ * host-emulation build of the test suite. */
+int hx_metric_quantiles(hx_core *core, const char *capability, const hx_metric *specs, int nspecs,
+                        const double *weights, const double *probs, int nprobs, double *out,
+                        long long *n_part);
+
+/* Weighted probabilities of outcome classes, per recorded year.  edges[nedges]: finite, strictly
+ * ascending, 1 <= nedges <= 31.  The bin of x is the number of edges <= x (numpy's
+ * searchsorted(edges, x, side="right")): bin 0 is x < edges[0], bin nedges is x >= edges[nedges-1];
+ * a value equal to an edge lies in the upper bin.  A member takes part exactly as in
+ * hx_ensemble_quantiles (q_m > 0 with the same integer weights q, value not NaN).
+ *   sums[(year - year0) * (nedges + 1) + b] = Q_b, the integer sum of q over the members in bin b
+ *   prob[same index] = (double) Q_b / (double) W,  W = sum_b Q_b
+ *   n_part[year - year0] = members that took part;  nobody: prob NaN, sums 0, n_part 0.
+ * sums and n_part may be NULL.  Every sum is an exact integer: the result does not depend on lane
+ * order or shard split.  Cost: ONE read of every row (a select needs up to nine); a core of several
+ * shards adds the shards' sums on the host; a communicator of several processes is refused.  The
+ * core is not prepared, spun up or dirtied.  Errors: those of hx_ensemble_quantiles for capability,
+ * dates and weights; nedges outside 1..31; edges not finite or not strictly ascending.  Not
+ * available in the host-emulation build of the test suite. */
+int hx_ensemble_probabilities(hx_core *core, const char *capability, int year0, int year1,
+                              const double *weights, const double *edges, int nedges, double *prob,
+                              unsigned long long *sums, long long *n_part);
+
+/* The same over metrics: row s is metric s of every member (computed and binned on the device);
+ * prob[s * (nedges + 1) + b], sums likewise, n_part[s]. */
+int hx_metric_probabilities(hx_core *core, const char *capability, const hx_metric *specs,
+                            int nspecs, const double *weights, const double *edges, int nedges,
+                            double *prob, unsigned long long *sums, long long *n_part);
+
 /* per-member model-error bitmask (HX_ERR_* below), host array of n_members */
 int hx_status(hx_core *core, unsigned *out);
 int hx_spinup_steps(hx_core *core, int member, int *steps);
