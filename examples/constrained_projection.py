@@ -4,7 +4,8 @@ observed record, weight the members by their likelihood and report the weighted 
 band -- without a trajectory leaving the GPU (Core.score, Core.quantiles) -- and then what a user
 reports: the constrained 2081-2100 warming relative to 1850-1900, the distribution of the
 peak-warming year and the probability of the warming classes in 2100 (Core.metric_quantiles,
-Core.metric_probabilities).  The "observations" here are pseudo-observations: one held-out member
+Core.metric_probabilities), a constrained sea-level band, the crossing year of a 20-year mean and
+an emissions what-if on held series (Core.hold, Core.derive).  The "observations" here are pseudo-observations: one held-out member
 plus seeded noise.
 Needs an MI355X:  python examples/constrained_projection.py [n_members]"""
 import os
@@ -65,6 +66,29 @@ def main(n=20000, truth=0, **core_kwargs):
     classes = core.metric_probabilities(GLOBAL_TAS(), [Metric("mean", 2100, baseline=base)], (1.5, 2.0, 3.0),
                                         weights=weights)[0]
     print("constrained 2100 warming: P(< 1.5 K) %.3f  P(1.5-2 K) %.3f  P(2-3 K) %.3f  P(>= 3 K) %.3f" % tuple(classes))
+
+    # a diagnostic the core derives on the device takes the same verbs: the constrained sea-level band
+    slr = core.quantiles("slr", PROBS, (2100, 2100), weights=weights)[0]
+    print("constrained 2100 sea-level rise: %.3f (%.3f-%.3f) m" % (slr[1], slr[0], slr[2]))
+    # the year a centred 20-year mean of the warming crosses 1.5 K: two series, composed by name
+    core.derive("warming", "anomaly", GLOBAL_TAS(), years=base)
+    core.derive("warming20", "runmean", "warming", width=20, align="centred")
+    cross, = core.metric_quantiles("warming20", [Metric("first_ge", (1900, 2090), threshold=1.5)], PROBS,
+                                   weights=weights)
+    print("constrained crossing year of 1.5 K (20-year mean): %.0f (%.0f-%.0f)" % (cross[1], cross[0], cross[2]))
+
+    # an emissions what-if: hold this run's warming, cut the fossil emissions from 2030 on, run again
+    # and summarise the per-member avoided warming -- both trajectories stay on the device
+    core.hold("reference_tas", GLOBAL_TAS())
+    cut = np.arange(2030, 2101)
+    core.setvar_dated("ffi_emissions", cut, np.full(cut.size, 2.0), "Pg C/yr")
+    hector_amd.reset(core)
+    hector_amd.run(core, 2100)
+    core.derive("avoided", "sub", "reference_tas", GLOBAL_TAS())
+    avoided = core.quantiles("avoided", PROBS, (2100, 2100), weights=weights)[0]
+    classes = core.probabilities("avoided", (0.5, 1.0), (2100, 2100), weights=weights)[0]
+    print("constrained avoided warming in 2100: %.2f (%.2f-%.2f) K   P(< 0.5 K) %.3f  P(0.5-1 K) %.3f  P(>= 1 K) %.3f"
+          % (avoided[1], avoided[0], avoided[2], classes[0], classes[1], classes[2]))
     hector_amd.shutdown(core)
     return band, weights
 

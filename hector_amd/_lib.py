@@ -179,6 +179,10 @@ def _declare(lib):
                                       c.POINTER(c.c_ulonglong), c.POINTER(c.c_longlong)],
         "hx_metric_probabilities": [P, c.c_char_p, c.c_void_p, c.c_int, dp, dp, c.c_int, dp,
                                     c.POINTER(c.c_ulonglong), c.POINTER(c.c_longlong)],
+        "hx_series_define": [P, c.c_char_p, c.c_char_p, c.c_void_p],
+        "hx_series_drop": [P, c.c_char_p],
+        "hx_series_list": [P, c.POINTER(c.POINTER(c.c_char_p)), c.POINTER(c.POINTER(c.c_int)),
+                           c.POINTER(c.c_int)],
         "hx_status": [P, c.POINTER(c.c_uint)],
         "hx_spinup_steps": [P, c.c_int, c.POINTER(c.c_int)],
         "hx_state_row": [P, c.c_int, dp],
@@ -212,4 +216,5 @@ ABI_SYMBOLS = ["hx_backend", "hx_build_info", "hx_last_error", "hx_newcore", "hx
                "hx_comm_info", "hx_ensemble_stats", "hx_set_lane_calibration", "hx_lanes_calibrated", "hx_lane_order_source", "hx_set_cost_model",
                "hx_cost_models_export", "hx_cost_models_load", "hx_set_prewarm", "hx_last_run_prewarmed",
                "hx_member_score", "hx_ensemble_quantiles", "hx_member_metrics", "hx_metric_quantiles",
-               "hx_ensemble_probabilities", "hx_metric_probabilities"]
+               "hx_ensemble_probabilities", "hx_metric_probabilities",
+               "hx_series_define", "hx_series_drop", "hx_series_list"]

@@ -19,6 +19,18 @@ METRIC_OPS = {"mean": 0, "min": 1, "max": 2, "year_of_min": 3, "year_of_max": 4,
               "count_ge": 6, "slope": 7}    # HX_MET_* of include/hector_amd.h
 
 
+SERIES_OPS = {"copy": 0, "add": 1, "sub": 2, "mul": 3, "div": 4, "anomaly": 5, "cumsum": 6,
+              "runmean": 7, "delta": 8}     # HX_SER_* of include/hector_amd.h
+
+
+class _HxSeriesOp(ctypes.Structure):   # hx_series_op
+    _fields_ = [("op", ctypes.c_int), ("year0", ctypes.c_int), ("year1", ctypes.c_int),
+                ("width", ctypes.c_int), ("align", ctypes.c_int), ("lag", ctypes.c_int),
+                ("b_kind", ctypes.c_int), ("b_first_year", ctypes.c_int), ("b_n", ctypes.c_int),
+                ("reserved", ctypes.c_int), ("b_scalar", ctypes.c_double), ("b", ctypes.c_char_p),
+                ("b_values", ctypes.POINTER(ctypes.c_double))]
+
+
 class _HxMetric(ctypes.Structure):   # hx_metric
     _fields_ = [("op", ctypes.c_int), ("year0", ctypes.c_int), ("year1", ctypes.c_int),
                 ("base_year0", ctypes.c_int), ("base_year1", ctypes.c_int), ("reserved", ctypes.c_int),
@@ -491,6 +503,62 @@ class Core:
             "metric_probabilities",
             lambda *a: self._lib.hx_metric_probabilities(self._h, var.encode(), ctypes.byref(arr), ns, *a),
             ns, edges, weights, counts, sums)
+
+    def hold(self, name, var):
+        """Keep the trajectory of every member of `var` -- a recorded output, a derived diagnostic
+        or a series -- as the series `name` (hx_series_define, COPY): a snapshot on the device that
+        later reset / run / setvar do not touch, and that every summary verb and fetchvars take
+        like a variable."""
+        return self.derive(name, "copy", var)
+
+    def derive(self, name, op, a, b=None, *, years=None, width=None, align="trailing", lag=None,
+               first_year=None):
+        """Define the series `name` from the per-member variable `a` on the device, one operation
+        per call (hx_series_define in include/hector_amd.h fixes every order: numpy reproduces the
+        result bit for bit).  op: "copy"; "add" / "sub" / "mul" / "div" with b = a variable name, a
+        number, or a per-year vector that starts at first_year (NaN outside its span); "anomaly"
+        with years = (year0, year1), the member's own reference period; "cumsum" with years = the
+        first year; "runmean" with width and align = "trailing" or "centred"; "delta" with lag.
+        Defining an existing series replaces it; the operands may name it."""
+        if op not in SERIES_OPS:
+            raise HectorAmdError("hx_series_define: unknown op %r (one of %s)" % (op, ", ".join(SERIES_OPS)))
+        o = _HxSeriesOp()
+        o.op = SERIES_OPS[op]
+        keep = None
+        if years is not None:
+            y = np.atleast_1d(np.asarray(years)).astype(np.int64)
+            o.year0, o.year1 = int(y.min()), int(y.max())
+        if width is not None:
+            o.width = int(width)
+        if align not in ("trailing", "centred", "centered"):
+            raise HectorAmdError("hx_series_define: align must be 'trailing' or 'centred'")
+        o.align = 0 if align == "trailing" else 1
+        if lag is not None:
+            o.lag = int(lag)
+        if isinstance(b, str):
+            o.b_kind, o.b = 1, b.encode()
+        elif b is not None and np.ndim(b) == 0:
+            o.b_kind, o.b_scalar = 2, float(b)
+        elif b is not None:
+            if first_year is None:
+                raise HectorAmdError("hx_series_define: a per-year vector b needs first_year")
+            keep = np.ascontiguousarray(np.asarray(b, dtype=np.float64).ravel())
+            o.b_kind, o.b_first_year, o.b_n = 3, int(first_year), int(keep.size)
+            o.b_values = keep.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        self._ck(self._lib.hx_series_define(self._h, name.encode(), a.encode(), ctypes.byref(o)))
+        return self
+
+    def drop_series(self, name):
+        self._ck(self._lib.hx_series_drop(self._h, name.encode()))
+        return self
+
+    def series(self):
+        """-> {name: the last year that holds values} of the core's series, in definition order."""
+        names = ctypes.POINTER(ctypes.c_char_p)()
+        years = ctypes.POINTER(ctypes.c_int)()
+        n = ctypes.c_int()
+        self._ck(self._lib.hx_series_list(self._h, ctypes.byref(names), ctypes.byref(years), ctypes.byref(n)))
+        return {names[i].decode(): int(years[i]) for i in range(n.value)}
 
     def status(self):
         out = np.zeros(self.n_members, dtype=np.uint32)

@@ -48,7 +48,7 @@ hipError_t hx_launch_derive(const double *params, double *derived, const double 
 hipError_t hx_launch_doeclim_kernel(const double *diff_row, double *ker, int ns, int count,
                                     int stride, hipStream_t st);
 // the post-processing kernels (hx_dev_post.h): compiled into hx_post.hip's object for the GPU; the
-// host-emulation build takes the score kernel and its launcher in here
+// host-emulation build takes the lane-local ones (score, metrics, series) and their launchers in here
 #ifdef HX_HOST_EMULATION
 #include "hx_dev_post.h"
 #else
@@ -56,6 +56,16 @@ hipError_t hx_launch_score(const double *var, int n, int npad, const int *iy, co
                            const double *sigma, int nobs, int b0, int b1, double *out, hipStream_t st);
 hipError_t hx_launch_metric(const double *var, int n, int npad, const void *groups, int ngroups,
                             const int *rows, int year_start, double *out, hipStream_t st);
+hipError_t hx_launch_series_ew(int op, const double *a, const double *b, const double *bvec, const double *base,
+                               int npad, int ns, int y_lo, int y_hi, double c0, double c1, double *z,
+                               hipStream_t st);
+hipError_t hx_launch_series_base(const double *a, int npad, int r0, int r1, double *base, hipStream_t st);
+hipError_t hx_launch_series_cumsum(const double *a, int npad, int ns, int y0, int y_hi, double *z,
+                                   hipStream_t st);
+hipError_t hx_launch_series_runmean(const double *a, int npad, int ns, int w, int back, int y_hi, double *z,
+                                    hipStream_t st);
+hipError_t hx_launch_series_permute(const double *src, const int *src_lane, int npad, int ns, double *dst,
+                                    hipStream_t st);
 hipError_t hx_launch_bin(const double *var, int n, int npad, int iy0, int nrows, const unsigned long long *q,
                          const double *edges, int K, unsigned long long *sums, hipStream_t stream);
 hipError_t hx_launch_q_minmax(const double *var, int n, int npad, int iy0, int ny,
@@ -67,6 +77,11 @@ hipError_t hx_launch_q_hist(const double *var, int n, int npad, int iy0, int ny,
                             int np, int aggregate, unsigned long long *hist, hipStream_t stream);
 hipError_t hx_launch_q_pick(int ny, int *lo, unsigned long long *prefix, unsigned long long *rem, int np,
                             unsigned long long *hist, hipStream_t stream);
+#endif
+
+#ifndef HX_HOST_EMULATION
+#define HXS_ANOM_APPLY 100   // hx_dev_post.h
+#define HXS_COMBINE 101
 #endif
 
 namespace hx {
@@ -341,6 +356,7 @@ EnsembleCore::~EnsembleCore() {
   if (aux_stream_) { (void)hipStreamSynchronize(aux_stream_); (void)hipStreamDestroy(aux_stream_); }
   if (d_prewarm_) (void)hipFree(d_prewarm_);
   free_device();
+  free_series();
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
   if (stream_) (void)hipStreamDestroy(stream_);
@@ -553,6 +569,7 @@ void EnsembleCore::free_device() {
   d_hist_ = nullptr; d_hist_status_ = nullptr;
   for (int k = 0; k < HXM_N; ++k) { fr(d_mseries_[k]); d_mseries_[k] = nullptr; if (!member_series_[k].empty()) mseries_dirty_ = true; }
   fr(d_diag_); fr(d_slr_); d_diag_ = d_slr_ = nullptr; diag_cap_ = 0; slr_valid_to_ = -1;
+  free_derived_cache();   // (the series stay: they are snapshots that outlive a new layout)
   d_derived_ = nullptr; d_dpart_ = nullptr; d_gather_ = nullptr; d_lane_of_member_ = nullptr;
   gather_cap_ = 0;
   d_params_ = d_state_ = d_shared_ = d_ker_ = nullptr; d_status_ = nullptr; d_spin_steps_ = nullptr;
@@ -2037,12 +2054,14 @@ void EnsembleCore::prepare() {
   }
   spin_valid_ = uniform;
   need_spinup_ = false;
+  ++out_epoch_;
   last_iy_ = 0;
   hist_valid_to_ = 0;
   dirty_from_iy_ = -1;
 }
 
 void EnsembleCore::reset(double date) {
+  ++out_epoch_;   // (the current date moves: the kept blocks of derived diagnostics cover another range)
   if (date < scen_.start) {  // core.cpp:511-549: rerun spinup
     need_spinup_ = true; spin_valid_ = false;
     last_iy_ = 0;
@@ -2209,6 +2228,7 @@ void EnsembleCore::run(double runtodate) {
   check(hipEventRecord(ev1_, stream_), "event");
   run_timed_ = true;
   slr_valid_to_ = -1;
+  ++out_epoch_;
   if (d_hist_) hist_valid_to_ = target;  // slabs last_iy_+1..target were just (re)written
   last_iy_ = target;
 }
@@ -2447,6 +2467,7 @@ void EnsembleCore::var_info(const std::string &capability_in, std::string *compo
     if (units) *units = u;
   };
   for (const VarInfo &v : kVarInfo) if (cap == v.variable) return set(v.component, v.units);
+  if (find_series(capability_in) >= 0) return set("series", "");   // a held or derived series: no units
   if (cap.compare(0, 3, "RF_") == 0 && cap.find("_constrain") == std::string::npos)
     return set("forcing", "W/m2");
   for (const ParamDef &d : kParams)
@@ -2532,8 +2553,9 @@ bool EnsembleCore::host_output(const std::string &capability) {
 }
 
 // Diagnostics derived on the device from recorded outputs; the result is a lane-ordered
-// [ny][npad] block in d_diag_.
-void EnsembleCore::compute_derived(const std::string &capability, int iy0, int ny) {
+// [ny][npad] block in dst (fetchvars: d_diag_; the verbs' resolver: a block of its own).  The slr
+// family is kept whole in d_slr_; dst == nullptr only brings that up to date.
+void EnsembleCore::compute_derived(const std::string &capability, int iy0, int ny, double *dst) {
   const DerivedDef *d = derived_of(capability);
   auto need = [&](const char *name) -> const double * {
     const int v = out_index(name);
@@ -2551,8 +2573,9 @@ void EnsembleCore::compute_derived(const std::string &capability, int iy0, int n
             "slr kernel");
       slr_valid_to_ = last_iy_;
     }
-    check(hipMemcpyAsync(d_diag_, d_slr_ + (size_t)(d->kind - DK_SLR) * ns * np + (size_t)iy0 * np,
-                         sizeof(double) * (size_t)ny * np, hipMemcpyDeviceToDevice, stream_), "slr rows");
+    if (dst && ny > 0)
+      check(hipMemcpyAsync(dst, d_slr_ + (size_t)(d->kind - DK_SLR) * ns * np + (size_t)iy0 * np,
+                           sizeof(double) * (size_t)ny * np, hipMemcpyDeviceToDevice, stream_), "slr rows");
     return;
   }
   HxDiagArgs a{};
@@ -2581,7 +2604,7 @@ void EnsembleCore::compute_derived(const std::string &capability, int iy0, int n
     case HXG_RF_O3: a.o3 = need("O3_concentration"); break;
     default: throw std::runtime_error("unknown diagnostic");
   }
-  check(hx_launch_diag(d->kind, a, d_diag_, stream_), "diag kernel");
+  check(hx_launch_diag(d->kind, a, dst, stream_), "diag kernel");
 }
 
 // A disabled component registers no capabilities: asking for its variables fails like
@@ -2651,10 +2674,15 @@ void EnsembleCore::fetchvars(const std::string &capability, int year0, int year1
   }
   const bool n2o_members = capability == "N2O_concentration" && d_mseries_[HXM_N2O];
   const DerivedDef *dd = derived_of(capability);
-  const int v = (dd || n2o_members) ? -1 : out_index(capability);
-  if (!dd && !n2o_members && !d_out_[v])
+  const int si = find_series(capability);   // a series: its kept block, valid to its own date
+  const int v = (dd || n2o_members || si >= 0) ? -1 : out_index(capability);
+  if (!dd && !n2o_members && si < 0 && !d_out_[v])
     throw std::runtime_error("variable " + capability + " was not enabled with set_outputs()");
-  if (year0 < scen_.start || year1 > last_date() || year1 < year0)
+  if (si >= 0 && (year0 < scen_.start || year1 > scen_.start + series_[(size_t)si].valid_iy || year1 < year0))
+    throw std::runtime_error("fetchvars: dates must lie between startDate and " +
+                             std::to_string(scen_.start + series_[(size_t)si].valid_iy) + ", the date series " +
+                             capability + " was defined at");
+  if (si < 0 && (year0 < scen_.start || year1 > last_date() || year1 < year0))
     throw std::runtime_error("fetchvars: dates must lie between startDate and the current date");
   sync();
   const int iy0 = year0 - scen_.start, ny = year1 - year0 + 1;
@@ -2674,8 +2702,11 @@ void EnsembleCore::fetchvars(const std::string &capability, int year0, int year1
       check(hipMalloc(&d_diag_, sizeof(double) * dneed), "hipMalloc diag");
       diag_cap_ = dneed;
     }
-    compute_derived(capability, iy0, ny);
+    compute_derived(capability, iy0, ny, d_diag_);
     src = d_diag_;
+  } else if (si >= 0) {
+    series_to_current_lanes(series_[(size_t)si]);
+    src = series_[(size_t)si].block + (size_t)iy0 * npad_;
   } else if (n2o_members) {
     src = d_mseries_[HXM_N2O] + (size_t)iy0 * npad_;
   } else {
@@ -2691,12 +2722,12 @@ void EnsembleCore::fetchvars(const std::string &capability, int year0, int year1
   check(hipStreamSynchronize(stream_), "fetch sync");
 }
 
-const double *EnsembleCore::device_var(const std::string &capability, int *npad) const {
-  const int v = out_index(capability);
-  if (!d_out_[v])
+const double *EnsembleCore::device_var(const std::string &capability, int *npad) {
+  const PostSource ps = post_source(capability, "hx_device_var");
+  if (ps.v >= 0 && !d_out_[ps.v])
     throw std::runtime_error("variable " + capability + " was not enabled with set_outputs()");
   if (npad) *npad = npad_;
-  return d_out_[v];
+  return ps.block;
 }
 
 void EnsembleCore::stats_device(const std::string &capability, int year0, int year1,
@@ -2707,12 +2738,12 @@ void EnsembleCore::stats_device(const std::string &capability, int year0, int ye
 
 void EnsembleCore::stats_async(const std::string &capability, int year0, int year1,
                                double *d_stats) {
-  const int v = out_index(capability);
-  if (!d_out_[v])
+  const PostSource ps = post_source(capability, "stats");
+  if (ps.v >= 0 && !d_out_[ps.v])
     throw std::runtime_error("variable " + capability + " was not enabled with set_outputs()");
-  if (year0 < scen_.start || year1 > last_date() || year1 < year0)
+  if (year0 < scen_.start || year1 > scen_.start + ps.last_iy || year1 < year0)
     throw std::runtime_error("stats: dates must lie between startDate and the current date");
-  check(hx_launch_stats(d_out_[v], n_, npad_, year0 - scen_.start, year1 - year0 + 1, d_stats,
+  check(hx_launch_stats(ps.block, n_, npad_, year0 - scen_.start, year1 - year0 + 1, d_stats,
                         stream_), "stats kernel");
 }
 
@@ -2752,10 +2783,10 @@ int EnsembleCore::member_score(const std::string &capability, const int *years, 
                                double *out_host) {
   if (n < 1 || !years || !obs || !out_host)
     throw std::runtime_error("hx_member_score: n < 1 or a null argument");
-  const int v = out_index(capability);
-  if (!d_out_[v])
+  const PostSource ps = post_source(capability, "hx_member_score");
+  if (ps.v >= 0 && !d_out_[ps.v])
     throw std::runtime_error("variable " + capability + " was not enabled with set_outputs()");
-  const int last = last_date();
+  const int last = scen_.start + ps.last_iy;   // (the source's own valid range: the current date for a recorded output)
   const bool has_base = base_year0 <= base_year1;
   std::vector<int> iy((size_t)n);
   int used = 0;
@@ -2783,7 +2814,7 @@ int EnsembleCore::member_score(const std::string &capability, const int *years, 
   if (sigma)
     check(hipMemcpyAsync(d_sig, sigma, sizeof(double) * nn, hipMemcpyHostToDevice, stream_), "score sigma");
   check(hipMemcpyAsync(d_iy, iy.data(), sizeof(int) * nn, hipMemcpyHostToDevice, stream_), "score years");
-  check(hx_launch_score(d_out_[v], n_, npad_, d_iy, d_obs, sigma ? d_sig : nullptr, n,
+  check(hx_launch_score(ps.block, n_, npad_, d_iy, d_obs, sigma ? d_sig : nullptr, n,
                         has_base ? base_year0 - scen_.start : 1, has_base ? base_year1 - scen_.start : 0,
                         d_lane, stream_), "score kernel");
   check(hx_launch_gather(d_lane, d_lane_of_member_, d_mem, n_, npad_, 1, stream_), "score gather");
@@ -2824,20 +2855,22 @@ double hxq_key_to_double(unsigned long long key) {
   return x;
 }
 
-int EnsembleCore::q_check(const std::string &capability, int year0, int year1, int nprobs, const char *fn) {
+const double *EnsembleCore::q_check(const std::string &capability, int year0, int year1, int nprobs,
+                                    const char *fn) {
   const std::string f(fn);
   if (nprobs < 1 || nprobs > 16)
     throw std::runtime_error(f + ": nprobs must lie in 1..16");
-  const int v = out_index(capability);
+  const PostSource ps = post_source(capability, fn);
+  const int v = ps.v;
   const bool is_q = f == "hx_ensemble_quantiles";   // (its messages stay as they were)
-  if (is_q ? !d_out_[v] : !out_enabled_[v])
+  if (v >= 0 && (is_q ? !d_out_[v] : !out_enabled_[v]))
     throw std::runtime_error((is_q ? std::string() : f + ": ") + "variable " + capability +
                              " was not enabled with set_outputs()");
-  if (year0 < scen_.start || year1 > last_date() || year1 < year0)
+  if (year0 < scen_.start || year1 > scen_.start + ps.last_iy || year1 < year0)
     throw std::runtime_error(f + ": dates must lie between startDate and the current date");
-  if (!d_lane_of_member_ || !d_out_[v]) throw std::runtime_error(f + ": run the core first");
+  if (!d_lane_of_member_ || !ps.block) throw std::runtime_error(f + ": run the core first");
   if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
-  return v;
+  return ps.block;
 }
 
 namespace {
@@ -2940,9 +2973,9 @@ void EnsembleCore::quantiles(const std::string &capability, int year0, int year1
   (void)capability; (void)year0; (void)year1; (void)q; (void)probs; (void)nprobs; (void)out_host; (void)n_part;
   throw std::runtime_error(std::string("hx_ensemble_quantiles") + kEmulRefusal);
 #else
-  const int v = q_check(capability, year0, year1, nprobs);
+  const double *src = q_check(capability, year0, year1, nprobs);
   sync();
-  q_select(d_out_[v], year0 - scen_.start, year1 - year0 + 1, q, probs, nprobs, out_host, n_part);
+  q_select(src, year0 - scen_.start, year1 - year0 + 1, q, probs, nprobs, out_host, n_part);
 #endif
 }
 
@@ -2952,9 +2985,9 @@ void EnsembleCore::q_begin(const std::string &capability, int year0, int year1,
   quantiles(capability, year0, year1, q, nullptr, nprobs, nullptr, nullptr);
   (void)st_host;
 #else
-  const int v = q_check(capability, year0, year1, nprobs);
+  const double *src = q_check(capability, year0, year1, nprobs);
   sync();
-  q_begin_block(d_out_[v], year0 - scen_.start, year1 - year0 + 1, q, nprobs, st_host);
+  q_begin_block(src, year0 - scen_.start, year1 - year0 + 1, q, nprobs, st_host);
 #endif
 }
 
@@ -2979,14 +3012,15 @@ void EnsembleCore::q_pass(const int *lo, const unsigned long long *prefix, unsig
 // ---- per-member metrics, their quantiles, and bin probabilities ----------------------------------
 
 int EnsembleCore::metric_check(const std::string &capability, const hx_metric *specs, int nspecs,
-                               const char *fn) {
+                               const char *fn, const double **src) {
   const std::string f(fn);
   if (nspecs < 1 || nspecs > HX_MET_MAX_SPECS || !specs)
     throw std::runtime_error(f + ": nspecs must lie in 1..32");
-  const int v = out_index(capability);
-  if (!out_enabled_[v])
+  const PostSource ps = post_source(capability, fn);
+  const int v = ps.v;
+  if (v >= 0 && !out_enabled_[v])
     throw std::runtime_error(f + ": variable " + capability + " was not enabled with set_outputs()");
-  const int last = last_date();
+  const int last = scen_.start + ps.last_iy;   // (the source's own valid range)
   for (int i = 0; i < nspecs; ++i) {
     const hx_metric &m = specs[i];
     const std::string which = " (specification " + std::to_string(i) + ")";
@@ -2999,7 +3033,8 @@ int EnsembleCore::metric_check(const std::string &capability, const hx_metric *s
     if ((m.op == HX_MET_FIRST_GE || m.op == HX_MET_COUNT_GE) && !(m.threshold == m.threshold))
       throw std::runtime_error(f + ": the threshold is NaN" + which);
   }
-  if (!d_lane_of_member_ || !d_out_[v]) throw std::runtime_error(f + ": run the core first");
+  if (!d_lane_of_member_ || !ps.block) throw std::runtime_error(f + ": run the core first");
+  *src = ps.block;
   return v;
 }
 
@@ -3027,7 +3062,7 @@ void append_rows(const std::vector<std::pair<int, int>> &ranges, std::vector<int
 
 // the specifications, four to a group in the caller's order, into the device's records and row
 // lists; the kernel is queued on stream_ and d_met_ [nspecs rounded up to groups][npad_] returned
-const double *EnsembleCore::metric_block(int v, const hx_metric *specs, int nspecs) {
+const double *EnsembleCore::metric_block(const double *src, const hx_metric *specs, int nspecs) {
   const int ngroups = (nspecs + kMetGroup - 1) / kMetGroup;
   std::vector<MetGroup> groups((size_t)ngroups);
   std::vector<int> rows;
@@ -3071,7 +3106,7 @@ const double *EnsembleCore::metric_block(int v, const hx_metric *specs, int nspe
   check(hipMemcpyAsync(d_metplan_, groups.data(), gbytes, hipMemcpyHostToDevice, stream_), "metric groups");
   check(hipMemcpyAsync(d_metplan_ + gbytes, rows.data(), rbytes, hipMemcpyHostToDevice, stream_), "metric rows");
   check(hipStreamSynchronize(stream_), "metric plan");   // groups / rows are this call's locals
-  check(hx_launch_metric(d_out_[v], n_, npad_, d_metplan_, ngroups,
+  check(hx_launch_metric(src, n_, npad_, d_metplan_, ngroups,
                          reinterpret_cast<const int *>(d_metplan_ + gbytes), scen_.start, d_met_, stream_),
         "metric kernel");
   return d_met_;
@@ -3079,10 +3114,11 @@ const double *EnsembleCore::metric_block(int v, const hx_metric *specs, int nspe
 
 void EnsembleCore::member_metrics(const std::string &capability, const hx_metric *specs, int nspecs,
                                   double *out_host, const char *fn) {
-  const int v = metric_check(capability, specs, nspecs, fn);
+  const double *src = nullptr;
+  metric_check(capability, specs, nspecs, fn, &src);
   if (!out_host) throw std::runtime_error(std::string(fn) + ": null argument");
   sync();
-  const double *blk = metric_block(v, specs, nspecs);
+  const double *blk = metric_block(src, specs, nspecs);
   // member order through the score scratch: [nspecs][n_]
   const size_t bytes = sizeof(double) * (size_t)nspecs * (size_t)n_;
   if (bytes > score_cap_) {
@@ -3103,11 +3139,12 @@ void EnsembleCore::metric_quantiles(const std::string &capability, const hx_metr
   (void)capability; (void)specs; (void)nspecs; (void)q; (void)probs; (void)nprobs; (void)out_host; (void)n_part;
   throw std::runtime_error(std::string("hx_metric_quantiles") + kEmulRefusal);
 #else
-  const int v = metric_check(capability, specs, nspecs, "hx_metric_quantiles");
+  const double *src = nullptr;
+  metric_check(capability, specs, nspecs, "hx_metric_quantiles", &src);
   if (nprobs < 1 || nprobs > 16) throw std::runtime_error("hx_metric_quantiles: nprobs must lie in 1..16");
   if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
   sync();
-  q_select(metric_block(v, specs, nspecs), 0, nspecs, q, probs, nprobs, out_host, n_part);
+  q_select(metric_block(src, specs, nspecs), 0, nspecs, q, probs, nprobs, out_host, n_part);
 #endif
 }
 
@@ -3117,11 +3154,12 @@ void EnsembleCore::mq_begin(const std::string &capability, const hx_metric *spec
   (void)st_host;
   metric_quantiles(capability, specs, nspecs, q, nullptr, nprobs, nullptr, nullptr);
 #else
-  const int v = metric_check(capability, specs, nspecs, "hx_metric_quantiles");
+  const double *src = nullptr;
+  metric_check(capability, specs, nspecs, "hx_metric_quantiles", &src);
   if (nprobs < 1 || nprobs > 16) throw std::runtime_error("hx_metric_quantiles: nprobs must lie in 1..16");
   if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
   sync();
-  q_begin_block(metric_block(v, specs, nspecs), 0, nspecs, q, nprobs, st_host);
+  q_begin_block(metric_block(src, specs, nspecs), 0, nspecs, q, nprobs, st_host);
 #endif
 }
 
@@ -3156,9 +3194,9 @@ void EnsembleCore::bin_sums(const std::string &capability, int year0, int year1,
   (void)capability; (void)year0; (void)year1; (void)q; (void)edges; (void)nedges; (void)sums_host;
   throw std::runtime_error(std::string("hx_ensemble_probabilities") + kEmulRefusal);
 #else
-  const int v = q_check(capability, year0, year1, 1, "hx_ensemble_probabilities");
+  const double *src = q_check(capability, year0, year1, 1, "hx_ensemble_probabilities");
   sync();
-  bin_block(d_out_[v], year0 - scen_.start, year1 - year0 + 1, q, edges, nedges, sums_host);
+  bin_block(src, year0 - scen_.start, year1 - year0 + 1, q, edges, nedges, sums_host);
 #endif
 }
 
@@ -3169,10 +3207,291 @@ void EnsembleCore::metric_bin_sums(const std::string &capability, const hx_metri
   (void)capability; (void)specs; (void)nspecs; (void)q; (void)edges; (void)nedges; (void)sums_host;
   throw std::runtime_error(std::string("hx_metric_probabilities") + kEmulRefusal);
 #else
-  const int v = metric_check(capability, specs, nspecs, "hx_metric_probabilities");
+  const double *src = nullptr;
+  metric_check(capability, specs, nspecs, "hx_metric_probabilities", &src);
   sync();
-  bin_block(metric_block(v, specs, nspecs), 0, nspecs, q, edges, nedges, sums_host);
+  bin_block(metric_block(src, specs, nspecs), 0, nspecs, q, edges, nedges, sums_host);
 #endif
+}
+
+// ---- the resolver of the verbs, and series (hx_series_define in hector_amd.h) ----------------------
+
+namespace {
+// whole-surface values: area-weighted low / high latitude (ocean_component.cpp:466-503)
+const char *const kCombos[][3] = {{"pH", "LL_pH", "HL_pH"}, {"PCO2", "LL_PCO2", "HL_PCO2"},
+                                  {"DIC", "LL_DIC", "HL_DIC"}, {"CO3", "LL_CO3", "HL_CO3"},
+                                  {"ML_ocean_c", "LL_ocean_c", "HL_ocean_c"}};
+const char *const *combo_of(const std::string &name) {
+  for (auto &c : kCombos) if (name == c[0]) return c;
+  return nullptr;
+}
+}  // namespace
+
+int EnsembleCore::find_series(const std::string &name) const {
+  for (size_t i = 0; i < series_.size(); ++i) if (series_[i].name == name) return (int)i;
+  return -1;
+}
+
+void EnsembleCore::free_series() {
+  for (Series &s : series_) if (s.block) (void)hipFree(s.block);
+  series_.clear();
+  if (d_ser_vec_) (void)hipFree(d_ser_vec_);
+  if (d_ser_perm_) (void)hipFree(d_ser_perm_);
+  d_ser_vec_ = nullptr; d_ser_perm_ = nullptr;
+}
+
+void EnsembleCore::free_derived_cache() {
+  for (DerivedBlock &b : derived_cache_) {
+    if (b.block) (void)hipFree(b.block);
+    b.block = nullptr; b.name.clear(); b.epoch = 0; b.used = 0;
+  }
+  if (d_ps_tmp_) (void)hipFree(d_ps_tmp_);
+  d_ps_tmp_ = nullptr;
+}
+
+// A series is stored in the lane order of its definition (or of its last use).  If the core has
+// reordered its lanes since -- assign_lanes() through a changed sorting switch, a newly varying
+// parameter or the measured-cost calibration -- the block is permuted on the device, once, before it
+// is read: new lane l holds member member_of_lane_[l], whose row sat in the old lane
+// lane_of_member[that member].
+void EnsembleCore::series_to_current_lanes(Series &s) {
+  if (s.lane_of_member == lane_of_member_) return;
+  const size_t np = (size_t)npad_, ns = (size_t)scen_.ns();
+  std::vector<int> src_lane(np);
+  for (size_t l = 0; l < np; ++l) src_lane[l] = s.lane_of_member[(size_t)member_of_lane_[l]];
+  if (!d_ser_perm_) check(hipMalloc(&d_ser_perm_, sizeof(int) * np), "hipMalloc series lane map");
+  double *dst = nullptr;
+  if (hipMalloc(&dst, sizeof(double) * ns * np) != hipSuccess || !dst) {
+    (void)hipGetLastError();
+    throw std::runtime_error("series " + s.name + ": no device memory to move it to the core's new lane "
+                             "order (" + std::to_string((sizeof(double) * ns * np) >> 20) + " MiB)");
+  }
+  try {
+    check(hipMemcpy(d_ser_perm_, src_lane.data(), sizeof(int) * np, hipMemcpyHostToDevice), "series lane map");
+    check(hx_launch_series_permute(s.block, d_ser_perm_, npad_, (int)ns, dst, stream_), "series permute kernel");
+    check(hipStreamSynchronize(stream_), "series permute");
+  } catch (...) { (void)hipFree(dst); throw; }
+  (void)hipFree(s.block);
+  s.block = dst;
+  s.lane_of_member = lane_of_member_;
+}
+
+// The kept block of a derived diagnostic (not the slr family: d_slr_ holds it whole) or of a
+// whole-surface combination, rows 0..last_iy_, computed on stream_.  Two blocks, the one used longest
+// ago is given up; a block stands while out_epoch_ does (no run, reset or new layout since).
+const double *EnsembleCore::derived_block(const std::string &capability) {
+  for (DerivedBlock &b : derived_cache_)
+    if (b.block && b.epoch == out_epoch_ && b.name == capability) { b.used = ++derived_clock_; return b.block; }
+  DerivedBlock *slot = nullptr;
+  for (DerivedBlock &b : derived_cache_) if (b.name == capability) slot = &b;
+  if (!slot) for (DerivedBlock &b : derived_cache_) if (!b.block && !slot) slot = &b;
+  if (!slot) slot = derived_cache_[0].used <= derived_cache_[1].used ? &derived_cache_[0] : &derived_cache_[1];
+  const size_t np = (size_t)npad_, ns = (size_t)scen_.ns();
+  slot->name.clear(); slot->epoch = 0;
+  if (!slot->block) check(hipMalloc(&slot->block, sizeof(double) * ns * np), "hipMalloc derived block");
+  const int ny = last_iy_ + 1;
+  if (const char *const *c = combo_of(capability)) {
+    // the order fetchvars() uses on the host: part_low * ll + part_high * hl; ML_ocean_c: ll + hl
+    const double *part[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; ++k) {
+      const std::string name = c[1 + k];
+      if (derived_of(name)) {
+        if (!d_ps_tmp_) check(hipMalloc(&d_ps_tmp_, sizeof(double) * 2 * ns * np), "hipMalloc combination parts");
+        compute_derived(name, 0, ny, d_ps_tmp_ + (size_t)k * ns * np);
+        part[k] = d_ps_tmp_ + (size_t)k * ns * np;
+      } else {
+        const int v = out_index(name);
+        if (!d_out_[v])
+          throw std::runtime_error("variable " + capability + " needs " + name + ": enable it (or " +
+                                   capability + ") with set_outputs()");
+        part[k] = d_out_[v];
+      }
+    }
+    const bool sum = capability == "ML_ocean_c";
+    const double part_high = 0.15, part_low = 1 - 0.15;
+    check(hx_launch_series_ew(sum ? HX_SER_ADD : HXS_COMBINE, part[0], part[1], nullptr, nullptr, npad_, (int)ns,
+                              0, last_iy_, part_low, part_high, slot->block, stream_), "combination kernel");
+  } else {
+    compute_derived(capability, 0, ny, slot->block);
+  }
+  slot->name = capability; slot->epoch = out_epoch_; slot->used = ++derived_clock_;
+  return slot->block;
+}
+
+EnsembleCore::PostSource EnsembleCore::post_source(const std::string &capability, const char *fn) {
+  const std::string f(fn);
+  const int si = find_series(capability);
+  if (si >= 0) {
+    Series &s = series_[(size_t)si];
+    series_to_current_lanes(s);
+    return {s.block, s.valid_iy, -1};
+  }
+  const DerivedDef *dd = derived_of(capability);
+  if (dd || combo_of(capability)) {
+    check_component_enabled(capability);
+    if (!d_lane_of_member_) throw std::runtime_error(f + ": run the core first");
+    if (dd && dd->kind >= DK_SLR) {
+      compute_derived(capability, 0, 0, nullptr);   // d_slr_ up to date
+      const size_t np = (size_t)npad_, ns = (size_t)scen_.ns();
+      return {d_slr_ + (size_t)(dd->kind - DK_SLR) * ns * np, last_iy_, -1};
+    }
+    return {derived_block(capability), last_iy_, -1};
+  }
+  int v = -1;
+  try {
+    v = out_index(capability);
+  } catch (const std::runtime_error &e) {
+    bool host = false;
+    try { host = host_output(capability); } catch (...) {}
+    if (host)
+      throw std::runtime_error(f + ": variable " + capability + " is the same for every member (fetchvars "
+                               "answers it on the host); the per-member verbs take recorded outputs, "
+                               "derived diagnostics and series");
+    // (the verbs whose messages carried no function name keep them as they were)
+    if (f == "hx_ensemble_quantiles" || f == "hx_member_score" || f == "stats" || f == "hx_device_var") throw;
+    throw std::runtime_error(f + ": " + e.what());
+  }
+  return {d_out_[v], last_iy_, v};
+}
+
+void EnsembleCore::series_list(std::vector<std::string> *names, std::vector<int> *valid_to) const {
+  if (names) names->clear();
+  if (valid_to) valid_to->clear();
+  for (const Series &s : series_) {
+    if (names) names->push_back(s.name);
+    if (valid_to) valid_to->push_back(scen_.start + s.valid_iy);
+  }
+}
+
+void EnsembleCore::series_drop(const std::string &name) {
+  const int si = find_series(name);
+  if (si < 0) throw std::runtime_error("hx_series_drop: no series named '" + name + "'");
+  sync();
+  (void)hipFree(series_[(size_t)si].block);
+  series_.erase(series_.begin() + si);
+}
+
+void EnsembleCore::series_define(const std::string &name, const std::string &a_name, const hx_series_op &op) {
+  const std::string f = "hx_series_define";
+  {  // [A-Za-z_][A-Za-z0-9_]{0,62}
+    bool ok = !name.empty() && name.size() <= 63;
+    for (size_t i = 0; ok && i < name.size(); ++i) {
+      const char c = name[i];
+      const bool alpha = (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || c == '_';
+      ok = alpha || (i > 0 && c >= '0' && c <= '9');
+    }
+    if (!ok) throw std::runtime_error(f + ": bad series name '" + name + "' (a letter or _, then up to 62 "
+                                      "letters, digits or _)");
+  }
+  const int existing = find_series(name);
+  if (existing < 0) {  // a name the core already answers
+    bool answered = derived_of(name) || combo_of(name) || name == "ocean_timesteps" || name == "N2O_concentration";
+    for (auto &o : kOutputs) if (name == o.name) answered = true;
+    if (!answered) { try { answered = host_output(name); } catch (...) {} }
+    if (answered)
+      throw std::runtime_error(f + ": '" + name + "' is a variable of the core; a series needs a name of its own");
+    if ((int)series_.size() >= HX_SER_MAX)
+      throw std::runtime_error(f + ": the core holds " + std::to_string(HX_SER_MAX) + " series already "
+                               "(hx_series_drop frees one)");
+  }
+  if (op.op < 0 || op.op >= HX_SER_NOPS) throw std::runtime_error(f + ": unknown op " + std::to_string(op.op));
+  const bool binary = op.op >= HX_SER_ADD && op.op <= HX_SER_DIV;
+  const int ns = scen_.ns();
+  if (binary) {
+    if (op.b_kind == HX_SER_B_VAR) { if (!op.b) throw std::runtime_error(f + ": operand b is null"); }
+    else if (op.b_kind == HX_SER_B_VECTOR) {
+      if (!op.b_values || op.b_n < 1) throw std::runtime_error(f + ": the vector operand b is empty");
+    } else if (op.b_kind != HX_SER_B_SCALAR)
+      throw std::runtime_error(f + ": this op needs an operand b (a variable, a scalar or a per-year vector)");
+  }
+  if (op.op == HX_SER_RUNMEAN) {
+    if (op.width < 1) throw std::runtime_error(f + ": width < 1");
+    if (op.width > ns) throw std::runtime_error(f + ": width exceeds the " + std::to_string(ns) + " years of the core");
+    if (op.align != HX_SER_TRAILING && op.align != HX_SER_CENTRED) throw std::runtime_error(f + ": unknown align");
+  }
+  if (op.op == HX_SER_DELTA && (op.lag < 1 || op.lag >= ns))
+    throw std::runtime_error(f + ": lag must lie in 1.." + std::to_string(ns - 1));
+  if (!d_lane_of_member_ || lane_of_member_.empty()) throw std::runtime_error(f + ": run the core first");
+  sync();
+  auto operand = [&](const std::string &cap) {
+    const PostSource ps = post_source(cap, "hx_series_define");
+    if (ps.v >= 0 && !out_enabled_[ps.v])
+      throw std::runtime_error(f + ": variable " + cap + " was not enabled with set_outputs()");
+    if (!ps.block) throw std::runtime_error(f + ": run the core first");
+    return ps;
+  };
+  const PostSource pa = operand(a_name);
+  PostSource pb{nullptr, pa.last_iy, -1};
+  if (binary && op.b_kind == HX_SER_B_VAR) pb = operand(op.b);
+  // (both operands are in the current lane order now: resolving b does not move a's block -- a
+  //  series is permuted at most once per lane order, and a derived a keeps its cache slot: b takes
+  //  the other one)
+  const int valid = std::min(pa.last_iy, pb.last_iy);
+  const int last = scen_.start + pa.last_iy;
+  if (op.op == HX_SER_ANOMALY && (op.year1 < op.year0 || op.year0 < scen_.start || op.year1 > last))
+    throw std::runtime_error(f + ": the reference period must lie between startDate and " + std::to_string(last) +
+                             ", the end of " + a_name);
+  if (op.op == HX_SER_CUMSUM && (op.year0 < scen_.start || op.year0 > last))
+    throw std::runtime_error(f + ": year0 must lie between startDate and " + std::to_string(last) +
+                             ", the end of " + a_name);
+  const size_t np = (size_t)npad_;
+  if (!d_ser_vec_) check(hipMalloc(&d_ser_vec_, sizeof(double) * ((size_t)ns + np)), "hipMalloc series operand");
+  double *d_bvec = d_ser_vec_, *d_base = d_ser_vec_ + ns;
+  if (binary && op.b_kind != HX_SER_B_VAR) {
+    std::vector<double> bv((size_t)ns, op.b_kind == HX_SER_B_SCALAR ? op.b_scalar : std::nan(""));
+    if (op.b_kind == HX_SER_B_VECTOR)
+      for (int i = 0; i < op.b_n; ++i) {
+        const long long iy = (long long)op.b_first_year + i - scen_.start;
+        if (iy >= 0 && iy < ns) bv[(size_t)iy] = op.b_values[i];
+      }
+    check(hipMemcpy(d_bvec, bv.data(), sizeof(double) * (size_t)ns, hipMemcpyHostToDevice), "series operand");
+  }
+  double *z = nullptr;
+  if (hipMalloc(&z, sizeof(double) * (size_t)ns * np) != hipSuccess || !z) {
+    (void)hipGetLastError();
+    throw std::runtime_error(f + ": no device memory for the block of series " + name + " (" +
+                             std::to_string((sizeof(double) * (size_t)ns * np) >> 20) + " MiB)");
+  }
+  try {
+    switch (op.op) {
+      case HX_SER_COPY:
+        check(hx_launch_series_ew(HX_SER_COPY, pa.block, nullptr, nullptr, nullptr, npad_, ns, 0, valid, 0.0, 0.0,
+                                  z, stream_), "series kernel");
+        break;
+      case HX_SER_ADD: case HX_SER_SUB: case HX_SER_MUL: case HX_SER_DIV:
+        check(hx_launch_series_ew(op.op, pa.block, pb.block, pb.block ? nullptr : d_bvec, nullptr, npad_, ns, 0,
+                                  valid, 0.0, 0.0, z, stream_), "series kernel");
+        break;
+      case HX_SER_ANOMALY:
+        check(hx_launch_series_base(pa.block, npad_, op.year0 - scen_.start, op.year1 - scen_.start, d_base,
+                                    stream_), "series base kernel");
+        check(hx_launch_series_ew(HXS_ANOM_APPLY, pa.block, nullptr, nullptr, d_base, npad_, ns, 0, valid, 0.0,
+                                  0.0, z, stream_), "series kernel");
+        break;
+      case HX_SER_CUMSUM:
+        check(hx_launch_series_cumsum(pa.block, npad_, ns, op.year0 - scen_.start, valid, z, stream_),
+              "series cumsum kernel");
+        break;
+      case HX_SER_RUNMEAN:
+        check(hx_launch_series_runmean(pa.block, npad_, ns, op.width,
+                                       op.align == HX_SER_CENTRED ? (op.width - 1) / 2 : op.width - 1, valid, z,
+                                       stream_), "series running-mean kernel");
+        break;
+      default:  // HX_SER_DELTA: a itself `lag` rows earlier (rows below `lag` are never loaded)
+        check(hx_launch_series_ew(HX_SER_SUB, pa.block, pa.block - (size_t)op.lag * np, nullptr, nullptr, npad_,
+                                  ns, op.lag, valid, 0.0, 0.0, z, stream_), "series kernel");
+        break;
+    }
+    check(hipStreamSynchronize(stream_), "series sync");   // (the old block of a replaced series is freed below)
+  } catch (...) { (void)hipFree(z); throw; }
+  Series s;
+  s.name = name; s.block = z; s.valid_iy = valid; s.lane_of_member = lane_of_member_;
+  if (existing >= 0) {
+    (void)hipFree(series_[(size_t)existing].block);
+    series_[(size_t)existing] = std::move(s);
+  } else {
+    series_.push_back(std::move(s));
+  }
 }
 
 }  // namespace hx

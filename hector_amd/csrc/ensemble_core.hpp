@@ -135,7 +135,7 @@ class EnsembleCore {
   void var_info(const std::string &capability, std::string *component, std::string *units) const;
   const std::vector<std::string> &halocarbon_names() const { return halo_names_; }
   // device pointer to the [ns][npad] array of an output variable
-  const double *device_var(const std::string &capability, int *npad) const;
+  const double *device_var(const std::string &capability, int *npad);
   // per-year ensemble statistics {count,sum,sumsq,min,max} into a DEVICE buffer
   // of (year1-year0+1)*5 doubles (caller-owned, e.g. a torch tensor for RCCL)
   void stats_device(const std::string &capability, int year0, int year1, double *d_stats);
@@ -176,6 +176,10 @@ class EnsembleCore {
   void metric_bin_sums(const std::string &capability, const hx_metric *specs, int nspecs,
                        const unsigned long long *q, const double *edges, int nedges,
                        unsigned long long *sums_host);
+  // ---- held and derived per-member series (hx_series_define in hector_amd.h) ----------------------
+  void series_define(const std::string &name, const std::string &a, const hx_series_op &op);
+  void series_drop(const std::string &name);
+  void series_list(std::vector<std::string> *names, std::vector<int> *valid_to) const;
   int device() const { return device_; }
   void status(unsigned *out_host);
   void state_row(int row, double *out_host);
@@ -291,7 +295,7 @@ class EnsembleCore {
   int slr_valid_to_ = -1;
   void check_parameters() const;
   bool fetch_host(const std::string &capability, int year0, int year1, double *out_host);
-  void compute_derived(const std::string &capability, int iy0, int ny);
+  void compute_derived(const std::string &capability, int iy0, int ny, double *dst);
   // scratch of member_score / quantiles
   double *d_score_ = nullptr;                 // [obs n][sigma n][chi2 npad][chi2 in member order n_] + years
   size_t score_cap_ = 0;
@@ -303,8 +307,8 @@ class EnsembleCore {
   int q_iy0_ = 0, q_ny_ = 0, q_np_ = 0;
   bool q_weighted_ = false;
   int post_flags_ = 0;                        // HECTOR_AMD_POST_AB (measurements): 1 no prefix skip, 2 with wave aggregation
-  int q_check(const std::string &capability, int year0, int year1, int nprobs,
-              const char *fn = "hx_ensemble_quantiles");
+  const double *q_check(const std::string &capability, int year0, int year1, int nprobs,
+                        const char *fn = "hx_ensemble_quantiles");   // -> the source block
   void q_upload(const unsigned long long *q, int ny, int np);
   // the select over the rows iy0 .. iy0 + ny - 1 of a [rows][npad_] block in lane order
   void q_select(const double *src, int iy0, int ny, const unsigned long long *q, const double *probs,
@@ -319,8 +323,36 @@ class EnsembleCore {
   size_t metplan_cap_ = 0, met_cap_ = 0;
   unsigned long long *d_bin_ = nullptr;       // [32 edges as doubles][rows][nedges + 2]
   size_t bin_cap_ = 0;
-  int metric_check(const std::string &capability, const hx_metric *specs, int nspecs, const char *fn);
-  const double *metric_block(int v, const hx_metric *specs, int nspecs);   // -> d_met_, queued on stream_
+  int metric_check(const std::string &capability, const hx_metric *specs, int nspecs, const char *fn,
+                   const double **src);
+  const double *metric_block(const double *src, const hx_metric *specs, int nspecs);   // -> d_met_, queued on stream_
+  // ---- "a per-member variable on the device": the one resolver of the verbs -----------------------
+  // block: [ns][npad_] in the CURRENT lane order, rows 0..last_iy hold values; v: the index of a
+  // recorded output (its block may still be null: the callers keep their own messages for that), -1
+  // for a derived diagnostic, a whole-surface combination or a series
+  struct PostSource { const double *block; int last_iy; int v; };
+  // fn: the ABI function on whose behalf it is resolved (named in the messages of the new cases).
+  // Derived diagnostics and combinations are computed on stream_ into a block kept in derived_cache_.
+  PostSource post_source(const std::string &capability, const char *fn);
+  struct Series {
+    std::string name;
+    double *block = nullptr;             // [ns][npad_], lane order `lane_of_member`
+    int valid_iy = 0;
+    std::vector<int> lane_of_member;     // the lane order the block is stored in
+  };
+  std::vector<Series> series_;
+  int find_series(const std::string &name) const;
+  void series_to_current_lanes(Series &s);   // permutes the block on the device if the lanes have moved
+  void free_series();
+  // the kept blocks of derived diagnostics / combinations: valid while out_epoch_ stands
+  struct DerivedBlock { std::string name; double *block = nullptr; unsigned long long epoch = 0, used = 0; };
+  DerivedBlock derived_cache_[2];
+  unsigned long long out_epoch_ = 1, derived_clock_ = 0;   // out_epoch_: bumped whenever recorded rows may change
+  double *d_ps_tmp_ = nullptr;               // [ns][npad_]: the high-latitude part of a combination
+  double *d_ser_vec_ = nullptr;              // [ns] a per-year operand + [npad_] ANOMALY's bases
+  int *d_ser_perm_ = nullptr;                // [npad_] source lanes of a permutation
+  void free_derived_cache();
+  const double *derived_block(const std::string &capability);
   hipStream_t stream_ = nullptr;
   hipStream_t aux_stream_ = nullptr;          // the prewarm loop's (non-blocking)
   unsigned char *d_prewarm_ = nullptr;        // its stop flag (+ a sink)

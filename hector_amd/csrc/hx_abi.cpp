@@ -398,6 +398,27 @@ int hx_metric_probabilities(hx_core *core, const char *capability, const hx_metr
   HX_TRY(core->core->probabilities(capability, 0, 0, specs, nspecs, weights, edges, nedges, prob, sums,
                                    n_part))
 }
+int hx_series_define(hx_core *core, const char *name, const char *a, const hx_series_op *op) {
+  if (!name || !a || !op) return fail("hx_series_define: null argument");
+  HX_TRY(core->core->series_define(name, a, *op))
+}
+int hx_series_drop(hx_core *core, const char *name) {
+  if (!name) return fail("hx_series_drop: null argument");
+  HX_TRY(core->core->series_drop(name))
+}
+int hx_series_list(hx_core *core, const char *const **names, const int **valid_to, int *count) {
+  static thread_local std::vector<std::string> store;
+  static thread_local std::vector<const char *> ptrs;
+  static thread_local std::vector<int> years;
+  HX_TRY({
+    core->core->series_list(&store, &years);
+    ptrs.clear();
+    for (auto &n : store) ptrs.push_back(n.c_str());
+    if (names) *names = ptrs.data();
+    if (valid_to) *valid_to = years.data();
+    if (count) *count = (int)store.size();
+  })
+}
 int hx_status(hx_core *core, unsigned *out) {
   if (!out) return fail("hx_status: null argument");
   HX_TRY(core->core->status(out))

@@ -271,6 +271,221 @@ hipError_t hx_launch_metric(const double *var, int n, int npad, const void *grou
   return hipGetLastError();
 }
 
+// ===========================================================================
+// Series: kept [ns][npad] blocks in lane order that small lane-local kernels fill from a source
+// block (hx_series_define in hector_amd.h defines every operation and its order; contraction is
+// off as in the score kernel).  One lane per member, rows read coalesced, nothing exchanged between
+// lanes.  Every kernel writes ALL ns rows of z: NaN where the operation has no value.
+//   hx_series_ew_kernel     the elementwise operations, a pure stream: a lane takes HXS_BATCH rows of
+//                           each operand into registers, all loads in flight, then computes and stores
+//   hx_series_base_kernel   the lane's own mean over a reference period (ANOMALY's first step)
+//   hx_series_cumsum_kernel walks the years of a lane; the next batch of rows is in flight while the
+//                           running sum consumes the current one
+//   hx_series_runmean_kernel one (lane, year) per thread: a FRESH ascending sum of the window, whose
+//                           rows neighbouring years re-read from L2
+//   hx_series_permute_kernel a block into another lane order
+// ===========================================================================
+#define HXS_BATCH 16
+#define HXS_ANOM_APPLY 100   // internal: z = a - base[lane]
+#define HXS_COMBINE 101      // internal: z = (c0 * a) + (c1 * b), the whole-surface combinations
+
+template <int OP>
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__device__ __forceinline__ double hxs_apply(double a, double b, double c0, double c1) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  if (OP == HX_SER_ADD) return a + b;
+  if (OP == HX_SER_SUB || OP == HXS_ANOM_APPLY) return a - b;
+  if (OP == HX_SER_MUL) return a * b;
+  if (OP == HX_SER_DIV) return a / b;
+  if (OP == HXS_COMBINE) { const double p = c0 * a; const double q = c1 * b; return p + q; }
+  return a;   // HX_SER_COPY
+}
+
+// rows y_lo..y_hi are computed, every other row of 0..ns-1 is NaN.  b != nullptr: a block (DELTA
+// passes a itself k rows earlier: rows below y_lo = k are never loaded); else bvec[ns], one value a
+// year for every lane (a wave-uniform read); HXS_ANOM_APPLY: base[lane].  grid (lanes / 256, years /
+// HXS_BATCH)
+template <int OP>
+__global__ __launch_bounds__(256) void hx_series_ew_kernel(const double *__restrict__ a,
+                                                           const double *__restrict__ b,
+                                                           const double *__restrict__ bvec,
+                                                           const double *__restrict__ base, int npad, int ns,
+                                                           int y_lo, int y_hi, double c0, double c1,
+                                                           double *__restrict__ z) {
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= npad) return;
+  const int y0 = (int)blockIdx.y * HXS_BATCH;
+  constexpr bool unary = OP == HX_SER_COPY || OP == HXS_ANOM_APPLY;
+  double xa[HXS_BATCH], xb[HXS_BATCH];
+#pragma unroll
+  for (int e = 0; e < HXS_BATCH; ++e) {
+    const int y = y0 + e;
+    const bool on = y >= y_lo && y <= y_hi;   // wave-uniform
+    xa[e] = 0.0; xb[e] = 0.0;
+    if (on) {
+      xa[e] = a[(size_t)y * (size_t)npad + (size_t)lane];
+      if (!unary) xb[e] = b ? b[(size_t)y * (size_t)npad + (size_t)lane] : bvec[y];
+    }
+  }
+  const double bl = OP == HXS_ANOM_APPLY ? base[lane] : 0.0;
+#pragma unroll
+  for (int e = 0; e < HXS_BATCH; ++e) {
+    const int y = y0 + e;
+    if (y >= ns) continue;
+    const bool on = y >= y_lo && y <= y_hi;
+    const double r = hxs_apply<OP>(xa[e], OP == HXS_ANOM_APPLY ? bl : xb[e], c0, c1);
+    z[(size_t)y * (size_t)npad + (size_t)lane] = on ? r : __builtin_nan("");
+  }
+}
+
+// base[lane] = (sum of a over the rows r0..r1 ascending, starting from 0.0) / count
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__global__ __launch_bounds__(256) void hx_series_base_kernel(const double *__restrict__ a, int npad, int r0,
+                                                             int r1, double *__restrict__ base) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= npad) return;
+  const double *col = a + lane;
+  double s = 0.0;
+  for (int k = r0; k <= r1; k += HXS_BATCH) {
+    double x[HXS_BATCH];
+#pragma unroll
+    for (int e = 0; e < HXS_BATCH; ++e) x[e] = k + e <= r1 ? col[(size_t)(k + e) * (size_t)npad] : 0.0;
+#pragma unroll
+    for (int e = 0; e < HXS_BATCH; ++e) if (k + e <= r1) s = s + x[e];
+  }
+  base[lane] = s / (double)(r1 - r0 + 1);
+}
+
+// NaN before row y0; z_y0 = a_y0, z_y = z_(y-1) + a_y up to row y_hi; NaN behind it
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__global__ __launch_bounds__(256) void hx_series_cumsum_kernel(const double *__restrict__ a, int npad, int ns,
+                                                               int y0, int y_hi, double *__restrict__ z) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= npad) return;
+  const double *col = a + lane;
+  double *out = z + lane;
+  const double nan = __builtin_nan("");
+  for (int y = 0; y < y0; ++y) out[(size_t)y * (size_t)npad] = nan;
+  double xa[HXS_BATCH], xb[HXS_BATCH];
+  auto load = [&](int k, double (&x)[HXS_BATCH]) {
+#pragma unroll
+    for (int e = 0; e < HXS_BATCH; ++e) x[e] = k + e <= y_hi ? col[(size_t)(k + e) * (size_t)npad] : 0.0;
+  };
+  double s = 0.0;
+  load(y0, xa);
+  for (int k = y0; k <= y_hi; k += HXS_BATCH) {
+    const bool more = k + HXS_BATCH <= y_hi;
+    if (more) load(k + HXS_BATCH, xb);   // in flight while this batch is consumed
+#pragma unroll
+    for (int e = 0; e < HXS_BATCH; ++e) {
+      if (k + e > y_hi) continue;
+      s = k + e == y0 ? xa[e] : s + xa[e];
+      out[(size_t)(k + e) * (size_t)npad] = s;
+    }
+    if (more) {
+#pragma unroll
+      for (int e = 0; e < HXS_BATCH; ++e) xa[e] = xb[e];
+    }
+  }
+  for (int y = y_hi + 1; y < ns; ++y) out[(size_t)y * (size_t)npad] = nan;
+}
+
+// z_y = (fresh ascending sum of a over the rows y - back .. y - back + w - 1, from 0.0) / w; NaN
+// where the window leaves 0..y_hi.  grid (lanes / 256, ns)
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__global__ __launch_bounds__(256) void hx_series_runmean_kernel(const double *__restrict__ a, int npad, int w,
+                                                                int back, int y_hi, double *__restrict__ z) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= npad) return;
+  const int y = (int)blockIdx.y;
+  const int wl = y - back, wh = wl + w - 1;   // (w <= ns is checked by the host: no overflow)
+  double r = __builtin_nan("");
+  if (wl >= 0 && wh <= y_hi) {
+    const double *col = a + lane;
+    double s = 0.0;
+    for (int k = wl; k <= wh; k += HXS_BATCH) {
+      double x[HXS_BATCH];
+#pragma unroll
+      for (int e = 0; e < HXS_BATCH; ++e) x[e] = k + e <= wh ? col[(size_t)(k + e) * (size_t)npad] : 0.0;
+#pragma unroll
+      for (int e = 0; e < HXS_BATCH; ++e) if (k + e <= wh) s = s + x[e];
+    }
+    r = s / (double)w;
+  }
+  z[(size_t)y * (size_t)npad + (size_t)lane] = r;
+}
+
+// dst[y][l] = src[y][src_lane[l]]: a block into another lane order.  grid (lanes / 256, ns)
+__global__ __launch_bounds__(256) void hx_series_permute_kernel(const double *__restrict__ src,
+                                                                const int *__restrict__ src_lane, int npad,
+                                                                double *__restrict__ dst) {
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= npad) return;
+  const size_t row = (size_t)blockIdx.y * (size_t)npad;
+  dst[row + (size_t)lane] = src[row + (size_t)src_lane[lane]];
+}
+
+hipError_t hx_launch_series_ew(int op, const double *a, const double *b, const double *bvec, const double *base,
+                               int npad, int ns, int y_lo, int y_hi, double c0, double c1, double *z,
+                               hipStream_t st) {
+  const dim3 grid((npad + 255) / 256, (ns + HXS_BATCH - 1) / HXS_BATCH), block(256);
+#define HXS_EW(OP) \
+  hipLaunchKernelGGL(hx_series_ew_kernel<OP>, grid, block, 0, st, a, b, bvec, base, npad, ns, y_lo, y_hi, c0, c1, z)
+  switch (op) {
+    case HX_SER_COPY: HXS_EW(HX_SER_COPY); break;
+    case HX_SER_ADD: HXS_EW(HX_SER_ADD); break;
+    case HX_SER_SUB: HXS_EW(HX_SER_SUB); break;
+    case HX_SER_MUL: HXS_EW(HX_SER_MUL); break;
+    case HX_SER_DIV: HXS_EW(HX_SER_DIV); break;
+    case HXS_ANOM_APPLY: HXS_EW(HXS_ANOM_APPLY); break;
+    case HXS_COMBINE: HXS_EW(HXS_COMBINE); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef HXS_EW
+  return hipGetLastError();
+}
+hipError_t hx_launch_series_base(const double *a, int npad, int r0, int r1, double *base, hipStream_t st) {
+  hipLaunchKernelGGL(hx_series_base_kernel, dim3((npad + 255) / 256), dim3(256), 0, st, a, npad, r0, r1, base);
+  return hipGetLastError();
+}
+hipError_t hx_launch_series_cumsum(const double *a, int npad, int ns, int y0, int y_hi, double *z,
+                                   hipStream_t st) {
+  hipLaunchKernelGGL(hx_series_cumsum_kernel, dim3((npad + 255) / 256), dim3(256), 0, st, a, npad, ns, y0,
+                     y_hi, z);
+  return hipGetLastError();
+}
+hipError_t hx_launch_series_runmean(const double *a, int npad, int ns, int w, int back, int y_hi, double *z,
+                                    hipStream_t st) {
+  hipLaunchKernelGGL(hx_series_runmean_kernel, dim3((npad + 255) / 256, ns), dim3(256), 0, st, a, npad, w,
+                     back, y_hi, z);
+  return hipGetLastError();
+}
+hipError_t hx_launch_series_permute(const double *src, const int *src_lane, int npad, int ns, double *dst,
+                                    hipStream_t st) {
+  hipLaunchKernelGGL(hx_series_permute_kernel, dim3((npad + 255) / 256, ns), dim3(256), 0, st, src, src_lane,
+                     npad, dst);
+  return hipGetLastError();
+}
+
 #ifndef HX_HOST_EMULATION
 // ===========================================================================
 // Weighted quantiles (inverted CDF, Hyndman-Fan type 1) of a year row by an exact radix select.

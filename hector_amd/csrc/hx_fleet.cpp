@@ -550,6 +550,11 @@ void Fleet::probabilities(const std::string &cap, int year0, int year1, const hx
   }
 }
 
+void Fleet::series_define(const std::string &name, const std::string &a, const hx_series_op &op) {
+  HX_EACH(series_define(name, a, op))
+}
+void Fleet::series_drop(const std::string &name) { HX_EACH(series_drop(name)) }
+
 void Fleet::state_row(int row, double *out) {
   for (Shard &s : shards_) { use(s); s.core->state_row(row, out + s.offset); }
 }

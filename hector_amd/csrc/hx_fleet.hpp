@@ -106,6 +106,13 @@ class Fleet {
   void probabilities(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
                      const double *weights, const double *edges, int nedges, double *prob,
                      unsigned long long *sums, long long *n_part);
+  // hx_series_define / hx_series_drop: forwarded to every shard (the kernels are lane-local: nothing
+  // crosses shards); hx_series_list: the first shard's list (all shards hold the same names)
+  void series_define(const std::string &name, const std::string &a, const hx_series_op &op);
+  void series_drop(const std::string &name);
+  void series_list(std::vector<std::string> *names, std::vector<int> *valid_to) const {
+    shards_[0].core->series_list(names, valid_to);
+  }
   void state_row(int row, double *out_host);
   int spinup_steps(int member);
   void tracking_data(int member, int year0, int year1, double *values, double *fractions,

@@ -387,6 +387,94 @@ int hx_metric_probabilities(hx_core *core, const char *capability, const hx_metr
                             int nspecs, const double *weights, const double *edges, int nedges,
                             double *prob, unsigned long long *sums, long long *n_part);
 
+/* ---- Held and derived per-member series -----------------------------------------------------------
+ * What the six verbs above, hx_fetchvars, hx_stats_device / hx_ensemble_stats and hx_device_var call
+ * `capability` is "a per-member variable on the device", one of
+ *   - a RECORDED output (hx_set_outputs), valid to the current date: exactly as before;
+ *   - a diagnostic the core derives on the device from recorded outputs -- slr, sl_rc, slr_no_ice,
+ *     sl_rc_no_ice, HL_/LL_sst, _DIC, _CO3, _Revelle, _OmegaAr, _OmegaCa, ocean_tas, RF_N2O, RF_CH4,
+ *     RF_H2O_strat, RF_O3_trop -- or a whole-surface combination pH, PCO2, DIC, CO3
+ *     ((0.85 * LL) + (0.15 * HL), each product rounded) or ML_ocean_c (LL + HL): computed for
+ *     startDate..current date into a block the core keeps until the next run or reset; the outputs it
+ *     is derived from must be recorded ("needs ...: enable it ...");
+ *   - a SERIES, below: valid to the date it was defined at, NaN behind it.
+ * Dates are checked against the variable's own valid range.  A variable that is the same for every
+ * member (scenario inputs, the shared gas cycles: hx_fetchvars answers them on the host) is refused by
+ * the per-member verbs with a message that says so.  (hx_fetchvars of a diagnostic keeps computing just
+ * the rows asked for; hx_device_var of one returns the kept block.)
+ *
+ * A series is a named [years][members] block of doubles that belongs to the core, filled ONCE by
+ * hx_series_define from its operands as they are at the call (the core's pending work is waited for
+ * first).  It is a snapshot: later hx_reset, hx_run, hx_setvar, hx_set_outputs do not touch it, and
+ * when the core reorders its lanes the block is permuted on the device, so a series always means
+ * "member m's trajectory".  At most HX_SER_MAX series per core; hx_shutdown frees them.
+ * Names match [A-Za-z_][A-Za-z0-9_]{0,62} and must not be a name the core already answers (recorded,
+ * derived, combination, host-answered; a "<biome>.<pool>" cannot match the pattern).  Defining an
+ * existing series replaces it; the operands may name it (everything is read before the new block
+ * takes the name).
+ *
+ * a: any per-member variable as above, valid for startDate..end_a.  The operation (one per call;
+ * compose by name), per member, y ascending from startDate, in IEEE double without fused
+ * multiply-add, so that numpy reproduces every result bit for bit:
+ *   COPY              z_y = a_y
+ *   ADD SUB MUL DIV   z_y = a_y op b_y.  b (b_kind): HX_SER_B_VAR a per-member variable `b` (the result
+ *                     is valid to min(end_a, end_b)); HX_SER_B_SCALAR b_y = b_scalar;
+ *                     HX_SER_B_VECTOR b_y = b_values[y - b_first_year] for b_n years, NaN outside them
+ *   ANOMALY           s = 0.0; for y = year0..year1: s = s + a_y;  base = s / count;  z_y = a_y - base
+ *                     (hx_member_score's baseline)
+ *   CUMSUM            NaN before year0;  z_year0 = a_year0;  z_y = z_(y-1) + a_y  (numpy's cumsum)
+ *   RUNMEAN           the window is y-width+1 .. y (align HX_SER_TRAILING) or y-(width-1)/2 .. y+width/2
+ *                     (HX_SER_CENTRED, integer division);  s = 0.0; s = s + a_k for k ascending over the
+ *                     window -- a fresh sum for every y --;  z_y = s / width;  NaN where the window
+ *                     leaves startDate..end_a
+ *   DELTA             z_y = a_y - a_(y-lag);  NaN for the first `lag` years
+ * Rows behind the valid end hold NaN; a NaN in an operand propagates by IEEE arithmetic, and the
+ * verbs' NaN rules then leave that member or year out.
+ * Cost: one kernel (ANOMALY two), one lane per member, rows read coalesced; the elementwise
+ * operations are a stream with 16 rows of each operand in flight per lane, CUMSUM walks the years of a
+ * lane, RUNMEAN re-reads the window per year.  Nothing reaches the host.  A core of several shards
+ * forwards the call to every shard; nothing crosses shards or processes.
+ * Errors (every message names hx_series_define; a refused call changes nothing): a bad name, a name
+ * the core already answers, a 17th series, an unknown op / b_kind / align, width < 1 or beyond the
+ * number of years, lag < 1, a reference period or year0 outside startDate..end_a, an operand that is
+ * unknown, not recorded, answered on the host, or dropped, a core that has not run, no device memory
+ * for the block. */
+#define HX_SER_COPY 0
+#define HX_SER_ADD 1
+#define HX_SER_SUB 2
+#define HX_SER_MUL 3
+#define HX_SER_DIV 4
+#define HX_SER_ANOMALY 5
+#define HX_SER_CUMSUM 6
+#define HX_SER_RUNMEAN 7
+#define HX_SER_DELTA 8
+#define HX_SER_NOPS 9
+#define HX_SER_B_NONE 0
+#define HX_SER_B_VAR 1
+#define HX_SER_B_SCALAR 2
+#define HX_SER_B_VECTOR 3
+#define HX_SER_TRAILING 0
+#define HX_SER_CENTRED 1
+#define HX_SER_MAX 16
+typedef struct {
+  int op;               /* HX_SER_* */
+  int year0, year1;     /* ANOMALY: the reference period; CUMSUM: year0 = the first year */
+  int width, align;     /* RUNMEAN */
+  int lag;              /* DELTA */
+  int b_kind;           /* ADD SUB MUL DIV: HX_SER_B_* */
+  int b_first_year, b_n; /* HX_SER_B_VECTOR */
+  int reserved;
+  double b_scalar;      /* HX_SER_B_SCALAR */
+  const char *b;        /* HX_SER_B_VAR */
+  const double *b_values; /* HX_SER_B_VECTOR: b_n values from b_first_year on */
+} hx_series_op;
+int hx_series_define(hx_core *core, const char *name, const char *a, const hx_series_op *op);
+/* Frees a series; an unknown name is an error that names hx_series_drop. */
+int hx_series_drop(hx_core *core, const char *name);
+/* The series of the core in the order they were first defined: names[i], valid_to[i] (the last year
+ * that holds values); either may be NULL.  The arrays stay valid until the next call on this thread. */
+int hx_series_list(hx_core *core, const char *const **names, const int **valid_to, int *count);
+
 /* per-member model-error bitmask (HX_ERR_* below), host array of n_members */
 int hx_status(hx_core *core, unsigned *out);
 int hx_spinup_steps(hx_core *core, int member, int *steps);
