@@ -5,7 +5,8 @@ band -- without a trajectory leaving the GPU (Core.score, Core.quantiles) -- and
 reports: the constrained 2081-2100 warming relative to 1850-1900, the distribution of the
 peak-warming year and the probability of the warming classes in 2100 (Core.metric_quantiles,
 Core.metric_probabilities), a constrained sea-level band, the crossing year of a 20-year mean and
-an emissions what-if on held series (Core.hold, Core.derive).  The "observations" here are pseudo-observations: one held-out member
+an emissions what-if on held series (Core.hold, Core.derive), and which parameter drives the 2100
+warming before and after the constraint (Core.moments).  The "observations" here are pseudo-observations: one held-out member
 plus seeded noise.
 Needs an MI355X:  python examples/constrained_projection.py [n_members]"""
 import os
@@ -67,11 +68,22 @@ def main(n=20000, truth=0, **core_kwargs):
                                         weights=weights)[0]
     print("constrained 2100 warming: P(< 1.5 K) %.3f  P(1.5-2 K) %.3f  P(2-3 K) %.3f  P(>= 3 K) %.3f" % tuple(classes))
 
+    # which parameter drives the spread of the 2100 warming, before and after the constraint: the
+    # weighted moments and cross moments with the parameters, reduced on the device
+    core.derive("warming", "anomaly", GLOBAL_TAS(), years=base)
+    drivers = [ECS(), Q10_RH(), BETA()]
+    for name, wts in (("prior", None), ("constrained", weights)):
+        mom = core.moments("warming", (2100, 2100), weights=wts, against=drivers)
+        q = core.quantiles("warming", PROBS, (2100, 2100), weights=wts)[0]
+        print("%-12s 2100 warming %.2f +- %.2f K (median %.2f, 5-95 %% %.2f-%.2f)"
+              % (name, mom.mean[0], mom.sd[0], q[1], q[0], q[2]))
+        print("%-12s   correlation with %s" % ("", "  ".join("%s %+.3f" % (p, r) for p, r in zip(drivers, mom.corr[0]))))
+        print("%-12s   SRC              %s" % ("", "  ".join("%s %+.3f" % (p, r) for p, r in zip(drivers, mom.src()[0]))))
+
     # a diagnostic the core derives on the device takes the same verbs: the constrained sea-level band
     slr = core.quantiles("slr", PROBS, (2100, 2100), weights=weights)[0]
     print("constrained 2100 sea-level rise: %.3f (%.3f-%.3f) m" % (slr[1], slr[0], slr[2]))
     # the year a centred 20-year mean of the warming crosses 1.5 K: two series, composed by name
-    core.derive("warming", "anomaly", GLOBAL_TAS(), years=base)
     core.derive("warming20", "runmean", "warming", width=20, align="centred")
     cross, = core.metric_quantiles("warming20", [Metric("first_ge", (1900, 2090), threshold=1.5)], PROBS,
                                    weights=weights)

@@ -62,6 +62,115 @@ class Metric:
         return _HxMetric(METRIC_OPS[self.op], self.years[0], self.years[1], b0, b1, 0, self.threshold)
 
 
+MOMENTS_MAX_AGAINST = 8   # HX_MOM_MAX_PRED
+
+
+class Moments:
+    """What hx_ensemble_moments / hx_metric_moments return, and the statistics they define
+    (include/hector_amd.h), all in float64.  R rows (years or metrics), K predictors.
+    Raw: shift[R] = c_y, the smallest participating value of the row; sums[R, 2 + 3 K] = A, B, then
+    C_k, D_k, E_k per predictor; wsum[R] = W (uint64); n_part[R]; names[K]; pshift[K] = c_k.
+    Derived:  mean = shift + A/W;  var = B/W - (A/W)**2 (population);  pmean = pshift + C/W and
+    pvar = D/W - (C/W)**2, [R, K];  cov = E/W - (A/W)(C/W);  corr = cov / sqrt(var * pvar);
+    slope = cov / pvar.  corr is NaN where var or pvar is 0, slope where pvar is 0; a row nobody takes
+    part in is NaN throughout.  wsum and sums scale with the quantisation of the weights (weights=None
+    is q = 1, weights of all ones q = 2**32: wsum and sums exactly 2**32 times larger); only the
+    derived statistics do not depend on the scale of the weights."""
+
+    def __init__(self, shift, sums, wsum, n_part, names=(), pshift=None, q=None, predictors=None):
+        self.shift = np.asarray(shift, dtype=np.float64)
+        self.sums = np.asarray(sums, dtype=np.float64).reshape(self.shift.size, -1)
+        self.wsum = np.asarray(wsum, dtype=np.uint64)
+        self.n_part = np.asarray(n_part, dtype=np.int64)
+        self.names = list(names)
+        k = len(self.names)
+        if self.sums.shape[1] != 2 + 3 * k:
+            raise HectorAmdError("Moments: sums must have 2 + 3 * len(names) columns")
+        self.pshift = np.zeros(k) if pshift is None else np.asarray(pshift, dtype=np.float64)
+        self._q = None if q is None else np.asarray(q, dtype=np.uint64)
+        self._pred = None if predictors is None else np.asarray(predictors, dtype=np.float64).reshape(k, -1)
+
+    def _over_w(self, cols):
+        w = self.wsum.astype(np.float64)
+        w = np.where(w > 0, w, np.nan)
+        with np.errstate(invalid="ignore"):
+            return cols / (w if cols.ndim == 1 else w[:, None])
+
+    @property
+    def mean(self):
+        return self.shift + self._over_w(self.sums[:, 0])
+
+    @property
+    def var(self):
+        a = self._over_w(self.sums[:, 0])
+        return self._over_w(self.sums[:, 1]) - a * a
+
+    @property
+    def sd(self):
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(self.var)
+
+    @property
+    def pmean(self):
+        return self.pshift[None, :] + self._over_w(self.sums[:, 2::3])
+
+    @property
+    def pvar(self):
+        c = self._over_w(self.sums[:, 2::3])
+        return self._over_w(self.sums[:, 3::3]) - c * c
+
+    @property
+    def cov(self):
+        return self._over_w(self.sums[:, 4::3]) - self._over_w(self.sums[:, 0])[:, None] * self._over_w(self.sums[:, 2::3])
+
+    @property
+    def corr(self):
+        v = self.var[:, None] * self.pvar
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(v > 0, self.cov / np.sqrt(np.where(v > 0, v, 1.0)), np.nan)
+
+    @property
+    def slope(self):
+        pv = self.pvar
+        ok = (pv > 0) & (self.var[:, None] == self.var[:, None])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(ok, self.cov / np.where(pv > 0, pv, 1.0), np.nan)
+
+    def src(self):
+        """Standardised regression coefficients of all predictors jointly -> [R, K]: R_pp beta =
+        corr per row, with R_pp the weighted correlation matrix of the predictors, computed here in
+        numpy from the integer weights q and the predictor arrays over the members with q > 0 and
+        all predictors finite.  A row whose n_part differs from the number of those members (some
+        of them were NaN in that row) gets NaN: its participants are not those of R_pp."""
+        k = len(self.names)
+        out = np.full((self.shift.size, k), np.nan)
+        if k == 0:
+            return out
+        if self._q is None or self._pred is None:
+            raise HectorAmdError("Moments.src: needs the weights q and the predictor arrays")
+        on = (self._q > 0) & np.isfinite(self._pred).all(axis=0)
+        if not on.any():
+            return out
+        w = self._q[on].astype(np.float64)
+        p = self._pred[:, on]
+        z = p - (p * w).sum(axis=1, keepdims=True) / w.sum()
+        cpp = (z * w) @ z.T / w.sum()
+        sd = np.sqrt(np.diag(cpp))
+        if not (sd > 0).all():
+            return out
+        rpp = cpp / np.outer(sd, sd)
+        rows = (self.n_part == int(on.sum())) & ~np.isnan(self.corr).any(axis=1)
+        if rows.any():
+            try:
+                out[rows] = np.linalg.solve(rpp, self.corr[rows].T).T
+            except np.linalg.LinAlgError:
+                pass
+        return out
+
+    def __repr__(self):
+        return "Moments(rows=%d, against=%r)" % (self.shift.size, self.names)
+
+
 class Core:
     """An N-member ensemble core bound to one GPU (device=) or sharded over a list of GPUs
     (devices=[...]: contiguous member blocks, hx_newcore_devices)."""
@@ -503,6 +612,83 @@ class Core:
             "metric_probabilities",
             lambda *a: self._lib.hx_metric_probabilities(self._h, var.encode(), ctypes.byref(arr), ns, *a),
             ns, edges, weights, counts, sums)
+
+    def _against(self, against, weights, what):
+        """-> (names, predictors [K, n_members] or None, weights or None, q [n_members] uint64,
+        pshift [K]).  q and pshift restate the library's definition (include/hector_amd.h: q =
+        rint(w / wmax * 2^32), c_k the smallest predictor over the members with q > 0 and all
+        predictors finite) for Moments.pmean and Moments.src(); tests/test_gpu_moments.py holds wsum
+        and pshift against the same definition."""
+        w = self._weights(weights, what)
+        single = isinstance(against, str) or (isinstance(against, tuple) and len(against) == 2 and
+                                               isinstance(against[1], Metric)) or \
+            (isinstance(against, np.ndarray) and against.ndim == 1)   # one array is one entry
+        entries = [] if against is None else ([against] if single else list(against))
+        if len(entries) > MOMENTS_MAX_AGAINST:
+            raise HectorAmdError("%s: at most %d entries in against" % (what, MOMENTS_MAX_AGAINST))
+        names, cols = [], []
+        for i, a in enumerate(entries):
+            if isinstance(a, str):
+                names.append(a)
+                cols.append(self.getvar(a))
+            elif isinstance(a, tuple) and len(a) == 2 and isinstance(a[1], Metric):
+                names.append("%s %r" % (a[0], a[1]))
+                cols.append(self.metrics(a[0], [a[1]])[0])
+            else:
+                v = np.asarray(a, dtype=np.float64)
+                if v.shape != (self.n_members,):
+                    raise HectorAmdError("%s: entry %d of against must have n_members values" % (what, i))
+                names.append("against[%d]" % i)
+                cols.append(v)
+        pred = np.ascontiguousarray(np.stack(cols)) if cols else None
+        # the integer weights and predictor shifts as include/hector_amd.h defines them (for pmean, src)
+        if w is None:
+            q = np.ones(self.n_members, dtype=np.uint64)
+        else:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                q = np.rint(w / w.max() * 2.0 ** 32)
+            q = np.where(np.isfinite(q) & (q > 0), q, 0).astype(np.uint64)   # (a bad weight: the call refuses it)
+        pshift = np.full(len(names), np.nan)
+        if pred is not None:
+            on = (q > 0) & np.isfinite(pred).all(axis=0)
+            if on.any():
+                pshift = pred[:, on].min(axis=1)
+        return names, pred, w, q, pshift
+
+    def _moments(self, what, call, nrows, weights, against):
+        dp = ctypes.POINTER(ctypes.c_double)
+        names, pred, w, q, pshift = self._against(against, weights, what)
+        k = len(names)
+        shift = np.empty(nrows)
+        sums = np.zeros((nrows, 2 + 3 * k))
+        wsum = np.zeros(nrows, dtype=np.uint64)
+        npart = np.zeros(nrows, dtype=np.int64)
+        self._ck(call(w.ctypes.data_as(dp) if w is not None else None,
+                      pred.ctypes.data_as(dp) if pred is not None else None, k,
+                      shift.ctypes.data_as(dp), sums.ctypes.data_as(dp),
+                      wsum.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
+                      npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return Moments(shift, sums, wsum, npart, names, pshift, q, pred)
+
+    def moments(self, var, dates=None, weights=None, against=None):
+        """Per-year weighted mean and variance of `var` over the ensemble and its covariance,
+        correlation and regression slope against per-member quantities, on the device
+        (hx_ensemble_moments) -> Moments.  against: a list of parameter names (getvar), arrays
+        [n_members] or (var, Metric) pairs (metrics), at most 8.  A member takes part in a year if
+        its weight is not 0, its value is not NaN and all its `against` values are finite."""
+        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
+            (int(min(dates)), int(max(dates)))
+        return self._moments(
+            "moments", lambda *a: self._lib.hx_ensemble_moments(self._h, var.encode(), y0, y1, *a),
+            max(y1 - y0 + 1, 0), weights, against)
+
+    def metric_moments(self, var, specs, weights=None, against=None):
+        """The same over metrics (hx_metric_moments): one row per specification -> Moments."""
+        arr, ns = self._metric_array(specs, "metric_moments")
+        return self._moments(
+            "metric_moments",
+            lambda *a: self._lib.hx_metric_moments(self._h, var.encode(), ctypes.byref(arr), ns, *a),
+            ns, weights, against)
 
     def hold(self, name, var):
         """Keep the trajectory of every member of `var` -- a recorded output, a derived diagnostic

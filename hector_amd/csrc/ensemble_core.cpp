@@ -77,6 +77,13 @@ hipError_t hx_launch_q_hist(const double *var, int n, int npad, int iy0, int ny,
                             int np, int aggregate, unsigned long long *hist, hipStream_t stream);
 hipError_t hx_launch_q_pick(int ny, int *lo, unsigned long long *prefix, unsigned long long *rem, int np,
                             unsigned long long *hist, hipStream_t stream);
+hipError_t hx_launch_mom_prepare(const unsigned long long *q_mem, const double *pred_mem, int npred, int n,
+                                 int npad, const int *lane_of_member, const double *c,
+                                 unsigned long long *q_lane, double *qd_lane, double *e_lane, hipStream_t st);
+int hx_mom_chunks(int n);
+hipError_t hx_launch_moments(const double *var, int n, int npad, int iy0, int nrows, const double *qd,
+                             const double *e, int npred, const double *shift, double *part, double *out,
+                             hipStream_t st);
 #endif
 
 #ifndef HX_HOST_EMULATION
@@ -563,6 +570,7 @@ void EnsembleCore::free_device() {
   fr(d_bscratch_); d_bscratch_ = nullptr;
   fr(d_spin_rec_); d_spin_rec_ = nullptr;
   fr(d_score_); fr(d_q_); fr(d_qstate_); fr(d_qhist_); fr(d_metplan_); fr(d_met_); fr(d_bin_);
+  fr(d_mom_); d_mom_ = nullptr; mom_cap_ = 0; mom_src_ = nullptr;
   d_score_ = nullptr; d_q_ = d_qstate_ = d_qhist_ = nullptr;
   d_metplan_ = nullptr; d_met_ = nullptr; d_bin_ = nullptr;
   score_cap_ = qstate_cap_ = qhist_cap_ = metplan_cap_ = met_cap_ = bin_cap_ = 0; q_src_ = nullptr;
@@ -3211,6 +3219,109 @@ void EnsembleCore::metric_bin_sums(const std::string &capability, const hx_metri
   metric_check(capability, specs, nspecs, "hx_metric_probabilities", &src);
   sync();
   bin_block(metric_block(src, specs, nspecs), 0, nspecs, q, edges, nedges, sums_host);
+#endif
+}
+
+// ---- weighted moments and cross moments with predictors (hx_ensemble_moments, hx_metric_moments) ---
+
+namespace {
+// d_mom_ in 8-byte words: the call's weights and predictors in member order and in lane order, the
+// predictor shifts, the rows' records and shifts, the chunks' partial sums and the sums
+struct MomBuf {
+  unsigned long long *q_mem, *q_lane, *st;
+  double *pred_mem, *c, *qd_lane, *e_lane, *shift, *part, *out;
+  size_t words, lane_words;
+  MomBuf(unsigned long long *base, int n, int npad, int npred, int ny, int nchunks) {
+    const size_t N = (size_t)n, P = (size_t)npad, K = (size_t)npred, Y = (size_t)ny;
+    const size_t nc = 2 + 3 * K;
+    q_lane = base;                                             // [npad]  } zeroed before the prepare
+    qd_lane = reinterpret_cast<double *>(q_lane + P);          // [npad]  } kernel: padding lanes
+    e_lane = qd_lane + P;                                      // [npred][npad] } take no part
+    lane_words = (2 + K) * P;
+    q_mem = base + lane_words;                                 // [n]
+    pred_mem = reinterpret_cast<double *>(q_mem + N);          // [npred][n]
+    c = pred_mem + K * N;                                      // [8]
+    st = reinterpret_cast<unsigned long long *>(c + 8);        // [ny][4]
+    shift = reinterpret_cast<double *>(st + 4 * Y);            // [ny]
+    part = shift + Y;                                          // [ny][nchunks][nc]
+    out = part + Y * (size_t)nchunks * nc;                     // [ny][nc]
+    words = lane_words + N + K * N + 8 + 5 * Y + Y * (size_t)nchunks * nc + Y * nc;
+  }
+};
+}  // namespace
+
+// the minimum pass over the rows iy0 .. iy0 + ny - 1 of a [rows][npad_] block in lane order, with
+// the call's effective weights; st_host[ny][4] as q_begin_block returns it
+void EnsembleCore::mom_begin_block(const double *src, int iy0, int ny, const unsigned long long *q,
+                                   const double *pred, int npred, const double *c,
+                                   unsigned long long *st_host) {
+#ifdef HX_HOST_EMULATION
+  (void)src; (void)iy0; (void)ny; (void)q; (void)pred; (void)npred; (void)c; (void)st_host;
+#else
+  const int nchunks = hx_mom_chunks(n_);
+  const size_t words = MomBuf(nullptr, n_, npad_, npred, ny, nchunks).words;
+  if (words > mom_cap_) {
+    if (d_mom_) (void)hipFree(d_mom_);
+    d_mom_ = nullptr; mom_cap_ = 0;
+    check(hipMalloc(&d_mom_, 8 * words), "hipMalloc moments");
+    mom_cap_ = words;
+  }
+  MomBuf b(d_mom_, n_, npad_, npred, ny, nchunks);
+  const size_t N = (size_t)n_;
+  check(hipMemsetAsync(b.q_lane, 0, 8 * b.lane_words, stream_), "moments lanes");
+  check(hipMemsetAsync(b.st, 0, 8 * 4 * (size_t)ny, stream_), "moments state");
+  check(hipMemcpyAsync(b.q_mem, q, 8 * N, hipMemcpyHostToDevice, stream_), "moments weights");
+  if (npred)
+    check(hipMemcpyAsync(b.pred_mem, pred, 8 * N * (size_t)npred, hipMemcpyHostToDevice, stream_),
+          "moments predictors");
+  check(hipMemcpyAsync(b.c, c, 8 * 8, hipMemcpyHostToDevice, stream_), "moments predictor shifts");
+  check(hx_launch_mom_prepare(b.q_mem, b.pred_mem, npred, n_, npad_, d_lane_of_member_, b.c, b.q_lane,
+                              b.qd_lane, b.e_lane, stream_), "moments prepare kernel");
+  check(hx_launch_q_minmax(src, n_, npad_, iy0, ny, b.q_lane, b.st, stream_), "moments min kernel");
+  check(hipMemcpyAsync(st_host, b.st, 8 * 4 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "moments fetch");
+  check(hipStreamSynchronize(stream_), "moments sync");   // (q, pred and c are the caller's until here)
+  mom_src_ = src; mom_iy0_ = iy0; mom_ny_ = ny; mom_npred_ = npred;
+#endif
+}
+
+void EnsembleCore::mom_begin(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                             int nspecs, const unsigned long long *q, const double *pred, int npred,
+                             const double *c, unsigned long long *st_host, const char *fn) {
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)year0; (void)year1; (void)specs; (void)nspecs; (void)q; (void)pred; (void)npred;
+  (void)c; (void)st_host;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  const double *src = nullptr;
+  if (specs) {
+    metric_check(capability, specs, nspecs, fn, &src);
+    sync();
+    mom_begin_block(metric_block(src, specs, nspecs), 0, nspecs, q, pred, npred, c, st_host);
+  } else {
+    src = q_check(capability, year0, year1, 1, fn);
+    sync();
+    mom_begin_block(src, year0 - scen_.start, year1 - year0 + 1, q, pred, npred, c, st_host);
+  }
+#endif
+}
+
+// the sum pass over the block mom_begin prepared: shift_host[ny] (the smallest participating value
+// of every row over ALL shards) -> sums_host[ny][2 + 3 npred] of this core's members
+void EnsembleCore::mom_finish(const double *shift_host, double *sums_host) {
+#ifdef HX_HOST_EMULATION
+  (void)shift_host; (void)sums_host;
+  throw std::runtime_error(std::string("hx_ensemble_moments") + kEmulRefusal);
+#else
+  if (!mom_src_) throw std::runtime_error("moment sums without mom_begin");
+  const int ny = mom_ny_, npred = mom_npred_;
+  MomBuf b(d_mom_, n_, npad_, npred, ny, hx_mom_chunks(n_));
+  const size_t nc = 2 + 3 * (size_t)npred;
+  check(hipMemcpyAsync(b.shift, shift_host, 8 * (size_t)ny, hipMemcpyHostToDevice, stream_), "moments shifts");
+  check(hx_launch_moments(mom_src_, n_, npad_, mom_iy0_, ny, b.qd_lane, b.e_lane, npred, b.shift, b.part,
+                          b.out, stream_), "moments kernel");
+  check(hipMemcpyAsync(sums_host, b.out, 8 * (size_t)ny * nc, hipMemcpyDeviceToHost, stream_), "moments fetch");
+  check(hipStreamSynchronize(stream_), "moments sync");
+  mom_src_ = nullptr;
 #endif
 }
 

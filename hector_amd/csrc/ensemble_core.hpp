@@ -176,6 +176,16 @@ class EnsembleCore {
   void metric_bin_sums(const std::string &capability, const hx_metric *specs, int nspecs,
                        const unsigned long long *q, const double *edges, int nedges,
                        unsigned long long *sums_host);
+  // weighted moments (hx_ensemble_moments; specs != nullptr: hx_metric_moments over the metric
+  // block), in the two steps hx_fleet.cpp drives for one shard or several.  mom_begin validates,
+  // brings q[n_] (effective integer weights: 0 where a predictor is not finite) and pred[npred][n_]
+  // (member order) to lane order with the predictor shifts c[8] subtracted, and reduces {~min key,
+  // max key, sum q, count} of every row into st_host[rows][4]; mom_finish takes the rows' shifts over
+  // ALL shards and returns this core's sums_host[rows][2 + 3 npred]
+  void mom_begin(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                 const unsigned long long *q, const double *pred, int npred, const double *c,
+                 unsigned long long *st_host, const char *fn);
+  void mom_finish(const double *shift_host, double *sums_host);
   // ---- held and derived per-member series (hx_series_define in hector_amd.h) ----------------------
   void series_define(const std::string &name, const std::string &a, const hx_series_op &op);
   void series_drop(const std::string &name);
@@ -323,6 +333,12 @@ class EnsembleCore {
   size_t metplan_cap_ = 0, met_cap_ = 0;
   unsigned long long *d_bin_ = nullptr;       // [32 edges as doubles][rows][nedges + 2]
   size_t bin_cap_ = 0;
+  unsigned long long *d_mom_ = nullptr;       // scratch of the moment verbs (MomBuf in ensemble_core.cpp)
+  size_t mom_cap_ = 0;
+  const double *mom_src_ = nullptr;           // the block mom_begin prepared for mom_finish
+  int mom_iy0_ = 0, mom_ny_ = 0, mom_npred_ = 0;
+  void mom_begin_block(const double *src, int iy0, int ny, const unsigned long long *q, const double *pred,
+                       int npred, const double *c, unsigned long long *st_host);
   int metric_check(const std::string &capability, const hx_metric *specs, int nspecs, const char *fn,
                    const double **src);
   const double *metric_block(const double *src, const hx_metric *specs, int nspecs);   // -> d_met_, queued on stream_

@@ -398,6 +398,20 @@ int hx_metric_probabilities(hx_core *core, const char *capability, const hx_metr
   HX_TRY(core->core->probabilities(capability, 0, 0, specs, nspecs, weights, edges, nedges, prob, sums,
                                    n_part))
 }
+int hx_ensemble_moments(hx_core *core, const char *capability, int year0, int year1,
+                        const double *weights, const double *predictors, int npred, double *shift,
+                        double *sums, unsigned long long *wsum, long long *n_part) {
+  if (!capability || !shift || !sums) return fail("hx_ensemble_moments: null argument");
+  HX_TRY(core->core->moments(capability, year0, year1, nullptr, 0, weights, predictors, npred, shift, sums,
+                             wsum, n_part))
+}
+int hx_metric_moments(hx_core *core, const char *capability, const hx_metric *specs, int nspecs,
+                      const double *weights, const double *predictors, int npred, double *shift,
+                      double *sums, unsigned long long *wsum, long long *n_part) {
+  if (!capability || !specs || !shift || !sums) return fail("hx_metric_moments: null argument");
+  HX_TRY(core->core->moments(capability, 0, 0, specs, nspecs, weights, predictors, npred, shift, sums, wsum,
+                             n_part))
+}
 int hx_series_define(hx_core *core, const char *name, const char *a, const hx_series_op *op) {
   if (!name || !a || !op) return fail("hx_series_define: null argument");
   HX_TRY(core->core->series_define(name, a, *op))

@@ -1,12 +1,13 @@
 // hx_dev_post.h -- what a user does with a finished ensemble, on the device: a per-member misfit
 // of a recorded output against an observation series (hx_score_kernel), per-member metrics of a
-// window (hx_metric_kernel), exact weighted quantiles over the members (hx_q_* kernels) and
-// weighted bin sums against fixed edges (hx_bin_kernel).  The reference has no counterpart: its
+// window (hx_metric_kernel), exact weighted quantiles over the members (hx_q_* kernels),
+// weighted bin sums against fixed edges (hx_bin_kernel) and weighted moments with per-member
+// predictors (hx_mom_* / hx_moments_kernel).  The reference has no counterpart: its
 // hosts aggregate fetchvars() data frames in R.  Compiled for the GPU through hx_post.hip -- a
 // translation unit of its own, so the year-loop kernels' code generation does not see it -- and
 // for the host-emulation build through ensemble_core.cpp (score and metric kernels only: the
-// quantile and bin kernels are cooperative -- LDS atomics, cross-lane -- and one lane at a time
-// cannot run them).
+// quantile, bin and moment kernels are cooperative -- LDS atomics, cross-lane -- and one lane at a
+// time cannot run them).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -807,6 +808,153 @@ hipError_t hx_launch_bin(const double *var, int n, int npad, int iy0, int nrows,
     hipLaunchKernelGGL(hx_bin_kernel<true>, grid, dim3(HXQ_BLOCK), 0, stream, var, n, npad, iy0, q, edges, K, sums);
   else
     hipLaunchKernelGGL(hx_bin_kernel<false>, grid, dim3(HXQ_BLOCK), 0, stream, var, n, npad, iy0, q, edges, K, sums);
+  return hipGetLastError();
+}
+
+// ===========================================================================
+// Weighted moments of rows and their cross moments with per-member predictors (hx_ensemble_moments,
+// hx_metric_moments in hector_amd.h define the sums).  Three steps:
+//   hx_mom_prepare_kernel  lane-local: the call's effective integer weights (the host has zeroed q
+//                          where a predictor is not finite) and predictors arrive in member order
+//                          and go to lane order; e_k = p_k - c_k (0 where q is 0, so that no NaN
+//                          reaches a product)
+//   hx_q_minmax_kernel     with that q: the row's smallest participating value c_y, W and the count
+//   hx_moments_kernel<NP>  grid (row chunks, rows) like hx_q_hist_kernel: a lane takes its HXQ_PER
+//                          values of the chunk into registers, a batch at a time with every load of
+//                          the batch in flight -- the row is read once from memory; q and the
+//                          predictors of the same members, which every row re-reads, come from the
+//                          cache.  2 + 3 NP private accumulators, all terms >= 0.
+// No floating atomics: a fixed shuffle tree per wavefront, the four wavefronts added in order, one
+// partial per (row, chunk), and hx_mom_reduce_kernel adds the chunks in ascending order -- the same
+// bits from call to call for one lane order and shard layout.
+// ===========================================================================
+#define HXMOM_MAXP 8
+__global__ __launch_bounds__(256) void hx_mom_prepare_kernel(const hxq_u64 *__restrict__ q_mem,
+                                                             const double *__restrict__ pred_mem, int npred,
+                                                             int n, int npad,
+                                                             const int *__restrict__ lane_of_member,
+                                                             const double *__restrict__ c,
+                                                             hxq_u64 *__restrict__ q_lane,
+                                                             double *__restrict__ qd_lane,
+                                                             double *__restrict__ e_lane) {
+  const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (m >= n) return;
+  const int lane = lane_of_member[m];
+  if (lane < 0 || lane >= npad) return;
+  const hxq_u64 q = q_mem[m];   // (the host has zeroed it where a predictor is not finite)
+  q_lane[lane] = q;
+  qd_lane[lane] = (double)q;   // q <= 2^32: exact
+  for (int k = 0; k < npred; ++k)
+    e_lane[(size_t)k * (size_t)npad + (size_t)lane] = q ? pred_mem[(size_t)k * (size_t)n + (size_t)m] - c[k] : 0.0;
+}
+
+// part[(row * nchunks + chunk) * (2 + 3 NP) + ...] = A, B, then C_k, D_k, E_k of the chunk
+template <int NP>
+__global__ __launch_bounds__(HXQ_BLOCK) void hx_moments_kernel(const double *__restrict__ var, int n, int npad,
+                                                               int iy0, const double *__restrict__ qd,
+                                                               const double *__restrict__ e,
+                                                               const double *__restrict__ shift,
+                                                               double *__restrict__ part) {
+  constexpr int NC = 2 + 3 * NP;
+  static_assert(HXQ_BLOCK == 256, "the combine below adds four wavefronts in a fixed order");
+  __shared__ double red[HXQ_BLOCK / 64][NC];
+  const int tid = (int)threadIdx.x;
+  const int y = (int)blockIdx.y;
+  const double *row = var + (size_t)(iy0 + y) * npad;
+  const int beg = (int)blockIdx.x * HXQ_CHUNK, end = min(beg + HXQ_CHUNK, n);
+  const double c = shift[y];
+  double acc[NC];
+#pragma unroll
+  for (int a = 0; a < NC; ++a) acc[a] = 0.0;
+  // HXQ_PER elements a lane in batches of B: the row values, weights and predictors of a batch are
+  // all in flight at once; B shrinks with NP so that a batch and the accumulators stay in registers
+  constexpr int B = NP == 0 ? HXQ_PER : NP <= 3 ? HXQ_PER / 2 : HXQ_PER / 4;
+#pragma unroll 1
+  for (int j0 = 0; j0 < HXQ_PER; j0 += B) {
+    const int i0 = beg + j0 * HXQ_BLOCK + tid;
+    if (i0 - tid >= end) break;   // (the same for the whole workgroup)
+    double x[B], w[B], ek[NP > 0 ? NP * B : 1];
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+      const int i = i0 + j * HXQ_BLOCK;
+      const bool in = i < end;
+      x[j] = __builtin_nan("");
+      w[j] = 0.0;
+      if (in) { x[j] = row[i]; w[j] = qd[i]; }
+#pragma unroll
+      for (int k = 0; k < NP; ++k) {
+        ek[k * B + j] = 0.0;
+        if (in) ek[k * B + j] = e[(size_t)k * (size_t)npad + (size_t)i];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+      const bool on = x[j] == x[j] && w[j] > 0.0;   // (on: somebody takes part, so c is a member's value)
+      const double ww = on ? w[j] : 0.0;
+      const double d = on ? x[j] - c : 0.0;
+      const double wd = ww * d;
+      acc[0] += wd;
+      acc[1] += wd * d;
+#pragma unroll
+      for (int k = 0; k < NP; ++k) {
+        const double we = ww * ek[k * B + j];
+        acc[2 + 3 * k] += we;
+        acc[3 + 3 * k] += we * ek[k * B + j];
+        acc[4 + 3 * k] += wd * ek[k * B + j];
+      }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NC; ++a) {
+    double v = acc[a];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((tid & 63) == 0) red[tid >> 6][a] = v;
+  }
+  __syncthreads();
+  if (tid < NC)
+    part[((size_t)y * gridDim.x + blockIdx.x) * NC + tid] =
+        ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// out[row][nc] = the chunks' partials added in ascending chunk order
+__global__ __launch_bounds__(256) void hx_mom_reduce_kernel(const double *__restrict__ part, int nchunks, int nc,
+                                                            int total, double *__restrict__ out) {
+  const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (idx >= total) return;
+  const int y = idx / nc, a = idx - y * nc;
+  double s = 0.0;
+  for (int ch = 0; ch < nchunks; ++ch) s += part[((size_t)y * nchunks + ch) * nc + a];
+  out[idx] = s;
+}
+
+hipError_t hx_launch_mom_prepare(const unsigned long long *q_mem, const double *pred_mem, int npred, int n,
+                                 int npad, const int *lane_of_member, const double *c,
+                                 unsigned long long *q_lane, double *qd_lane, double *e_lane, hipStream_t st) {
+  hipLaunchKernelGGL(hx_mom_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, st, q_mem, pred_mem, npred, n,
+                     npad, lane_of_member, c, q_lane, qd_lane, e_lane);
+  return hipGetLastError();
+}
+int hx_mom_chunks(int n) { return (n + HXQ_CHUNK - 1) / HXQ_CHUNK; }
+// part: [nrows][hx_mom_chunks(n)][2 + 3 npred] scratch; out: [nrows][2 + 3 npred]
+hipError_t hx_launch_moments(const double *var, int n, int npad, int iy0, int nrows, const double *qd,
+                             const double *e, int npred, const double *shift, double *part, double *out,
+                             hipStream_t st) {
+  const int nchunks = hx_mom_chunks(n), nc = 2 + 3 * npred;
+  const dim3 grid(nchunks, nrows), block(HXQ_BLOCK);
+#define HXMOM_CASE(NP) \
+  case NP: hipLaunchKernelGGL(hx_moments_kernel<NP>, grid, block, 0, st, var, n, npad, iy0, qd, e, shift, part); break;
+  switch (npred) {
+    HXMOM_CASE(0) HXMOM_CASE(1) HXMOM_CASE(2) HXMOM_CASE(3) HXMOM_CASE(4)
+    HXMOM_CASE(5) HXMOM_CASE(6) HXMOM_CASE(7) HXMOM_CASE(8)
+    default: return hipErrorInvalidValue;
+  }
+#undef HXMOM_CASE
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  const int total = nrows * nc;
+  hipLaunchKernelGGL(hx_mom_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, part, nchunks, nc, total,
+                     out);
   return hipGetLastError();
 }
 #endif  // !HX_HOST_EMULATION

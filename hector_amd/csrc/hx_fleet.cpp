@@ -550,6 +550,69 @@ void Fleet::probabilities(const std::string &cap, int year0, int year1, const hx
   }
 }
 
+void Fleet::moments(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
+                    const double *weights, const double *predictors, int npred, double *shift, double *sums,
+                    unsigned long long *wsum, long long *n_part) {
+  check_poison();
+  const char *fn = specs ? "hx_metric_moments" : "hx_ensemble_moments";
+  const std::string f(fn);
+  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
+    throw std::runtime_error(f + ": nspecs must lie in 1..32");
+  if (npred < 0 || npred > HX_MOM_MAX_PRED)
+    throw std::runtime_error(f + ": npred must lie in 0..8");
+  if (npred > 0 && !predictors)
+    throw std::runtime_error(f + ": predictors is NULL with npred > 0");
+  refuse_processes(fn, "moments");
+  std::vector<unsigned long long> q;
+  quantise_weights(weights, fn, q);
+  if (!weights) q.assign((size_t)n_, 1ull);
+  const int nrows = specs ? nspecs : year1 - year0 + 1;
+  if (nrows < 1) throw std::runtime_error(f + ": year1 < year0");
+  // the call's effective weights, and the predictor shifts over the members they leave
+  const size_t N = (size_t)n_, K = (size_t)npred, R = (size_t)nrows, nc = 2 + 3 * K;
+  for (size_t k = 0; k < K; ++k)
+    for (size_t m = 0; m < N; ++m)
+      if (!std::isfinite(predictors[k * N + m])) q[m] = 0;
+  double c[HX_MOM_MAX_PRED];
+  for (size_t k = 0; k < HX_MOM_MAX_PRED; ++k) {
+    c[k] = std::nan("");
+    if (k >= K) continue;
+    for (size_t m = 0; m < N; ++m)
+      if (q[m] && !(c[k] <= predictors[k * N + m])) c[k] = predictors[k * N + m];
+  }
+  // 1. every shard's minimum, W and count of every row; the minimum over the shards is the shift
+  std::vector<unsigned long long> st(4 * R, 0ull), part(4 * R);
+  std::vector<double> pred;
+  for (Shard &s : shards_) {
+    use(s);
+    pred.resize(K * (size_t)s.count);
+    for (size_t k = 0; k < K; ++k)
+      std::copy(predictors + k * N + (size_t)s.offset, predictors + k * N + (size_t)(s.offset + s.count),
+                pred.begin() + k * (size_t)s.count);
+    s.core->mom_begin(cap, year0, year1, specs, nspecs, q.data() + s.offset, pred.data(), npred, c,
+                      part.data(), fn);
+    for (size_t y = 0; y < R; ++y) {
+      if (!part[4 * y + 3]) continue;
+      st[4 * y] = std::max(st[4 * y], part[4 * y]);
+      st[4 * y + 2] += part[4 * y + 2];
+      st[4 * y + 3] += part[4 * y + 3];
+    }
+  }
+  for (size_t y = 0; y < R; ++y) {
+    shift[y] = st[4 * y + 3] ? hxq_key_to_double(~st[4 * y]) : std::nan("");
+    if (wsum) wsum[y] = st[4 * y + 2];
+    if (n_part) n_part[y] = (long long)st[4 * y + 3];
+  }
+  // 2. every shard's sums about that shift, added in ascending shard order
+  std::fill(sums, sums + R * nc, 0.0);
+  std::vector<double> sp(R * nc);
+  for (Shard &s : shards_) {
+    use(s);
+    s.core->mom_finish(shift, sp.data());
+    for (size_t i = 0; i < R * nc; ++i) sums[i] += sp[i];
+  }
+}
+
 void Fleet::series_define(const std::string &name, const std::string &a, const hx_series_op &op) {
   HX_EACH(series_define(name, a, op))
 }

@@ -106,6 +106,13 @@ class Fleet {
   void probabilities(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
                      const double *weights, const double *edges, int nedges, double *prob,
                      unsigned long long *sums, long long *n_part);
+  // hx_ensemble_moments (specs == nullptr: the rows year0..year1) and hx_metric_moments: the weights
+  // quantised as for quantiles, zeroed where a predictor is not finite, the predictor shifts taken
+  // here; then two steps over the shards -- the rows' minima (their minimum is the shift), the sums
+  // about it -- with the predictor arrays split by shard offsets and the sums added in shard order
+  void moments(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+               const double *weights, const double *predictors, int npred, double *shift, double *sums,
+               unsigned long long *wsum, long long *n_part);
   // hx_series_define / hx_series_drop: forwarded to every shard (the kernels are lane-local: nothing
   // crosses shards); hx_series_list: the first shard's list (all shards hold the same names)
   void series_define(const std::string &name, const std::string &a, const hx_series_op &op);

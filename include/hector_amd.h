@@ -387,6 +387,56 @@ int hx_metric_probabilities(hx_core *core, const char *capability, const hx_metr
                             int nspecs, const double *weights, const double *edges, int nedges,
                             double *prob, unsigned long long *sums, long long *n_part);
 
+/* Weighted moments of every recorded year over the ensemble, and its cross moments with up to 8
+ * per-member predictors (parameters, metrics): what a weighted mean, variance, correlation or
+ * regression of an output against the members' parameters needs, year by year, without the
+ * trajectories leaving the device.  No counterpart in the reference.
+ *   weights[n_members] (member order) or NULL; predictors[k * n_members + m], 0 <= npred <= 8.
+ * The weights become the integers q exactly as in hx_ensemble_quantiles (wmax over the WHOLE
+ * ensemble; NULL: q_m = 1).  A member takes part in a row if q_m > 0, its value x in that row is not
+ * NaN, and every one of its predictor values is finite (so a NaN metric used as a predictor removes
+ * the member, as a NaN value does).
+ * Shifts: c_y = the smallest participating x of the row (an exact value some member has); c_k = the
+ * smallest of predictor k over the members with q_m > 0 and all predictors finite.  d = x - c_y and
+ * e_k = p_k - c_k are each ONE IEEE subtraction -- that rounding is part of the definition -- and
+ * both are >= 0.  Over the participants of the row:
+ *   W = sum q (exact integer)      A = sum q d        B = sum q d d
+ *   C_k = sum q e_k                D_k = sum q e_k e_k        E_k = sum q d e_k
+ *   shift[y] = c_y;  wsum[y] = W;  n_part[y] = participants (wsum, n_part may be NULL);
+ *   sums[y * (2 + 3 npred) + ...] = A, B, then C_k, D_k, E_k for k = 0 .. npred - 1.
+ * A row in which nobody takes part: shift NaN, sums 0, W 0, n_part 0.  Every term is >= 0, so a sum
+ * in any order is within (n_part + 8) 2^-53 of the exact one, relatively, and the statistics below
+ * are conditioned by the spread of the row and not by its magnitude.  In double:
+ *   mean = c_y + A/W        var = B/W - (A/W)^2   (the population variance)
+ *   pmean_k = c_k + C_k/W   pvar_k = D_k/W - (C_k/W)^2
+ *   cov_k = E_k/W - (A/W)(C_k/W)    corr_k = cov_k / sqrt(var pvar_k)    slope_k = cov_k / pvar_k
+ * (corr and slope are undefined where a variance is 0; c_k is not returned: it is the smallest
+ * predictor value over the members named above.)  W and the sums scale with the quantisation: NULL
+ * weights give q_m = 1, weights of all ones q_m = 2^32, so W and every sum of the second call are
+ * exactly 2^32 times those of the first; only the statistics above do not depend on the scale of
+ * the weights (those two calls give them bit for bit).
+ * Reproducibility: W, n_part and c_y are exact under any lane order or shard split.  The floating
+ * sums are NOT bit-identical across lane orders or shard splits, unlike the integer verbs above; they
+ * ARE bit-identical from call to call for the same core, lane order and shard layout: no floating
+ * atomics, a fixed reduction tree inside a workgroup, workgroup partials added in ascending chunk
+ * order, shards added on the host in ascending shard order.
+ * Cost: the predictors and weights go to lane order (one lane-local kernel), one read of every row
+ * for the minimum and one for all sums; 2 + 3 npred (+ 4) values a row back to the host.  A
+ * communicator of several processes is refused.  The core is not prepared, spun up or dirtied.
+ * Errors (every message names the function; a refused call changes nothing): those of
+ * hx_ensemble_quantiles for capability, dates and weights; npred outside 0..8; predictors NULL with
+ * npred > 0; a core that has not run.  Not available in the host-emulation build of the test suite. */
+#define HX_MOM_MAX_PRED 8
+int hx_ensemble_moments(hx_core *core, const char *capability, int year0, int year1,
+                        const double *weights, const double *predictors, int npred, double *shift,
+                        double *sums, unsigned long long *wsum, long long *n_part);
+
+/* The same over metrics: row s is metric s of every member (as hx_member_metrics defines it,
+ * computed on the device); shift[s], sums[s * (2 + 3 npred) + ...], wsum[s], n_part[s]. */
+int hx_metric_moments(hx_core *core, const char *capability, const hx_metric *specs, int nspecs,
+                      const double *weights, const double *predictors, int npred, double *shift,
+                      double *sums, unsigned long long *wsum, long long *n_part);
+
 /* ---- Held and derived per-member series -----------------------------------------------------------
  * What the six verbs above, hx_fetchvars, hx_stats_device / hx_ensemble_stats and hx_device_var call
  * `capability` is "a per-member variable on the device", one of
