@@ -183,6 +183,8 @@ def _declare(lib):
                                 c.POINTER(c.c_ulonglong), c.POINTER(c.c_longlong)],
         "hx_metric_moments": [P, c.c_char_p, c.c_void_p, c.c_int, dp, dp, c.c_int, dp, dp,
                               c.POINTER(c.c_ulonglong), c.POINTER(c.c_longlong)],
+        "hx_ensemble_comoments": [P, c.c_char_p, c.c_int, c.c_int, c.c_char_p, c.c_int, c.c_int, dp, dp, dp,
+                                  dp, dp, dp, c.POINTER(c.c_ulonglong), c.POINTER(c.c_longlong)],
         "hx_series_define": [P, c.c_char_p, c.c_char_p, c.c_void_p],
         "hx_series_drop": [P, c.c_char_p],
         "hx_series_list": [P, c.POINTER(c.POINTER(c.c_char_p)), c.POINTER(c.POINTER(c.c_int)),
@@ -221,5 +223,5 @@ ABI_SYMBOLS = ["hx_backend", "hx_build_info", "hx_last_error", "hx_newcore", "hx
                "hx_cost_models_export", "hx_cost_models_load", "hx_set_prewarm", "hx_last_run_prewarmed",
                "hx_member_score", "hx_ensemble_quantiles", "hx_member_metrics", "hx_metric_quantiles",
                "hx_ensemble_probabilities", "hx_metric_probabilities",
-               "hx_ensemble_moments", "hx_metric_moments",
+               "hx_ensemble_moments", "hx_metric_moments", "hx_ensemble_comoments",
                "hx_series_define", "hx_series_drop", "hx_series_list"]

@@ -171,6 +171,98 @@ class Moments:
         return "Moments(rows=%d, against=%r)" % (self.shift.size, self.names)
 
 
+class CoMoments:
+    """What hx_ensemble_comoments returns, and the statistics it defines (include/hector_amd.h), all
+    in float64.  Window A has na rows (years_a), window B nb rows (years_b); participation is by
+    complete cases, so there is ONE wsum (W) and ONE n_part.
+    Raw: shift_a[na], shift_b[nb] = the rows' smallest participating values; sums_a[na, 2],
+    sums_b[nb, 2] = (sum q d, sum q d d); cross[na, nb] = sum (q d_a) d_b; symmetric: B is A.
+    Derived: mean_a = shift_a + S_a/W, var_a = T_a/W - (S_a/W)**2 (population), mean_b / var_b
+    likewise; cov = cross/W - (S_a/W)(S_b/W); corr = cov / sqrt(var_a var_b); slope = cov / var_b
+    (the regression of A's year on B's year).  corr is NaN where var_a or var_b is 0, slope where
+    var_b is 0; everything is NaN when nobody takes part."""
+
+    def __init__(self, shift_a, sums_a, shift_b, sums_b, cross, wsum, n_part, years_a=None, years_b=None,
+                 symmetric=False):
+        self.shift_a = np.asarray(shift_a, dtype=np.float64).reshape(-1)
+        self.shift_b = np.asarray(shift_b, dtype=np.float64).reshape(-1)
+        na, nb = self.shift_a.size, self.shift_b.size
+        self.sums_a = np.asarray(sums_a, dtype=np.float64).reshape(-1, 2)
+        self.sums_b = np.asarray(sums_b, dtype=np.float64).reshape(-1, 2)
+        self.cross = np.asarray(cross, dtype=np.float64)
+        if self.sums_a.shape[0] != na or self.sums_b.shape[0] != nb or self.cross.shape != (na, nb):
+            raise HectorAmdError("CoMoments: sums_a [na, 2], sums_b [nb, 2] and cross [na, nb] must match the shifts")
+        self.wsum = int(wsum)
+        self.n_part = int(n_part)
+        self.years_a = np.arange(na) if years_a is None else np.asarray(years_a)
+        self.years_b = np.arange(nb) if years_b is None else np.asarray(years_b)
+        self.symmetric = bool(symmetric)
+
+    def _over_w(self, x):
+        return x / np.float64(self.wsum) if self.wsum > 0 else np.full(np.shape(x), np.nan)
+
+    @property
+    def mean_a(self):
+        return self.shift_a + self._over_w(self.sums_a[:, 0])
+
+    @property
+    def mean_b(self):
+        return self.shift_b + self._over_w(self.sums_b[:, 0])
+
+    @property
+    def var_a(self):
+        s = self._over_w(self.sums_a[:, 0])
+        return self._over_w(self.sums_a[:, 1]) - s * s
+
+    @property
+    def var_b(self):
+        s = self._over_w(self.sums_b[:, 0])
+        return self._over_w(self.sums_b[:, 1]) - s * s
+
+    @property
+    def cov(self):
+        return self._over_w(self.cross) - np.outer(self._over_w(self.sums_a[:, 0]), self._over_w(self.sums_b[:, 0]))
+
+    @property
+    def corr(self):
+        v = np.outer(self.var_a, self.var_b)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(v > 0, self.cov / np.sqrt(np.where(v > 0, v, 1.0)), np.nan)
+
+    @property
+    def slope(self):
+        vb = np.broadcast_to(self.var_b[None, :], self.cross.shape)
+        ok = (vb > 0) & (self.var_a[:, None] == self.var_a[:, None])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(ok, self.cov / np.where(vb > 0, vb, 1.0), np.nan)
+
+    def pca(self, k):
+        """The k leading principal components of a symmetric result (numpy.linalg.eigh of cov, on
+        the host) -> (eigenvalues [k] descending, their share of the trace [k], patterns [k, na]).
+        The sign of a pattern is fixed so that its largest-magnitude component is positive."""
+        if not self.symmetric:
+            raise HectorAmdError("CoMoments.pca: needs a symmetric result (comoments(var, dates) without var_b)")
+        na = self.shift_a.size
+        k = int(k)
+        if k < 1 or k > na:
+            raise HectorAmdError("CoMoments.pca: k must lie in 1..%d" % na)
+        cov = self.cov
+        if not np.isfinite(cov).all():
+            raise HectorAmdError("CoMoments.pca: the covariance is not finite (nobody takes part)")
+        val, vec = np.linalg.eigh(cov)
+        order = np.argsort(val)[::-1][:k]
+        val, pat = val[order], vec[:, order].T.copy()
+        for p in pat:
+            if p[np.argmax(np.abs(p))] < 0:
+                p *= -1.0
+        tr = np.trace(cov)
+        return val, (val / tr if tr > 0 else np.full(k, np.nan)), pat
+
+    def __repr__(self):
+        return "CoMoments(na=%d, nb=%d, symmetric=%r, n_part=%d)" % (self.shift_a.size, self.shift_b.size,
+                                                                     self.symmetric, self.n_part)
+
+
 class Core:
     """An N-member ensemble core bound to one GPU (device=) or sharded over a list of GPUs
     (devices=[...]: contiguous member blocks, hx_newcore_devices)."""
@@ -689,6 +781,40 @@ class Core:
             "metric_moments",
             lambda *a: self._lib.hx_metric_moments(self._h, var.encode(), ctypes.byref(arr), ns, *a),
             ns, weights, against)
+
+    def comoments(self, var_a, dates_a=None, var_b=None, dates_b=None, weights=None):
+        """Year-by-year weighted co-moments of two windows over the ensemble, on the device
+        (hx_ensemble_comoments) -> CoMoments: the covariance / correlation matrix of the years
+        dates_a of var_a against the years dates_b of var_b.  var_b=None and dates_b=None is the
+        symmetric call (B is A; only the blocks on or above the diagonal are computed and mirrored:
+        an exactly symmetric matrix; CoMoments.pca);
+        dates_b alone means var_b = var_a.  A member takes part if its weight is not 0 and none of
+        its values in either window is NaN (complete cases: one W, one n_part)."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        w = self._weights(weights, "comoments")
+        whole = (self.strtdate, self.current_date)
+        a0, a1 = whole if dates_a is None else (int(min(dates_a)), int(max(dates_a)))
+        sym = var_b is None and dates_b is None
+        if sym:
+            b0, b1, vb = a0, a1, None
+        else:
+            b0, b1 = whole if dates_b is None else (int(min(dates_b)), int(max(dates_b)))
+            vb = (var_a if var_b is None else var_b).encode()
+        for y0, y1 in ((a0, a1), (b0, b1)):   # (nothing is sized from a window outside the scenario)
+            if y0 < self.strtdate or y1 > self.enddate or y1 < y0:
+                raise HectorAmdError("hx_ensemble_comoments: dates must lie between startDate and the "
+                                     "current date")
+        na, nb = a1 - a0 + 1, b1 - b0 + 1
+        shift_a, sums_a = np.empty(na), np.zeros((na, 2))
+        shift_b, sums_b = np.empty(nb), np.zeros((nb, 2))
+        cross = np.zeros((na, nb))
+        wsum, npart = ctypes.c_ulonglong(0), ctypes.c_longlong(0)
+        self._ck(self._lib.hx_ensemble_comoments(
+            self._h, var_a.encode(), a0, a1, vb, b0, b1, w.ctypes.data_as(dp) if w is not None else None,
+            shift_a.ctypes.data_as(dp), sums_a.ctypes.data_as(dp), shift_b.ctypes.data_as(dp),
+            sums_b.ctypes.data_as(dp), cross.ctypes.data_as(dp), ctypes.byref(wsum), ctypes.byref(npart)))
+        return CoMoments(shift_a, sums_a, shift_b, sums_b, cross, wsum.value, npart.value,
+                         np.arange(a0, a1 + 1), np.arange(b0, b1 + 1), symmetric=sym)
 
     def hold(self, name, var):
         """Keep the trajectory of every member of `var` -- a recorded output, a derived diagnostic

@@ -84,6 +84,12 @@ int hx_mom_chunks(int n);
 hipError_t hx_launch_moments(const double *var, int n, int npad, int iy0, int nrows, const double *qd,
                              const double *e, int npred, const double *shift, double *part, double *out,
                              hipStream_t st);
+hipError_t hx_launch_co_mask(const double *va, int ia0, int na, const double *vb, int ib0, int nb, int npad,
+                             unsigned long long *q_lane, double *qd_lane, hipStream_t st);
+int hx_co_chunks(int n, int na, int nb);
+hipError_t hx_launch_co_gram(const double *va, int ia0, int na, const double *vb, int ib0, int nb, int n,
+                             int npad, int sym, const double *qd, const double *shift_a,
+                             const double *shift_b, double *part, double *cross, hipStream_t st);
 #endif
 
 #ifndef HX_HOST_EMULATION
@@ -571,6 +577,7 @@ void EnsembleCore::free_device() {
   fr(d_spin_rec_); d_spin_rec_ = nullptr;
   fr(d_score_); fr(d_q_); fr(d_qstate_); fr(d_qhist_); fr(d_metplan_); fr(d_met_); fr(d_bin_);
   fr(d_mom_); d_mom_ = nullptr; mom_cap_ = 0; mom_src_ = nullptr;
+  fr(d_comom_); d_comom_ = nullptr; comom_cap_ = 0; co_a_ = nullptr;
   d_score_ = nullptr; d_q_ = d_qstate_ = d_qhist_ = nullptr;
   d_metplan_ = nullptr; d_met_ = nullptr; d_bin_ = nullptr;
   score_cap_ = qstate_cap_ = qhist_cap_ = metplan_cap_ = met_cap_ = bin_cap_ = 0; q_src_ = nullptr;
@@ -3322,6 +3329,120 @@ void EnsembleCore::mom_finish(const double *shift_host, double *sums_host) {
   check(hipMemcpyAsync(sums_host, b.out, 8 * (size_t)ny * nc, hipMemcpyDeviceToHost, stream_), "moments fetch");
   check(hipStreamSynchronize(stream_), "moments sync");
   mom_src_ = nullptr;
+#endif
+}
+
+// ---- year-by-year co-moments of two windows (hx_ensemble_comoments) --------------------------------
+
+namespace {
+// d_comom_ in 8-byte words.  R = na + nb rows (na in the symmetric call: B is A).  The partials of
+// the Gram kernel are bounded: hx_co_chunks() grows the member chunk until chunks x na x nb stays
+// within 8 Mi doubles (64 MiB), whatever the windows; the rest is 2 npad + n + 8 R + na nb words
+// and the row sums' partials, 2 R hx_mom_chunks(n).
+struct CoBuf {
+  unsigned long long *q_lane, *q_mem, *st;
+  double *qd_lane, *shift, *mpart, *mout, *gpart, *cross;
+  size_t words, lane_words;
+  CoBuf(unsigned long long *base, int n, int npad, int na, int nb, int rows, int mchunks, int gchunks) {
+    const size_t N = (size_t)n, P = (size_t)npad, R = (size_t)rows, C = (size_t)na * (size_t)nb;
+    q_lane = base;                                              // [npad] } zeroed before the prepare
+    qd_lane = reinterpret_cast<double *>(q_lane + P);           // [npad] } kernel: padding lanes 0
+    lane_words = 2 * P;
+    q_mem = base + lane_words;                                  // [n]
+    st = q_mem + N;                                             // [R][4]
+    shift = reinterpret_cast<double *>(st + 4 * R);             // [R]
+    mpart = shift + R;                                          // [R][mchunks][2]
+    mout = mpart + 2 * R * (size_t)mchunks;                     // [R][2]
+    cross = mout + 2 * R;                                       // [na][nb]
+    gpart = cross + C;                                          // [gchunks][na][nb]
+    words = lane_words + N + 7 * R + 2 * R * (size_t)mchunks + C + C * (size_t)gchunks;
+  }
+};
+}  // namespace
+
+// The windows' capabilities and dates against this core, before anything is sized from them.
+void EnsembleCore::comom_check(const std::string &cap_a, int a0, int a1, const std::string *cap_b, int b0,
+                               int b1) {
+  const char *fn = "hx_ensemble_comoments";
+#ifdef HX_HOST_EMULATION
+  (void)cap_a; (void)a0; (void)a1; (void)cap_b; (void)b0; (void)b1;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  (void)q_check(cap_a, a0, a1, 1, fn);
+  if (cap_b) (void)q_check(*cap_b, b0, b1, 1, fn);
+#endif
+}
+
+// Validates both windows (nothing is changed by a refused call), brings q[n_] to lane order, zeroes
+// it where a value of either window is NaN, and reduces {~min key, max key, sum q, count} of every
+// row -- A's na rows, then B's nb unless cap_b is nullptr -- into st_host[rows][4].
+void EnsembleCore::comom_begin(const std::string &cap_a, int a0, int a1, const std::string *cap_b, int b0,
+                               int b1, const unsigned long long *q, unsigned long long *st_host) {
+  const char *fn = "hx_ensemble_comoments";
+#ifdef HX_HOST_EMULATION
+  (void)cap_a; (void)a0; (void)a1; (void)cap_b; (void)b0; (void)b1; (void)q; (void)st_host;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  const double *sa = q_check(cap_a, a0, a1, 1, fn), *sb = sa;
+  if (cap_b) {
+    sb = q_check(*cap_b, b0, b1, 1, fn);
+    sa = q_check(cap_a, a0, a1, 1, fn);   // (two derived blocks are kept: B's has not displaced A's)
+  }
+  if (npad_ % 32) throw std::runtime_error(std::string(fn) + ": the lane count is not a multiple of 32");
+  sync();
+  const bool sym = cap_b == nullptr;
+  const int na = a1 - a0 + 1, nb = sym ? na : b1 - b0 + 1, rows = sym ? na : na + nb;
+  const int ia0 = a0 - scen_.start, ib0 = sym ? ia0 : b0 - scen_.start;
+  const int mchunks = hx_mom_chunks(n_), gchunks = hx_co_chunks(n_, na, nb);
+  const size_t words = CoBuf(nullptr, n_, npad_, na, nb, rows, mchunks, gchunks).words;
+  if (words > comom_cap_) {
+    if (d_comom_) (void)hipFree(d_comom_);
+    d_comom_ = nullptr; comom_cap_ = 0;
+    check(hipMalloc(&d_comom_, 8 * words), "hipMalloc co-moments");
+    comom_cap_ = words;
+  }
+  CoBuf b(d_comom_, n_, npad_, na, nb, rows, mchunks, gchunks);
+  check(hipMemsetAsync(b.q_lane, 0, 8 * b.lane_words, stream_), "co-moments lanes");
+  check(hipMemsetAsync(b.st, 0, 8 * 4 * (size_t)rows, stream_), "co-moments state");
+  check(hipMemcpyAsync(b.q_mem, q, 8 * (size_t)n_, hipMemcpyHostToDevice, stream_), "co-moments weights");
+  check(hx_launch_mom_prepare(b.q_mem, nullptr, 0, n_, npad_, d_lane_of_member_, nullptr, b.q_lane, b.qd_lane,
+                              nullptr, stream_), "co-moments prepare kernel");
+  check(hx_launch_co_mask(sa, ia0, na, sb, ib0, sym ? 0 : nb, npad_, b.q_lane, b.qd_lane, stream_),
+        "co-moments mask kernel");
+  check(hx_launch_q_minmax(sa, n_, npad_, ia0, na, b.q_lane, b.st, stream_), "co-moments min kernel");
+  if (!sym)
+    check(hx_launch_q_minmax(sb, n_, npad_, ib0, nb, b.q_lane, b.st + 4 * (size_t)na, stream_),
+          "co-moments min kernel");
+  check(hipMemcpyAsync(st_host, b.st, 8 * 4 * (size_t)rows, hipMemcpyDeviceToHost, stream_), "co-moments fetch");
+  check(hipStreamSynchronize(stream_), "co-moments sync");   // (q is the caller's until here)
+  co_a_ = sa; co_b_ = sb; co_ia0_ = ia0; co_ib0_ = ib0; co_na_ = na; co_nb_ = nb; co_sym_ = sym;
+#endif
+}
+
+// the sums of this core's members about shift_host[rows] (the rows' smallest participating values
+// over ALL shards): sums_host[rows][2] and cross_host[na][nb]
+void EnsembleCore::comom_finish(const double *shift_host, double *sums_host, double *cross_host) {
+#ifdef HX_HOST_EMULATION
+  (void)shift_host; (void)sums_host; (void)cross_host;
+  throw std::runtime_error(std::string("hx_ensemble_comoments") + kEmulRefusal);
+#else
+  if (!co_a_) throw std::runtime_error("co-moment sums without comom_begin");
+  const int na = co_na_, nb = co_nb_, rows = co_sym_ ? na : na + nb;
+  CoBuf b(d_comom_, n_, npad_, na, nb, rows, hx_mom_chunks(n_), hx_co_chunks(n_, na, nb));
+  const size_t C = (size_t)na * (size_t)nb;
+  check(hipMemcpyAsync(b.shift, shift_host, 8 * (size_t)rows, hipMemcpyHostToDevice, stream_), "co-moments shifts");
+  check(hx_launch_moments(co_a_, n_, npad_, co_ia0_, na, b.qd_lane, nullptr, 0, b.shift, b.mpart, b.mout,
+                          stream_), "co-moments row sums");
+  if (!co_sym_)
+    check(hx_launch_moments(co_b_, n_, npad_, co_ib0_, nb, b.qd_lane, nullptr, 0, b.shift + na,
+                            b.mpart + 2 * (size_t)na * (size_t)hx_mom_chunks(n_), b.mout + 2 * (size_t)na,
+                            stream_), "co-moments row sums");
+  check(hx_launch_co_gram(co_a_, co_ia0_, na, co_b_, co_ib0_, nb, n_, npad_, co_sym_ ? 1 : 0, b.qd_lane, b.shift,
+                          co_sym_ ? b.shift : b.shift + na, b.gpart, b.cross, stream_), "co-moments Gram kernel");
+  check(hipMemcpyAsync(sums_host, b.mout, 8 * 2 * (size_t)rows, hipMemcpyDeviceToHost, stream_), "co-moments fetch");
+  check(hipMemcpyAsync(cross_host, b.cross, 8 * C, hipMemcpyDeviceToHost, stream_), "co-moments fetch");
+  check(hipStreamSynchronize(stream_), "co-moments sync");
+  co_a_ = nullptr;
 #endif
 }
 

@@ -186,6 +186,16 @@ class EnsembleCore {
                  const unsigned long long *q, const double *pred, int npred, const double *c,
                  unsigned long long *st_host, const char *fn);
   void mom_finish(const double *shift_host, double *sums_host);
+  // year-by-year co-moments (hx_ensemble_comoments), in the same two steps.  comom_begin validates
+  // both windows (cap_b == nullptr: the symmetric call, B is A), brings q[n_] to lane order, zeroes
+  // it where any value of either window is NaN (complete cases) and reduces the rows' records into
+  // st_host[na (+ nb)][4]; comom_finish takes the rows' shifts over ALL shards and returns this
+  // core's sums_host[na (+ nb)][2] and cross_host[na][nb].  No prepare(), no spinup, not dirtied.
+  // comom_check is the validation alone: the caller sizes its buffers from windows that passed it.
+  void comom_check(const std::string &cap_a, int a0, int a1, const std::string *cap_b, int b0, int b1);
+  void comom_begin(const std::string &cap_a, int a0, int a1, const std::string *cap_b, int b0, int b1,
+                   const unsigned long long *q, unsigned long long *st_host);
+  void comom_finish(const double *shift_host, double *sums_host, double *cross_host);
   // ---- held and derived per-member series (hx_series_define in hector_amd.h) ----------------------
   void series_define(const std::string &name, const std::string &a, const hx_series_op &op);
   void series_drop(const std::string &name);
@@ -337,6 +347,11 @@ class EnsembleCore {
   size_t mom_cap_ = 0;
   const double *mom_src_ = nullptr;           // the block mom_begin prepared for mom_finish
   int mom_iy0_ = 0, mom_ny_ = 0, mom_npred_ = 0;
+  unsigned long long *d_comom_ = nullptr;     // scratch of hx_ensemble_comoments (CoBuf in ensemble_core.cpp)
+  size_t comom_cap_ = 0;
+  const double *co_a_ = nullptr, *co_b_ = nullptr;   // the windows comom_begin prepared for comom_finish
+  int co_ia0_ = 0, co_ib0_ = 0, co_na_ = 0, co_nb_ = 0;
+  bool co_sym_ = false;
   void mom_begin_block(const double *src, int iy0, int ny, const unsigned long long *q, const double *pred,
                        int npred, const double *c, unsigned long long *st_host);
   int metric_check(const std::string &capability, const hx_metric *specs, int nspecs, const char *fn,

@@ -412,6 +412,15 @@ int hx_metric_moments(hx_core *core, const char *capability, const hx_metric *sp
   HX_TRY(core->core->moments(capability, 0, 0, specs, nspecs, weights, predictors, npred, shift, sums, wsum,
                              n_part))
 }
+int hx_ensemble_comoments(hx_core *core, const char *cap_a, int a_year0, int a_year1, const char *cap_b,
+                          int b_year0, int b_year1, const double *weights, double *shift_a, double *sums_a,
+                          double *shift_b, double *sums_b, double *cross, unsigned long long *wsum,
+                          long long *n_part) {
+  if (!cap_a || !shift_a || !sums_a || !cross || (cap_b && (!shift_b || !sums_b)))
+    return fail("hx_ensemble_comoments: null argument");
+  HX_TRY(core->core->comoments(cap_a, a_year0, a_year1, cap_b, b_year0, b_year1, weights, shift_a, sums_a,
+                               shift_b, sums_b, cross, wsum, n_part))
+}
 int hx_series_define(hx_core *core, const char *name, const char *a, const hx_series_op *op) {
   if (!name || !a || !op) return fail("hx_series_define: null argument");
   HX_TRY(core->core->series_define(name, a, *op))

@@ -957,4 +957,185 @@ hipError_t hx_launch_moments(const double *var, int n, int npad, int iy0, int nr
                      out);
   return hipGetLastError();
 }
+
+// ===========================================================================
+// Year-by-year co-moments of two windows of rows (hx_ensemble_comoments in hector_amd.h defines the
+// sums): cross[a][b] = sum over the members of (q d_a) d_b, a Gram matrix contracted over the member
+// axis on the fp64 matrix pipe.  Four steps:
+//   hx_mom_prepare_kernel  (npred = 0) the integer weights to lane order, padding lanes 0
+//   hx_co_mask_kernel      lane-local: q = 0 where any row of either window is NaN (complete cases)
+//   hx_q_minmax_kernel     with that q: every row's smallest participating value, W and the count;
+//                          hx_moments_kernel<0> then gives the rows' own sums
+//   hx_co_gram_kernel      grid (member chunks, row-tile pairs), 4 wavefronts: a workgroup holds an
+//                          HXC_TILE x HXC_TILE block of the matrix, a wavefront 2 x 2 tiles of
+//                          16 x 16 in 16 accumulator registers a lane.  v_mfma_f64_16x16x4_f64 takes
+//                          A[i][k] from lane (i = lane & 15, k = lane >> 4) and B[k][j] from lane
+//                          (j = lane & 15, k = lane >> 4); the four k of one instruction may be ANY
+//                          four members, so lane (c, g) owns the HXC_PER consecutive members
+//                          m0 + HXC_PER g .. of row a0 + c -- half a cache line, four 16-byte loads
+//                          from the row as it sits in memory -- and instruction j contracts the
+//                          members m0 + HXC_PER g + j, g < 4.  The weight, the shifts and the
+//                          participation select are applied in registers on the way in: no LDS.
+// Split-k: a chunk of members per workgroup, one partial block per chunk, and hx_co_reduce_kernel
+// adds the chunks in ascending order (no floating atomics: the same bits from call to call).  The
+// symmetric call computes the tile pairs on or above the diagonal only and the reduce mirrors the
+// entries above the diagonal, so cross is symmetric bit for bit.
+// ===========================================================================
+#define HXC_TILE 64       // rows of either window per workgroup
+#define HXC_CHUNK 1024    // members per workgroup at the least; the host takes a multiple of it
+#define HXC_PER 8         // consecutive members of a row per lane and step (16, a full line: measured slower)
+#define HXC_STEP (4 * HXC_PER)   // members per wavefront and step
+#define HXC_PART_WORDS (8u << 20)   // the host grows the chunk until the partials fit (64 MiB)
+
+// q_lane / qd_lane (lane order, padding lanes 0): zeroed where a value of any of the na rows of A
+// or the nb rows of B is NaN; a lane whose q is 0 already reads nothing
+__global__ __launch_bounds__(256) void hx_co_mask_kernel(const double *__restrict__ va, int ia0, int na,
+                                                         const double *__restrict__ vb, int ib0, int nb,
+                                                         int npad, hxq_u64 *__restrict__ q_lane,
+                                                         double *__restrict__ qd_lane) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= npad) return;
+  if (!q_lane[i]) return;
+  bool bad = false;
+  const double *pa = va + (size_t)ia0 * npad + i;
+#pragma unroll 8
+  for (int r = 0; r < na; ++r) { const double x = pa[(size_t)r * npad]; bad = bad || x != x; }
+  const double *pb = vb + (size_t)ib0 * npad + i;
+#pragma unroll 8
+  for (int r = 0; r < nb; ++r) { const double x = pb[(size_t)r * npad]; bad = bad || x != x; }
+  if (bad) { q_lane[i] = 0; qd_lane[i] = 0.0; }
+}
+
+// part[(chunk * na + a) * nb + b]; mchunk: a multiple of HXC_STEP; mend: the members to go through,
+// <= npad and a multiple of HXC_STEP (lanes >= n hold qd = 0)
+__global__ __launch_bounds__(256) void hx_co_gram_kernel(const double *__restrict__ va, int ia0, int na,
+                                                         const double *__restrict__ vb, int ib0, int nb,
+                                                         int npad, int mend, int mchunk, int sym,
+                                                         const double *__restrict__ qd,
+                                                         const double *__restrict__ shift_a,
+                                                         const double *__restrict__ shift_b,
+                                                         double *__restrict__ part) {
+  typedef double d4 __attribute__((ext_vector_type(4)));
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  static_assert(HXC_TILE == 64 && HXC_PER % 2 == 0, "four wavefronts of 2 x 2 tiles; 16-byte loads");
+  const int nbb = (nb + HXC_TILE - 1) / HXC_TILE;
+  const int bi = (int)blockIdx.y / nbb, bj = (int)blockIdx.y - bi * nbb;
+  if (sym && bj < bi) return;   // (the whole workgroup: the reduce reads the mirrored entry)
+  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
+  // (a diagonal block's lower 32 x 32 quadrant lies below the diagonal: the reduce never reads it)
+  if (sym && bj == bi && wave == 2) return;
+  const int a0 = bi * HXC_TILE + 32 * (wave >> 1), b0 = bj * HXC_TILE + 32 * (wave & 1);
+  // rows past the window are read as its last row (inside the block) and not stored
+  const double *ra[2], *rb[2];
+  double ca[2], cb[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int a = min(a0 + 16 * t + c, na - 1), b = min(b0 + 16 * t + c, nb - 1);
+    ra[t] = va + (size_t)(ia0 + a) * npad + HXC_PER * g;
+    rb[t] = vb + (size_t)(ib0 + b) * npad + HXC_PER * g;
+    ca[t] = shift_a[a];
+    cb[t] = shift_b[b];
+  }
+  const double *qp = qd + HXC_PER * g;
+  d4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = d4{0, 0, 0, 0};
+  const int mbeg = (int)blockIdx.x * mchunk, mstop = min(mbeg + mchunk, mend);
+  for (int m = mbeg; m < mstop; m += HXC_STEP) {
+    double w[HXC_PER], xa[2][HXC_PER], xb[2][HXC_PER];
+#pragma unroll
+    for (int j = 0; j < HXC_PER; j += 2) {
+      const d2 v = *reinterpret_cast<const d2 *>(qp + m + j);
+      w[j] = v.x; w[j + 1] = v.y;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const d2 u = *reinterpret_cast<const d2 *>(ra[t] + m + j);
+        const d2 s = *reinterpret_cast<const d2 *>(rb[t] + m + j);
+        xa[t][j] = u.x; xa[t][j + 1] = u.y;
+        xb[t][j] = s.x; xb[t][j + 1] = s.y;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < HXC_PER; ++j) {
+      const bool on = w[j] > 0.0;   // (a participant: none of its values is NaN, the shifts are members' values)
+      double A[2], B[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        A[t] = on ? w[j] * (xa[t][j] - ca[t]) : 0.0;
+        B[t] = on ? xb[t][j] - cb[t] : 0.0;
+      }
+#pragma unroll
+      for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj)
+          acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(A[ti], B[tj], acc[ti][tj], 0, 0, 0);
+    }
+  }
+  // D[(lane >> 4) + 4 r][lane & 15]
+  double *po = part + (size_t)blockIdx.x * (size_t)na * (size_t)nb;
+#pragma unroll
+  for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int a = a0 + 16 * ti + g + 4 * r, b = b0 + 16 * tj + c;
+        if (a < na && b < nb) po[(size_t)a * nb + b] = acc[ti][tj][r];
+      }
+}
+
+// cross[a][b] = the chunks' partials added in ascending chunk order; sym: the entry below the
+// diagonal is the one above it
+__global__ __launch_bounds__(256) void hx_co_reduce_kernel(const double *__restrict__ part, int nchunks, int na,
+                                                           int nb, int sym, double *__restrict__ cross) {
+  const size_t total = (size_t)na * (size_t)nb;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  int a = (int)(idx / (size_t)nb), b = (int)(idx - (size_t)a * nb);
+  if (sym && a > b) { const int t = a; a = b; b = t; }
+  const double *p = part + (size_t)a * nb + b;
+  double s = 0.0;
+  for (int ch = 0; ch < nchunks; ++ch) s += p[(size_t)ch * total];
+  cross[idx] = s;
+}
+
+hipError_t hx_launch_co_mask(const double *va, int ia0, int na, const double *vb, int ib0, int nb, int npad,
+                             unsigned long long *q_lane, double *qd_lane, hipStream_t st) {
+  hipLaunchKernelGGL(hx_co_mask_kernel, dim3((npad + 255) / 256), dim3(256), 0, st, va, ia0, na, vb, ib0, nb,
+                     npad, q_lane, qd_lane);
+  return hipGetLastError();
+}
+// the members a workgroup takes: the smallest multiple of HXC_CHUNK with which the partials of an
+// na x nb matrix stay within HXC_PART_WORDS doubles (one chunk, whatever its size, if even two do not)
+int hx_co_chunk(int n, int na, int nb) {
+  const size_t cell = (size_t)na * (size_t)nb;
+  size_t maxchunks = HXC_PART_WORDS / cell;
+  if (maxchunks < 1) maxchunks = 1;
+  const size_t base = ((size_t)n + HXC_CHUNK - 1) / HXC_CHUNK;   // chunks of HXC_CHUNK
+  const size_t k = (base + maxchunks - 1) / maxchunks;
+  return (int)((k ? k : 1) * HXC_CHUNK);
+}
+int hx_co_chunks(int n, int na, int nb) {
+  const int ch = hx_co_chunk(n, na, nb);
+  return (n + ch - 1) / ch;
+}
+// part: [hx_co_chunks][na][nb] scratch; cross: [na][nb]; npad must be a multiple of HXC_STEP
+hipError_t hx_launch_co_gram(const double *va, int ia0, int na, const double *vb, int ib0, int nb, int n,
+                             int npad, int sym, const double *qd, const double *shift_a,
+                             const double *shift_b, double *part, double *cross, hipStream_t st) {
+  if (npad % HXC_STEP || n > npad || na < 1 || nb < 1) return hipErrorInvalidValue;
+  const int chunk = hx_co_chunk(n, na, nb), nchunks = hx_co_chunks(n, na, nb);
+  const int mend = (n + HXC_STEP - 1) / HXC_STEP * HXC_STEP;
+  const int nba = (na + HXC_TILE - 1) / HXC_TILE, nbb = (nb + HXC_TILE - 1) / HXC_TILE;
+  hipLaunchKernelGGL(hx_co_gram_kernel, dim3(nchunks, nba * nbb), dim3(256), 0, st, va, ia0, na, vb, ib0, nb,
+                     npad, mend, chunk, sym, qd, shift_a, shift_b, part);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  const size_t total = (size_t)na * (size_t)nb;
+  hipLaunchKernelGGL(hx_co_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part, nchunks,
+                     na, nb, sym, cross);
+  return hipGetLastError();
+}
 #endif  // !HX_HOST_EMULATION

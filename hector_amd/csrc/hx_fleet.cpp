@@ -613,6 +613,54 @@ void Fleet::moments(const std::string &cap, int year0, int year1, const hx_metri
   }
 }
 
+void Fleet::comoments(const std::string &cap_a, int a0, int a1, const char *cap_b, int b0, int b1,
+                      const double *weights, double *shift_a, double *sums_a, double *shift_b, double *sums_b,
+                      double *cross, unsigned long long *wsum, long long *n_part) {
+  check_poison();
+  const char *fn = "hx_ensemble_comoments";
+  refuse_processes(fn, "co-moments");
+  std::vector<unsigned long long> q;
+  quantise_weights(weights, fn, q);
+  if (!weights) q.assign((size_t)n_, 1ull);
+  const bool sym = cap_b == nullptr;
+  const std::string sb = sym ? std::string() : std::string(cap_b);
+  // (the windows are held to the scenario's rows before anything is sized from them)
+  use(shards_.front());
+  shards_.front().core->comom_check(cap_a, a0, a1, sym ? nullptr : &sb, b0, b1);
+  const size_t na = (size_t)(a1 - a0 + 1), nb = sym ? na : (size_t)(b1 - b0 + 1), R = sym ? na : na + nb;
+  // 1. every shard's mask, and the minimum, W and count of every row; the minimum over the shards is
+  //    the shift.  (Complete cases: W and the count are those of any row.)
+  std::vector<unsigned long long> st(4 * R, 0ull), part(4 * R);
+  for (Shard &s : shards_) {
+    use(s);
+    s.core->comom_begin(cap_a, a0, a1, sym ? nullptr : &sb, b0, b1, q.data() + s.offset, part.data());
+    for (size_t y = 0; y < R; ++y) {
+      if (!part[4 * y + 3]) continue;
+      st[4 * y] = std::max(st[4 * y], part[4 * y]);
+      st[4 * y + 2] += part[4 * y + 2];
+      st[4 * y + 3] += part[4 * y + 3];
+    }
+  }
+  std::vector<double> shift(R);
+  for (size_t y = 0; y < R; ++y) shift[y] = st[4 * y + 3] ? hxq_key_to_double(~st[4 * y]) : std::nan("");
+  // 2. every shard's sums about the common shifts, added in ascending shard order
+  std::vector<double> sums(2 * R, 0.0), sp(2 * R), cp(na * nb);
+  std::fill(cross, cross + na * nb, 0.0);
+  for (Shard &s : shards_) {
+    use(s);
+    s.core->comom_finish(shift.data(), sp.data(), cp.data());
+    for (size_t i = 0; i < 2 * R; ++i) sums[i] += sp[i];
+    for (size_t i = 0; i < na * nb; ++i) cross[i] += cp[i];
+  }
+  if (sym) for (size_t a = 0; a < na; ++a) sums[2 * a + 1] = cross[a * nb + a];
+  std::copy(shift.begin(), shift.begin() + na, shift_a);
+  std::copy(sums.begin(), sums.begin() + 2 * na, sums_a);
+  if (shift_b) std::copy(shift.begin() + (sym ? 0 : na), shift.begin() + (sym ? na : R), shift_b);
+  if (sums_b) std::copy(sums.begin() + (sym ? 0 : 2 * na), sums.begin() + (sym ? 2 * na : 2 * R), sums_b);
+  if (wsum) *wsum = st[2];
+  if (n_part) *n_part = (long long)st[3];
+}
+
 void Fleet::series_define(const std::string &name, const std::string &a, const hx_series_op &op) {
   HX_EACH(series_define(name, a, op))
 }

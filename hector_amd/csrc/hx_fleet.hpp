@@ -113,6 +113,12 @@ class Fleet {
   void moments(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
                const double *weights, const double *predictors, int npred, double *shift, double *sums,
                unsigned long long *wsum, long long *n_part);
+  // hx_ensemble_comoments (cap_b == nullptr: the symmetric call): the weights quantised once; the
+  // shards' masks and row minima, then their minimum, W and count; then the shards' sums and cross
+  // sums about the common shifts, added in ascending shard order
+  void comoments(const std::string &cap_a, int a0, int a1, const char *cap_b, int b0, int b1,
+                 const double *weights, double *shift_a, double *sums_a, double *shift_b, double *sums_b,
+                 double *cross, unsigned long long *wsum, long long *n_part);
   // hx_series_define / hx_series_drop: forwarded to every shard (the kernels are lane-local: nothing
   // crosses shards); hx_series_list: the first shard's list (all shards hold the same names)
   void series_define(const std::string &name, const std::string &a, const hx_series_op &op);

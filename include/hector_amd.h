@@ -437,6 +437,57 @@ int hx_metric_moments(hx_core *core, const char *capability, const hx_metric *sp
                       const double *weights, const double *predictors, int npred, double *shift,
                       double *sums, unsigned long long *wsum, long long *n_part);
 
+/* Year-by-year co-moments of two windows of rows over the ensemble: what a full year x year
+ * covariance or correlation matrix needs -- an emergent constraint as a map over (observed year,
+ * projected year), the EOFs / PCA of the trajectories, the auto-covariance of a residual -- without
+ * the trajectories leaving the device.  No counterpart in the reference.
+ *   Window A: the rows a_year0..a_year1 of cap_a (na rows); window B: b_year0..b_year1 of cap_b (nb).
+ *   cap_a and cap_b are per-member variables on the device like every other verb's `capability`.
+ *   cap_b NULL is the SYMMETRIC call: B is A (b_year0, b_year1 are ignored; shift_b, sums_b may be
+ *   NULL and receive A's values if they are not).
+ *   weights[n_members] (member order) or NULL.
+ * The weights become the integers q exactly as in hx_ensemble_quantiles (wmax over the WHOLE
+ * ensemble; NULL: q_m = 1).  Participation is by COMPLETE CASES: a member takes part in the call if
+ * q_m > 0 and none of its values in the na rows of A and the nb rows of B is NaN.  The call has
+ * therefore ONE W = sum q (an exact integer) and ONE n_part.  This differs from
+ * hx_ensemble_moments, where participation is per row: a covariance matrix whose entries are taken
+ * over differing member sets need not be positive semi-definite.
+ * Shifts: c_a = the smallest participating value of row a of A, c_b likewise of B (exact values
+ * some member has).  d_a = x_a - c_a and d_b = x_b - c_b are each ONE IEEE subtraction -- that
+ * rounding is part of the definition -- and both are >= 0.  Over the participants:
+ *   sums_a[a * 2 + ...] = S_a = sum q d_a,  T_a = sum q d_a d_a;   sums_b[b * 2 + ...] likewise
+ *   cross[a * nb + b] = sum (q d_a) d_b
+ *   shift_a[a] = c_a;  shift_b[b] = c_b;  *wsum = W;  *n_part = participants (may be NULL).
+ * Every term is >= 0, so every sum, in any order and with fused multiply-adds, is within
+ * (n_part + 8) 2^-53 of the exact one, relatively.  In double:
+ *   mean_a = c_a + S_a/W        var_a = T_a/W - (S_a/W)^2   (the population variance)
+ *   cov[a][b] = cross[a][b]/W - (S_a/W)(S_b/W)
+ *   corr[a][b] = cov[a][b] / sqrt(var_a var_b)      slope[a][b] = cov[a][b] / var_b
+ * (corr and slope are undefined where a variance is 0.)
+ * The symmetric call computes only the blocks of the matrix on or above the diagonal and mirrors
+ * them -- towards half of the contraction's work as the matrix grows (36 of 64 quadrants of 32 x 32
+ * for 251 rows), as EOFs want it: cross is then EXACTLY symmetric, and sums_a[a * 2 + 1] is
+ * set to cross[a * na + a].
+ * Nobody takes part: the shifts are NaN, the sums and cross are 0, W and n_part are 0.
+ * Reproducibility: W, n_part and the shifts are exact under any lane order or shard split.  The
+ * floating sums are NOT bit-identical across lane orders or shard splits; they ARE bit-identical
+ * from call to call for the same core, lane order and shard layout: no floating atomics, a fixed
+ * reduction tree, the member chunks' partials added in ascending chunk order, shards added on the
+ * host in ascending shard order.
+ * Cost: one lane-local read of every row of both windows for the participation mask, one for the
+ * minima, one for the rows' own sums, and the contraction over the members on the fp64 matrix pipe
+ * (v_mfma_f64_16x16x4_f64): 2 na nb n flops, each row re-read once per 64 rows of the other window.
+ * na + nb is limited by the scenario's rows only.  A communicator of several processes is refused.
+ * The core is not prepared, spun up or dirtied.
+ * Errors (every message names the function; a refused call changes nothing): those of
+ * hx_ensemble_quantiles for capability, dates and weights, for either window; a core that has not
+ * run.  Not available in the host-emulation build of the test suite.
+ * Out of scope: a metric x metric variant, and per-entry (pairwise) participation. */
+int hx_ensemble_comoments(hx_core *core, const char *cap_a, int a_year0, int a_year1,
+                          const char *cap_b, int b_year0, int b_year1, const double *weights,
+                          double *shift_a, double *sums_a, double *shift_b, double *sums_b,
+                          double *cross, unsigned long long *wsum, long long *n_part);
+
 /* ---- Held and derived per-member series -----------------------------------------------------------
  * What the six verbs above, hx_fetchvars, hx_stats_device / hx_ensemble_stats and hx_device_var call
  * `capability` is "a per-member variable on the device", one of
