@@ -5,8 +5,9 @@ against the uniform ensemble.)"""
 import numpy as np
 import pytest
 
-from test_one_factor import (DEFAULTS, EDGES, FLAVOURS, OUTS, PARAMS, assert_flavour, biome_values,
-                             capability, cases, check_vs_oracle, make_core)
+from test_one_factor import (DEFAULTS, EDGES, FLAVOURS, OUTS, PARAMS, TRACK_DATE, assert_flavour,
+                             biome_values, capability, cases, check_vs_oracle, make_core, oracle_params)
+from test_tracking import FRAC_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -44,6 +45,32 @@ def outputs(c, outs):
     return {v: c.fetchvars(v, (1745, RUN_TO)) for v in outs}
 
 
+_ORACLE_MAPS = {}
+
+
+def check_maps_vs_oracle(o, c, i, name, value, B, where):
+    """Member i's origin maps against the oracle's, at the tolerances of tests/test_tracking.py
+    (the companion wavefronts of two biomes: the host build cannot hold them to anything).
+    -> the member's (values, fractions) of the tracked span."""
+    key = (name, float(value), B)
+    if key not in _ORACLE_MAPS:   # (the probes come in pairs of one value)
+        ov, of, _, err = o.run_tracking(oracle_params(o, name, value, B), TRACK_DATE, RUN_TO)
+        assert err == 0, where
+        k0, k1 = TRACK_DATE - o.start, RUN_TO - o.start + 1
+        _ORACLE_MAPS[key] = (ov[k0:k1].copy(), of[k0:k1].copy())
+    ov, of = _ORACLE_MAPS[key]
+    gv, gf = c.tracking_data(i, (TRACK_DATE, RUN_TO))
+    assert np.abs(gv - ov).max() < 1e-10 * np.abs(ov).max(), where
+    assert np.abs(gf - of).max() < FRAC_TOL, (where, np.abs(gf - of).max())
+    assert np.abs(gf.sum(axis=2) - 1.0).max() < 1e-12, where
+    return gv, gf
+
+
+def assert_maps_are(c, i, maps, where):
+    gv, gf = c.tracking_data(i, (TRACK_DATE, RUN_TO))
+    assert np.array_equal(gv, maps[0]) and np.array_equal(gf, maps[1]), (where, "tracking")
+
+
 @pytest.mark.parametrize("flavour,name", cases(GPU_FLAVOURS), ids=["-".join(c) for c in cases(GPU_FLAVOURS)])
 def test_one_parameter_varied_alone_on_gpu(hip_lib, oracle, monkeypatch, flavour, name):
     fl = FLAVOURS[flavour]
@@ -64,6 +91,10 @@ def test_one_parameter_varied_alone_on_gpu(hip_lib, oracle, monkeypatch, flavour
     ill = []
     for i in (range(N) if fl["B"] == 1 else probe_members(name)):
         check_vs_oracle(oracle, c, i, name, vals[i], fl["B"], RUN_TO, (flavour, name, i), ill)
+    maps = {}
+    if fl.get("track"):
+        maps = {i: check_maps_vs_oracle(oracle, c, i, name, vals[i], fl["B"], (flavour, name, i))
+                for i in probe_members(name)}
     # the same members next to other neighbours: a fixed shuffle (a second edit of the same row) ...
     cap = capability(name, fl["B"])
     c.setvar(cap, biome_values(name, vals[SHUFFLE], fl["B"]), PARAMS[name][2])
@@ -78,6 +109,9 @@ def test_one_parameter_varied_alone_on_gpu(hip_lib, oracle, monkeypatch, flavour
     for v in outs:
         assert np.array_equal(again[v], first[v][:, SHUFFLE]), (flavour, name, "shuffled", v)
     assert [c.spinup_steps(i) for i in range(N)] == [steps[j] for j in SHUFFLE]
+    for i in range(N):   # (member i holds what member SHUFFLE[i] held)
+        if SHUFFLE[i] in maps:
+            assert_maps_are(c, i, maps[SHUFFLE[i]], (flavour, name, "shuffled", i))
     # ... and in member order (no sorting by the parameter)
     c.set_member_sorting(False)
     c.setvar(cap, biome_values(name, vals, fl["B"]), PARAMS[name][2])
@@ -87,6 +121,8 @@ def test_one_parameter_varied_alone_on_gpu(hip_lib, oracle, monkeypatch, flavour
     again = outputs(c, outs)
     for v in outs:
         assert np.array_equal(again[v], first[v]), (flavour, name, "unsorted", v)
+    for i in maps:
+        assert_maps_are(c, i, maps[i], (flavour, name, "unsorted", i))
     c.shutdown()
     if ill:
         print("ill-conditioned members:", ill)

@@ -185,6 +185,186 @@ def test_tracking_refuses_carbon_constraints(emul_lib, tmp_path):
         c.run(1850)
 
 
+# ---------------------------------------------------------------------------------------------
+# Every member's maps against the oracle, on an ensemble whose lanes part ways and whose edge
+# members empty a pool.  (tests/test_gpu_tracking_maps.py: the same checker on the device, where
+# one and two biomes keep their maps on companion wavefronts -- code the host build never runs.)
+#
+# 70 members: one full wavefront and six lanes.  S, the Q10 and beta are spread widely, so the
+# lanes of a wavefront take different numbers of stashes in many years (the companions' partial-
+# wavefront protocol, TRKR_ACTIVE); members at fixed indices sit at the values where a pool or a
+# flux is exactly zero: permafrost_c = 0 (the permafrost map is "a zero total, shared equally
+# among the names of the map", fluxpool.hpp:243-251, every year -- next to lanes with ordinary
+# maps), fpf_static = 1 and 0, beta = 0, f_litterd = 1.  Member 0 holds the INI defaults.
+EDGE_N = 70
+EDGE_PF0 = (7, 30, 58)
+EDGE_MEMBERS = (0,) + EDGE_PF0 + (12, 41, 23, 50)   # the host tier's eight
+EDGE_SPANS = {"ssp245": (1950, 2100), "ssp534-over": (2000, 2150)}   # tracking date, run to
+_oracles, _oracle_runs = {}, {}
+
+
+def edge_ensemble(diff=False):
+    """-> {parameter: values[EDGE_N]}, in the units of the unsplit core."""
+    from test_one_factor import DEFAULTS
+    rng = np.random.default_rng(2025)
+    e = {"S": rng.uniform(1.5, 6.0, EDGE_N), "q10_rh": rng.uniform(1.1, 3.0, EDGE_N),
+         "beta": rng.uniform(0.2, 0.9, EDGE_N)}
+    for k in ("permafrost_c", "fpf_static", "f_litterd"):
+        e[k] = np.full(EDGE_N, DEFAULTS[k])
+    if diff:   # (its own stream: the other rows are the same with and without it)
+        e["diff"] = np.random.default_rng(2026).uniform(0.8, 2.4, EDGE_N)
+    for k in ("S", "q10_rh", "beta"):
+        e[k][0] = DEFAULTS[k]
+    e["permafrost_c"][list(EDGE_PF0)] = 0.0
+    e["fpf_static"][12], e["fpf_static"][41] = 1.0, 0.0
+    e["beta"][23] = 0.0
+    e["f_litterd"][50] = 1.0
+    return e
+
+
+def scenario_oracle(name):
+    """(pack path, its oracle) of a shipped scenario."""
+    import os
+    import oracle_binding
+    from conftest import ROOT
+    path = os.path.join(ROOT, "hector_amd", "data", name + ".hxs")
+    if name not in _oracles:
+        _oracles[name] = oracle_binding.Oracle(path)
+    return path, _oracles[name]
+
+
+def edge_core(lib, path, ens, nb, date, members=None, **kw):
+    """The core of `ens` (its `members`, default all): per-biome parameters in the LAST of `nb`
+    equal biomes, pools scaled by the biome's share (test_one_factor.make_core)."""
+    from test_one_factor import PARAMS, biome_values, capability
+    idx = np.arange(EDGE_N) if members is None else np.asarray(members)
+    c = hector_amd.Core(path, len(idx), lib_path=lib, **kw)
+    if nb > 1:
+        c.split_biome(["b%d" % b for b in range(nb)])
+    c.set_pair_kernel_limit(0)
+    c.setvar("trackingDate", [date])
+    for k, v in ens.items():
+        c.setvar(capability(k, nb), biome_values(k, v[idx], nb), PARAMS[k][2])
+    c.set_outputs(["CO2_concentration", "timesteps"] + [pool_variable(p) for p in c.tracking_pools()])
+    return c
+
+
+def edge_params(o, ens, i, nb):
+    from test_one_factor import ORACLE_SCALARS, biome_values
+    p = o.default_params()
+    if nb > 1:
+        p = o.split_equal(p, nb)
+    p.nbiome = nb
+    for k, v in ens.items():
+        if k in ORACLE_SCALARS:
+            setattr(p, k, v[i])
+        else:
+            getattr(p, k)[nb - 1] = biome_values(k, [v[i]], nb)[0]
+    return p
+
+
+def pool_variable(pool):
+    return {"HL": "HL_ocean_c", "LL": "LL_ocean_c", "intermediate": "IO_ocean_c", "deep": "DO_ocean_c"}.get(pool, pool)
+
+
+def oracle_maps(oracle, p, T0, END):
+    """(values, fractions, stashes per year) of the tracked span; computed once per member."""
+    key = (oracle.sc, bytes(p), T0, END)
+    if key not in _oracle_runs:
+        k0, k1 = T0 - oracle.start, END - oracle.start + 1
+        ov, of, _, err = oracle.run_tracking(p, T0, END)
+        assert err == 0
+        r, err, _ = oracle.run(p, END)
+        assert err == 0
+        _oracle_runs[key] = (ov[k0:k1].copy(), of[k0:k1].copy(), r["timesteps"][k0 + 1:k1].copy())
+    return _oracle_runs[key]
+
+
+def check_maps_every_member(core, oracle, params_of_member, T0, END, daccs=False, wavefront=True,
+                            min_divergent=1.0 / 3.0, min_counts=3):
+    """EVERY member's tracking_data(i, (T0, END), masks=True) of a core that has run to END
+    against oracle.run_tracking(params_of_member(i)), at this file's tolerances.  -> the worst
+    pool (relative to the largest pool) and fraction deviations.
+
+    First, on the oracle's output alone, that the case exercises what it is there for:
+    - wavefront: within lanes 0-63 the stashes per year differ between lanes in at least
+      `min_divergent` of the tracked years (the host build runs its lanes one after the other:
+      nothing parts there);
+    - every permafrost_c = 0 member's permafrost row is equal shares in every tracked year, with
+      at least `min_counts` different numbers of sources over the span;
+    - daccs: earth_c ends up less than 99 % itself (direct air capture moves atmosphere there)."""
+    n = core.n_members
+    assert (core.status() == 0).all()
+    pools = core.tracking_pools()
+    tp = len(pools)
+    nb = (tp - 6) // 5
+    ref = [oracle_maps(oracle, params_of_member(i), T0, END) for i in range(n)]
+    if wavefront:
+        lanes = core.lane_of_member()
+        ts = np.array([ref[i][2] for i in range(n) if lanes[i] < 64])
+        parted = int((ts.max(axis=0) != ts.min(axis=0)).sum())
+        print("lanes take different numbers of stashes in %d of %d years; stashes a year %s"
+              % (parted, ts.shape[1], sorted(set(ts.ravel().astype(int)))))
+        assert parted >= min_divergent * ts.shape[1], (parted, ts.shape[1])
+    zero_pf = 0
+    for i in range(n):
+        p = params_of_member(i)
+        for b in range(nb):
+            if p.permafrost_c[b] == 0.0:
+                row = ref[i][1][:, 2 + 5 * b + 3, :]
+                cnt = (row > 0).sum(axis=1)
+                assert np.array_equal(row, np.where(row > 0, 1.0 / cnt[:, None], 0.0)), i
+                assert len(set(cnt)) >= min_counts, (i, sorted(set(cnt)))
+                zero_pf += 1
+    if daccs:
+        assert max(r[1][-1, 1, 1] for r in ref) < 0.99
+    recorded = {pool: core.fetchvars(pool_variable(pool), (T0, END)) for pool in pools}
+    worst_v = worst_f = 0.0
+    for i in range(n):
+        ov, of, _ = ref[i]
+        gv, gf, held = core.tracking_data(i, (T0, END), masks=True)
+        dv, df = np.abs(gv - ov).max() / np.abs(ov).max(), np.abs(gf - of).max()
+        worst_v, worst_f = max(worst_v, dv), max(worst_f, df)
+        assert dv < 1e-10, (i, dv)
+        assert df < FRAC_TOL, (i, df)
+        assert np.abs(gf.sum(axis=2) - 1.0).max() < 1e-12, i
+        assert (gf[~held] == 0.0).all(), i
+        assert held[:, np.arange(tp), np.arange(tp)].all(), i
+        for k, pool in enumerate(pools):
+            assert np.array_equal(gv[:, k], recorded[pool][:, i]), (i, pool)
+    print("%d members, %d pools (%d with permafrost_c = 0): worst pool deviation %.2e relative, "
+          "worst fraction deviation %.2e" % (n, tp, zero_pf, worst_v, worst_f))
+    return worst_v, worst_f
+
+
+HOST_EDGE_CASES = [("ssp245", 1), ("ssp245", 2), ("ssp245", 4), ("ssp245", 13), ("ssp534-over", 1),
+                   ("ssp534-over", 2)]
+
+
+def edge_min_counts(scenario, T0):
+    """How many different source counts the oracle's equal-shares permafrost row shows: the names
+    arrive with the first non-zero flux of each kind, so a span that starts in 1950 on ssp245
+    passes through 4, 9, 10 and 11 names (one biome); by 2000 on ssp534-over every flux runs and
+    the row holds every name from the first stash on; 1900-1960 sees two counts."""
+    return 3 if (scenario, T0) == ("ssp245", 1950) else 2 if scenario == "ssp245" else 1
+
+
+@pytest.mark.parametrize("scenario,nb", HOST_EDGE_CASES, ids=["%s-%d" % c for c in HOST_EDGE_CASES])
+def test_maps_of_edge_members_vs_oracle(emul_lib, scenario, nb):
+    """The inline maps (track_stash) on the host build where a pool or a flux is exactly zero:
+    the edge members and the default one, 1-13 biomes (13: 71 pools, the zero pool's bits in the
+    second mask word), with and without direct air capture."""
+    path, o = scenario_oracle(scenario)
+    T0, END = (1900, 1960) if nb == 13 else EDGE_SPANS[scenario]
+    ens = edge_ensemble()
+    c = edge_core(emul_lib, path, ens, nb, T0, members=EDGE_MEMBERS, allow_emulation=True)
+    c.run(END)
+    assert c.last_run_kernel() == "run" and c.last_run_variant() == 2
+    check_maps_every_member(c, o, lambda i: edge_params(o, ens, EDGE_MEMBERS[i], nb), T0, END,
+                            daccs=scenario == "ssp534-over", wavefront=False,
+                            min_counts=edge_min_counts(scenario, T0))
+
+
 TRACK_BOTH_WAYS = """
 import sys, numpy as np, hector_amd
 from hector_amd import ensemble
