@@ -7,6 +7,43 @@
 
 namespace {
 
+// Lane masks of the step loop's control (solve_year) as what the hardware makes of them: one bit
+// per lane in a scalar register pair.  A comparison leaves such a mask (hx_mask_gt: the v_cmp
+// itself), masks combine with scalar AND / OR, the wavefront's vote is `mask != 0` (one scalar
+// comparison), and hx_lane() hands a mask back as the per-lane condition of a masked region or a
+// select without a vector instruction.  Written with booleans, every vote (__any takes an int)
+// went through a v_cndmask / v_cmp pair, and every boolean changed inside a divergent region was
+// rebuilt at the join with three scalar operations on the exec mask.
+// Host emulation: one lane at a time, bit 0 is the lane.
+// -DHX_STEP_CONTROL_OLD: the step loop's control as it was up to round 6 (booleans, __any) in
+// every kernel.
+typedef unsigned long long hx_mask;
+#ifndef HX_HOST_EMULATION
+__device__ __forceinline__ hx_mask hx_mask_gt(double a, double b) { return __builtin_amdgcn_fcmp(a, b, 2); }  // ordered >
+__device__ __forceinline__ hx_mask hx_mask_gt(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 38); }      // signed >
+__device__ __forceinline__ hx_mask hx_mask_of(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ bool hx_lane(hx_mask k) { return __builtin_amdgcn_inverse_ballot_w64(k); }
+#else
+__device__ __forceinline__ hx_mask hx_mask_gt(double a, double b) { return a > b; }
+__device__ __forceinline__ hx_mask hx_mask_gt(int a, int b) { return a > b; }
+__device__ __forceinline__ hx_mask hx_mask_of(bool p) { return p; }
+__device__ __forceinline__ bool hx_lane(hx_mask k) { return (k & 1) != 0; }
+#endif
+
+// Which instantiations take the flat control: those that hold a year's working set in registers
+// (one to four biomes, the two-wave flavour; plain, diagnostics and extended).  The kernels at the
+// register file's limit -- five and more biomes, looped, carbon tracking: 512 registers and
+// scratch -- keep the nested form: there the masks and the candidate time of the flat one are
+// spill slots (seven of them gained 4 to 20 bytes of scratch with it), and their time is not in
+// the step loop's control.
+template <int B, int CON> constexpr bool hx_flat_control() {
+#ifdef HX_STEP_CONTROL_OLD
+  return false;
+#else
+  return CON < 2 && ((B >= 1 && B <= 4) || B == HX_B1W2);
+#endif
+}
+
 // rhs constants that only change at a stash (pools frozen in between,
 // src/simpleNbox-runtime.cpp:809-840)
 struct Interval {
@@ -949,7 +986,12 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
     rhs<B, SPIN, CON>(m, K, K2, yc, t, y, dxdt);
     if constexpr (LAND2) dxdt[1] = hx_div1(m.luc_e, (y[1] + y[2]) + y[3]);   // (the loss rate itself: see LAND2)
     int fails = 0;
-    bool stepping = seg;
+    constexpr bool FLAT = hx_flat_control<B, CON>();
+    bool stepping = seg;   // (nested form; the flat one uses it inside the retry block only)
+    // The lanes that are stepping, as the wavefront's lane mask in a scalar register pair (see the
+    // end of the pass): votes are scalar comparisons of it, and nothing rebuilds it from booleans.
+    [[maybe_unused]] hx_mask ST = FLAT ? hx_mask_of(seg) : 0;
+#define HX_STEP_GO() (FLAT ? ST != 0 : (bool)__any(stepping))
     HX_TAB_HEAD();
     if constexpr (hx_w2<B>()) w2_park_out<B>(m);
     // One pass = one dopri5 attempt of every stepping lane.  The attempt itself is straight-line
@@ -962,9 +1004,9 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
     // the loop header, which the compiler may not duplicate (a convergent operation), so the loop
     // stays top-tested and every value that leaves it -- t, dt, the pools, their derivatives -- is
     // copied to its exit register at the top of EVERY pass)
-    for (bool go_ = __any(stepping); go_; go_ = __any(stepping)) {
+    for (bool go_ = HX_STEP_GO(); go_; go_ = HX_STEP_GO()) {
 #else
-    while (__any(stepping)) {
+    while (HX_STEP_GO()) {
 #endif
       HX_STAMP(m, 10);
       HX_COUNT(m, 16);  // step-loop iterations
@@ -977,14 +1019,21 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
         T = kc.tab + toff;
       }
 #endif
-      if (stepping && ((t + dtl) - t_target) > EPS) dtl = t_target - t;
+      // (flat: the clip as a select, no divergent region around one subtraction)
+      if constexpr (FLAT) dtl = hx_lane(ST & hx_mask_gt((t + dtl) - t_target, EPS)) ? t_target - t : dtl;
+      else if (stepping && ((t + dtl) - t_target) > EPS) dtl = t_target - t;
       // Every dopri5 stage time is <= t+dtl, and the model refuses any RHS
       // evaluation beyond max_timestep (ocean_component.cpp:621-625), so the
       // attempt throws CARBON_CYCLE_RETRY iff its last stage does.  A retry
       // (carbon-cycle-solver.cpp:266-276) is bookkeeping -- target halved, pools reloaded, a
       // fresh stepper -- and the attempt towards the new target follows in the same pass.
-      bool need = stepping && ((t + dtl) - m.ode_start) > m.max_ts;
-      if (__builtin_expect(__any(need), 0)) {
+      bool need = false;
+      [[maybe_unused]] hx_mask needm = 0;
+      if constexpr (FLAT) needm = ST & hx_mask_gt((t + dtl) - m.ode_start, m.max_ts);
+      else need = stepping && ((t + dtl) - m.ode_start) > m.max_ts;
+      if (__builtin_expect(FLAT ? needm != 0 : (bool)__any(need), 0)) {
+        if constexpr (FLAT) { need = hx_lane(needm); stepping = hx_lane(ST); }
+        HX_COUNT(m, 22);  // passes with a retry
         bool reload = false;
         while (need) {
           ++retry;
@@ -994,13 +1043,17 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
           dtl = m.sdt;
           reload = true;
           fails = 0;
-          if (retry >= 8) { m.status |= HX_ERR_RETRIES; alive = false; stepping = false; }
+          if (retry >= 8) {
+            m.status |= HX_ERR_RETRIES; stepping = false;
+            if constexpr (!FLAT) alive = false;   // (flat: `alive` follows from the status after the loop)
+          }
           need = stepping && ((t + dtl) - m.ode_start) > m.max_ts;
         }
         if (reload) {
           load_pools(true); rhs<B, SPIN, CON>(m, K, K2, yc, t, y, dxdt);
           if constexpr (LAND2) dxdt[1] = hx_div1(m.luc_e, (y[1] + y[2]) + y[3]);
         }
+        if constexpr (FLAT) ST = hx_mask_of(stepping);
       }
       double k2[NP], k3[NP], k4[NP], k5[NP], k6[NP], xt[NP], xn[NP], dn[NP];
       // the land-use loss rates of the attempt's stage times (see rhs): five independent
@@ -1348,6 +1401,56 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
       HX_TAB_HEAD();   // (experiment builds: the next pass's first rows)
       // increase_step: err < 0.5 -> dt *= 0.9 * max(err, 5^-5)^(-1/5)
       const double grow = 0.9 * pow_m15(fmax(0.00032, err));
+      // The control of a pass, flat (hx_flat_control; the nested form of rounds 1-6 is below, the
+      // same arithmetic and the same decisions).  A stepping lane either accepts or rejects:
+      //  - an accepted step is committed where the values live, in ONE masked region with nothing
+      //    on its other side -- no candidate copies into the registers a join expects;
+      //  - a rejecting lane changes dt and its failure count only, in a block the wavefront enters
+      //    when one of its lanes rejects; no state of the other lanes passes through it;
+      //  - the stepping lanes stay a lane mask: the time an accepted step would reach is compared
+      //    in every lane, and the next pass's mask is two scalar operations;
+      //  - the limits on failures and on accepted steps are two comparisons and ONE vote a pass;
+      //    the block behind the vote flags the lane and takes it out in the same pass, so the
+      //    loop is bounded exactly as before.  `alive` is not touched inside the loop: a lane is
+      //    alive as long as its status word is clean (see below the loop).
+      if constexpr (FLAT) {
+        const hx_mask gt1 = hx_mask_gt(err, 1.0);
+        const hx_mask rejm = ST & gt1;      // default_step_adjuster::decrease_step
+        const hx_mask accm = ST & ~gt1;
+        const double tn = t + dtl;
+        const hx_mask contm = hx_mask_gt(t_target - tn, EPS);   // (not set: integrate_adaptive done)
+#ifdef HX_PHASE_CLOCK   // (profiling build: how often the wavefront meets a rejection)
+        if (rejm != 0) HX_COUNT(m, 20);   // passes with a rejecting lane
+        else HX_COUNT(m, 21);             // passes whose stepping lanes all accept
+#endif
+        if (hx_lane(accm)) {
+          // pools with a constant derivative over the interval advance exactly
+          l4 += dtl * K.k4; l7 += dtl * K.k7;
+          if constexpr (!hx_nbp<CON>()) l5 += dtl * K.k5;
+          t = tn;
+          if (err < 0.5) dtl *= grow;
+#pragma unroll
+          for (int i = 0; i < NP; ++i) { y[i] = xn[i]; dxdt[i] = dn[i]; }
+          fails = 0;
+          m.nsteps++;
+        }
+        if (__builtin_expect(rejm != 0, 0)) {
+          const double shrink = fmax(0.9 * pow_m13(err), 0.2);
+          if (hx_lane(rejm)) { dtl *= shrink; ++fails; }
+        }
+        // odeint puts no limit on accepted steps; a launch needs one (a member takes 3-8
+        // steps a year, a stiff one a few hundred)
+        const hx_mask overm = ST & (hx_mask_gt(fails, 500) | hx_mask_gt(m.nsteps, HX_MAX_STEPS_PER_YEAR));
+        ST = rejm | (accm & contm);
+        if (__builtin_expect(overm != 0, 0)) {
+          if (hx_lane(overm)) m.status |= HX_ERR_STEPFAIL;
+          ST &= ~overm;
+        }
+      } else {
+#ifdef HX_PHASE_CLOCK   // (profiling build: how often the wavefront meets a rejection)
+      if (__any(stepping && err > 1.0)) HX_COUNT(m, 20);   // passes with a rejecting lane
+      else HX_COUNT(m, 21);                                // passes whose stepping lanes all accept
+#endif
       if (stepping) {
         if (__builtin_expect(err > 1.0, 0)) {  // reject (rare): default_step_adjuster::decrease_step
           dtl *= fmax(0.9 * pow_m13(err), 0.2);
@@ -1370,9 +1473,11 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
           }
         }
       }
+      }
       HX_STAMP(m, 6);   // dopri5 attempts (+ retries)
     }
     if constexpr (hx_w2<B>()) w2_park_in<B>(m);
+    if constexpr (FLAT) alive = m.status == 0;   // (a lane the loop has flagged -- retries, step limits -- is out of the year)
     HX_STAMP(m, 10);
     HX_COUNT(m, 17);    // segments
     if (seg && alive) {
@@ -1386,6 +1491,7 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
 }
 
 }  // namespace
+#undef HX_STEP_GO
 #ifndef HX_TAB_LITERALS
 #undef b21
 #undef f2

@@ -68,6 +68,11 @@ def main():
            "ticks_per_year_slowest_total": float(tot[slow] / 555),
            "step_loop_iterations_per_year": {"mean": float(t[16].mean() / 555), "slowest": float(t[16, slow] / 555)},
            "segments_per_year": {"mean": float(t[17].mean() / 555), "slowest": float(t[17, slow] / 555)},
+           # of the step loop's passes: those in which some lane of the wavefront rejects, those in
+           # which every stepping lane accepts, those with a retry (HX_COUNT slots 20-22)
+           "passes_with_a_rejecting_lane_per_year": {"mean": float(t[20].mean() / 555), "slowest": float(t[20, slow] / 555)},
+           "passes_all_accepting_per_year": {"mean": float(t[21].mean() / 555), "slowest": float(t[21, slow] / 555)},
+           "passes_with_a_retry_per_year": {"mean": float(t[22].mean() / 555), "slowest": float(t[22, slow] / 555)},
            "sections": {}}
     for k, name in SECTIONS.items():
         out["sections"][name] = {"mean_ticks_per_year": float(t[k].mean() / 555),
