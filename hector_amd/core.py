@@ -23,6 +23,34 @@ SERIES_OPS = {"copy": 0, "add": 1, "sub": 2, "mul": 3, "div": 4, "anomaly": 5, "
               "runmean": 7, "delta": 8}     # HX_SER_* of include/hector_amd.h
 
 
+_SCORE_WHITENED_MAX = 256   # HX_SCORE_WHITENED_MAX
+
+
+def _whiten(cov, who):
+    C = np.asarray(cov, dtype=np.float64)
+    if C.ndim != 2 or C.shape[0] != C.shape[1] or C.shape[0] < 1:
+        raise HectorAmdError("%s: the covariance must be a square matrix" % who)
+    if not np.isfinite(C).all():
+        raise HectorAmdError("%s: the covariance has a NaN or infinite entry" % who)
+    if not (C == C.T).all():
+        raise HectorAmdError("%s: the covariance is not symmetric" % who)
+    try:
+        L = np.linalg.cholesky(C)
+    except np.linalg.LinAlgError:
+        raise HectorAmdError("%s: the covariance is not positive definite" % who) from None
+    n = C.shape[0]
+    W = np.tril(np.linalg.solve(L, np.eye(n)))
+    return W, 2.0 * float(np.sum(np.log(np.diag(L))))
+
+
+def whiten(cov):
+    """-> (W, logdet) of an error covariance C = L L^T (Cholesky): W = L^-1, lower-triangular with an
+    exact zero above the diagonal, so that r^T C^-1 r = |W r|^2 -- what Core.score(..., whiten=W)
+    and hx_member_score_whitened take -- and logdet = log det C = 2 sum log diag L, the other half of
+    the Gaussian log-likelihood.  C must be square, finite, symmetric and positive definite."""
+    return _whiten(cov, "whiten")
+
+
 class _HxSeriesOp(ctypes.Structure):   # hx_series_op
     _fields_ = [("op", ctypes.c_int), ("year0", ctypes.c_int), ("year1", ctypes.c_int),
                 ("width", ctypes.c_int), ("align", ctypes.c_int), ("lag", ctypes.c_int),
@@ -576,12 +604,26 @@ class Core:
         self._ck(self._lib.hx_stats_device(self._h, var.encode(), int(year0), int(year1),
                                            ctypes.c_void_p(d_ptr)))
 
-    def score(self, var, years, obs, sigma=None, baseline=None, return_used=False):
+    def score(self, var, years, obs, sigma=None, baseline=None, return_used=False, *, cov=None, ar1=None,
+              whiten=None):
         """chi2 of every member against an observed record, on the device (hx_member_score):
         sum over i of (((x(years[i]) - base) - obs[i]) / sigma[i])**2 -> ndarray [n_members].
         obs NaN: that year is skipped; sigma None: no division; baseline = (year0, year1): base is
         the member's own mean of x over those years, None: nothing is subtracted.  The evaluation
-        order is fixed (include/hector_amd.h): numpy reproduces the result bit for bit."""
+        order is fixed (include/hector_amd.h): numpy reproduces the result bit for bit.
+
+        Correlated observation errors (hx_member_score_whitened: chi2 = r^T C^-1 r = |W r|^2, at
+        most 256 years), by ONE of
+          cov=C        the n x n error covariance (not with sigma);
+          ar1=rho      with sigma (scalar or per year): C_ij = sigma_i sigma_j rho^|years_i - years_j|,
+                       0 <= rho < 1;
+          whiten=W     a ready lower-triangular W = L^-1 of C = L L^T (hector_amd.whiten(C)[0]): what
+                       a calibration loop factorises once.
+        With cov and ar1 the years whose obs is NaN are dropped BEFORE the factorisation (their rows
+        and columns of C deleted: the Gaussian's marginal) and n_used is what remains; with whiten a
+        NaN observation is an error."""
+        if cov is not None or ar1 is not None or whiten is not None:
+            return self._score_whitened(var, years, obs, sigma, baseline, return_used, cov, ar1, whiten)
         dp = ctypes.POINTER(ctypes.c_double)
         yr = np.ascontiguousarray(np.atleast_1d(np.asarray(years)).astype(np.int32))
         ob = np.ascontiguousarray(np.atleast_1d(np.asarray(obs, dtype=np.float64)))
@@ -598,6 +640,58 @@ class Core:
             sg.ctypes.data_as(dp) if sg is not None else None, int(yr.size), b0, b1,
             out.ctypes.data_as(dp), ctypes.byref(used)))
         return (out, used.value) if return_used else out
+
+    def _score_whitened(self, var, years, obs, sigma, baseline, return_used, cov, ar1, whiten):
+        """score() with cov=, ar1= or whiten=: builds W and calls hx_member_score_whitened."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        if sum(a is not None for a in (cov, ar1, whiten)) != 1:
+            raise HectorAmdError("score: cov, ar1 and whiten are mutually exclusive")
+        yr = np.ascontiguousarray(np.atleast_1d(np.asarray(years)).astype(np.int32))
+        ob = np.ascontiguousarray(np.atleast_1d(np.asarray(obs, dtype=np.float64)))
+        if ob.shape != yr.shape or yr.ndim != 1:
+            raise HectorAmdError("score: years and obs must be one-dimensional and of equal length")
+        n = int(yr.size)
+        if ar1 is None and sigma is not None:
+            raise HectorAmdError("score: sigma goes with ar1 only; cov and whiten carry the variances themselves")
+        if whiten is not None:
+            W = np.asarray(whiten, dtype=np.float64)
+            if W.shape != (n, n):
+                raise HectorAmdError("score: whiten must be n x n for n years")
+            if np.isnan(ob).any():
+                raise HectorAmdError("score: a NaN observation cannot be skipped under whiten (drop the year "
+                                     "and factorise the remaining covariance: cov= and ar1= do that)")
+        else:
+            if ar1 is not None:
+                if sigma is None:
+                    raise HectorAmdError("score: ar1 needs sigma")
+                rho = float(ar1)
+                if not 0.0 <= rho < 1.0:
+                    raise HectorAmdError("score: ar1 must lie in [0, 1)")
+                sg = np.broadcast_to(np.asarray(sigma, dtype=np.float64), yr.shape)
+                lag = np.abs(yr[:, None].astype(np.int64) - yr[None, :].astype(np.int64))
+                C = sg[:, None] * sg[None, :] * rho ** lag
+            else:
+                C = np.asarray(cov, dtype=np.float64)
+                if C.shape != (n, n):
+                    raise HectorAmdError("score: cov must be n x n for n years")
+            keep = ~np.isnan(ob)
+            if not keep.all():
+                yr, ob, C = np.ascontiguousarray(yr[keep]), np.ascontiguousarray(ob[keep]), C[np.ix_(keep, keep)]
+                n = int(yr.size)
+            if n < 1:
+                raise HectorAmdError("score: no observation is left")
+            if n <= _SCORE_WHITENED_MAX:   # (more: refused below, before a factorisation of that size)
+                W = _whiten(C, "score")[0]
+        if n > _SCORE_WHITENED_MAX:
+            raise HectorAmdError("score: more than %d years (hx_member_score_whitened takes 1..%d)"
+                                 % (_SCORE_WHITENED_MAX, _SCORE_WHITENED_MAX))
+        W = np.ascontiguousarray(W)
+        b0, b1 = (1, 0) if baseline is None else (int(baseline[0]), int(baseline[1]))
+        out = np.empty(self.n_members)
+        self._ck(self._lib.hx_member_score_whitened(
+            self._h, var.encode(), yr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ob.ctypes.data_as(dp),
+            W.ctypes.data_as(dp), n, b0, b1, out.ctypes.data_as(dp)))
+        return (out, n) if return_used else out
 
     def quantiles(self, var, probs, dates=None, weights=None, counts=False):
         """Per-year weighted quantiles over every member, on the device (hx_ensemble_quantiles:

@@ -90,6 +90,10 @@ int hx_co_chunks(int n, int na, int nb);
 hipError_t hx_launch_co_gram(const double *va, int ia0, int na, const double *vb, int ib0, int nb, int n,
                              int npad, int sym, const double *qd, const double *shift_a,
                              const double *shift_b, double *part, double *cross, hipStream_t st);
+int hx_sw_padded(int n);
+void hx_sw_pack(const double *whiten, int n, double *wf);
+hipError_t hx_launch_score_whiten(const double *var, int nmem, int npad, const int *iy, const double *obs,
+                                  const double *wf, int n, const double *base, double *out, hipStream_t st);
 #endif
 
 #ifndef HX_HOST_EMULATION
@@ -578,6 +582,7 @@ void EnsembleCore::free_device() {
   fr(d_score_); fr(d_q_); fr(d_qstate_); fr(d_qhist_); fr(d_metplan_); fr(d_met_); fr(d_bin_);
   fr(d_mom_); d_mom_ = nullptr; mom_cap_ = 0; mom_src_ = nullptr;
   fr(d_comom_); d_comom_ = nullptr; comom_cap_ = 0; co_a_ = nullptr;
+  fr(d_whiten_); d_whiten_ = nullptr; whiten_cap_ = 0;
   d_score_ = nullptr; d_q_ = d_qstate_ = d_qhist_ = nullptr;
   d_metplan_ = nullptr; d_met_ = nullptr; d_bin_ = nullptr;
   score_cap_ = qstate_cap_ = qhist_cap_ = metplan_cap_ = met_cap_ = bin_cap_ = 0; q_src_ = nullptr;
@@ -3329,6 +3334,73 @@ void EnsembleCore::mom_finish(const double *shift_host, double *sums_host) {
   check(hipMemcpyAsync(sums_host, b.out, 8 * (size_t)ny * nc, hipMemcpyDeviceToHost, stream_), "moments fetch");
   check(hipStreamSynchronize(stream_), "moments sync");
   mom_src_ = nullptr;
+#endif
+}
+
+// ---- score against observations with correlated errors (hx_member_score_whitened) ----------------
+
+void EnsembleCore::member_score_whitened(const std::string &capability, const int *years, const double *obs,
+                                         const double *whiten, int n, int base_year0, int base_year1,
+                                         double *out_host) {
+  const std::string f = "hx_member_score_whitened";
+  if (!years || !obs || !whiten || !out_host) throw std::runtime_error(f + ": null argument");
+  if (n < 1 || n > HX_SCORE_WHITENED_MAX) throw std::runtime_error(f + ": n must lie in 1..256");
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(obs[i]))
+      throw std::runtime_error(f + ": an observation is NaN or infinite (there is no skipping: drop the "
+                                   "year and factorise the remaining covariance)");
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k <= i; ++k)
+      if (!std::isfinite(whiten[(size_t)i * n + k]))
+        throw std::runtime_error(f + ": an entry of whiten on or below the diagonal is NaN or infinite");
+  const PostSource ps = post_source(capability, f.c_str());
+  if (ps.v >= 0 && !d_out_[ps.v])
+    throw std::runtime_error(f + ": variable " + capability + " was not enabled with set_outputs()");
+  const int last = scen_.start + ps.last_iy;
+  const bool has_base = base_year0 <= base_year1;
+  for (int i = 0; i < n; ++i)
+    if (years[i] < scen_.start || years[i] > last)
+      throw std::runtime_error(f + ": dates must lie between startDate and the current date");
+  if (has_base && (base_year0 < scen_.start || base_year1 > last))
+    throw std::runtime_error(f + ": the reference period must lie between startDate and the current date");
+  if (!d_lane_of_member_ || !ps.block) throw std::runtime_error(f + ": run the core first");
+#ifdef HX_HOST_EMULATION
+  throw std::runtime_error(f + kEmulRefusal);
+#else
+  sync();
+  const int np = hx_sw_padded(n);
+  const size_t NP = (size_t)np, NL = NP + 8, P = (size_t)npad_;   // (the lists: padded by two steps of the kernel)
+  // [wf NP^2][obs NL][base npad][chi2 npad][chi2 in member order n_] doubles, then the rows [NL] ints
+  const size_t doubles = NP * NP + NL + 2 * P + (size_t)n_;
+  const size_t bytes = sizeof(double) * doubles + sizeof(int) * NL;
+  if (bytes > whiten_cap_) {
+    if (d_whiten_) (void)hipFree(d_whiten_);
+    d_whiten_ = nullptr; whiten_cap_ = 0;
+    check(hipMalloc(&d_whiten_, bytes), "hipMalloc whitened score");
+    whiten_cap_ = bytes;
+  }
+  double *d_wf = d_whiten_, *d_obs = d_wf + NP * NP, *d_base = d_obs + NL, *d_lane = d_base + P, *d_mem = d_lane + P;
+  int *d_iy = reinterpret_cast<int *>(d_mem + n_);
+  // one upload: W in fragment order (zeros above the diagonal and in the padding), the observations
+  // and, behind the device-only part, the rows -- both padded with a valid row / 0.0 (never consumed)
+  std::vector<double> h(NP * NP + NL, 0.0);
+  hx_sw_pack(whiten, n, h.data());
+  std::vector<int> iy(NL, years[n - 1] - scen_.start);
+  for (int i = 0; i < n; ++i) {
+    h[NP * NP + (size_t)i] = obs[i];
+    iy[(size_t)i] = years[i] - scen_.start;
+  }
+  check(hipMemcpyAsync(d_wf, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, stream_), "whitened score W");
+  check(hipMemcpyAsync(d_iy, iy.data(), sizeof(int) * NL, hipMemcpyHostToDevice, stream_), "whitened score years");
+  if (has_base)
+    check(hx_launch_series_base(ps.block, npad_, base_year0 - scen_.start, base_year1 - scen_.start, d_base,
+                                stream_), "whitened score base kernel");
+  check(hx_launch_score_whiten(ps.block, n_, npad_, d_iy, d_obs, d_wf, n, has_base ? d_base : nullptr, d_lane,
+                               stream_), "whitened score kernel");
+  check(hx_launch_gather(d_lane, d_lane_of_member_, d_mem, n_, npad_, 1, stream_), "whitened score gather");
+  check(hipMemcpyAsync(out_host, d_mem, sizeof(double) * (size_t)n_, hipMemcpyDeviceToHost, stream_),
+        "whitened score fetch");
+  check(hipStreamSynchronize(stream_), "whitened score sync");   // (h and iy are pageable: copied by now)
 #endif
 }
 

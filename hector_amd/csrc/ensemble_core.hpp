@@ -147,6 +147,10 @@ class EnsembleCore {
   // in member order; -> the number of observations that counted
   int member_score(const std::string &capability, const int *years, const double *obs,
                    const double *sigma, int n, int base_year0, int base_year1, double *out_host);
+  // chi2[member] = |W r|^2 against obs with correlated errors (hx_member_score_whitened in
+  // hector_amd.h): whiten[n x n] row-major, only k <= i read; out_host[n_] in member order
+  void member_score_whitened(const std::string &capability, const int *years, const double *obs,
+                             const double *whiten, int n, int base_year0, int base_year1, double *out_host);
   // weighted quantiles (hx_ensemble_quantiles): q[n_] integer weights in member order (nullptr:
   // every member 1), out_host[(year - year0) * nprobs + j], n_part[year - year0] (may be nullptr)
   void quantiles(const std::string &capability, int year0, int year1, const unsigned long long *q,
@@ -319,6 +323,10 @@ class EnsembleCore {
   // scratch of member_score / quantiles
   double *d_score_ = nullptr;                 // [obs n][sigma n][chi2 npad][chi2 in member order n_] + years
   size_t score_cap_ = 0;
+  // scratch of member_score_whitened: [W in fragment order np^2][obs np][base npad][chi2 npad][chi2 in
+  // member order n_] + rows np
+  double *d_whiten_ = nullptr;
+  size_t whiten_cap_ = 0;
   unsigned long long *d_q_ = nullptr;         // integer weights in lane order [npad]
   unsigned long long *d_qstate_ = nullptr;    // per year {HxQYear, lo}, per (year, prob) {prefix, rem}, probs
   unsigned long long *d_qhist_ = nullptr;     // [ny][nprobs][256]

@@ -367,6 +367,14 @@ int hx_member_score(hx_core *core, const char *capability, const int *years, con
                                                    base_year1, out);
          if (n_used) *n_used = used)
 }
+int hx_member_score_whitened(hx_core *core, const char *capability, const int *years, const double *obs,
+                             const double *whiten, int n, int base_year0, int base_year1, double *out) {
+  if (!capability || !years || !obs || !whiten || !out)
+    return fail("hx_member_score_whitened: null argument");
+  if (n < 1 || n > HX_SCORE_WHITENED_MAX)
+    return fail("hx_member_score_whitened: n must lie in 1..256");
+  HX_TRY(core->core->member_score_whitened(capability, years, obs, whiten, n, base_year0, base_year1, out))
+}
 int hx_ensemble_quantiles(hx_core *core, const char *capability, int year0, int year1,
                           const double *weights, const double *probs, int nprobs, double *out,
                           long long *n_part) {

@@ -1138,4 +1138,150 @@ hipError_t hx_launch_co_gram(const double *va, int ia0, int na, const double *vb
                      na, nb, sym, cross);
   return hipGetLastError();
 }
+
+// ===========================================================================
+// Score against observations with correlated errors (hx_member_score_whitened in hector_amd.h defines
+// it): chi2[lane] = sum_i y_i^2, Y = W R with W the lower-triangular whitening matrix and R the
+// residuals [year k][member], on v_mfma_f64_16x16x4_f64 with M = whitened component i, N = member,
+// K = year k.  A[i][k] comes from lane (i = lane & 15, k = lane >> 4), B[k][j] from lane
+// (member j = lane & 15, k = lane >> 4), D sits at row (lane >> 4) + 4 reg, column lane & 15.
+//   Ownership   one wavefront a workgroup; it owns MT tiles of HXW_TILE members and all NT tiles of
+//               HXW_TILE outputs, 4 NT MT <= 64 accumulator doubles a lane for <4,4> (n <= 64), <8,2>
+//               (n <= 128), <12,1> (n <= 192: an annual instrumental record) and <16,1> (n <= 256):
+//               nothing is exchanged with another wavefront, no partials, no atomics, no LDS.
+//   Loop        k0 in steps of 4.  Lane (c, g) reads x[iy[k0 + g]][m0 + 16 t + c] -- four whole
+//               128-byte segments of the [year][lane] rows a load, every row read once -- a step
+//               ahead of its use, and forms r with two IEEE subtractions.  The row number is read
+//               two steps ahead, so no load waits for another.
+//   W           the host (EnsembleCore::member_score_whitened) packs it in fragment order,
+//               wf[((k0 / 4) NT + tile) 64 + lane], so that an A fragment is one 512-byte read from
+//               L2; entries with k > i, i >= n or k >= n are written as exact 0.0 THERE: the caller's
+//               upper triangle is never read, let alone multiplied in.  r is selected to an exact 0.0
+//               for k >= n.  Output tiles wholly above the diagonal (16 tile + 15 < k0) are skipped:
+//               the k loop is unrolled over the tile T the diagonal crosses, and the code of T
+//               holds the tiles T .. NT - 1 only, without a branch among its loads and MFMAs.  A
+//               tile past n inside the template (zero rows: an exact 0) is computed, which is why
+//               there are four sizes and not three.
+//   Reduction   a lane squares its 4 values of every tile and adds them in ascending (tile, reg)
+//               order, then the four lane groups g are added by xor 16, xor 32 -- (s_g + s_g^1) +
+//               (s_g^2 + s_g^3), the same bits in every group since IEEE addition commutes -- and
+//               the lanes g = 0 store to the lane-ordered buffer; hx_launch_gather brings it to
+//               member order.  Every member's sums are formed in one fixed order, whatever column it
+//               sits in; columns >= n members or >= npad are computed from whatever they hold and
+//               not stored.
+// ===========================================================================
+#define HXW_TILE 16       // members per B tile, outputs per A tile (the MFMA's M and N)
+#define HXW_ACC 16        // NT x MT at the most: a wavefront takes MT = HXW_ACC / NT tiles of members, 64, 32 or 16 members
+#define HXW_MAX 256       // HX_SCORE_WHITENED_MAX
+static_assert(HXW_MAX == HX_SCORE_WHITENED_MAX, "the header's limit");
+
+// the template's padded size for n observations: 64, 128, 192 or 256
+int hx_sw_padded(int n) { return n <= 64 ? 64 : n <= 128 ? 128 : n <= 192 ? 192 : HXW_MAX; }
+
+// wf[np x np] in fragment order from whiten[n x n] (row-major; only k <= i is read)
+void hx_sw_pack(const double *whiten, int n, double *wf) {
+  const int np = hx_sw_padded(n), nt = np / HXW_TILE;
+  for (int ks = 0; ks < np / 4; ++ks)
+    for (int tile = 0; tile < nt; ++tile)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int i = HXW_TILE * tile + (lane & 15), k = 4 * ks + (lane >> 4);
+        wf[((size_t)ks * nt + tile) * 64 + lane] = (i < n && k <= i) ? whiten[(size_t)i * n + k] : 0.0;
+      }
+}
+
+// iy[np + 8], obs[np + 8] (padded: a valid row, any finite value); base: nullptr = none, else [npad]
+template <int NT, int MT>
+__global__ __launch_bounds__(64) void hx_score_whiten_kernel(const double *__restrict__ var, int nmem, int npad,
+                                                             const int *__restrict__ iy,
+                                                             const double *__restrict__ obs,
+                                                             const double *__restrict__ wf, int n,
+                                                             const double *__restrict__ base,
+                                                             double *__restrict__ out) {
+  typedef double d4 __attribute__((ext_vector_type(4)));
+  static_assert(NT * MT <= HXW_ACC && NT * HXW_TILE <= HXW_MAX, "64 accumulator doubles a lane at the most");
+  const int lane = (int)threadIdx.x, c = lane & 15, g = lane >> 4;
+  const int m0 = (int)blockIdx.x * (MT * HXW_TILE);
+  int col[MT];
+  double bs[MT], x[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    col[t] = min(m0 + HXW_TILE * t + c, npad - 1);   // (a column past the block: read inside it, never stored)
+    bs[t] = base ? base[col[t]] : 0.0;
+  }
+  d4 acc[NT][MT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int t = 0; t < MT; ++t) acc[i][t] = d4{0, 0, 0, 0};
+  const int ntiles = (n + HXW_TILE - 1) / HXW_TILE;
+  // lane group g takes year k0 + g of a step: its row number is read two steps ahead of its use,
+  // its values and its observation one step ahead (iy and obs are padded by two steps)
+  int rnext = iy[4 + g];
+  double onext = obs[g];
+  {
+    const size_t r = (size_t)iy[g] * (size_t)npad;
+#pragma unroll
+    for (int t = 0; t < MT; ++t) x[t] = var[r + (size_t)col[t]];
+  }
+  // T: the output tile the diagonal crosses during these four steps; the tiles below T are wholly
+  // above the diagonal and do not appear in the code of this T at all
+#pragma unroll
+  for (int T = 0; T < NT; ++T) {
+    if (T < ntiles) {
+      const int kend = min(HXW_TILE * (T + 1), n);
+      for (int k0 = HXW_TILE * T; k0 < kend; k0 += 4) {
+        const double *wk = wf + (size_t)(k0 >> 2) * (NT * 64) + lane;
+        double a[NT];
+#pragma unroll
+        for (int i = T; i < NT; ++i) a[i] = wk[i * 64];   // (a tile past n: packed zeros, an exact 0)
+        const double o = onext;
+        const bool on = k0 + g < n;
+        double r[MT];
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+          const double d = (x[t] - bs[t]) - o;   // (no baseline: bs = 0.0 and x - 0.0 is x, bit for bit)
+          r[t] = on ? d : 0.0;
+        }
+        // the next step's rows, in flight during this step's contraction (past n: the padding's valid row)
+        const size_t rn = (size_t)rnext * (size_t)npad;
+#pragma unroll
+        for (int t = 0; t < MT; ++t) x[t] = var[rn + (size_t)col[t]];
+        onext = obs[k0 + 4 + g];
+        rnext = iy[k0 + 8 + g];
+#pragma unroll
+        for (int i = T; i < NT; ++i)
+#pragma unroll
+          for (int t = 0; t < MT; ++t)
+            acc[i][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], r[t], acc[i][t], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) s += acc[i][t][q] * acc[i][t][q];
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    const int m = m0 + HXW_TILE * t + c;
+    if (g == 0 && m < nmem) out[m] = s;
+  }
+}
+
+// iy / obs: [hx_sw_padded(n) + 8]; wf: hx_sw_pack's; base: nullptr or [npad]; out: [npad] in lane order
+hipError_t hx_launch_score_whiten(const double *var, int nmem, int npad, const int *iy, const double *obs,
+                                  const double *wf, int n, const double *base, double *out, hipStream_t st) {
+  if (n < 1 || n > HXW_MAX || nmem < 1 || nmem > npad) return hipErrorInvalidValue;
+#define HXW_CASE(NT, MT) \
+  hipLaunchKernelGGL((hx_score_whiten_kernel<NT, MT>), dim3((nmem + MT * HXW_TILE - 1) / (MT * HXW_TILE)), \
+                     dim3(64), 0, st, var, nmem, npad, iy, obs, wf, n, base, out)
+  if (n <= 64) HXW_CASE(4, 4);
+  else if (n <= 128) HXW_CASE(8, 2);
+  else if (n <= 192) HXW_CASE(12, 1);
+  else HXW_CASE(16, 1);
+#undef HXW_CASE
+  return hipGetLastError();
+}
 #endif  // !HX_HOST_EMULATION

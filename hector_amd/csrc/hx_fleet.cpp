@@ -350,6 +350,15 @@ int Fleet::member_score(const std::string &cap, const int *years, const double *
   return used;
 }
 
+void Fleet::member_score_whitened(const std::string &cap, const int *years, const double *obs,
+                                  const double *whiten, int n, int base_year0, int base_year1, double *out) {
+  check_poison();
+  for (Shard &s : shards_) {
+    use(s);
+    s.core->member_score_whitened(cap, years, obs, whiten, n, base_year0, base_year1, out + s.offset);
+  }
+}
+
 void Fleet::quantise_weights(const double *weights, const char *fn, std::vector<unsigned long long> &q) const {
   // integer weights: q = rint(w / wmax * 2^32), wmax over ALL shards
   q.clear();

@@ -278,6 +278,38 @@ int hx_member_score(hx_core *core, const char *capability, const int *years, con
                     const double *sigma, int n, int base_year0, int base_year1,
                     double *out, int *n_used);
 
+/* Misfit of every member against an observed record whose errors are CORRELATED, on the device: the
+ * generalised chi-square r^T C^-1 r for an error covariance C = L L^T, given as the whitening matrix
+ * W = L^-1 (lower-triangular, n x n, row-major: whiten[i * n + k]); no counterpart in the reference.
+ *   r_k = (x(years[k], member) - base(member)) - obs[k]      (no baseline: r_k = x - obs[k])
+ *   y_i = sum_{k <= i} whiten[i * n + k] * r_k,    chi2[member] = sum_i y_i^2
+ * x, years (any order, repeats allowed; W refers to the order given) and base as in hx_member_score:
+ * base is the sequential sum s = 0.0; s = s + x_y over base_year0..base_year1 and ONE division;
+ * base_year0 > base_year1: no baseline.  r is two IEEE subtractions, nothing is fused into them.
+ * ONLY the entries with k <= i are read: the upper triangle of whiten may hold anything, NaN included.
+ * 1 <= n <= HX_SCORE_WHITENED_MAX.  There is NO skipping: a NaN or infinite obs is an error (dropping
+ * a year changes the factorisation, which is the caller's to redo), and so is a non-finite whiten
+ * entry at k <= i.  A member whose x is NaN in a scored year or in the reference period gets NaN (an
+ * infinite x: NaN or infinity); no other member is affected.
+ * The ORDER of the sums and the use of fused multiply-adds are NOT part of the definition (the
+ * contraction runs on the fp64 matrix pipe).  The error bound is: with s_i = sum_{k <= i}
+ * |whiten[i * n + k] * r_k| and the r_k as above,
+ *   |chi2 - sum_i y_i^2 evaluated exactly| <= (3 n + 8) 2^-53 sum_i s_i^2
+ * (each y_i within n 2^-53 s_i of its exact value, |y_i| <= s_i, and the squares and their n additions
+ * of non-negative terms add (n + 1) 2^-53), whatever the order.  Every member's sums are formed in ONE
+ * fixed order: the result for a member is bit-identical from call to call and depends neither on lane
+ * order, kernel flavour or shard layout, nor on which other members exist.
+ * out[n_members] in the caller's member order.  Cost: one read of the n (+ reference period) rows,
+ * about n^2 n_members flops on the matrix pipe, an n x n upload and n_members doubles back to the
+ * host; returns when they are there.  The core is not prepared, spun up or dirtied; a core of several
+ * shards or in a communicator of several processes scores shard by shard (nothing crosses members).
+ * The host-emulation build refuses the call after the argument checks.  Errors: a null argument, n
+ * outside 1..HX_SCORE_WHITENED_MAX, a non-finite obs or whiten entry, dates or a reference period
+ * outside startDate..current date, an unrecorded capability, a core that has not run. */
+#define HX_SCORE_WHITENED_MAX 256
+int hx_member_score_whitened(hx_core *core, const char *capability, const int *years, const double *obs,
+                             const double *whiten, int n, int base_year0, int base_year1, double *out);
+
 /* Per-year weighted quantiles over the whole ensemble, on the device; no counterpart in the
  * reference.  out[(year - year0) * nprobs + j] = the probs[j]-quantile of x(year, .) over the members
  * that take part, weighted by weights[n_members] (member order; NULL = every member weight 1);
