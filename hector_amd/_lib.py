@@ -171,6 +171,7 @@ def _declare(lib):
         "hx_member_score": [P, c.c_char_p, c.POINTER(c.c_int), dp, dp, c.c_int, c.c_int, c.c_int, dp,
                             c.POINTER(c.c_int)],
         "hx_member_score_whitened": [P, c.c_char_p, c.POINTER(c.c_int), dp, dp, c.c_int, c.c_int, c.c_int, dp],
+        "hx_member_project": [P, c.c_char_p, c.POINTER(c.c_int), dp, dp, c.c_int, c.c_int, c.c_int, c.c_int, dp],
         "hx_ensemble_quantiles": [P, c.c_char_p, c.c_int, c.c_int, dp, dp, c.c_int, dp,
                                   c.POINTER(c.c_longlong)],
         "hx_member_metrics": [P, c.c_char_p, c.c_void_p, c.c_int, dp],
@@ -222,7 +223,7 @@ ABI_SYMBOLS = ["hx_backend", "hx_build_info", "hx_last_error", "hx_newcore", "hx
                "hx_device_var_shard", "hx_stream_shard", "hx_comm_unique_id", "hx_comm_init_rank",
                "hx_comm_info", "hx_ensemble_stats", "hx_set_lane_calibration", "hx_lanes_calibrated", "hx_lane_order_source", "hx_set_cost_model",
                "hx_cost_models_export", "hx_cost_models_load", "hx_set_prewarm", "hx_last_run_prewarmed",
-               "hx_member_score", "hx_member_score_whitened", "hx_ensemble_quantiles", "hx_member_metrics", "hx_metric_quantiles",
+               "hx_member_score", "hx_member_score_whitened", "hx_member_project", "hx_ensemble_quantiles", "hx_member_metrics", "hx_metric_quantiles",
                "hx_ensemble_probabilities", "hx_metric_probabilities",
                "hx_ensemble_moments", "hx_metric_moments", "hx_ensemble_comoments",
                "hx_series_define", "hx_series_drop", "hx_series_list"]

@@ -24,6 +24,7 @@ SERIES_OPS = {"copy": 0, "add": 1, "sub": 2, "mul": 3, "div": 4, "anomaly": 5, "
 
 
 _SCORE_WHITENED_MAX = 256   # HX_SCORE_WHITENED_MAX
+_PROJECT_MAX_OUT, _PROJECT_MAX_YEARS = 64, 1024   # HX_PROJECT_MAX_OUT, HX_PROJECT_MAX_YEARS
 
 
 def _whiten(cov, who):
@@ -285,6 +286,13 @@ class CoMoments:
                 p *= -1.0
         tr = np.trace(cov)
         return val, (val / tr if tr > 0 else np.full(k, np.nan)), pat
+
+    def scores(self, core, var, k):
+        """The k leading principal-component scores of every member, on the device: pattern .
+        (trajectory - mean) -> ndarray [k, n_members]; core.project(var, years_a, pca(k)[2],
+        center=mean_a).  var is the variable this result was taken of; a result that is not
+        symmetric is refused as pca refuses it."""
+        return core.project(var, self.years_a, self.pca(k)[2], center=self.mean_a)
 
     def __repr__(self):
         return "CoMoments(na=%d, nb=%d, symmetric=%r, n_part=%d)" % (self.shift_a.size, self.shift_b.size,
@@ -692,6 +700,55 @@ class Core:
             self._h, var.encode(), yr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ob.ctypes.data_as(dp),
             W.ctypes.data_as(dp), n, b0, b1, out.ctypes.data_as(dp)))
         return (out, n) if return_used else out
+
+    def project(self, var, years, basis, center=None, baseline=None):
+        """A matrix applied to every member's series, on the device (hx_member_project):
+          r_k = (x(years[k], member) - base(member)) - center[k]
+          out[j, member] = sum over k of basis[j, k] * r_k
+        -> ndarray [m, n_members] for basis [m, n]; a one-dimensional basis of n entries -> [n_members].
+        years in any order, repeats allowed (basis refers to the order given), 1 <= n <= 1024 and
+        1 <= m <= 64; center None: zeros; baseline = (year0, year1): base is the member's own mean
+        of x over those years, None: nothing is subtracted.  basis and center must be finite; a
+        member with a NaN in a year read or in the reference period is NaN in all m outputs.
+        The order of the sum is not part of the definition (fp64 matrix pipe): with s_j = sum_k
+        |basis[j, k] r_k| every output lies within (n + 2) 2^-53 s_j of the exact sum.  An output is
+        bit-identical from call to call and independent of lane order, shards, the other members
+        and the other rows of basis."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        yr = np.ascontiguousarray(np.atleast_1d(np.asarray(years)).astype(np.int32))
+        if yr.ndim != 1 or yr.size < 1:
+            raise HectorAmdError("project: years must be one-dimensional and not empty")
+        n = int(yr.size)
+        B = np.asarray(basis, dtype=np.float64)
+        one = B.ndim == 1
+        if one:
+            B = B[None, :]
+        if B.ndim != 2 or B.shape[1] != n or B.shape[0] < 1:
+            raise HectorAmdError("project: basis must be [m, n] (or [n]) for n years")
+        m = int(B.shape[0])
+        if n > _PROJECT_MAX_YEARS:
+            raise HectorAmdError("project: more than %d years (hx_member_project takes 1..%d)"
+                                 % (_PROJECT_MAX_YEARS, _PROJECT_MAX_YEARS))
+        if m > _PROJECT_MAX_OUT:
+            raise HectorAmdError("project: more than %d basis rows (hx_member_project takes 1..%d)"
+                                 % (_PROJECT_MAX_OUT, _PROJECT_MAX_OUT))
+        if not np.isfinite(B).all():
+            raise HectorAmdError("project: basis has a NaN or infinite entry")
+        B = np.ascontiguousarray(B)
+        cp = None
+        if center is not None:
+            ce = np.ascontiguousarray(np.atleast_1d(np.asarray(center, dtype=np.float64)))
+            if ce.shape != yr.shape:
+                raise HectorAmdError("project: center must have one entry per year")
+            if not np.isfinite(ce).all():
+                raise HectorAmdError("project: center has a NaN or infinite entry")
+            cp = ce.ctypes.data_as(dp)
+        b0, b1 = (1, 0) if baseline is None else (int(baseline[0]), int(baseline[1]))
+        out = np.empty((m, self.n_members))
+        self._ck(self._lib.hx_member_project(
+            self._h, var.encode(), yr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), cp, B.ctypes.data_as(dp),
+            n, m, b0, b1, out.ctypes.data_as(dp)))
+        return out[0] if one else out
 
     def quantiles(self, var, probs, dates=None, weights=None, counts=False):
         """Per-year weighted quantiles over every member, on the device (hx_ensemble_quantiles:

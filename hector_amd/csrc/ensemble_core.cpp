@@ -94,6 +94,10 @@ int hx_sw_padded(int n);
 void hx_sw_pack(const double *whiten, int n, double *wf);
 hipError_t hx_launch_score_whiten(const double *var, int nmem, int npad, const int *iy, const double *obs,
                                   const double *wf, int n, const double *base, double *out, hipStream_t st);
+int hx_project_steps(int n);
+void hx_project_pack(const double *basis, int n, int m, double *bf);
+hipError_t hx_launch_project(const double *var, int nmem, int npad, const int *iy, const double *center,
+                             const double *bf, int n, int m, const double *base, double *out, hipStream_t st);
 #endif
 
 #ifndef HX_HOST_EMULATION
@@ -583,6 +587,7 @@ void EnsembleCore::free_device() {
   fr(d_mom_); d_mom_ = nullptr; mom_cap_ = 0; mom_src_ = nullptr;
   fr(d_comom_); d_comom_ = nullptr; comom_cap_ = 0; co_a_ = nullptr;
   fr(d_whiten_); d_whiten_ = nullptr; whiten_cap_ = 0;
+  fr(d_project_); d_project_ = nullptr; project_cap_ = 0;
   d_score_ = nullptr; d_q_ = d_qstate_ = d_qhist_ = nullptr;
   d_metplan_ = nullptr; d_met_ = nullptr; d_bin_ = nullptr;
   score_cap_ = qstate_cap_ = qhist_cap_ = metplan_cap_ = met_cap_ = bin_cap_ = 0; q_src_ = nullptr;
@@ -3401,6 +3406,79 @@ void EnsembleCore::member_score_whitened(const std::string &capability, const in
   check(hipMemcpyAsync(out_host, d_mem, sizeof(double) * (size_t)n_, hipMemcpyDeviceToHost, stream_),
         "whitened score fetch");
   check(hipStreamSynchronize(stream_), "whitened score sync");   // (h and iy are pageable: copied by now)
+#endif
+}
+
+// ---- projection onto a caller's basis (hx_member_project) -------------------------------------------
+
+void EnsembleCore::member_project(const std::string &capability, const int *years, const double *center,
+                                  const double *basis, int n, int m, int base_year0, int base_year1,
+                                  double *out_host, size_t row_pitch) {
+  const std::string f = "hx_member_project";
+  if (!years || !basis || !out_host) throw std::runtime_error(f + ": null argument");
+  if (n < 1 || n > HX_PROJECT_MAX_YEARS) throw std::runtime_error(f + ": n must lie in 1..1024");
+  if (m < 1 || m > HX_PROJECT_MAX_OUT) throw std::runtime_error(f + ": m must lie in 1..64");
+  if (center)
+    for (int i = 0; i < n; ++i)
+      if (!std::isfinite(center[i]))
+        throw std::runtime_error(f + ": an entry of center is NaN or infinite (there is no skipping)");
+  for (size_t i = 0; i < (size_t)m * (size_t)n; ++i)
+    if (!std::isfinite(basis[i])) throw std::runtime_error(f + ": an entry of basis is NaN or infinite");
+  const PostSource ps = post_source(capability, f.c_str());
+  if (ps.v >= 0 && !d_out_[ps.v])
+    throw std::runtime_error(f + ": variable " + capability + " was not enabled with set_outputs()");
+  const int last = scen_.start + ps.last_iy;
+  const bool has_base = base_year0 <= base_year1;
+  for (int i = 0; i < n; ++i)
+    if (years[i] < scen_.start || years[i] > last)
+      throw std::runtime_error(f + ": dates must lie between startDate and the current date");
+  if (has_base && (base_year0 < scen_.start || base_year1 > last))
+    throw std::runtime_error(f + ": the reference period must lie between startDate and the current date");
+  if (!d_lane_of_member_ || !ps.block) throw std::runtime_error(f + ": run the core first");
+#ifdef HX_HOST_EMULATION
+  (void)row_pitch;
+  throw std::runtime_error(f + kEmulRefusal);
+#else
+  sync();
+  const int nt = (m + 15) / 16;
+  const size_t NB = (size_t)hx_project_steps(n) * (size_t)nt * 64;   // the basis in fragment order
+  const size_t NL = 4 * (size_t)hx_project_steps(n) + 8;             // (the lists: padded by two steps of the kernel)
+  const size_t P = (size_t)npad_, M = (size_t)m;
+  // [bf NB][center NL][base npad][out m x npad][out in member order m x n_] doubles, then the rows [NL] ints
+  const size_t doubles = NB + NL + P + M * P + M * (size_t)n_;
+  const size_t bytes = sizeof(double) * doubles + sizeof(int) * NL;
+  if (bytes > project_cap_) {
+    if (d_project_) (void)hipFree(d_project_);
+    d_project_ = nullptr; project_cap_ = 0;
+    check(hipMalloc(&d_project_, bytes), "hipMalloc project");
+    project_cap_ = bytes;
+  }
+  double *d_bf = d_project_, *d_center = d_bf + NB, *d_base = d_center + NL, *d_lane = d_base + P, *d_mem = d_lane + M * P;
+  int *d_iy = reinterpret_cast<int *>(d_mem + M * (size_t)n_);
+  // one upload: the basis in fragment order (zeros in the padding) and the centre, and one of the rows
+  // -- both lists padded with 0.0 / a valid row (never consumed)
+  std::vector<double> h(NB + NL, 0.0);
+  hx_project_pack(basis, n, m, h.data());
+  std::vector<int> iy(NL, years[n - 1] - scen_.start);
+  for (int i = 0; i < n; ++i) {
+    if (center) h[NB + (size_t)i] = center[i];
+    iy[(size_t)i] = years[i] - scen_.start;
+  }
+  check(hipMemcpyAsync(d_bf, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, stream_), "project basis");
+  check(hipMemcpyAsync(d_iy, iy.data(), sizeof(int) * NL, hipMemcpyHostToDevice, stream_), "project years");
+  if (has_base)
+    check(hx_launch_series_base(ps.block, npad_, base_year0 - scen_.start, base_year1 - scen_.start, d_base,
+                                stream_), "project base kernel");
+  check(hx_launch_project(ps.block, n_, npad_, d_iy, d_center, d_bf, n, m, has_base ? d_base : nullptr, d_lane,
+                          stream_), "project kernel");
+  check(hx_launch_gather(d_lane, d_lane_of_member_, d_mem, n_, npad_, m, stream_), "project gather");
+  if (row_pitch)
+    check(hipMemcpy2DAsync(out_host, sizeof(double) * row_pitch, d_mem, sizeof(double) * (size_t)n_,
+                           sizeof(double) * (size_t)n_, M, hipMemcpyDeviceToHost, stream_), "project fetch");
+  else
+    check(hipMemcpyAsync(out_host, d_mem, sizeof(double) * M * (size_t)n_, hipMemcpyDeviceToHost, stream_),
+          "project fetch");
+  check(hipStreamSynchronize(stream_), "project sync");   // (h and iy are pageable: copied by now)
 #endif
 }
 

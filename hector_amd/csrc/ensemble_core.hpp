@@ -151,6 +151,11 @@ class EnsembleCore {
   // hector_amd.h): whiten[n x n] row-major, only k <= i read; out_host[n_] in member order
   void member_score_whitened(const std::string &capability, const int *years, const double *obs,
                              const double *whiten, int n, int base_year0, int base_year1, double *out_host);
+  // out[j][member] = sum_k basis[j * n + k] r_k (hx_member_project in hector_amd.h): basis[m x n]
+  // row-major, center nullptr = zeros; out_host row j at out_host + j * row_pitch (0: n_), member order
+  void member_project(const std::string &capability, const int *years, const double *center,
+                      const double *basis, int n, int m, int base_year0, int base_year1, double *out_host,
+                      size_t row_pitch = 0);
   // weighted quantiles (hx_ensemble_quantiles): q[n_] integer weights in member order (nullptr:
   // every member 1), out_host[(year - year0) * nprobs + j], n_part[year - year0] (may be nullptr)
   void quantiles(const std::string &capability, int year0, int year1, const unsigned long long *q,
@@ -327,6 +332,10 @@ class EnsembleCore {
   // member order n_] + rows np
   double *d_whiten_ = nullptr;
   size_t whiten_cap_ = 0;
+  // scratch of member_project: [basis in fragment order][center][base npad][out m x npad][out in member
+  // order m x n_] + rows
+  double *d_project_ = nullptr;
+  size_t project_cap_ = 0;
   unsigned long long *d_q_ = nullptr;         // integer weights in lane order [npad]
   unsigned long long *d_qstate_ = nullptr;    // per year {HxQYear, lo}, per (year, prob) {prefix, rem}, probs
   unsigned long long *d_qhist_ = nullptr;     // [ny][nprobs][256]

@@ -375,6 +375,16 @@ int hx_member_score_whitened(hx_core *core, const char *capability, const int *y
     return fail("hx_member_score_whitened: n must lie in 1..256");
   HX_TRY(core->core->member_score_whitened(capability, years, obs, whiten, n, base_year0, base_year1, out))
 }
+int hx_member_project(hx_core *core, const char *capability, const int *years, const double *center,
+                      const double *basis, int n, int m, int base_year0, int base_year1, double *out) {
+  if (!capability || !years || !basis || !out)
+    return fail("hx_member_project: null argument");
+  if (n < 1 || n > HX_PROJECT_MAX_YEARS)
+    return fail("hx_member_project: n must lie in 1..1024");
+  if (m < 1 || m > HX_PROJECT_MAX_OUT)
+    return fail("hx_member_project: m must lie in 1..64");
+  HX_TRY(core->core->member_project(capability, years, center, basis, n, m, base_year0, base_year1, out))
+}
 int hx_ensemble_quantiles(hx_core *core, const char *capability, int year0, int year1,
                           const double *weights, const double *probs, int nprobs, double *out,
                           long long *n_part) {

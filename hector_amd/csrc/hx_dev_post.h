@@ -1284,4 +1284,140 @@ hipError_t hx_launch_score_whiten(const double *var, int nmem, int npad, const i
 #undef HXW_CASE
   return hipGetLastError();
 }
+
+// ===========================================================================
+// Projection of every member's residuals onto a caller's basis (hx_member_project in hector_amd.h
+// defines it): Y = B R with B the dense m x n basis and R the residuals [year k][member], on
+// v_mfma_f64_16x16x4_f64 with M = output j, N = member, K = year k.  A[j][k] comes from lane
+// (j = lane & 15, k = lane >> 4), B[k][member] from lane (member = lane & 15, k = lane >> 4), D sits
+// at row (lane >> 4) + 4 reg, column lane & 15 -- the layout of the whitened score above.
+//   Ownership   one wavefront a workgroup; it owns HXP_MT tiles of HXP_TILE members (64 members) and
+//               all NT = ceil(m / 16) tiles of HXP_TILE outputs, 4 NT HXP_MT <= 64 accumulator doubles
+//               a lane: nothing is exchanged with another wavefront, no partials, no atomics, no LDS.
+//   Loop        k0 in steps of 4 over all of n (the matrix is dense: no tile is skipped).  Lane (c, g)
+//               reads x[iy[k0 + g]][m0 + 16 t + c] -- four whole 128-byte segments of the
+//               [year][lane] rows a load, every row read once -- a step ahead of its use, and forms r
+//               with two IEEE subtractions.  The row number is read two steps ahead, so no load
+//               waits for another; iy and center are padded by two steps with a valid row / 0.0.
+//   Basis       the host (EnsembleCore::member_project) packs it in fragment order,
+//               bf[((k0 / 4) NT + tile) 64 + lane], so that an A fragment is one 512-byte read from
+//               L2; entries with j >= m or k >= n are exact 0.0, and r is selected to an exact 0.0
+//               for k >= n.  Every D element is its own chain of fused multiply-adds over k, the
+//               same chain in every flavour: an output does not depend on which other rows the
+//               basis has, nor on the tile or register its row falls in.
+//   Store       lane (c, g), output tile i, member tile t, register q holds output j = 16 i + g + 4 q
+//               of member m0 + 16 t + c and writes it to the lane-ordered buffer out[j][npad], sixteen
+//               consecutive doubles a lane group, for j < m and member < nmem only; hx_launch_gather
+//               with m rows brings it to member order.  Columns >= n members or >= npad are computed
+//               from whatever they hold and not stored.
+// ===========================================================================
+#define HXP_TILE 16          // members per B tile, outputs per A tile (the MFMA's M and N)
+#define HXP_MT 4             // member tiles a wavefront: 64 members
+#define HXP_MAX_OUT 64       // HX_PROJECT_MAX_OUT: 4 output tiles x HXP_MT = 16 accumulator quads a lane
+#define HXP_MAX_YEARS 1024   // HX_PROJECT_MAX_YEARS
+static_assert(HXP_MAX_OUT == HX_PROJECT_MAX_OUT && HXP_MAX_YEARS == HX_PROJECT_MAX_YEARS, "the header's limits");
+static_assert(HXP_MAX_OUT % HXP_TILE == 0 && HXP_MAX_OUT / HXP_TILE * HXP_MT <= 16, "64 accumulator doubles a lane");
+
+// the steps of 4 years the k loop takes for n years; iy and center hold 4 hx_project_steps(n) + 8 entries
+int hx_project_steps(int n) { return (n + 3) / 4; }
+
+// bf[hx_project_steps(n) x NT x 64] in fragment order from basis[m x n] (row-major), NT = ceil(m / 16)
+void hx_project_pack(const double *basis, int n, int m, double *bf) {
+  const int nt = (m + HXP_TILE - 1) / HXP_TILE, ns = hx_project_steps(n);
+  for (int ks = 0; ks < ns; ++ks)
+    for (int tile = 0; tile < nt; ++tile)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int j = HXP_TILE * tile + (lane & 15), k = 4 * ks + (lane >> 4);
+        bf[((size_t)ks * nt + tile) * 64 + lane] = (j < m && k < n) ? basis[(size_t)j * n + k] : 0.0;
+      }
+}
+
+// iy[4 steps + 8], center[4 steps + 8] (padded: a valid row, 0.0); base: nullptr = none, else [npad]
+template <int NT>
+__global__ __launch_bounds__(64) void hx_project_kernel(const double *__restrict__ var, int nmem, int npad,
+                                                        const int *__restrict__ iy,
+                                                        const double *__restrict__ center,
+                                                        const double *__restrict__ bf, int n, int m,
+                                                        const double *__restrict__ base,
+                                                        double *__restrict__ out) {
+  typedef double d4 __attribute__((ext_vector_type(4)));
+  static_assert(NT >= 1 && NT * HXP_TILE <= HXP_MAX_OUT, "64 accumulator doubles a lane at the most");
+  const int lane = (int)threadIdx.x, c = lane & 15, g = lane >> 4;
+  const int m0 = (int)blockIdx.x * (HXP_MT * HXP_TILE);
+  int col[HXP_MT];
+  double bs[HXP_MT], x[HXP_MT];
+#pragma unroll
+  for (int t = 0; t < HXP_MT; ++t) {
+    col[t] = min(m0 + HXP_TILE * t + c, npad - 1);   // (a column past the block: read inside it, never stored)
+    bs[t] = base ? base[col[t]] : 0.0;
+  }
+  d4 acc[NT][HXP_MT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int t = 0; t < HXP_MT; ++t) acc[i][t] = d4{0, 0, 0, 0};
+  // lane group g takes year k0 + g of a step: its row number is read two steps ahead of its use,
+  // its values and its centre one step ahead (iy and center are padded by two steps)
+  int rnext = iy[4 + g];
+  double cnext = center[g];
+  {
+    const size_t r = (size_t)iy[g] * (size_t)npad;
+#pragma unroll
+    for (int t = 0; t < HXP_MT; ++t) x[t] = var[r + (size_t)col[t]];
+  }
+  for (int k0 = 0; k0 < n; k0 += 4) {
+    const double *bk = bf + (size_t)(k0 >> 2) * (NT * 64) + lane;
+    double a[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) a[i] = bk[i * 64];   // (j >= m, k >= n: packed zeros)
+    const double o = cnext;
+    const bool on = k0 + g < n;
+    double r[HXP_MT];
+#pragma unroll
+    for (int t = 0; t < HXP_MT; ++t) {
+      const double d = (x[t] - bs[t]) - o;   // (no baseline: bs = 0.0 and x - 0.0 is x, bit for bit)
+      r[t] = on ? d : 0.0;
+    }
+    // the next step's rows, in flight during this step's contraction (past n: the padding's valid row)
+    const size_t rn = (size_t)rnext * (size_t)npad;
+#pragma unroll
+    for (int t = 0; t < HXP_MT; ++t) x[t] = var[rn + (size_t)col[t]];
+    cnext = center[k0 + 4 + g];
+    rnext = iy[k0 + 8 + g];
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+      for (int t = 0; t < HXP_MT; ++t)
+        acc[i][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], r[t], acc[i][t], 0, 0, 0);
+  }
+#pragma unroll
+  for (int t = 0; t < HXP_MT; ++t) {
+    const int mem = m0 + HXP_TILE * t + c;
+    if (mem < nmem) {
+#pragma unroll
+      for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int j = HXP_TILE * i + g + 4 * q;
+          if (j < m) out[(size_t)j * (size_t)npad + (size_t)mem] = acc[i][t][q];
+        }
+    }
+  }
+}
+
+// iy / center: [4 hx_project_steps(n) + 8]; bf: hx_project_pack's; base: nullptr or [npad]; out: [m][npad] in lane order
+hipError_t hx_launch_project(const double *var, int nmem, int npad, const int *iy, const double *center,
+                             const double *bf, int n, int m, const double *base, double *out, hipStream_t st) {
+  if (n < 1 || n > HXP_MAX_YEARS || m < 1 || m > HXP_MAX_OUT || nmem < 1 || nmem > npad) return hipErrorInvalidValue;
+#define HXP_CASE(NT) \
+  hipLaunchKernelGGL((hx_project_kernel<NT>), dim3((nmem + HXP_MT * HXP_TILE - 1) / (HXP_MT * HXP_TILE)), \
+                     dim3(64), 0, st, var, nmem, npad, iy, center, bf, n, m, base, out)
+  const int nt = (m + HXP_TILE - 1) / HXP_TILE;
+  if (nt == 1) HXP_CASE(1);
+  else if (nt == 2) HXP_CASE(2);
+  else if (nt == 3) HXP_CASE(3);
+  else HXP_CASE(4);
+#undef HXP_CASE
+  return hipGetLastError();
+}
 #endif  // !HX_HOST_EMULATION

@@ -359,6 +359,15 @@ void Fleet::member_score_whitened(const std::string &cap, const int *years, cons
   }
 }
 
+void Fleet::member_project(const std::string &cap, const int *years, const double *center, const double *basis,
+                           int n, int m, int base_year0, int base_year1, double *out) {
+  check_poison();
+  for (Shard &s : shards_) {   // every shard copies its members straight into its columns of out[m][n_]
+    use(s);
+    s.core->member_project(cap, years, center, basis, n, m, base_year0, base_year1, out + s.offset, (size_t)n_);
+  }
+}
+
 void Fleet::quantise_weights(const double *weights, const char *fn, std::vector<unsigned long long> &q) const {
   // integer weights: q = rint(w / wmax * 2^32), wmax over ALL shards
   q.clear();

@@ -93,6 +93,9 @@ class Fleet {
   // hx_member_score_whitened: shard by shard like member_score (nothing crosses members)
   void member_score_whitened(const std::string &capability, const int *years, const double *obs,
                              const double *whiten, int n, int base_year0, int base_year1, double *out_host);
+  // hx_member_project: shard by shard like member_score_whitened; out_host[m][n_], a shard fills its columns
+  void member_project(const std::string &capability, const int *years, const double *center,
+                      const double *basis, int n, int m, int base_year0, int base_year1, double *out_host);
   // hx_ensemble_quantiles: weights checked and quantised against the largest of the WHOLE ensemble;
   // one shard runs the select on its GPU, several shards fill integer histograms that are added
   // and searched here, pass by pass (exact: the same bits as one core)

@@ -310,6 +310,41 @@ int hx_member_score(hx_core *core, const char *capability, const int *years, con
 int hx_member_score_whitened(hx_core *core, const char *capability, const int *years, const double *obs,
                              const double *whiten, int n, int base_year0, int base_year1, double *out);
 
+/* Projection of every member's trajectory onto a caller's basis, on the device: a dense m x n matrix
+ * (row-major: basis[j * n + k]) applied to every member's residuals -- principal-component scores,
+ * the update of an ensemble smoother, any fixed linear functional; no counterpart in the reference.
+ *   r_k = (x(years[k], member) - base(member)) - center[k]      (no baseline: r_k = x - center[k])
+ *   out[j * n_members + member] = sum_{k < n} basis[j * n + k] * r_k,    j < m
+ * x, years (any order, repeats allowed; basis refers to the order given) and base as in
+ * hx_member_score: base is the sequential sum s = 0.0; s = s + x_y over base_year0..base_year1 and ONE
+ * division; base_year0 > base_year1: no baseline.  r is two IEEE subtractions, nothing is fused into
+ * them.  center == NULL means zeros: the second subtraction is then - 0.0.
+ * 1 <= n <= HX_PROJECT_MAX_YEARS and 1 <= m <= HX_PROJECT_MAX_OUT.  There is NO skipping: a NaN or
+ * infinite center or basis entry is an error.  A member whose x is NaN in any year read or in the
+ * reference period gets NaN in ALL m outputs -- a zero coefficient does not mask it (an infinite x:
+ * NaN or infinity); no other member is affected.
+ * The ORDER of the sum and the use of fused multiply-adds are NOT part of the definition (the
+ * contraction runs on the fp64 matrix pipe).  The error bound is: with s_j = sum_k
+ * |basis[j * n + k] * r_k| and the r_k as above,
+ *   |out_j - sum_k basis[j * n + k] * r_k evaluated exactly| <= (n + 2) 2^-53 s_j
+ * (a dot product of length n in any order, fused or not, is within (n + 1) 2^-53 s_j of exact while
+ * n 2^-53 << 1; one more for slack).  Every (output, member) sum is formed in ONE fixed order: the
+ * result is bit-identical from call to call and depends neither on lane order, member sorting, kernel
+ * flavour or shard layout, nor on which other members exist, nor on which other rows basis has or at
+ * which position row j stands.
+ * out[m * n_members], row j in the caller's member order.  Cost: one read of the n (+ reference
+ * period) rows, 2 n m n_members flops on the matrix pipe, an n x m upload and m x n_members doubles
+ * back to the host; returns when they are there.  The core is not prepared, spun up or dirtied; a
+ * core of several shards or in a communicator of several processes projects shard by shard (nothing
+ * crosses members).  The host-emulation build refuses the call after the argument checks.  Errors: a
+ * null argument (center excepted), n outside 1..HX_PROJECT_MAX_YEARS, m outside 1..HX_PROJECT_MAX_OUT,
+ * a non-finite center or basis entry, dates or a reference period outside startDate..current date,
+ * an unrecorded capability, a core that has not run. */
+#define HX_PROJECT_MAX_OUT   64
+#define HX_PROJECT_MAX_YEARS 1024
+int hx_member_project(hx_core *core, const char *capability, const int *years, const double *center,
+                      const double *basis, int n, int m, int base_year0, int base_year1, double *out);
+
 /* Per-year weighted quantiles over the whole ensemble, on the device; no counterpart in the
  * reference.  out[(year - year0) * nprobs + j] = the probs[j]-quantile of x(year, .) over the members
  * that take part, weighted by weights[n_members] (member order; NULL = every member weight 1);
