@@ -91,6 +91,52 @@ class Metric:
         return _HxMetric(METRIC_OPS[self.op], self.years[0], self.years[1], b0, b1, 0, self.threshold)
 
 
+class _HxPairMetric(ctypes.Structure):   # hx_pair_metric
+    _fields_ = [("op", ctypes.c_int), ("year0", ctypes.c_int), ("year1", ctypes.c_int),
+                ("base_a0", ctypes.c_int), ("base_a1", ctypes.c_int), ("base_b0", ctypes.c_int),
+                ("base_b1", ctypes.c_int), ("reserved", ctypes.c_int), ("threshold", ctypes.c_double)]
+
+
+PAIR_METRIC_OPS = {"slope": 0, "intercept": 1, "r2": 2, "at_first_ge": 3, "at_max": 4, "at_min": 5,
+                   "mean_where_ge": 6, "end_ratio": 7}   # HX_PMET_*
+
+
+class PairMetric:
+    """One number per member from a window of TWO series of that member, a (reported / dependent) and
+    b (condition / independent) (hx_pair_metric in include/hector_amd.h).
+    op: "slope", "intercept", "r2" (the regression of a on b), "at_first_ge" (a in the first year with
+    b >= threshold), "at_max", "at_min" (a in the first year that holds the largest / smallest b),
+    "mean_where_ge" (the mean of a over the years with b >= threshold) or "end_ratio"
+    ((a_year1 - a_year0) / (b_year1 - b_year0));
+    years = (year0, year1) or one year; baseline / baseline_b = (year0, year1): the member's own mean
+    of a / of b over those years is subtracted first; threshold: for the two "_ge" operations."""
+
+    def __init__(self, op, years, baseline=None, baseline_b=None, threshold=float("nan")):
+        if op not in PAIR_METRIC_OPS:
+            raise HectorAmdError("PairMetric: unknown op %r (one of %s)" % (op, ", ".join(PAIR_METRIC_OPS)))
+        y = np.atleast_1d(np.asarray(years)).astype(np.int64)
+        if y.size < 1:
+            raise HectorAmdError("PairMetric: years must be a year or (year0, year1)")
+        self.op = op
+        self.years = (int(y.min()), int(y.max()))
+        for name, b in (("baseline", baseline), ("baseline_b", baseline_b)):
+            if b is not None and (len(b) != 2 or int(b[1]) < int(b[0])):
+                raise HectorAmdError("PairMetric: %s must be (year0, year1) with year0 <= year1" % name)
+        self.baseline = None if baseline is None else (int(baseline[0]), int(baseline[1]))
+        self.baseline_b = None if baseline_b is None else (int(baseline_b[0]), int(baseline_b[1]))
+        self.threshold = float(threshold)
+
+    def __repr__(self):
+        return "PairMetric(%r, %r, baseline=%r, baseline_b=%r, threshold=%r)" % (
+            self.op, self.years, self.baseline, self.baseline_b, self.threshold)
+
+    def _c(self):
+        a0, a1 = (1, 0) if self.baseline is None else self.baseline
+        b0, b1 = (1, 0) if self.baseline_b is None else self.baseline_b
+        return _HxPairMetric(PAIR_METRIC_OPS[self.op], self.years[0], self.years[1], a0, a1, b0, b1, 0,
+                             self.threshold)
+
+
 MOMENTS_MAX_AGAINST = 8   # HX_MOM_MAX_PRED
 
 
@@ -856,6 +902,86 @@ class Core:
             lambda *a: self._lib.hx_metric_probabilities(self._h, var.encode(), ctypes.byref(arr), ns, *a),
             ns, edges, weights, counts, sums)
 
+    def _pair_args(self, b, specs, what):
+        """-> (the leading arguments of the hx_*pair_metric* functions after cap_a, n_specs, what
+        must stay alive during the call)."""
+        if isinstance(specs, PairMetric):
+            specs = [specs]
+        specs = list(specs)
+        if not all(isinstance(m, PairMetric) for m in specs):
+            raise HectorAmdError("%s: specs must be hector_amd.PairMetric objects" % what)
+        arr = (_HxPairMetric * max(len(specs), 1))(*[m._c() for m in specs])
+        if isinstance(b, str):
+            lead, keep = (b.encode(), None, 0, 0), arr
+        else:
+            try:
+                years, values = b
+            except (TypeError, ValueError):
+                raise HectorAmdError("%s: b is a variable name or a (years, values) pair" % what)
+            yr = np.atleast_1d(np.asarray(years)).astype(np.int64)
+            v = np.ascontiguousarray(np.atleast_1d(np.asarray(values, dtype=np.float64)))
+            if yr.ndim != 1 or yr.size < 1 or v.shape != yr.shape:
+                raise HectorAmdError("%s: the vector b needs one value per year" % what)
+            if yr.size > 1 and not (np.diff(yr) == 1).all():
+                raise HectorAmdError("%s: the years of the vector b must be consecutive and ascending" % what)
+            lead = (None, v.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(yr[0]), int(yr[-1]))
+            keep = (arr, v)
+        return lead + (ctypes.byref(arr), len(specs)), len(specs), keep
+
+    def pair_metrics(self, var_a, b, specs):
+        """One number per member and specification from TWO series of that member, on the device
+        (hx_member_pair_metrics): the regression of var_a on b (slope, intercept, r2), var_a where b
+        first reaches a threshold / peaks / bottoms out, its mean while b is at or above a threshold,
+        or the ratio of the two end-to-end changes -> ndarray [n_specs, n_members].
+        b: a variable name, or (years, values) -- a per-year vector that is the same for every member
+        (cumulative emissions, the year itself).  The evaluation order is fixed
+        (include/hector_amd.h): numpy reproduces the result bit for bit."""
+        lead, ns, keep = self._pair_args(b, specs, "pair_metrics")
+        out = np.empty((ns, self.n_members))
+        self._ck(self._lib.hx_member_pair_metrics(self._h, var_a.encode(), *lead,
+                                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        del keep
+        return out
+
+    def pair_metric_quantiles(self, var_a, b, specs, probs, weights=None, counts=False):
+        """Weighted quantiles of every pair metric over the ensemble (hx_pair_metric_quantiles;
+        definition as metric_quantiles()) -> ndarray [n_specs, n_probs] (+ counts [n_specs])."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        lead, ns, keep = self._pair_args(b, specs, "pair_metric_quantiles")
+        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if pr.ndim != 1:
+            raise HectorAmdError("pair_metric_quantiles: probs must be one-dimensional")
+        w = self._weights(weights, "pair_metric_quantiles")
+        out = np.empty((ns, pr.size))
+        npart = np.zeros(ns, dtype=np.int64)
+        self._ck(self._lib.hx_pair_metric_quantiles(
+            self._h, var_a.encode(), *lead, w.ctypes.data_as(dp) if w is not None else None,
+            pr.ctypes.data_as(dp), int(pr.size), out.ctypes.data_as(dp),
+            npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        del keep
+        return (out, npart) if counts else out
+
+    def pair_metric_probabilities(self, var_a, b, specs, edges, weights=None, counts=False, sums=False):
+        """The classes of probabilities() over pair metrics (hx_pair_metric_probabilities) -> ndarray
+        [n_specs, n_edges + 1] (+ counts [n_specs], + sums)."""
+        lead, ns, keep = self._pair_args(b, specs, "pair_metric_probabilities")
+        res = self._probabilities(
+            "pair_metric_probabilities",
+            lambda *a: self._lib.hx_pair_metric_probabilities(self._h, var_a.encode(), *(lead + a)),
+            ns, edges, weights, counts, sums)
+        del keep
+        return res
+
+    def pair_metric_moments(self, var_a, b, specs, weights=None, against=None):
+        """moments() over pair metrics (hx_pair_metric_moments): one row per specification -> Moments."""
+        lead, ns, keep = self._pair_args(b, specs, "pair_metric_moments")
+        res = self._moments(
+            "pair_metric_moments",
+            lambda *a: self._lib.hx_pair_metric_moments(self._h, var_a.encode(), *(lead + a)),
+            ns, weights, against)
+        del keep
+        return res
+
     def _against(self, against, weights, what):
         """-> (names, predictors [K, n_members] or None, weights or None, q [n_members] uint64,
         pshift [K]).  q and pshift restate the library's definition (include/hector_amd.h: q =
@@ -865,6 +991,7 @@ class Core:
         w = self._weights(weights, what)
         single = isinstance(against, str) or (isinstance(against, tuple) and len(against) == 2 and
                                                isinstance(against[1], Metric)) or \
+            (isinstance(against, tuple) and len(against) == 3 and isinstance(against[2], PairMetric)) or \
             (isinstance(against, np.ndarray) and against.ndim == 1)   # one array is one entry
         entries = [] if against is None else ([against] if single else list(against))
         if len(entries) > MOMENTS_MAX_AGAINST:
@@ -877,6 +1004,9 @@ class Core:
             elif isinstance(a, tuple) and len(a) == 2 and isinstance(a[1], Metric):
                 names.append("%s %r" % (a[0], a[1]))
                 cols.append(self.metrics(a[0], [a[1]])[0])
+            elif isinstance(a, tuple) and len(a) == 3 and isinstance(a[2], PairMetric):
+                names.append("%s | %s %r" % (a[0], a[1] if isinstance(a[1], str) else "vector", a[2]))
+                cols.append(self.pair_metrics(a[0], a[1], [a[2]])[0])
             else:
                 v = np.asarray(a, dtype=np.float64)
                 if v.shape != (self.n_members,):
@@ -917,7 +1047,8 @@ class Core:
         """Per-year weighted mean and variance of `var` over the ensemble and its covariance,
         correlation and regression slope against per-member quantities, on the device
         (hx_ensemble_moments) -> Moments.  against: a list of parameter names (getvar), arrays
-        [n_members] or (var, Metric) pairs (metrics), at most 8.  A member takes part in a year if
+        [n_members], (var, Metric) pairs (metrics) or (var_a, b, PairMetric) triples (pair_metrics),
+        at most 8.  A member takes part in a year if
         its weight is not 0, its value is not NaN and all its `against` values are finite."""
         y0, y1 = (self.strtdate, self.current_date) if dates is None else \
             (int(min(dates)), int(max(dates)))

@@ -48,7 +48,7 @@ hipError_t hx_launch_derive(const double *params, double *derived, const double 
 hipError_t hx_launch_doeclim_kernel(const double *diff_row, double *ker, int ns, int count,
                                     int stride, hipStream_t st);
 // the post-processing kernels (hx_dev_post.h): compiled into hx_post.hip's object for the GPU; the
-// host-emulation build takes the lane-local ones (score, metrics, series) and their launchers in here
+// host-emulation build takes the lane-local ones (score, metrics, pair metrics, series) and their launchers in here
 #ifdef HX_HOST_EMULATION
 #include "hx_dev_post.h"
 #else
@@ -56,6 +56,8 @@ hipError_t hx_launch_score(const double *var, int n, int npad, const int *iy, co
                            const double *sigma, int nobs, int b0, int b1, double *out, hipStream_t st);
 hipError_t hx_launch_metric(const double *var, int n, int npad, const void *groups, int ngroups,
                             const int *rows, int year_start, double *out, hipStream_t st);
+hipError_t hx_launch_pair_metric(const double *a, const double *b, const double *bvec, int bvec_iy0, int n,
+                                 int npad, const void *specs, int nspecs, double *out, hipStream_t st);
 hipError_t hx_launch_series_ew(int op, const double *a, const double *b, const double *bvec, const double *base,
                                int npad, int ns, int y_lo, int y_hi, double c0, double c1, double *z,
                                hipStream_t st);
@@ -3236,6 +3238,185 @@ void EnsembleCore::metric_bin_sums(const std::string &capability, const hx_metri
   metric_check(capability, specs, nspecs, "hx_metric_probabilities", &src);
   sync();
   bin_block(metric_block(src, specs, nspecs), 0, nspecs, q, edges, nedges, sums_host);
+#endif
+}
+
+// ---- pair metrics: two series of the same member (hx_member_pair_metrics and its siblings) --------
+
+namespace {
+struct PairSpec { int op, iy0, iy1, a0, a1, b0, b1, pad; double thr; };   // the device's record (hx_dev_post.h)
+}  // namespace
+
+void EnsembleCore::pair_metric_check(const std::string &cap_a, const PairCall &pc, const char *fn,
+                                     const double **src_a, const double **src_b) {
+  const std::string f(fn);
+  if (pc.nspecs < 1 || pc.nspecs > HX_PMET_MAX_SPECS || !pc.specs)
+    throw std::runtime_error(f + ": nspecs must lie in 1..32");
+  if ((pc.cap_b != nullptr) == (pc.b_vec != nullptr))
+    throw std::runtime_error(f + ": operand b is exactly one of cap_b (a per-member variable) and b_vec (a "
+                             "per-year vector): " + (pc.cap_b ? "both were given" : "neither was given"));
+  if (pc.b_vec) {
+    if (pc.b_year1 < pc.b_year0) throw std::runtime_error(f + ": b_year1 < b_year0");
+    for (int y = pc.b_year0; y <= pc.b_year1; ++y)
+      if (!std::isfinite(pc.b_vec[y - pc.b_year0]))
+        throw std::runtime_error(f + ": b_vec is not finite in " + std::to_string(y));
+  }
+  auto operand = [&](const std::string &cap) {
+    const PostSource ps = post_source(cap, fn);
+    if (ps.v >= 0 && !out_enabled_[ps.v])
+      throw std::runtime_error(f + ": variable " + cap + " was not enabled with set_outputs()");
+    return ps;
+  };
+  PostSource pa = operand(cap_a), pb{nullptr, 0, -1};
+  if (pc.cap_b) {
+    pb = operand(pc.cap_b);
+    pa = operand(cap_a);   // (two derived blocks are kept: b's has not displaced a's)
+  }
+  // the years where both operands hold values
+  const int a_last = scen_.start + pa.last_iy;
+  const int b_first = pc.b_vec ? pc.b_year0 : scen_.start;
+  const int b_last = pc.b_vec ? pc.b_year1 : scen_.start + pb.last_iy;
+  const int first = std::max(scen_.start, b_first), last = std::min(a_last, b_last);
+  const std::string range = pc.b_vec ? "startDate, the current date and b_year0..b_year1"
+                                     : "startDate and the current date";
+  for (int i = 0; i < pc.nspecs; ++i) {
+    const hx_pair_metric &m = pc.specs[i];
+    const std::string which = " (specification " + std::to_string(i) + ")";
+    if (m.op < 0 || m.op >= HX_PMET_NOPS) throw std::runtime_error(f + ": unknown op" + which);
+    if (m.year1 < m.year0) throw std::runtime_error(f + ": year1 < year0" + which);
+    if (m.year0 < first || m.year1 > last)
+      throw std::runtime_error(f + ": the window must lie between " + range + which);
+    if (m.base_a0 <= m.base_a1 && (m.base_a0 < scen_.start || m.base_a1 > a_last))
+      throw std::runtime_error(f + ": the reference period of a must lie between startDate and the current date" +
+                               which);
+    if (m.base_b0 <= m.base_b1 && (m.base_b0 < b_first || m.base_b0 < scen_.start || m.base_b1 > b_last))
+      throw std::runtime_error(f + ": the reference period of b must lie between " + range + which);
+    if ((m.op == HX_PMET_AT_FIRST_GE || m.op == HX_PMET_MEAN_WHERE_GE) && !(m.threshold == m.threshold))
+      throw std::runtime_error(f + ": the threshold is NaN" + which);
+  }
+  if (!d_lane_of_member_ || !pa.block || (pc.cap_b && !pb.block)) throw std::runtime_error(f + ": run the core first");
+  *src_a = pa.block;
+  *src_b = pb.block;
+}
+
+// the specifications (and the vector operand, indexed from b_year0) into the metric plan scratch; the
+// kernel is queued on stream_ and d_met_ [nspecs][npad_] returned
+const double *EnsembleCore::pair_metric_block(const double *src_a, const double *src_b, const PairCall &pc) {
+  const int nspecs = pc.nspecs;
+  std::vector<PairSpec> recs((size_t)nspecs);
+  for (int i = 0; i < nspecs; ++i) {
+    const hx_pair_metric &m = pc.specs[i];
+    PairSpec &d = recs[(size_t)i];
+    d.op = m.op; d.iy0 = m.year0 - scen_.start; d.iy1 = m.year1 - scen_.start; d.pad = 0; d.thr = m.threshold;
+    d.a0 = 1; d.a1 = 0; d.b0 = 1; d.b1 = 0;
+    if (m.base_a0 <= m.base_a1) { d.a0 = m.base_a0 - scen_.start; d.a1 = m.base_a1 - scen_.start; }
+    if (m.base_b0 <= m.base_b1) { d.b0 = m.base_b0 - scen_.start; d.b1 = m.base_b1 - scen_.start; }
+  }
+  const size_t sbytes = sizeof(PairSpec) * recs.size();
+  const size_t vbytes = pc.b_vec ? sizeof(double) * (size_t)(pc.b_year1 - pc.b_year0 + 1) : 0;
+  if (sbytes + vbytes > metplan_cap_) {
+    if (d_metplan_) (void)hipFree(d_metplan_);
+    d_metplan_ = nullptr; metplan_cap_ = 0;
+    check(hipMalloc(&d_metplan_, sbytes + vbytes), "hipMalloc pair-metric plan");
+    metplan_cap_ = sbytes + vbytes;
+  }
+  const size_t words = (size_t)nspecs * (size_t)npad_;
+  if (words > met_cap_) {
+    if (d_met_) (void)hipFree(d_met_);
+    d_met_ = nullptr; met_cap_ = 0;
+    check(hipMalloc(&d_met_, sizeof(double) * words), "hipMalloc pair-metric block");
+    met_cap_ = words;
+  }
+  // (stream order: an earlier call's kernel has finished with the plan before this copy lands)
+  check(hipMemcpyAsync(d_metplan_, recs.data(), sbytes, hipMemcpyHostToDevice, stream_), "pair-metric specifications");
+  if (vbytes)
+    check(hipMemcpyAsync(d_metplan_ + sbytes, pc.b_vec, vbytes, hipMemcpyHostToDevice, stream_), "pair-metric vector");
+  check(hipStreamSynchronize(stream_), "pair-metric plan");   // recs is this call's local, b_vec the caller's
+  check(hx_launch_pair_metric(src_a, src_b, vbytes ? reinterpret_cast<const double *>(d_metplan_ + sbytes) : nullptr,
+                              pc.b_year0 - scen_.start, n_, npad_, d_metplan_, nspecs, d_met_, stream_),
+        "pair-metric kernel");
+  return d_met_;
+}
+
+void EnsembleCore::member_pair_metrics(const std::string &cap_a, const PairCall &pc, double *out_host,
+                                       size_t row_pitch) {
+  const char *fn = "hx_member_pair_metrics";
+  const double *sa = nullptr, *sb = nullptr;
+  pair_metric_check(cap_a, pc, fn, &sa, &sb);
+  if (!out_host) throw std::runtime_error(std::string(fn) + ": null argument");
+  sync();
+  const double *blk = pair_metric_block(sa, sb, pc);
+  // member order through the score scratch: [nspecs][n_]
+  const size_t row = sizeof(double) * (size_t)n_, bytes = row * (size_t)pc.nspecs;
+  if (bytes > score_cap_) {
+    if (d_score_) (void)hipFree(d_score_);
+    d_score_ = nullptr; score_cap_ = 0;
+    check(hipMalloc(&d_score_, bytes), "hipMalloc score");
+    score_cap_ = bytes;
+  }
+  check(hx_launch_gather(blk, d_lane_of_member_, d_score_, n_, npad_, pc.nspecs, stream_), "pair-metric gather");
+  check(hipMemcpy2DAsync(out_host, sizeof(double) * (row_pitch ? row_pitch : (size_t)n_), d_score_, row, row,
+                         (size_t)pc.nspecs, hipMemcpyDeviceToHost, stream_), "pair-metric fetch");
+  check(hipStreamSynchronize(stream_), "pair-metric sync");
+}
+
+void EnsembleCore::pair_metric_quantiles(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
+                                         const double *probs, int nprobs, double *out_host, long long *n_part) {
+  const char *fn = "hx_pair_metric_quantiles";
+  const double *sa = nullptr, *sb = nullptr;
+  pair_metric_check(cap_a, pc, fn, &sa, &sb);
+  if (nprobs < 1 || nprobs > 16) throw std::runtime_error(std::string(fn) + ": nprobs must lie in 1..16");
+#ifdef HX_HOST_EMULATION
+  (void)q; (void)probs; (void)out_host; (void)n_part;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
+  sync();
+  q_select(pair_metric_block(sa, sb, pc), 0, pc.nspecs, q, probs, nprobs, out_host, n_part);
+#endif
+}
+
+void EnsembleCore::pmq_begin(const std::string &cap_a, const PairCall &pc, const unsigned long long *q, int nprobs,
+                             unsigned long long *st_host) {
+#ifdef HX_HOST_EMULATION
+  (void)st_host;
+  pair_metric_quantiles(cap_a, pc, q, nullptr, nprobs, nullptr, nullptr);
+#else
+  const char *fn = "hx_pair_metric_quantiles";
+  const double *sa = nullptr, *sb = nullptr;
+  pair_metric_check(cap_a, pc, fn, &sa, &sb);
+  if (nprobs < 1 || nprobs > 16) throw std::runtime_error(std::string(fn) + ": nprobs must lie in 1..16");
+  if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
+  sync();
+  q_begin_block(pair_metric_block(sa, sb, pc), 0, pc.nspecs, q, nprobs, st_host);
+#endif
+}
+
+void EnsembleCore::pair_metric_bin_sums(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
+                                        const double *edges, int nedges, unsigned long long *sums_host) {
+  const char *fn = "hx_pair_metric_probabilities";
+  const double *sa = nullptr, *sb = nullptr;
+  pair_metric_check(cap_a, pc, fn, &sa, &sb);
+#ifdef HX_HOST_EMULATION
+  (void)q; (void)edges; (void)nedges; (void)sums_host;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  sync();
+  bin_block(pair_metric_block(sa, sb, pc), 0, pc.nspecs, q, edges, nedges, sums_host);
+#endif
+}
+
+void EnsembleCore::pair_mom_begin(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
+                                  const double *pred, int npred, const double *c, unsigned long long *st_host) {
+  const char *fn = "hx_pair_metric_moments";
+  const double *sa = nullptr, *sb = nullptr;
+  pair_metric_check(cap_a, pc, fn, &sa, &sb);
+#ifdef HX_HOST_EMULATION
+  (void)q; (void)pred; (void)npred; (void)c; (void)st_host;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  sync();
+  mom_begin_block(pair_metric_block(sa, sb, pc), 0, pc.nspecs, q, pred, npred, c, st_host);
 #endif
 }
 

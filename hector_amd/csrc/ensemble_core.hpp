@@ -24,6 +24,16 @@ namespace hx {
 int hx_cost_models_export_file(const char *path);
 int hx_cost_models_load_file(const char *path);
 
+// The operands b and the specifications of a pair-metric call (hx_member_pair_metrics in
+// hector_amd.h): exactly one of cap_b and b_vec[b_year0..b_year1] is set.
+struct PairCall {
+  const char *cap_b;
+  const double *b_vec;
+  int b_year0, b_year1;
+  const hx_pair_metric *specs;
+  int nspecs;
+};
+
 class EnsembleCore {
  public:
   EnsembleCore(const std::string &scenario_path, int n_members, int device);
@@ -195,6 +205,19 @@ class EnsembleCore {
                  const unsigned long long *q, const double *pred, int npred, const double *c,
                  unsigned long long *st_host, const char *fn);
   void mom_finish(const double *shift_host, double *sums_host);
+  // per-member pair metrics (hx_member_pair_metrics): two operands of a member, PairCall above;
+  // out_host row s at out_host + s * row_pitch (0: n_), member order.  The three block verbs are the
+  // metric verbs above with the pair block in place of the metric block (fn: the ABI function named
+  // in every message); mom_begin takes the pair call instead of specs.
+  void member_pair_metrics(const std::string &cap_a, const PairCall &pc, double *out_host, size_t row_pitch = 0);
+  void pair_metric_quantiles(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
+                             const double *probs, int nprobs, double *out_host, long long *n_part);
+  void pmq_begin(const std::string &cap_a, const PairCall &pc, const unsigned long long *q, int nprobs,
+                 unsigned long long *st_host);
+  void pair_metric_bin_sums(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
+                            const double *edges, int nedges, unsigned long long *sums_host);
+  void pair_mom_begin(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
+                      const double *pred, int npred, const double *c, unsigned long long *st_host);
   // year-by-year co-moments (hx_ensemble_comoments), in the same two steps.  comom_begin validates
   // both windows (cap_b == nullptr: the symmetric call, B is A), brings q[n_] to lane order, zeroes
   // it where any value of either window is NaN (complete cases) and reduces the rows' records into
@@ -374,6 +397,12 @@ class EnsembleCore {
   int metric_check(const std::string &capability, const hx_metric *specs, int nspecs, const char *fn,
                    const double **src);
   const double *metric_block(const double *src, const hx_metric *specs, int nspecs);   // -> d_met_, queued on stream_
+  // both operands of a pair call resolved and its specifications checked against the range where both
+  // are valid (fn is named in every message); *src_b stays nullptr for a vector b
+  void pair_metric_check(const std::string &cap_a, const PairCall &pc, const char *fn, const double **src_a,
+                         const double **src_b);
+  // the pair kernel queued on stream_ -> d_met_ [nspecs][npad_] in lane order, laid out like metric_block's
+  const double *pair_metric_block(const double *src_a, const double *src_b, const PairCall &pc);
   // ---- "a per-member variable on the device": the one resolver of the verbs -----------------------
   // block: [ns][npad_] in the CURRENT lane order, rows 0..last_iy hold values; v: the index of a
   // recorded output (its block may still be null: the callers keep their own messages for that), -1

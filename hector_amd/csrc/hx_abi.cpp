@@ -430,6 +430,37 @@ int hx_metric_moments(hx_core *core, const char *capability, const hx_metric *sp
   HX_TRY(core->core->moments(capability, 0, 0, specs, nspecs, weights, predictors, npred, shift, sums, wsum,
                              n_part))
 }
+int hx_member_pair_metrics(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
+                           int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs, double *out) {
+  if (!cap_a || !specs || !out) return fail("hx_member_pair_metrics: null argument");
+  const hx::PairCall pc{cap_b, b_vec, b_year0, b_year1, specs, nspecs};
+  HX_TRY(core->core->member_pair_metrics(cap_a, pc, out))
+}
+int hx_pair_metric_quantiles(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
+                             int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs,
+                             const double *weights, const double *probs, int nprobs, double *out,
+                             long long *n_part) {
+  if (!cap_a || !specs || !probs || !out) return fail("hx_pair_metric_quantiles: null argument");
+  const hx::PairCall pc{cap_b, b_vec, b_year0, b_year1, specs, nspecs};
+  HX_TRY(core->core->metric_quantiles(cap_a, nullptr, 0, weights, probs, nprobs, out, n_part, &pc))
+}
+int hx_pair_metric_probabilities(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
+                                 int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs,
+                                 const double *weights, const double *edges, int nedges, double *prob,
+                                 unsigned long long *sums, long long *n_part) {
+  if (!cap_a || !specs || !prob) return fail("hx_pair_metric_probabilities: null argument");
+  const hx::PairCall pc{cap_b, b_vec, b_year0, b_year1, specs, nspecs};
+  HX_TRY(core->core->probabilities(cap_a, 0, 0, nullptr, 0, weights, edges, nedges, prob, sums, n_part, &pc))
+}
+int hx_pair_metric_moments(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
+                           int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs,
+                           const double *weights, const double *predictors, int npred, double *shift,
+                           double *sums, unsigned long long *wsum, long long *n_part) {
+  if (!cap_a || !specs || !shift || !sums) return fail("hx_pair_metric_moments: null argument");
+  const hx::PairCall pc{cap_b, b_vec, b_year0, b_year1, specs, nspecs};
+  HX_TRY(core->core->moments(cap_a, 0, 0, nullptr, 0, weights, predictors, npred, shift, sums, wsum, n_part,
+                             &pc))
+}
 int hx_ensemble_comoments(hx_core *core, const char *cap_a, int a_year0, int a_year1, const char *cap_b,
                           int b_year0, int b_year1, const double *weights, double *shift_a, double *sums_a,
                           double *shift_b, double *sums_b, double *cross, unsigned long long *wsum,

@@ -1,11 +1,12 @@
 // hx_dev_post.h -- what a user does with a finished ensemble, on the device: a per-member misfit
 // of a recorded output against an observation series (hx_score_kernel), per-member metrics of a
-// window (hx_metric_kernel), exact weighted quantiles over the members (hx_q_* kernels),
+// window (hx_metric_kernel), of a window of two series (hx_pair_metric_kernel), exact weighted
+// quantiles over the members (hx_q_* kernels),
 // weighted bin sums against fixed edges (hx_bin_kernel) and weighted moments with per-member
 // predictors (hx_mom_* / hx_moments_kernel).  The reference has no counterpart: its
 // hosts aggregate fetchvars() data frames in R.  Compiled for the GPU through hx_post.hip -- a
 // translation unit of its own, so the year-loop kernels' code generation does not see it -- and
-// for the host-emulation build through ensemble_core.cpp (score and metric kernels only: the
+// for the host-emulation build through ensemble_core.cpp (score, metric, pair-metric and series kernels only: the
 // quantile, bin and moment kernels are cooperative -- LDS atomics, cross-lane -- and one lane at a
 // time cannot run them).
 #pragma once
@@ -484,6 +485,197 @@ hipError_t hx_launch_series_permute(const double *src, const int *src_lane, int 
                                     hipStream_t st) {
   hipLaunchKernelGGL(hx_series_permute_kernel, dim3((npad + 255) / 256, ns), dim3(256), 0, st, src, src_lane,
                      npad, dst);
+  return hipGetLastError();
+}
+
+// ===========================================================================
+// Pair metrics: one double per member from a window of TWO series of that member, a (reported /
+// dependent) and b (condition / independent) -- hx_member_pair_metrics in hector_amd.h defines every
+// operation and its order; contraction is off as in the score kernel.  One lane per member, nothing
+// exchanged between lanes; blockIdx.y picks ONE specification, whose record is a wave-uniform read
+// (scalar loads).  No grouping: a second specification re-reads its rows from L2.
+// Phases: the reference rows of a, the reference rows of b, the window (pass 1), and the window again
+// (pass 2) for SLOPE / INTERCEPT / R2 only; END_RATIO reads its two end rows instead of the window.
+// Every phase walks CONSECUTIVE rows, so there are no row lists: a lane takes HXP_BATCH rows of each
+// operand into registers, all loads in flight, and the next batch is issued before the current one is
+// consumed in the defined order (hxm_load's pattern; rows past the phase's last one are loaded from
+// that last row and never consumed).  BVEC: b is the caller's per-year vector, bvec[iy - bvec_iy0],
+// the same for every lane -- wave-uniform reads where the value is consumed, no b loads.
+// ===========================================================================
+#define HXP_BATCH 8
+struct HxPairSpec { int op, iy0, iy1, a0, a1, b0, b1, pad; double thr; };   // rows; a0 > a1 / b0 > b1: no reference period
+
+template <bool BVEC>
+__device__ __forceinline__ void hxp_load(const double *colA, const double *colB, int npad, int r, int last,
+                                         double (&xa)[HXP_BATCH], double (&xb)[HXP_BATCH]) {
+#pragma unroll
+  for (int e = 0; e < HXP_BATCH; ++e) {
+    const size_t off = (size_t)(r + e < last ? r + e : last) * (size_t)npad;
+    xa[e] = colA[off];
+    if (!BVEC) xb[e] = colB[off];
+  }
+}
+
+// s = 0.0; s = s + x_y over the rows r0..r1 of one column, ascending; bad: a NaN among them
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__device__ __forceinline__ double hxp_row_sum(const double *col, int npad, int r0, int r1, unsigned &bad) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double xa[HXP_BATCH], xn[HXP_BATCH], unused[HXP_BATCH];
+  double s = 0.0;
+  hxp_load<true>(col, nullptr, npad, r0, r1, xa, unused);
+  for (int r = r0; r <= r1; r += HXP_BATCH) {
+    const bool more = r + HXP_BATCH <= r1;
+    if (more) hxp_load<true>(col, nullptr, npad, r + HXP_BATCH, r1, xn, unused);
+#pragma unroll
+    for (int e = 0; e < HXP_BATCH; ++e) {
+      if (r + e > r1) continue;   // wave-uniform
+      s = s + xa[e];
+      bad |= xa[e] != xa[e] ? 1u : 0u;
+    }
+    if (more) {
+#pragma unroll
+      for (int e = 0; e < HXP_BATCH; ++e) xa[e] = xn[e];
+    }
+  }
+  return s;
+}
+
+// out[blockIdx.y][npad] in lane order; lanes >= n are not written
+template <bool BVEC>
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__global__ __launch_bounds__(256) void hx_pair_metric_kernel(const double *__restrict__ va,
+                                                             const double *__restrict__ vb,
+                                                             const double *__restrict__ bvec, int bvec_iy0,
+                                                             int n, int npad,
+                                                             const HxPairSpec *__restrict__ specs,
+                                                             double *__restrict__ out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= n) return;
+  const HxPairSpec &sp = specs[blockIdx.y];
+  const int op = sp.op, iy0 = sp.iy0, iy1 = sp.iy1;
+  const double thr = sp.thr;
+  const double *colA = va + lane;
+  const double *colB = BVEC ? nullptr : vb + lane;
+  unsigned bad = 0u;
+  // the reference means; +0.0 without a reference period (x - 0.0 is x, bit for bit)
+  double base_a = 0.0, base_b = 0.0;
+  if (sp.a0 <= sp.a1) base_a = hxp_row_sum(colA, npad, sp.a0, sp.a1, bad) / (double)(sp.a1 - sp.a0 + 1);
+  if (sp.b0 <= sp.b1) {
+    double s = 0.0;
+    if (BVEC) {
+      for (int y = sp.b0; y <= sp.b1; ++y) s = s + bvec[y - bvec_iy0];
+    } else {
+      s = hxp_row_sum(colB, npad, sp.b0, sp.b1, bad);
+    }
+    base_b = s / (double)(sp.b1 - sp.b0 + 1);
+  }
+  double v;
+  if (op == HX_PMET_END_RATIO) {
+    const double xa0 = colA[(size_t)iy0 * (size_t)npad], xa1 = colA[(size_t)iy1 * (size_t)npad];
+    const double xb0 = BVEC ? bvec[iy0 - bvec_iy0] : colB[(size_t)iy0 * (size_t)npad];
+    const double xb1 = BVEC ? bvec[iy1 - bvec_iy0] : colB[(size_t)iy1 * (size_t)npad];
+    bad |= (xa0 != xa0 || xa1 != xa1 || xb0 != xb0 || xb1 != xb1) ? 1u : 0u;
+    const double a0 = xa0 - base_a, a1 = xa1 - base_a, b0 = xb0 - base_b, b1 = xb1 - base_b;
+    const double da = a1 - a0, db = b1 - b0;
+    v = da / db;
+  } else {
+    const bool regress = op == HX_PMET_SLOPE || op == HX_PMET_INTERCEPT || op == HX_PMET_R2;
+    const bool negate = op == HX_PMET_AT_MAX;   // the largest b as the smallest -b: negation is exact
+    const double nyears = (double)(iy1 - iy0 + 1);
+    double xa[HXP_BATCH], xb[HXP_BATCH], na[HXP_BATCH], nb[HXP_BATCH];
+    // pass 1.  acc / aux: sa, sb (regression); the reported a and found flag (AT_FIRST_GE); the reported
+    // a and the extreme b (AT_MAX / AT_MIN); the sum and the count (MEAN_WHERE_GE)
+    double acc = op == HX_PMET_AT_FIRST_GE ? __builtin_nan("") : 0.0, aux = 0.0;
+    bool found = false;
+    hxp_load<BVEC>(colA, colB, npad, iy0, iy1, xa, xb);
+    for (int r = iy0; r <= iy1; r += HXP_BATCH) {
+      const bool more = r + HXP_BATCH <= iy1;
+      if (more) hxp_load<BVEC>(colA, colB, npad, r + HXP_BATCH, iy1, na, nb);   // in flight while this batch is consumed
+#pragma unroll
+      for (int e = 0; e < HXP_BATCH; ++e) {
+        if (r + e > iy1) continue;   // wave-uniform
+        const double rb = BVEC ? bvec[r + e - bvec_iy0] : xb[e];
+        bad |= (xa[e] != xa[e] || rb != rb) ? 1u : 0u;
+        const double a = xa[e] - base_a, b = rb - base_b;
+        if (regress) {
+          acc = acc + a;
+          aux = aux + b;
+        } else if (op == HX_PMET_AT_FIRST_GE) {
+          if (!found && b >= thr) { acc = a; found = true; }
+        } else if (op == HX_PMET_MEAN_WHERE_GE) {
+          if (b >= thr) { acc = acc + a; aux = aux + 1.0; }
+        } else {
+          const double c = negate ? -b : b;
+          if (r + e == iy0 || c < aux) { aux = c; acc = a; }
+        }
+      }
+      if (more) {
+#pragma unroll
+        for (int e = 0; e < HXP_BATCH; ++e) { xa[e] = na[e]; if (!BVEC) xb[e] = nb[e]; }
+      }
+    }
+    if (regress) {
+      const double ma = acc / nyears, mb = aux / nyears;
+      double sab = 0.0, sbb = 0.0, saa = 0.0;
+      hxp_load<BVEC>(colA, colB, npad, iy0, iy1, xa, xb);
+      for (int r = iy0; r <= iy1; r += HXP_BATCH) {
+        const bool more = r + HXP_BATCH <= iy1;
+        if (more) hxp_load<BVEC>(colA, colB, npad, r + HXP_BATCH, iy1, na, nb);
+#pragma unroll
+        for (int e = 0; e < HXP_BATCH; ++e) {
+          if (r + e > iy1) continue;
+          const double rb = BVEC ? bvec[r + e - bvec_iy0] : xb[e];
+          const double a = xa[e] - base_a, b = rb - base_b;
+          const double da = a - ma, db = b - mb;
+          const double pab = db * da, pbb = db * db, paa = da * da;
+          sab = sab + pab;
+          sbb = sbb + pbb;
+          saa = saa + paa;
+        }
+        if (more) {
+#pragma unroll
+          for (int e = 0; e < HXP_BATCH; ++e) { xa[e] = na[e]; if (!BVEC) xb[e] = nb[e]; }
+        }
+      }
+      const double slope = sab / sbb;
+      if (op == HX_PMET_SLOPE) {
+        v = slope;
+      } else if (op == HX_PMET_INTERCEPT) {
+        const double p = slope * mb;
+        v = ma - p;
+      } else {
+        const double num = sab * sab, den = sbb * saa;
+        v = num / den;
+      }
+    } else if (op == HX_PMET_MEAN_WHERE_GE) {
+      v = acc / aux;
+    } else {
+      v = acc;
+    }
+  }
+  if (bad) v = __builtin_nan("");
+  out[(size_t)blockIdx.y * (size_t)npad + (size_t)lane] = v;
+}
+
+// b: a [rows][npad] block in lane order, or nullptr with bvec[iy - bvec_iy0] on the device
+hipError_t hx_launch_pair_metric(const double *a, const double *b, const double *bvec, int bvec_iy0, int n,
+                                 int npad, const void *specs, int nspecs, double *out, hipStream_t st) {
+  const dim3 grid((n + 255) / 256, nspecs), block(256);
+  if (b)
+    hipLaunchKernelGGL(hx_pair_metric_kernel<false>, grid, block, 0, st, a, b, bvec, bvec_iy0, n, npad,
+                       (const HxPairSpec *)specs, out);
+  else
+    hipLaunchKernelGGL(hx_pair_metric_kernel<true>, grid, block, 0, st, a, b, bvec, bvec_iy0, n, npad,
+                       (const HxPairSpec *)specs, out);
   return hipGetLastError();
 }
 

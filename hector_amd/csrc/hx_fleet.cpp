@@ -430,24 +430,36 @@ void Fleet::quantiles(const std::string &cap, int year0, int year1, const double
 
 void Fleet::metric_quantiles(const std::string &cap, const hx_metric *specs, int nspecs,
                              const double *weights, const double *probs, int nprobs, double *out,
-                             long long *n_part) {
+                             long long *n_part, const PairCall *pair) {
   check_poison();
-  if (nspecs < 1 || nspecs > HX_MET_MAX_SPECS || !specs)
-    throw std::runtime_error("hx_metric_quantiles: nspecs must lie in 1..32");
-  check_probs(probs, nprobs, "hx_metric_quantiles");
-  refuse_processes("hx_metric_quantiles", "quantiles");
+  const char *fn = pair ? "hx_pair_metric_quantiles" : "hx_metric_quantiles";
+  if (pair) nspecs = pair->nspecs;
+  if (nspecs < 1 || nspecs > HX_MET_MAX_SPECS || !(pair ? (const void *)pair->specs : (const void *)specs))
+    throw std::runtime_error(std::string(fn) + ": nspecs must lie in 1..32");
+  check_probs(probs, nprobs, fn);
+  refuse_processes(fn, "quantiles");
   std::vector<unsigned long long> q;
-  quantise_weights(weights, "hx_metric_quantiles", q);
+  quantise_weights(weights, fn, q);
   const unsigned long long *qp = weights ? q.data() : nullptr;
   if (shards_.size() == 1) {
     use(shards_[0]);
-    shards_[0].core->metric_quantiles(cap, specs, nspecs, qp, probs, nprobs, out, n_part);
+    if (pair) shards_[0].core->pair_metric_quantiles(cap, *pair, qp, probs, nprobs, out, n_part);
+    else shards_[0].core->metric_quantiles(cap, specs, nspecs, qp, probs, nprobs, out, n_part);
     return;
   }
   select_rows(nspecs, qp, probs, nprobs, out, n_part,
               [&](Shard &s, const unsigned long long *qs, unsigned long long *part) {
-                s.core->mq_begin(cap, specs, nspecs, qs, nprobs, part);
+                if (pair) s.core->pmq_begin(cap, *pair, qs, nprobs, part);
+                else s.core->mq_begin(cap, specs, nspecs, qs, nprobs, part);
               });
+}
+
+void Fleet::member_pair_metrics(const std::string &cap_a, const PairCall &pc, double *out) {
+  check_poison();
+  for (Shard &s : shards_) {   // every shard copies its members straight into its columns of out[nspecs][n_]
+    use(s);
+    s.core->member_pair_metrics(cap_a, pc, out + s.offset, (size_t)n_);
+  }
 }
 
 void Fleet::select_rows(int ny, const unsigned long long *qp, const double *probs, int np, double *out,
@@ -528,11 +540,12 @@ void Fleet::member_metrics(const std::string &cap, const hx_metric *specs, int n
 
 void Fleet::probabilities(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
                           const double *weights, const double *edges, int nedges, double *prob,
-                          unsigned long long *sums, long long *n_part) {
+                          unsigned long long *sums, long long *n_part, const PairCall *pair) {
   check_poison();
-  const char *fn = specs ? "hx_metric_probabilities" : "hx_ensemble_probabilities";
+  const char *fn = pair ? "hx_pair_metric_probabilities" : specs ? "hx_metric_probabilities" : "hx_ensemble_probabilities";
   const std::string f(fn);
-  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
+  if (pair) nspecs = pair->nspecs;
+  if ((specs || pair) && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
     throw std::runtime_error(f + ": nspecs must lie in 1..32");
   if (nedges < 1 || nedges > HX_BIN_MAX_EDGES || !edges)
     throw std::runtime_error(f + ": nedges must lie in 1..31");
@@ -544,14 +557,15 @@ void Fleet::probabilities(const std::string &cap, int year0, int year1, const hx
   std::vector<unsigned long long> q;
   quantise_weights(weights, fn, q);
   const unsigned long long *qp = weights ? q.data() : nullptr;
-  const int nrows = specs ? nspecs : year1 - year0 + 1;
+  const int nrows = (specs || pair) ? nspecs : year1 - year0 + 1;
   if (nrows < 1) throw std::runtime_error(f + ": year1 < year0");
   const size_t stride = (size_t)nedges + 2, R = (size_t)nrows;
   std::vector<unsigned long long> tot(R * stride, 0ull), part(R * stride);
   for (Shard &s : shards_) {
     use(s);
     const unsigned long long *qs = qp ? qp + s.offset : nullptr;
-    if (specs) s.core->metric_bin_sums(cap, specs, nspecs, qs, edges, nedges, part.data());
+    if (pair) s.core->pair_metric_bin_sums(cap, *pair, qs, edges, nedges, part.data());
+    else if (specs) s.core->metric_bin_sums(cap, specs, nspecs, qs, edges, nedges, part.data());
     else s.core->bin_sums(cap, year0, year1, qs, edges, nedges, part.data());
     for (size_t i = 0; i < tot.size(); ++i) tot[i] += part[i];
   }
@@ -570,11 +584,12 @@ void Fleet::probabilities(const std::string &cap, int year0, int year1, const hx
 
 void Fleet::moments(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
                     const double *weights, const double *predictors, int npred, double *shift, double *sums,
-                    unsigned long long *wsum, long long *n_part) {
+                    unsigned long long *wsum, long long *n_part, const PairCall *pair) {
   check_poison();
-  const char *fn = specs ? "hx_metric_moments" : "hx_ensemble_moments";
+  const char *fn = pair ? "hx_pair_metric_moments" : specs ? "hx_metric_moments" : "hx_ensemble_moments";
   const std::string f(fn);
-  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
+  if (pair) nspecs = pair->nspecs;
+  if ((specs || pair) && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
     throw std::runtime_error(f + ": nspecs must lie in 1..32");
   if (npred < 0 || npred > HX_MOM_MAX_PRED)
     throw std::runtime_error(f + ": npred must lie in 0..8");
@@ -584,7 +599,7 @@ void Fleet::moments(const std::string &cap, int year0, int year1, const hx_metri
   std::vector<unsigned long long> q;
   quantise_weights(weights, fn, q);
   if (!weights) q.assign((size_t)n_, 1ull);
-  const int nrows = specs ? nspecs : year1 - year0 + 1;
+  const int nrows = (specs || pair) ? nspecs : year1 - year0 + 1;
   if (nrows < 1) throw std::runtime_error(f + ": year1 < year0");
   // the call's effective weights, and the predictor shifts over the members they leave
   const size_t N = (size_t)n_, K = (size_t)npred, R = (size_t)nrows, nc = 2 + 3 * K;
@@ -607,8 +622,9 @@ void Fleet::moments(const std::string &cap, int year0, int year1, const hx_metri
     for (size_t k = 0; k < K; ++k)
       std::copy(predictors + k * N + (size_t)s.offset, predictors + k * N + (size_t)(s.offset + s.count),
                 pred.begin() + k * (size_t)s.count);
-    s.core->mom_begin(cap, year0, year1, specs, nspecs, q.data() + s.offset, pred.data(), npred, c,
-                      part.data(), fn);
+    if (pair) s.core->pair_mom_begin(cap, *pair, q.data() + s.offset, pred.data(), npred, c, part.data());
+    else s.core->mom_begin(cap, year0, year1, specs, nspecs, q.data() + s.offset, pred.data(), npred, c,
+                           part.data(), fn);
     for (size_t y = 0; y < R; ++y) {
       if (!part[4 * y + 3]) continue;
       st[4 * y] = std::max(st[4 * y], part[4 * y]);

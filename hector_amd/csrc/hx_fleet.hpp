@@ -104,21 +104,25 @@ class Fleet {
   // hx_member_metrics: routed per shard like member_score
   void member_metrics(const std::string &capability, const hx_metric *specs, int nspecs, double *out_host);
   // hx_metric_quantiles: quantiles() over the metric block every shard computes on its GPU
+  // (pair != nullptr: hx_pair_metric_quantiles -- capability is operand a, the rows are the pair
+  //  metrics of *pair, specs / nspecs are not read; likewise in probabilities and moments below)
   void metric_quantiles(const std::string &capability, const hx_metric *specs, int nspecs,
                         const double *weights, const double *probs, int nprobs, double *out_host,
-                        long long *n_part);
+                        long long *n_part, const PairCall *pair = nullptr);
+  // hx_member_pair_metrics: shard by shard, every shard into its columns of out_host[nspecs][n_]
+  void member_pair_metrics(const std::string &cap_a, const PairCall &pc, double *out_host);
   // hx_ensemble_probabilities (specs == nullptr: the rows year0..year1) and hx_metric_probabilities
   // (the rows are the nspecs metrics): the shards' integer bin sums added here
   void probabilities(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
                      const double *weights, const double *edges, int nedges, double *prob,
-                     unsigned long long *sums, long long *n_part);
+                     unsigned long long *sums, long long *n_part, const PairCall *pair = nullptr);
   // hx_ensemble_moments (specs == nullptr: the rows year0..year1) and hx_metric_moments: the weights
   // quantised as for quantiles, zeroed where a predictor is not finite, the predictor shifts taken
   // here; then two steps over the shards -- the rows' minima (their minimum is the shift), the sums
   // about it -- with the predictor arrays split by shard offsets and the sums added in shard order
   void moments(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
                const double *weights, const double *predictors, int npred, double *shift, double *sums,
-               unsigned long long *wsum, long long *n_part);
+               unsigned long long *wsum, long long *n_part, const PairCall *pair = nullptr);
   // hx_ensemble_comoments (cap_b == nullptr: the symmetric call): the weights quantised once; the
   // shards' masks and row minima, then their minimum, W and count; then the shards' sums and cross
   // sums about the common shifts, added in ascending shard order

@@ -504,6 +504,103 @@ int hx_metric_moments(hx_core *core, const char *capability, const hx_metric *sp
                       const double *weights, const double *predictors, int npred, double *shift,
                       double *sums, unsigned long long *wsum, long long *n_part);
 
+/* ---- Two series of the same member: regress or sample one output on another ----------------------
+ * A pair-metric specification reduces the window year0..year1 of TWO series of a member, a (reported
+ * / dependent) and b (condition / independent), to one double per member: TCRE (the slope of
+ * global_tas on cumulative emissions), the CO2 concentration in the year a member crosses 1.5 K, the
+ * airborne fraction, a Gregory regression of heat flux on temperature, the pH while warming is above
+ * 2 K, the concentration at peak warming.  No counterpart in the reference (its hosts do this in R on
+ * fetchvars() data frames of two variables).
+ * base_a0 <= base_a1: a's own mean over that reference period is subtracted from a first; base_a0 >
+ * base_a1: nothing is subtracted.  base_b0, base_b1: the same for b, with b's own reference period.
+ * threshold: the two _GE operations only. */
+typedef struct {
+  int op, year0, year1;
+  int base_a0, base_a1;      /* reference period of a; base_a0 > base_a1: none */
+  int base_b0, base_b1;      /* reference period of b; likewise */
+  int reserved;
+  double threshold;
+} hx_pair_metric;
+#define HX_PMET_SLOPE 0          /* ordinary least-squares slope of a on b */
+#define HX_PMET_INTERCEPT 1      /* its intercept */
+#define HX_PMET_R2 2             /* its coefficient of determination */
+#define HX_PMET_AT_FIRST_GE 3    /* a in the first year with b >= threshold; NaN if there is none */
+#define HX_PMET_AT_MAX 4         /* a in the first year that holds the largest b */
+#define HX_PMET_AT_MIN 5         /* a in the first year that holds the smallest b */
+#define HX_PMET_MEAN_WHERE_GE 6  /* mean of a over the years with b >= threshold; NaN if there is none */
+#define HX_PMET_END_RATIO 7      /* (a_year1 - a_year0) / (b_year1 - b_year0) */
+#define HX_PMET_NOPS 8
+#define HX_PMET_MAX_SPECS 32
+
+/* out[s * n_members + member] = pair metric s of every member, in the caller's member order;
+ * 1 <= nspecs <= 32, all on the one pair of operands.
+ * cap_a: a per-member variable on the device like every other verb's `capability` (a recorded output,
+ * a derived diagnostic, a held / derived series).  b is EXACTLY ONE of (both or neither is an error)
+ *   - cap_b: a per-member variable, resolved the same way as cap_a (b_vec NULL; b_year0, b_year1 are
+ *     ignored), or
+ *   - b_vec: a caller's per-year vector, b_y = b_vec[y - b_year0] for b_year0..b_year1, the same for
+ *     every member (cumulative emissions, the year itself), with cap_b NULL.  Every window and every
+ *     reference period of b must lie inside b_year0..b_year1; a non-finite entry is an error that names
+ *     the year.
+ * Evaluated per member in exactly this order, in IEEE double, without fused multiply-add, so that
+ * numpy reproduces every result bit for bit under any lane order, kernel flavour or shard layout
+ * (xa_y, xb_y: the operands' values in year y):
+ *   base:  s = 0.0; for y = base_a0..base_a1: s = s + xa_y;  base_a = s / count
+ *   a_y = xa_y - base_a (with a reference period), a_y = xa_y (without); b_y likewise with b's own
+ *   reference period; y ascends from year0 to year1, n = year1 - year0 + 1
+ *   SLOPE, INTERCEPT, R2: two ascending passes.
+ *     pass 1:  sa = 0.0; sa = sa + a_y;  sb = 0.0; sb = sb + b_y;  ma = sa / n;  mb = sb / n
+ *     pass 2:  da = a_y - ma;  db = b_y - mb;  sab = sab + (db * da);  sbb = sbb + (db * db);
+ *              saa = saa + (da * da)  -- every product rounded before its sum
+ *     SLOPE = sab / sbb;  INTERCEPT = ma - (SLOPE * mb);  R2 = (sab * sab) / (sbb * saa)
+ *     Degenerate windows are whatever IEEE gives: a constant b or a one-year window is 0 / 0 = NaN;
+ *     there is no special case and no sqrt.
+ *   AT_FIRST_GE:  a_y of the first year with b_y >= threshold; NaN if there is none
+ *   AT_MAX / AT_MIN:  a_y of the first year that holds the largest / smallest b_y: a later year
+ *     replaces an earlier one only on strict > / <
+ *   MEAN_WHERE_GE:  s = 0.0; s = s + a_y over the years with b_y >= threshold, ascending, divided by
+ *     their count as a double; none: 0 / 0 = NaN
+ *   END_RATIO:  (a_year1 - a_year0) / (b_year1 - b_year0); reads only the two end rows and the
+ *     reference periods
+ *   NaN rule: a NaN of a or b in any row the specification reads (window and reference periods; for
+ *   END_RATIO the two end rows and the reference periods) makes the result NaN.
+ * Cost: one kernel, one lane per member, one specification per workgroup row (no grouping: a second
+ * specification re-reads its rows from L2); the reference rows, then one pass over the window (two
+ * for SLOPE / INTERCEPT / R2, none for END_RATIO) with eight rows of each operand of a lane in
+ * flight; nspecs x n_members doubles back to the host; returns when they are there.  A core of
+ * several shards or in a communicator of several processes runs shard by shard (nothing crosses
+ * members).  The core is not prepared, spun up or dirtied.
+ * Errors (every message names the function; a refused call changes nothing): a null argument, an
+ * unrecorded capability ("not enabled"), nspecs outside 1..32, an unknown op, year1 < year0, a
+ * window or reference period outside the range where both operands are valid (startDate..current
+ * date, a series' own end, b_year0..b_year1 of the vector), a NaN threshold for AT_FIRST_GE /
+ * MEAN_WHERE_GE, both or neither of cap_b / b_vec, a non-finite b_vec entry, a core that has not
+ * run. */
+int hx_member_pair_metrics(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
+                           int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs,
+                           double *out);
+
+/* The weighted quantiles, outcome-class probabilities and moments of every pair metric over the
+ * ensemble: the leading arguments of hx_member_pair_metrics, then those of hx_metric_quantiles /
+ * hx_metric_probabilities / hx_metric_moments, whose definitions, weights, limits and errors hold
+ * with the members' pair-metric values in place of the metric values; a member whose pair metric is
+ * NaN does not take part.  The block is computed on the device and reduced there: it never reaches
+ * the host.  A core of several shards is combined exactly as for the hx_metric_* functions; a
+ * communicator of several processes is refused.  Not available in the host-emulation build of the
+ * test suite (refused after the argument checks). */
+int hx_pair_metric_quantiles(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
+                             int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs,
+                             const double *weights, const double *probs, int nprobs, double *out,
+                             long long *n_part);
+int hx_pair_metric_probabilities(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
+                                 int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs,
+                                 const double *weights, const double *edges, int nedges, double *prob,
+                                 unsigned long long *sums, long long *n_part);
+int hx_pair_metric_moments(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
+                           int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs,
+                           const double *weights, const double *predictors, int npred, double *shift,
+                           double *sums, unsigned long long *wsum, long long *n_part);
+
 /* Year-by-year co-moments of two windows of rows over the ensemble: what a full year x year
  * covariance or correlation matrix needs -- an emergent constraint as a map over (observed year,
  * projected year), the EOFs / PCA of the trajectories, the auto-covariance of a residual -- without
