@@ -531,6 +531,32 @@ class Core:
             unit.encode() if unit else None))
         return self
 
+    def setvar_dated_mix(self, var, years, basis, coeff, unit=None):
+        """A different input series for every member as a mix of K shared year-vectors
+        (hx_setvar_dated_mix): basis[K, n_years], coeff[K, n_members], or both 1-D for K = 1.  In
+        `years` member m holds coeff[0, m] * basis[0, i] + coeff[1, m] * basis[1, i] + ... (each
+        product rounded, added in ascending k); the table is built on the device, and a new coeff
+        for the same years and basis costs K * n_members doubles of upload."""
+        y = np.ascontiguousarray(np.atleast_1d(np.asarray(years, dtype=np.int32)))
+        b = np.ascontiguousarray(np.atleast_2d(np.asarray(basis, dtype=np.float64)))
+        w = np.ascontiguousarray(np.atleast_2d(np.asarray(coeff, dtype=np.float64)))
+        if y.ndim != 1 or b.ndim != 2 or b.shape[1] != y.size:
+            raise HectorAmdError("setvar_dated_mix: basis must be [K, n_years]")
+        if w.ndim != 2 or w.shape != (b.shape[0], self.n_members):
+            raise HectorAmdError("setvar_dated_mix: coeff must be [K, n_members] with the K of basis")
+        if b.shape[0] < 1:
+            raise HectorAmdError("setvar_dated_mix: K = 0 (clear_mix removes a mix)")
+        self._ck(self._lib.hx_setvar_dated_mix(
+            self._h, var.encode(), y.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), y.size,
+            b.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), b.shape[0],
+            w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), unit.encode() if unit else None))
+        return self
+
+    def clear_mix(self, var):
+        """Remove the mix of `var`: the per-member table beneath it, or the shared series, again."""
+        self._ck(self._lib.hx_setvar_dated_mix(self._h, var.encode(), None, 0, None, 0, None, None))
+        return self
+
     def set_member_sorting(self, on=True):
         self._ck(self._lib.hx_set_member_sorting(self._h, 1 if on else 0))
         return self

@@ -68,6 +68,9 @@ hipError_t hx_launch_series_runmean(const double *a, int npad, int ns, int w, in
                                     hipStream_t st);
 hipError_t hx_launch_series_permute(const double *src, const int *src_lane, int npad, int ns, double *dst,
                                     hipStream_t st);
+hipError_t hx_launch_mseries_fill(const double *row, int ns, int npad, double *table, hipStream_t st);
+hipError_t hx_launch_mseries_mix(const double *coeff, const int *member_of_lane, int n, int npad, const int *rows,
+                                 const double *basis, int nrows, int nbasis, double *table, hipStream_t st);
 hipError_t hx_launch_bin(const double *var, int n, int npad, int iy0, int nrows, const unsigned long long *q,
                          const double *edges, int K, unsigned long long *sums, hipStream_t stream);
 hipError_t hx_launch_q_minmax(const double *var, int n, int npad, int iy0, int ny,
@@ -594,7 +597,11 @@ void EnsembleCore::free_device() {
   d_metplan_ = nullptr; d_met_ = nullptr; d_bin_ = nullptr;
   score_cap_ = qstate_cap_ = qhist_cap_ = metplan_cap_ = met_cap_ = bin_cap_ = 0; q_src_ = nullptr;
   d_hist_ = nullptr; d_hist_status_ = nullptr;
-  for (int k = 0; k < HXM_N; ++k) { fr(d_mseries_[k]); d_mseries_[k] = nullptr; if (!member_series_[k].empty()) mseries_dirty_ = true; }
+  for (int k = 0; k < HXM_N; ++k) {
+    fr(d_mseries_[k]); d_mseries_[k] = nullptr;
+    if (!member_series_[k].empty() || mix_[k].nbasis) mseries_dirty_ = true;
+  }
+  fr(d_mix_); d_mix_ = nullptr; mix_cap_ = 0;
   fr(d_diag_); fr(d_slr_); d_diag_ = d_slr_ = nullptr; diag_cap_ = 0; slr_valid_to_ = -1;
   free_derived_cache();   // (the series stay: they are snapshots that outlive a new layout)
   d_derived_ = nullptr; d_dpart_ = nullptr; d_gather_ = nullptr; d_lane_of_member_ = nullptr;
@@ -1203,6 +1210,27 @@ const MemberSeriesDef kMemberSeries[] = {
     {"CH4_constrain", HXM_CH4_CON, "CH4", "ppbv CH4", 0},
 };
 bool is_constraint_series(int k) { return k >= HXM_CO2_CON && k <= HXM_CH4_CON; }
+const char kMixNames[] = "ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions";
+// The definition of hx_setvar_dated_mix restated for the host (fetchvars), for year column i of
+// the recipe: every product rounded before it is added, ascending k -- contraction off whatever
+// the host compiler's default is, as in hx_mseries_mix_kernel.
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+void mix_year_host(const double *basis, const double *coeff, int nbasis, size_t ny, size_t i, size_t n,
+                   double *out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  for (size_t m = 0; m < n; ++m) {
+    double s = coeff[m] * basis[i];
+    for (int k = 1; k < nbasis; ++k) {
+      const double p = coeff[(size_t)k * n + m] * basis[(size_t)k * ny + i];
+      s = s + p;
+    }
+    out[m] = s;
+  }
+}
 bool interpolated_constraint(int k) { return k == HXM_TAS_CON || k == HXM_FTOT_CON; }
 int constraint_bit(int k) {
   switch (k) {
@@ -1241,6 +1269,13 @@ void EnsembleCore::setvar_dated(const std::string &capability, const int *years,
   if (units && units[0] && expect != units)
     throw std::runtime_error("Units: " + std::string(units) + " do not match expected: " + expect +
                              " for " + capability);
+  for (const MemberSeriesDef &d : kMemberSeries)
+    if (capability == d.name && mix_[d.k].nbasis)
+      for (int i = 0; i < n; ++i)
+        if (mix_[d.k].covers(years[i]))
+          throw std::runtime_error("hx_setvar_dated: " + capability + " has a mix that covers " +
+                                   std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
+                                   "with nbasis = 0)");
   int miny = scen_.end;
   for (int i = 0; i < n; ++i) {
     for (auto &sec : sections)
@@ -1251,6 +1286,7 @@ void EnsembleCore::setvar_dated(const std::string &capability, const int *years,
   // those: a value "for every member" goes into every member's row as well
   for (const MemberSeriesDef &d : kMemberSeries) {
     const int k = d.k;
+    if (capability == d.name && mix_[k].nbasis) mseries_dirty_ = true;  // the rows under the mix follow
     if (capability != d.name || member_series_[k].empty()) continue;
     if (interpolated_constraint(k)) {  // the interpolated years move with the points
       for (int i = 0; i < n; ++i) member_points_[k][years[i]].assign((size_t)n_, values[i]);
@@ -1281,6 +1317,12 @@ void EnsembleCore::setvar_dated_members(const std::string &capability, const int
   if (units && units[0] && std::string(units) != d->units)
     throw std::runtime_error("Units: " + std::string(units) + " do not match expected: " +
                              d->units + " for " + capability);
+  if (mix_[d->k].nbasis)
+    for (int i = 0; i < nyears; ++i)
+      if (mix_[d->k].covers(years[i]))
+        throw std::runtime_error("hx_setvar_dated_members: " + capability + " has a mix that covers " +
+                                 std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
+                                 "with nbasis = 0)");
   const int ns = scen_.ns();
   std::vector<double> &ms = member_series_[d->k];
   if (ms.empty()) {  // start from the scenario's series, the same for every member
@@ -1318,6 +1360,65 @@ void EnsembleCore::setvar_dated_members(const std::string &capability, const int
   if (target < last_iy_) dirty_from_iy_ = (dirty_from_iy_ < 0) ? target : std::min(dirty_from_iy_, target);
 }
 
+bool EnsembleCore::MemberMix::covers(int year) const {
+  return std::find(years.begin(), years.end(), year) != years.end();
+}
+
+void EnsembleCore::check_dated_mix(const std::string &capability, const int *years, int nyears,
+                                   const double *basis, int nbasis, const double *coeff,
+                                   const char *units) const {
+  const std::string fn = "hx_setvar_dated_mix: ";
+  const MemberSeriesDef *d = nullptr;
+  for (const MemberSeriesDef &m : kMemberSeries)
+    if (capability == m.name && !is_constraint_series(m.k)) d = &m;
+  if (!d)
+    throw std::runtime_error(fn + "a mix is not supported for " + capability + " (" + kMixNames + " are)");
+  if (units && units[0] && std::string(units) != d->units)
+    throw std::runtime_error(fn + "Units: " + std::string(units) + " do not match expected: " + d->units +
+                             " for " + capability);
+  if (nbasis < 0 || nbasis > HX_MIX_MAX_BASIS)
+    throw std::runtime_error(fn + "nbasis = " + std::to_string(nbasis) + " outside 0.." +
+                             std::to_string(HX_MIX_MAX_BASIS));
+  if (nbasis == 0) return;  // removes the mix: nothing else is read
+  if (!years || !basis || !coeff) throw std::runtime_error(fn + "null years, basis or coeff with nbasis > 0");
+  if (nyears < 1) throw std::runtime_error(fn + "nyears < 1");
+  std::vector<int> seen(years, years + nyears);
+  std::sort(seen.begin(), seen.end());
+  if (seen.front() < scen_.start || seen.back() > scen_.end)
+    throw std::runtime_error(fn + "date outside startDate..endDate");
+  for (int i = 1; i < nyears; ++i)
+    if (seen[(size_t)i] == seen[(size_t)i - 1])
+      throw std::runtime_error(fn + "year " + std::to_string(seen[(size_t)i]) + " listed twice");
+  for (size_t j = 0; j < (size_t)nbasis * (size_t)nyears; ++j)
+    if (!std::isfinite(basis[j])) throw std::runtime_error(fn + "a basis value is not finite");
+  for (size_t j = 0; j < (size_t)nbasis * (size_t)n_; ++j)
+    if (!std::isfinite(coeff[j])) throw std::runtime_error(fn + "a coefficient is not finite");
+}
+
+void EnsembleCore::setvar_dated_mix(const std::string &capability, const int *years, int nyears,
+                                    const double *basis, int nbasis, const double *coeff,
+                                    const char *units) {
+  check_dated_mix(capability, years, nyears, basis, nbasis, coeff, units);
+  const MemberSeriesDef *d = nullptr;
+  for (const MemberSeriesDef &m : kMemberSeries) if (capability == m.name) d = &m;
+  MemberMix &mx = mix_[d->k];
+  if (nbasis == 0 && mx.nbasis == 0) return;
+  int miny = scen_.end;   // the years the replaced mix gives back change as well
+  for (int y : mx.years) miny = std::min(miny, y);
+  if (nbasis == 0) {
+    mx = MemberMix();
+  } else {
+    mx.nbasis = nbasis;
+    mx.years.assign(years, years + nyears);
+    mx.basis.assign(basis, basis + (size_t)nbasis * (size_t)nyears);
+    mx.coeff.assign(coeff, coeff + (size_t)nbasis * (size_t)n_);
+    for (int y : mx.years) miny = std::min(miny, y);
+  }
+  mseries_dirty_ = true;
+  const int target = std::max(0, miny - 1 - scen_.start);
+  if (target < last_iy_) dirty_from_iy_ = (dirty_from_iy_ < 0) ? target : std::min(dirty_from_iy_, target);
+}
+
 // member_points_[k] -> member_series_[k]: every member's points densified by the rule of the
 // shared series (Scenario::densify_points: interpolation between a member's first and last date,
 // RF_tot_constrain flat before its first one; NaN points are no points)
@@ -1343,18 +1444,72 @@ void EnsembleCore::upload_member_series() {
   std::vector<double> flat;
   for (const MemberSeriesDef &d : kMemberSeries) {
     const std::vector<double> &ms = member_series_[d.k];
-    if (ms.empty()) continue;
+    if (ms.empty() && !mix_[d.k].nbasis) {
+      if (d_mseries_[d.k]) {  // its mix was removed and nothing lies beneath: shared again
+        check(hipStreamSynchronize(stream_), "sync member series");
+        (void)hipFree(d_mseries_[d.k]);
+        d_mseries_[d.k] = nullptr;
+      }
+      continue;
+    }
     if (!d_mseries_[d.k]) check(hipMalloc(&d_mseries_[d.k], sizeof(double) * ns * np), "hipMalloc member series");
-    flat.assign(ns * np, 0.0);
-    for (size_t iy = (size_t)d.lag; iy < ns; ++iy)
-      for (size_t l = 0; l < np; ++l)
-        flat[iy * np + l] = ms[(iy - (size_t)d.lag) * n_ + (size_t)std::min(member_of_lane_[l], n_ - 1)];
-    check(hipMemcpyAsync(d_mseries_[d.k], flat.data(), sizeof(double) * flat.size(),
-                         hipMemcpyHostToDevice, stream_), "upload member series");
-    check(hipStreamSynchronize(stream_), "sync member series");
+    if (!ms.empty()) {
+      flat.assign(ns * np, 0.0);
+      for (size_t iy = (size_t)d.lag; iy < ns; ++iy)
+        for (size_t l = 0; l < np; ++l)
+          flat[iy * np + l] = ms[(iy - (size_t)d.lag) * n_ + (size_t)std::min(member_of_lane_[l], n_ - 1)];
+      check(hipMemcpyAsync(d_mseries_[d.k], flat.data(), sizeof(double) * flat.size(),
+                           hipMemcpyHostToDevice, stream_), "upload member series");
+      check(hipStreamSynchronize(stream_), "sync member series");
+    }
+    if (mix_[d.k].nbasis) build_mix_table(d.k, d.lag, d.section, d.name, !ms.empty());
   }
   upload_args();
   mseries_dirty_ = false;
+}
+
+// Variable k's table where it has a mix, on the stream: without a dense table beneath (that one is
+// already uploaded) every row from the shared series -- rows below the lag zero, row iy the date
+// iy - lag, as upload_member_series() lays a dense table out -- then the mix kernel over the rows
+// of the covered years.  What goes up is the recipe: the lane map, the rows, nbasis x covered
+// years of basis and nbasis x n_ coefficients in member order.
+void EnsembleCore::build_mix_table(int k, int lag, const std::string &section, const std::string &capability,
+                                   bool dense) {
+  const MemberMix &mx = mix_[k];
+  const size_t np = (size_t)npad_, ns = (size_t)scen_.ns(), ny = mx.years.size(), K = (size_t)mx.nbasis;
+  std::vector<int> ints(member_of_lane_.begin(), member_of_lane_.begin() + (std::ptrdiff_t)np);
+  std::vector<size_t> col;   // the covered years that have a row (a lag-1 series never reads endDate's)
+  for (size_t i = 0; i < ny; ++i) {
+    const size_t r = (size_t)(mx.years[i] - scen_.start + lag);
+    if (r < ns) { ints.push_back((int)r); col.push_back(i); }
+  }
+  const size_t nr = col.size();
+  std::vector<double> dbl(ns + K * nr);   // the shared rows | the basis of the covered rows [K][nr]
+  if (!dense && scen_.has_series(section, capability)) {
+    const std::vector<double> &base = scen_.series(section, capability);
+    for (size_t iy = (size_t)lag; iy < ns; ++iy) dbl[iy] = base[iy - (size_t)lag];
+  }
+  for (size_t kk = 0; kk < K; ++kk)
+    for (size_t j = 0; j < nr; ++j) dbl[ns + kk * nr + j] = mx.basis[kk * ny + col[j]];
+  const size_t b_dbl = sizeof(double) * dbl.size(), b_coeff = sizeof(double) * K * (size_t)n_,
+               b_int = sizeof(int) * ints.size();
+  if (b_dbl + b_coeff + b_int > mix_cap_) {
+    check(hipStreamSynchronize(stream_), "sync mix scratch");
+    if (d_mix_) (void)hipFree(d_mix_);
+    d_mix_ = nullptr; mix_cap_ = 0;
+    check(hipMalloc(&d_mix_, b_dbl + b_coeff + b_int), "hipMalloc mix scratch");
+    mix_cap_ = b_dbl + b_coeff + b_int;
+  }
+  double *d_dbl = reinterpret_cast<double *>(d_mix_), *d_coeff = d_dbl + dbl.size();
+  int *d_int = reinterpret_cast<int *>(d_mix_ + b_dbl + b_coeff);
+  check(hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, stream_), "upload mix basis");
+  check(hipMemcpyAsync(d_coeff, mx.coeff.data(), b_coeff, hipMemcpyHostToDevice, stream_), "upload mix coefficients");
+  check(hipMemcpyAsync(d_int, ints.data(), b_int, hipMemcpyHostToDevice, stream_), "upload mix rows");
+  if (!dense) check(hx_launch_mseries_fill(d_dbl, (int)ns, npad_, d_mseries_[k], stream_), "member series fill kernel");
+  if (nr)
+    check(hx_launch_mseries_mix(d_coeff, d_int, n_, npad_, d_int + np, d_dbl + ns, (int)nr, mx.nbasis,
+                                d_mseries_[k], stream_), "member series mix kernel");
+  check(hipStreamSynchronize(stream_), "sync member series mix");   // (the staging vectors end here)
 }
 
 // the kernels' argument block: buffers + scenario scalars; the constraint mask also carries the
@@ -2010,7 +2165,8 @@ void EnsembleCore::prepare() {
     upload_params();
     clk.lap("upload_params");
     if (order_changed_)
-      for (int k = 0; k < HXM_N; ++k) if (!member_series_[k].empty()) mseries_dirty_ = true;  // lanes have moved
+      for (int k = 0; k < HXM_N; ++k)
+        if (!member_series_[k].empty() || mix_[k].nbasis) mseries_dirty_ = true;  // lanes have moved
     gas_dirty_ = true;
   }
   if (gas_dirty_ || (!gas_member_.empty() && !d_mseries_[HXM_N2O])) run_gas_kernel();
@@ -2305,12 +2461,24 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
     return scen_.has_series(sec, key) ? scen_.series(sec, key) : std::vector<double>((size_t)ns, dflt);
   };
   for (const MemberSeriesDef &d : kMemberSeries)
-    if (capability == d.name && !member_series_[d.k].empty()) {
+    if (capability == d.name && (!member_series_[d.k].empty() || mix_[d.k].nbasis)) {
       if (!out_host) return true;
       if (year0 < scen_.start || year1 > scen_.end || year1 < year0)
         throw std::runtime_error("fetchvars: dates must lie between startDate and endDate");
-      std::copy(member_series_[d.k].begin() + (size_t)(year0 - scen_.start) * n_,
-                member_series_[d.k].begin() + (size_t)(year1 - scen_.start + 1) * n_, out_host);
+      if (!member_series_[d.k].empty()) {
+        std::copy(member_series_[d.k].begin() + (size_t)(year0 - scen_.start) * n_,
+                  member_series_[d.k].begin() + (size_t)(year1 - scen_.start + 1) * n_, out_host);
+      } else {  // a mix over the shared series
+        const std::vector<double> base = input(d.section, capability, 0.0);
+        for (int y = year0; y <= year1; ++y)
+          std::fill(out_host + (size_t)(y - year0) * n_, out_host + (size_t)(y - year0 + 1) * n_,
+                    base[(size_t)(y - scen_.start)]);
+      }
+      const MemberMix &mx = mix_[d.k];   // the covered years: the definition's bits
+      for (size_t i = 0; i < mx.years.size(); ++i)
+        if (mx.years[i] >= year0 && mx.years[i] <= year1)
+          mix_year_host(mx.basis.data(), mx.coeff.data(), mx.nbasis, mx.years.size(), i, (size_t)n_,
+                        out_host + (size_t)(mx.years[i] - year0) * n_);
       return true;
     }
   for (const DatedDef &d : kDated)

@@ -123,6 +123,14 @@ class EnsembleCore {
   // (vignettes/ex_hector_apply.Rmd), for all members at once.
   void setvar_dated_members(const std::string &capability, const int *years, const double *values,
                             int nyears, const char *units);
+  // The same as a mix of nbasis shared year-vectors (hx_setvar_dated_mix in hector_amd.h):
+  // basis[k * nyears + i], coeff[k * n_members + member].  Kept as that recipe; prepare() expands
+  // it into the device table.  nbasis == 0 removes the variable's mix.
+  void setvar_dated_mix(const std::string &capability, const int *years, int nyears, const double *basis,
+                        int nbasis, const double *coeff, const char *units);
+  // every check of setvar_dated_mix, changing nothing (throws what it would throw)
+  void check_dated_mix(const std::string &capability, const int *years, int nyears, const double *basis,
+                       int nbasis, const double *coeff, const char *units) const;
   static const char *const *output_capabilities(int *count);
 
   void reset(double date);      // Core::reset: date < startDate => redo spinup
@@ -305,6 +313,18 @@ class EnsembleCore {
   double *d_mseries_[HXM_N] = {};
   bool mseries_dirty_ = false;
   void upload_member_series();
+  // A variable's mix (setvar_dated_mix): the recipe, never the n_ x years table.  It overlays
+  // member_series_[k] if that exists, else the scenario's shared series, in `years`.
+  struct MemberMix {
+    int nbasis = 0;                    // 0 = none
+    std::vector<int> years;            // [ny], as given
+    std::vector<double> basis, coeff;  // [nbasis][ny], [nbasis][n_] in member order
+    bool covers(int year) const;
+  };
+  MemberMix mix_[HXM_N];
+  char *d_mix_ = nullptr;              // scratch of the mix kernel: lane map, rows, basis, coefficients
+  size_t mix_cap_ = 0;
+  void build_mix_table(int k, int lag, const std::string &section, const std::string &capability, bool dense);
   void upload_args();
   bool component_disabled(const std::string &section) const;  // "enabled=0" in the INI section
   void check_component_enabled(const std::string &capability) const;

@@ -338,6 +338,11 @@ int hx_setvar_dated_members(hx_core *core, const char *capability, const int *ye
     return fail("hx_setvar_dated_members: bad arguments");
   HX_TRY(core->core->setvar_dated_members(capability, years, values, nyears, units))
 }
+int hx_setvar_dated_mix(hx_core *core, const char *capability, const int *years, int nyears,
+                        const double *basis, int nbasis, const double *coeff, const char *units) {
+  if (!core || !capability) return fail("hx_setvar_dated_mix: null core or capability");
+  HX_TRY(core->core->setvar_dated_mix(capability, years, nyears, basis, nbasis, coeff, units))
+}
 int hx_lane_of_member(hx_core *core, int *out) {
   if (!out) return fail("null argument");
   HX_TRY(core->core->lane_of_member(out))

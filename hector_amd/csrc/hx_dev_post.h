@@ -489,6 +489,70 @@ hipError_t hx_launch_series_permute(const double *src, const int *src_lane, int 
 }
 
 // ===========================================================================
+// Per-member input series as a mix of shared year-vectors (hx_setvar_dated_mix in hector_amd.h
+// defines the value and its order; contraction is off as in the score kernel): the [row][npad]
+// table the run kernels read behind an ms_mask bit, built on the device.
+//   fill: table[r][lane] = row[r] for every row -- the shared series under a mix that has no dense
+//         table beneath it.  grid (lanes / 256, ns)
+//   mix:  table[rows[i]][lane] = sum over k, ascending, of coeff[k][member(lane)] * basis[k][i], each
+//         product rounded before it is added.  The lane takes its coefficients once through
+//         member_of_lane (a padding lane: the last member's, as the dense upload does) and writes
+//         its element of HXMIX_TILE covered rows; rows[] and basis[] are indexed by blockIdx.y and
+//         the loop counter alone, so they stay in scalar registers.  grid (lanes / 256,
+//         ceil(nrows / HXMIX_TILE)): 65 536 lanes x 71 rows are 2304 blocks.  Lane-local: nothing
+//         is exchanged, the host-emulation build runs it as it stands.
+// ===========================================================================
+#define HXMIX_TILE 8
+__global__ __launch_bounds__(256) void hx_mseries_fill_kernel(const double *__restrict__ row, int npad,
+                                                              double *__restrict__ table) {
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= npad) return;
+  table[(size_t)blockIdx.y * (size_t)npad + (size_t)lane] = row[blockIdx.y];
+}
+
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__global__ __launch_bounds__(256) void hx_mseries_mix_kernel(const double *__restrict__ coeff,
+                                                             const int *__restrict__ member_of_lane, int n,
+                                                             int npad, const int *__restrict__ rows,
+                                                             const double *__restrict__ basis, int nrows,
+                                                             int nbasis, double *__restrict__ table) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= npad) return;
+  const int m = min(member_of_lane[lane], n - 1);
+  double c[HX_MIX_MAX_BASIS];
+#pragma unroll
+  for (int k = 0; k < HX_MIX_MAX_BASIS; ++k) c[k] = k < nbasis ? coeff[(size_t)k * (size_t)n + (size_t)m] : 0.0;
+  const int i0 = (int)blockIdx.y * HXMIX_TILE, i1 = min(i0 + HXMIX_TILE, nrows);
+  for (int i = i0; i < i1; ++i) {
+    double s = c[0] * basis[i];
+#pragma unroll
+    for (int k = 1; k < HX_MIX_MAX_BASIS; ++k)
+      if (k < nbasis) {
+        const double p = c[k] * basis[(size_t)k * (size_t)nrows + (size_t)i];
+        s = s + p;
+      }
+    table[(size_t)rows[i] * (size_t)npad + (size_t)lane] = s;
+  }
+}
+
+hipError_t hx_launch_mseries_fill(const double *row, int ns, int npad, double *table, hipStream_t st) {
+  hipLaunchKernelGGL(hx_mseries_fill_kernel, dim3((npad + 255) / 256, ns), dim3(256), 0, st, row, npad, table);
+  return hipGetLastError();
+}
+hipError_t hx_launch_mseries_mix(const double *coeff, const int *member_of_lane, int n, int npad, const int *rows,
+                                 const double *basis, int nrows, int nbasis, double *table, hipStream_t st) {
+  if (nrows < 1 || nbasis < 1 || nbasis > HX_MIX_MAX_BASIS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hx_mseries_mix_kernel, dim3((npad + 255) / 256, (nrows + HXMIX_TILE - 1) / HXMIX_TILE),
+                     dim3(256), 0, st, coeff, member_of_lane, n, npad, rows, basis, nrows, nbasis, table);
+  return hipGetLastError();
+}
+
+// ===========================================================================
 // Pair metrics: one double per member from a window of TWO series of that member, a (reported /
 // dependent) and b (condition / independent) -- hx_member_pair_metrics in hector_amd.h defines every
 // operation and its order; contraction is off as in the score kernel.  One lane per member, nothing

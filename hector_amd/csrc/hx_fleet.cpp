@@ -307,6 +307,28 @@ void Fleet::setvar_dated_members(const std::string &cap, const int *years, const
     s.core->setvar_dated_members(cap, years, part.data(), nyears, units);
   }
 }
+void Fleet::setvar_dated_mix(const std::string &cap, const int *years, int nyears, const double *basis,
+                             int nbasis, const double *coeff, const char *units) {
+  if (shards_.size() == 1) { shards_[0].core->setvar_dated_mix(cap, years, nyears, basis, nbasis, coeff, units); return; }
+  // every shard validates its own part: all of them first, so that a refused call changes nothing
+  std::vector<std::vector<double>> part(shards_.size());
+  for (size_t j = 0; j < shards_.size(); ++j) {  // coeff[k * n_members + member] -> this shard's [k][count]
+    Shard &s = shards_[j];
+    if (nbasis > 0 && nbasis <= HX_MIX_MAX_BASIS && coeff) {
+      part[j].resize((size_t)nbasis * (size_t)s.count);
+      for (int k = 0; k < nbasis; ++k)
+        std::memcpy(part[j].data() + (size_t)k * s.count, coeff + (size_t)k * n_ + s.offset,
+                    sizeof(double) * (size_t)s.count);
+    }
+    use(s);
+    s.core->check_dated_mix(cap, years, nyears, basis, nbasis, part[j].empty() ? nullptr : part[j].data(), units);
+  }
+  for (size_t j = 0; j < shards_.size(); ++j) {
+    use(shards_[j]);
+    shards_[j].core->setvar_dated_mix(cap, years, nyears, basis, nbasis,
+                                      part[j].empty() ? nullptr : part[j].data(), units);
+  }
+}
 void Fleet::lane_of_member(int *out) {
   for (Shard &s : shards_) { use(s); s.core->lane_of_member(out + s.offset); }
 }

@@ -79,6 +79,9 @@ class Fleet {
                     const char *units);
   void setvar_dated_members(const std::string &capability, const int *years, const double *values,
                             int nyears, const char *units);
+  // coeff[k * n_members + member]: every shard takes its members' columns and the whole basis
+  void setvar_dated_mix(const std::string &capability, const int *years, int nyears, const double *basis,
+                        int nbasis, const double *coeff, const char *units);
   void lane_of_member(int *out);  // lane inside the member's shard
   void reset(double date);
   void run(double runtodate);  // queues every device, waits for none

@@ -120,6 +120,36 @@ int hx_setvar_dated(hx_core *core, const char *capability, const int *years, con
  * -- 8 B per member-year of HBM each, once used. */
 int hx_setvar_dated_members(hx_core *core, const char *capability, const int *years,
                             const double *values, int nyears, const char *units);
+/* A different series for every member given as what it usually is: a MIX of a few shared
+ * year-vectors -- a scenario scaled per member, a blend of two scenarios with a per-member weight,
+ * a common pulse of per-member size.  basis[k * nyears + i] is vector k in years[i],
+ * coeff[k * n_members + member] the member's weight of it, nbasis <= HX_MIX_MAX_BASIS.
+ * DEFINITION.  In every years[i] the variable of member m is
+ *     s = coeff[0][m] * basis[0][i];   for k = 1 .. nbasis-1:  s = s + (coeff[k][m] * basis[k][i])
+ * each product rounded before it is added, in ascending k, in IEEE double without fused
+ * multiply-add: numpy reproduces it bit for bit under any lane order, kernel flavour or shard
+ * layout, and hx_fetchvars returns these bits ([year][member], member order; the other years hold
+ * the underlying value).  A variable has at most one mix.  It OVERLAYS, in the years it lists, the
+ * series beneath it: the per-member table of hx_setvar_dated_members if there is one, else the
+ * scenario's shared series.  A second call replaces the whole mix (years only the old one listed
+ * go back to the series beneath); nbasis = 0 removes it (years, basis, coeff are not read), and a
+ * variable without a per-member table is shared again.  While a mix exists, hx_setvar_dated and
+ * hx_setvar_dated_members of that variable are refused in a year it covers (remove the mix
+ * first); in the other years they work as without one.  Marks the core dirty from min(year)-1
+ * over the years of the new and of the replaced mix, like hx_setvar_dated_members.
+ * COST.  The host keeps the recipe, nbasis x (n_members + nyears) doubles, never a table of
+ * n_members x n_years.  The next hx_run uploads it and expands it on the device into the 8 B per
+ * member-year table the run kernels read (one store-bound kernel); new coefficients for the same
+ * years cost nbasis x n_members doubles of upload and that kernel again.
+ * ERRORS (every message names the function; a refused call changes nothing): a capability other
+ * than ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions (the constraint
+ * series, with NaN = none and interpolated points, are no linear mix); units that do not match
+ * (rule of hx_setvar_dated_members); nbasis outside 0..HX_MIX_MAX_BASIS; nyears < 1; a year
+ * outside startDate..endDate or listed twice; a basis value or coefficient that is not finite;
+ * NULL years, basis or coeff with nbasis > 0. */
+#define HX_MIX_MAX_BASIS 8
+int hx_setvar_dated_mix(hx_core *core, const char *capability, const int *years, int nyears,
+                        const double *basis, int nbasis, const double *coeff, const char *units);
 /* Keep every year's component state in HBM so hx_reset can return to any computed date --
  * what the reference's per-component tseries records provide (src/simpleNbox.cpp:708-840,
  * src/ocean_component.cpp:767-846).  272 B per member-year (one biome); default off. */
