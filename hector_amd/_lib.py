@@ -195,6 +195,10 @@ def _declare(lib):
                                    c.c_int, dp, dp, c.POINTER(c.c_ulonglong), c.POINTER(c.c_longlong)],
         "hx_ensemble_comoments": [P, c.c_char_p, c.c_int, c.c_int, c.c_char_p, c.c_int, c.c_int, dp, dp, dp,
                                   dp, dp, dp, c.POINTER(c.c_ulonglong), c.POINTER(c.c_longlong)],
+        "hx_ensemble_sobol": [P, c.c_char_p, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_ubyte), dp, dp,
+                              c.POINTER(c.c_longlong)],
+        "hx_metric_sobol": [P, c.c_char_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_ubyte), dp, dp,
+                            c.POINTER(c.c_longlong)],
         "hx_series_define": [P, c.c_char_p, c.c_char_p, c.c_void_p],
         "hx_series_drop": [P, c.c_char_p],
         "hx_series_list": [P, c.POINTER(c.POINTER(c.c_char_p)), c.POINTER(c.POINTER(c.c_int)),
@@ -235,5 +239,5 @@ ABI_SYMBOLS = ["hx_backend", "hx_build_info", "hx_last_error", "hx_newcore", "hx
                "hx_ensemble_probabilities", "hx_metric_probabilities",
                "hx_ensemble_moments", "hx_metric_moments", "hx_ensemble_comoments",
                "hx_member_pair_metrics", "hx_pair_metric_quantiles", "hx_pair_metric_probabilities",
-               "hx_pair_metric_moments",
+               "hx_pair_metric_moments", "hx_ensemble_sobol", "hx_metric_sobol",
                "hx_series_define", "hx_series_drop", "hx_series_list"]

@@ -246,6 +246,74 @@ class Moments:
         return "Moments(rows=%d, against=%r)" % (self.shift.size, self.names)
 
 
+SOBOL_MAX_FACTORS = 16   # HX_SOBOL_MAX_FACTORS
+
+
+class Sobol:
+    """What hx_ensemble_sobol / hx_metric_sobol return, and the statistics they define
+    (include/hector_amd.h), all in float64.  R rows (years or metrics), K factors of a Saltelli
+    design (hector_amd.ensemble.saltelli).
+    Raw: names[K]; shift[R] = c_y, the smallest participating x_A or x_B of the row; sums[R, 4 + 4 K]
+    = SA1, SA2, SB1, SB2, then T_i, TT_i, F_i, FF_i per factor; n_part[R] = participating groups n.
+    Derived:  m = (SA1 + SB1) / (2 n), mean = shift + m;  var = V = (SA2 + SB2) / (2 n) - m m, the
+    population variance of the 2 n pooled A and B values;  total = T / (2 n V) and first = 1 -
+    F / (2 n V), [R, K] (Jansen's estimators);  total_se = sqrt((TT / n - (T / n)**2) / n) / (2 V) and
+    first_se the same from F, FF: the standard errors of the numerators with V taken as known.
+    Where V is 0 or nobody takes part, the indices and their standard errors are NaN."""
+
+    def __init__(self, names, shift, sums, n_part):
+        self.names = list(names)
+        self.shift = np.asarray(shift, dtype=np.float64)
+        self.sums = np.asarray(sums, dtype=np.float64).reshape(self.shift.size, -1)
+        self.n_part = np.asarray(n_part, dtype=np.int64)
+        if self.sums.shape[1] != 4 + 4 * len(self.names):
+            raise HectorAmdError("Sobol: sums must have 4 + 4 * len(names) columns")
+
+    def _n(self):
+        n = self.n_part.astype(np.float64)
+        return np.where(n > 0, n, np.nan)
+
+    def _m(self):
+        return (self.sums[:, 0] + self.sums[:, 2]) / (2.0 * self._n())
+
+    @property
+    def mean(self):
+        return self.shift + self._m()
+
+    @property
+    def var(self):
+        m = self._m()
+        return (self.sums[:, 1] + self.sums[:, 3]) / (2.0 * self._n()) - m * m
+
+    def _v(self):
+        v = self.var
+        return np.where(v != 0, v, np.nan)[:, None]   # (V == 0: undefined)
+
+    @property
+    def total(self):
+        return self.sums[:, 4::4] / (2.0 * self._n()[:, None] * self._v())
+
+    @property
+    def first(self):
+        return 1.0 - self.sums[:, 6::4] / (2.0 * self._n()[:, None] * self._v())
+
+    def _se(self, s1, s2):
+        n = self._n()[:, None]
+        with np.errstate(invalid="ignore"):
+            return np.sqrt((s2 / n - (s1 / n) ** 2) / n) / (2.0 * self._v())
+
+    @property
+    def total_se(self):
+        return self._se(self.sums[:, 4::4], self.sums[:, 5::4])
+
+    @property
+    def first_se(self):
+        return self._se(self.sums[:, 6::4], self.sums[:, 7::4])
+
+    def __repr__(self):
+        return "Sobol(rows=%d, factors=%r)" % (self.shift.size, self.names)
+
+
 class CoMoments:
     """What hx_ensemble_comoments returns, and the statistics it defines (include/hector_amd.h), all
     in float64.  Window A has na rows (years_a), window B nb rows (years_b); participation is by
@@ -1089,6 +1157,49 @@ class Core:
             "metric_moments",
             lambda *a: self._lib.hx_metric_moments(self._h, var.encode(), ctypes.byref(arr), ns, *a),
             ns, weights, against)
+
+    def _sobol(self, what, call, nrows, factors, n_base, use):
+        names = ["factor[%d]" % i for i in range(int(factors))] if isinstance(factors, (int, np.integer)) \
+            else [str(f) for f in factors]
+        k = len(names)
+        if k > SOBOL_MAX_FACTORS:
+            raise HectorAmdError("%s: at most %d factors" % (what, SOBOL_MAX_FACTORS))
+        nb = self.n_members // (k + 2) if n_base is None else int(n_base)
+        u = None
+        if use is not None:
+            u = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
+            if u.shape != (nb,):
+                raise HectorAmdError("%s: use must have n_base entries" % what)
+        shift = np.empty(nrows)
+        sums = np.zeros((nrows, 4 + 4 * k))
+        npart = np.zeros(nrows, dtype=np.int64)
+        self._ck(call(k, nb, u.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if u is not None else None,
+                      shift.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                      sums.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                      npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return Sobol(names, shift, sums, npart)
+
+    def sobol(self, var, factors, dates=None, n_base=None, use=None):
+        """Per-year first-order and total Sobol indices of `var` with respect to the factors of a
+        Saltelli design, on the device (hx_ensemble_sobol) -> Sobol.  The members must be laid out as
+        hector_amd.ensemble.saltelli gives them: n_base groups of k + 2 consecutive members (A_j, B_j,
+        then A_j with factor i from B_j).  factors: the number of factors k or a list of k names
+        (labels only), at most 16; n_base defaults to n_members // (k + 2), members past
+        n_base * (k + 2) are ignored; use[n_base]: groups with a zero entry take no part.  A group
+        takes part in a year if none of its k + 2 values is NaN."""
+        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
+            (int(min(dates)), int(max(dates)))
+        return self._sobol(
+            "sobol", lambda *a: self._lib.hx_ensemble_sobol(self._h, var.encode(), y0, y1, *a),
+            max(y1 - y0 + 1, 0), factors, n_base, use)
+
+    def metric_sobol(self, var, specs, factors, n_base=None, use=None):
+        """The same over metrics (hx_metric_sobol): one row per specification -> Sobol."""
+        arr, ns = self._metric_array(specs, "metric_sobol")
+        return self._sobol(
+            "metric_sobol",
+            lambda *a: self._lib.hx_metric_sobol(self._h, var.encode(), ctypes.byref(arr), ns, *a),
+            ns, factors, n_base, use)
 
     def comoments(self, var_a, dates_a=None, var_b=None, dates_b=None, weights=None):
         """Year-by-year weighted co-moments of two windows over the ensemble, on the device

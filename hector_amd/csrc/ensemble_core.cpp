@@ -89,6 +89,14 @@ int hx_mom_chunks(int n);
 hipError_t hx_launch_moments(const double *var, int n, int npad, int iy0, int nrows, const double *qd,
                              const double *e, int npred, const double *shift, double *part, double *out,
                              hipStream_t st);
+int hx_sobol_chunks(int nb);
+hipError_t hx_launch_sobol_prepare(const int *lane_of_member, int npad, int k, int nb, const unsigned char *use,
+                                   int *tab, unsigned char *flag, hipStream_t st);
+hipError_t hx_launch_sobol_part(const double *var, int npad, int iy0, int nrows, const int *tab, int nb, int k,
+                                const unsigned char *flag, void *st, unsigned char *on, hipStream_t stream);
+hipError_t hx_launch_sobol_sums(const double *var, int npad, int iy0, int nrows, const int *tab, int nb, int k,
+                                const void *st, const unsigned char *on, double *part, double *sums, double *shift,
+                                long long *npart, hipStream_t stream);
 hipError_t hx_launch_co_mask(const double *va, int ia0, int na, const double *vb, int ib0, int nb, int npad,
                              unsigned long long *q_lane, double *qd_lane, hipStream_t st);
 int hx_co_chunks(int n, int na, int nb);
@@ -591,6 +599,7 @@ void EnsembleCore::free_device() {
   fr(d_score_); fr(d_q_); fr(d_qstate_); fr(d_qhist_); fr(d_metplan_); fr(d_met_); fr(d_bin_);
   fr(d_mom_); d_mom_ = nullptr; mom_cap_ = 0; mom_src_ = nullptr;
   fr(d_comom_); d_comom_ = nullptr; comom_cap_ = 0; co_a_ = nullptr;
+  fr(d_sobol_); d_sobol_ = nullptr; sobol_cap_ = 0; sob_src_ = nullptr;
   fr(d_whiten_); d_whiten_ = nullptr; whiten_cap_ = 0;
   fr(d_project_); d_project_ = nullptr; project_cap_ = 0;
   d_score_ = nullptr; d_q_ = d_qstate_ = d_qhist_ = nullptr;
@@ -3688,6 +3697,111 @@ void EnsembleCore::mom_finish(const double *shift_host, double *sums_host) {
   check(hipMemcpyAsync(sums_host, b.out, 8 * (size_t)ny * nc, hipMemcpyDeviceToHost, stream_), "moments fetch");
   check(hipStreamSynchronize(stream_), "moments sync");
   mom_src_ = nullptr;
+#endif
+}
+
+// ---- Sobol sums from a Saltelli design (hx_ensemble_sobol, hx_metric_sobol) -----------------------
+
+namespace {
+// d_sobol_ in 8-byte words: the rows' records, shifts, counts and sums, the chunks' partial sums, the
+// group-major lane table, the groups' flags (the caller's use; in use and every lane valid) and the
+// rows' participation bytes
+struct SobBuf {
+  unsigned long long *st;
+  double *shift, *out, *part;
+  long long *npart;
+  int *tab;
+  unsigned char *use, *flag, *on;
+  size_t words;
+  SobBuf(unsigned long long *base, int k, int nb, int ny, int nchunks) {
+    const size_t K = (size_t)k, NB = (size_t)nb, Y = (size_t)ny, nc = 4 + 4 * K;
+    const size_t gw = (NB + 7) / 8;                            // words of one byte per group
+    st = base;                                                 // [ny][2]
+    shift = reinterpret_cast<double *>(st + 2 * Y);            // [ny]
+    npart = reinterpret_cast<long long *>(shift + Y);          // [ny]
+    out = reinterpret_cast<double *>(npart + Y);               // [ny][nc]
+    part = out + Y * nc;                                       // [ny][nchunks][nc]
+    unsigned long long *w = reinterpret_cast<unsigned long long *>(part + Y * (size_t)nchunks * nc);
+    tab = reinterpret_cast<int *>(w);                          // [k + 2][nb]
+    w += ((K + 2) * NB + 1) / 2;
+    use = reinterpret_cast<unsigned char *>(w);                // [nb]
+    flag = reinterpret_cast<unsigned char *>(w + gw);          // [nb]
+    on = reinterpret_cast<unsigned char *>(w + 2 * gw);        // [ny][nb]
+    words = 4 * Y + Y * nc + Y * (size_t)nchunks * nc + ((K + 2) * NB + 1) / 2 + 2 * gw + (Y * NB + 7) / 8;
+  }
+};
+}  // namespace
+
+void EnsembleCore::sobol_check(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                               int nspecs, const char *fn) {
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)year0; (void)year1; (void)specs; (void)nspecs;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  const double *src = nullptr;
+  if (specs) metric_check(capability, specs, nspecs, fn, &src);
+  else (void)q_check(capability, year0, year1, 1, fn);
+#endif
+}
+
+void EnsembleCore::sobol_begin(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                               int nspecs, int k, int n_base, const unsigned char *use, const char *fn) {
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)year0; (void)year1; (void)specs; (void)nspecs; (void)k; (void)n_base; (void)use;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  const std::string f(fn);
+  if (k < 1 || k > HX_SOBOL_MAX_FACTORS) throw std::runtime_error(f + ": k must lie in 1..16");
+  if (n_base < 1 || (long long)n_base * (long long)(k + 2) > (long long)n_)
+    throw std::runtime_error(f + ": n_base * (k + 2) must lie in 1..n_members");
+  const double *src = nullptr;
+  int iy0 = 0, ny = nspecs;
+  if (specs) {
+    metric_check(capability, specs, nspecs, fn, &src);
+    sync();
+    src = metric_block(src, specs, nspecs);
+  } else {
+    src = q_check(capability, year0, year1, 1, fn);
+    sync();
+    iy0 = year0 - scen_.start; ny = year1 - year0 + 1;
+  }
+  const int nchunks = hx_sobol_chunks(n_base);
+  const size_t words = SobBuf(nullptr, k, n_base, ny, nchunks).words;
+  if (words > sobol_cap_) {
+    if (d_sobol_) (void)hipFree(d_sobol_);
+    d_sobol_ = nullptr; sobol_cap_ = 0;
+    check(hipMalloc(&d_sobol_, 8 * words), "hipMalloc sobol");
+    sobol_cap_ = words;
+  }
+  SobBuf b(d_sobol_, k, n_base, ny, nchunks);
+  check(hipMemsetAsync(b.st, 0, 8 * 2 * (size_t)ny, stream_), "sobol state");
+  if (use) check(hipMemcpyAsync(b.use, use, (size_t)n_base, hipMemcpyHostToDevice, stream_), "sobol use");
+  check(hx_launch_sobol_prepare(d_lane_of_member_, npad_, k, n_base, use ? b.use : nullptr, b.tab, b.flag, stream_),
+        "sobol prepare kernel");
+  check(hx_launch_sobol_part(src, npad_, iy0, ny, b.tab, n_base, k, b.flag, b.st, b.on, stream_),
+        "sobol participation kernel");
+  check(hipStreamSynchronize(stream_), "sobol sync");   // (use is the caller's until here)
+  sob_src_ = src; sob_iy0_ = iy0; sob_ny_ = ny; sob_k_ = k; sob_nb_ = n_base;
+#endif
+}
+
+// the sum pass over the block sobol_begin prepared -> shift_host[ny], sums_host[ny][4 + 4 k], n_part_host[ny]
+void EnsembleCore::sobol_finish(double *shift_host, double *sums_host, long long *n_part_host) {
+#ifdef HX_HOST_EMULATION
+  (void)shift_host; (void)sums_host; (void)n_part_host;
+  throw std::runtime_error(std::string("hx_ensemble_sobol") + kEmulRefusal);
+#else
+  if (!sob_src_) throw std::runtime_error("sobol sums without sobol_begin");
+  const int ny = sob_ny_, k = sob_k_, nb = sob_nb_;
+  SobBuf b(d_sobol_, k, nb, ny, hx_sobol_chunks(nb));
+  const size_t nc = 4 + 4 * (size_t)k;
+  check(hx_launch_sobol_sums(sob_src_, npad_, sob_iy0_, ny, b.tab, nb, k, b.st, b.on, b.part, b.out, b.shift,
+                             b.npart, stream_), "sobol kernel");
+  check(hipMemcpyAsync(sums_host, b.out, 8 * (size_t)ny * nc, hipMemcpyDeviceToHost, stream_), "sobol fetch");
+  check(hipMemcpyAsync(shift_host, b.shift, 8 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "sobol fetch");
+  check(hipMemcpyAsync(n_part_host, b.npart, 8 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "sobol fetch");
+  check(hipStreamSynchronize(stream_), "sobol sync");
+  sob_src_ = nullptr;
 #endif
 }
 

@@ -236,6 +236,18 @@ class EnsembleCore {
   void comom_begin(const std::string &cap_a, int a0, int a1, const std::string *cap_b, int b0, int b1,
                    const unsigned long long *q, unsigned long long *st_host);
   void comom_finish(const double *shift_host, double *sums_host, double *cross_host);
+  // Sobol sums of a Saltelli design (hx_ensemble_sobol; specs != nullptr: hx_metric_sobol over the
+  // metric block), one shard only: a group's k + 2 consecutive members must all live on this core.
+  // sobol_check is the validation alone (fn is named in every message; the host-emulation build
+  // refuses here); sobol_begin validates, turns the lane order into the group-major lane table with
+  // use[n_base] (nullptr: every group) and reduces every row's participation, min key and count on
+  // the device; sobol_finish runs the sum pass and returns shift_host[rows], sums_host[rows][4 + 4 k]
+  // and n_part_host[rows].  No prepare(), no spinup, not dirtied.
+  void sobol_check(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                   const char *fn);
+  void sobol_begin(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                   int k, int n_base, const unsigned char *use, const char *fn);
+  void sobol_finish(double *shift_host, double *sums_host, long long *n_part_host);
   // ---- held and derived per-member series (hx_series_define in hector_amd.h) ----------------------
   void series_define(const std::string &name, const std::string &a, const hx_series_op &op);
   void series_drop(const std::string &name);
@@ -412,6 +424,10 @@ class EnsembleCore {
   const double *co_a_ = nullptr, *co_b_ = nullptr;   // the windows comom_begin prepared for comom_finish
   int co_ia0_ = 0, co_ib0_ = 0, co_na_ = 0, co_nb_ = 0;
   bool co_sym_ = false;
+  unsigned long long *d_sobol_ = nullptr;     // scratch of the Sobol verbs (SobBuf in ensemble_core.cpp)
+  size_t sobol_cap_ = 0;
+  const double *sob_src_ = nullptr;           // the block sobol_begin prepared for sobol_finish
+  int sob_iy0_ = 0, sob_ny_ = 0, sob_k_ = 0, sob_nb_ = 0;
   void mom_begin_block(const double *src, int iy0, int ny, const unsigned long long *q, const double *pred,
                        int npred, const double *c, unsigned long long *st_host);
   int metric_check(const std::string &capability, const hx_metric *specs, int nspecs, const char *fn,

@@ -1215,6 +1215,265 @@ hipError_t hx_launch_moments(const double *var, int n, int npad, int iy0, int nr
 }
 
 // ===========================================================================
+// Variance-based (Sobol) sensitivity sums from a Saltelli design (hx_ensemble_sobol, hx_metric_sobol
+// in hector_amd.h define the sums).  The estimators compare members in matched groups -- member A_j
+// with B_j and AB_i,j, k + 2 consecutive members -- and members sit in cost-sorted lanes, so a
+// group's values are gathered 8-byte loads from a row of npad doubles.  Four steps:
+//   hx_sobol_prepare_kernel  lane-local: lane_of_member -> the group-major lane table
+//                            tab[k + 2][n_base] (the index loads of the passes are coalesced) and the
+//                            groups' use flags; a lane outside 0..npad-1 switches its group off
+//   hx_sobol_part_kernel     pass 1, one workgroup per (group chunk, row): a group takes part in a row if it is
+//                            in use and none of its k + 2 values is NaN -> on[row][n_base]; the
+//                            smallest x_A or x_B of the participants as an integer key and their
+//                            count, by integer atomics (as hx_q_minmax_kernel)
+//   hx_sobol_kernel<TF>      pass 2, one workgroup per (group chunk, row, factor tile): one lane per group per
+//                            batch, the 2 + TF gathered loads of every group of the batch in flight
+//                            before the arithmetic; 4 + 4 TF private accumulators, all terms >= 0.
+//                            A tile re-reads A and B from the cache; tile 0 writes the four A / B sums
+//   hx_mom_reduce_kernel     the chunks' partials in ascending order; hx_sobol_finish_kernel turns
+//                            the rows' records into shift and n_part
+// No floating atomics: a fixed shuffle tree per wavefront, the four wavefronts added in order, one
+// partial per (row, chunk) -- the same bits from call to call for one lane order.
+// ===========================================================================
+#define HXSB_BLOCK 256
+#define HXSB_PER 4                            // groups of a row per lane
+#define HXSB_CHUNK (HXSB_BLOCK * HXSB_PER)    // groups of a row per workgroup
+struct HxSobRow { hxq_u64 nkmin, cnt; };      // ~(min key of x_A, x_B), groups taking part
+
+// Workgroups whose linear ids agree modulo 8 share an XCD and its L2 (a speed matter only).  A
+// chunk's gathers touch cache lines all over its row, so the chunks of one row are given ids that
+// agree modulo 8: the row comes into ONE L2 once, not into each of them.  The grid is 8 nchunks
+// ceil(nrows / 8) workgroups; -> false for the workgroups past the last row.
+#define HXSB_XCDS 8
+__device__ __forceinline__ bool hxsb_place(int nchunks, int nrows, int *y, int *chunk) {
+  const int id = (int)blockIdx.x, slot = id / HXSB_XCDS;
+  *y = (slot / nchunks) * HXSB_XCDS + id % HXSB_XCDS;
+  *chunk = slot % nchunks;
+  return *y < nrows;
+}
+__host__ inline unsigned hxsb_grid(int nchunks, int nrows) {
+  return (unsigned)(HXSB_XCDS * nchunks * ((nrows + HXSB_XCDS - 1) / HXSB_XCDS));
+}
+
+__device__ __forceinline__ double hxsb_unkey(hxq_u64 key) {
+  const hxq_u64 b = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
+  return __longlong_as_double((long long)b);
+}
+
+__global__ __launch_bounds__(256) void hx_sobol_prepare_kernel(const int *__restrict__ lane_of_member, int npad,
+                                                               int k, int nb,
+                                                               const unsigned char *__restrict__ use,
+                                                               int *__restrict__ tab,
+                                                               unsigned char *__restrict__ flag) {
+  const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (j >= nb) return;
+  bool ok = use ? use[j] != 0 : true;
+  for (int r = 0; r < k + 2; ++r) {
+    int lane = lane_of_member[(size_t)j * (size_t)(k + 2) + (size_t)r];
+    if (lane < 0 || lane >= npad) { lane = 0; ok = false; }   // (every table entry is a lane that may be read)
+    tab[(size_t)r * (size_t)nb + (size_t)j] = lane;
+  }
+  flag[j] = ok ? 1 : 0;
+}
+
+// st[row] must be zero on entry (the min key is kept complemented so that zero is the identity of max)
+__global__ __launch_bounds__(HXSB_BLOCK) void hx_sobol_part_kernel(const double *__restrict__ var, int npad,
+                                                                   int iy0, const int *__restrict__ tab, int nb,
+                                                                   int k, const unsigned char *__restrict__ flag,
+                                                                   int nchunks, int nrows, HxSobRow *st,
+                                                                   unsigned char *__restrict__ on) {
+  int y, chunk;
+  if (!hxsb_place(nchunks, nrows, &y, &chunk)) return;   // (the same for the whole workgroup)
+  const double *row = var + (size_t)(iy0 + y) * npad;
+  const int beg = chunk * HXSB_CHUNK, end = min(beg + HXSB_CHUNK, nb);
+  hxq_u64 nkmin = 0, cnt = 0;
+  // the lane's HXSB_PER groups side by side, every load unconditional (a group past the end reads the
+  // chunk's last group and is left out): A and B, then the factors four at a time -- 4 HXSB_PER
+  // gathered loads in flight
+  const int i0 = beg + (int)threadIdx.x;
+  int j[HXSB_PER];
+  double xa[HXSB_PER], xb[HXSB_PER];
+  bool ok[HXSB_PER];
+#pragma unroll
+  for (int b = 0; b < HXSB_PER; ++b) {
+    j[b] = min(i0 + b * HXSB_BLOCK, end - 1);
+    xa[b] = row[tab[j[b]]];
+    xb[b] = row[tab[(size_t)nb + j[b]]];
+  }
+#pragma unroll
+  for (int b = 0; b < HXSB_PER; ++b)
+    ok[b] = (i0 + b * HXSB_BLOCK < end) & (flag[j[b]] != 0) & (xa[b] == xa[b]) & (xb[b] == xb[b]);
+  for (int r0 = 2; r0 < k + 2; r0 += 4) {
+    double v[4 * HXSB_PER];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t base = (size_t)min(r0 + u, k + 1) * (size_t)nb;
+#pragma unroll
+      for (int b = 0; b < HXSB_PER; ++b) v[u * HXSB_PER + b] = row[tab[base + j[b]]];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int b = 0; b < HXSB_PER; ++b) ok[b] = ok[b] & (v[u * HXSB_PER + b] == v[u * HXSB_PER + b]);
+  }
+#pragma unroll
+  for (int b = 0; b < HXSB_PER; ++b) {
+    if (i0 + b * HXSB_BLOCK < end) on[(size_t)y * (size_t)nb + j[b]] = ok[b] ? 1 : 0;
+    if (ok[b]) {
+      nkmin = max(nkmin, max(~hxq_key(xa[b]), ~hxq_key(xb[b])));
+      ++cnt;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    nkmin = max(nkmin, __shfl_down(nkmin, off, 64));
+    cnt += __shfl_down(cnt, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && cnt) {
+    HxSobRow *o = st + y;
+    atomicMax(&o->nkmin, nkmin); atomicAdd(&o->cnt, cnt);
+  }
+}
+
+// part[(row * nchunks + chunk) * (4 + 4 k) + ...] = SA1, SA2, SB1, SB2, then T_i, TT_i, F_i, FF_i of
+// the chunk; the workgroup (chunk, row, tile) writes the columns of the factors tile * TF ..
+template <int TF>
+__global__ __launch_bounds__(HXSB_BLOCK) void hx_sobol_kernel(const double *__restrict__ var, int npad, int iy0,
+                                                              const int *__restrict__ tab, int nb, int k,
+                                                              const HxSobRow *__restrict__ st,
+                                                              const unsigned char *__restrict__ on,
+                                                              int nchunks, int nrows, double *__restrict__ part) {
+  constexpr int NCB = 4 + 4 * TF;
+  constexpr int B = TF <= 4 ? HXSB_PER : HXSB_PER / 2;   // groups of a lane in flight at once
+  static_assert(HXSB_BLOCK == 256, "the combine below adds four wavefronts in a fixed order");
+  __shared__ double red[HXSB_BLOCK / 64][NCB];
+  const int tid = (int)threadIdx.x;
+  int y, chunk;
+  if (!hxsb_place(nchunks, nrows, &y, &chunk)) return;   // (the same for the whole workgroup: no barrier is skipped by a part of it)
+  const int f0 = (int)blockIdx.y * TF, nf = min(TF, k - f0);
+  const double *row = var + (size_t)(iy0 + y) * npad;
+  const unsigned char *onrow = on + (size_t)y * (size_t)nb;
+  const int beg = chunk * HXSB_CHUNK, end = min(beg + HXSB_CHUNK, nb);
+  const double c = st[y].cnt ? hxsb_unkey(~st[y].nkmin) : 0.0;   // (nobody takes part: no term uses it)
+  double acc[NCB];
+#pragma unroll
+  for (int a = 0; a < NCB; ++a) acc[a] = 0.0;
+#pragma unroll 1
+  for (int j0 = 0; j0 < HXSB_PER; j0 += B) {
+    const int i0 = beg + j0 * HXSB_BLOCK + tid;
+    if (i0 - tid >= end) break;   // (the same for the whole workgroup)
+    double xa[B], xb[B], xf[TF * B];
+    int la[B], lb[B], lf[TF * B];
+    unsigned char o[B];
+    bool p[B];
+    // every load is unconditional, the table's first, then the gathers: a group past the end reads
+    // the chunk's last group and is off, a factor past the tile's last reads that one again (its
+    // accumulators are not written)
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      const int j = min(i0 + b * HXSB_BLOCK, end - 1);
+      o[b] = onrow[j];
+      la[b] = tab[j];
+      lb[b] = tab[(size_t)nb + j];
+#pragma unroll
+      for (int f = 0; f < TF; ++f) lf[f * B + b] = tab[(size_t)(2 + f0 + min(f, nf - 1)) * (size_t)nb + j];
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      xa[b] = row[la[b]];
+      xb[b] = row[lb[b]];
+#pragma unroll
+      for (int f = 0; f < TF; ++f) xf[f * B + b] = row[lf[f * B + b]];
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      p[b] = (i0 + b * HXSB_BLOCK < end) & (o[b] != 0);
+      const double dA = p[b] ? xa[b] - c : 0.0, dB = p[b] ? xb[b] - c : 0.0;
+      acc[0] += dA;
+      acc[1] += dA * dA;
+      acc[2] += dB;
+      acc[3] += dB * dB;
+#pragma unroll
+      for (int f = 0; f < TF; ++f) {
+        const double e = p[b] ? xa[b] - xf[f * B + b] : 0.0, g = p[b] ? xb[b] - xf[f * B + b] : 0.0;
+        const double t = e * e, u = g * g;
+        acc[4 + 4 * f] += t;
+        acc[5 + 4 * f] += t * t;
+        acc[6 + 4 * f] += u;
+        acc[7 + 4 * f] += u * u;
+      }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NCB; ++a) {
+    double v = acc[a];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((tid & 63) == 0) red[tid >> 6][a] = v;
+  }
+  __syncthreads();
+  if (tid < NCB) {
+    const int f = (tid - 4) >> 2;
+    const bool mine = tid < 4 ? blockIdx.y == 0 : f < nf;
+    const int col = tid < 4 ? tid : 4 + 4 * (f0 + f) + ((tid - 4) & 3);
+    if (mine)
+      part[((size_t)y * nchunks + chunk) * (size_t)(4 + 4 * k) + col] =
+          ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+  }
+}
+
+__global__ __launch_bounds__(256) void hx_sobol_finish_kernel(const HxSobRow *__restrict__ st, int nrows,
+                                                              double *__restrict__ shift,
+                                                              long long *__restrict__ npart) {
+  const int y = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (y >= nrows) return;
+  shift[y] = st[y].cnt ? hxsb_unkey(~st[y].nkmin) : __builtin_nan("");
+  npart[y] = (long long)st[y].cnt;
+}
+
+int hx_sobol_chunks(int nb) { return (nb + HXSB_CHUNK - 1) / HXSB_CHUNK; }
+hipError_t hx_launch_sobol_prepare(const int *lane_of_member, int npad, int k, int nb, const unsigned char *use,
+                                   int *tab, unsigned char *flag, hipStream_t st) {
+  hipLaunchKernelGGL(hx_sobol_prepare_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, lane_of_member, npad, k, nb,
+                     use, tab, flag);
+  return hipGetLastError();
+}
+// pass 1.  st: [nrows][2] zeroed; on: [nrows][nb] bytes
+hipError_t hx_launch_sobol_part(const double *var, int npad, int iy0, int nrows, const int *tab, int nb, int k,
+                                const unsigned char *flag, void *st, unsigned char *on, hipStream_t stream) {
+  if (k < 1 || k > HX_SOBOL_MAX_FACTORS || nb < 1 || nrows < 1) return hipErrorInvalidValue;
+  const int nchunks = hx_sobol_chunks(nb);
+  hipLaunchKernelGGL(hx_sobol_part_kernel, dim3(hxsb_grid(nchunks, nrows)), dim3(HXSB_BLOCK), 0, stream, var, npad,
+                     iy0, tab, nb, k, flag, nchunks, nrows, static_cast<HxSobRow *>(st), on);
+  return hipGetLastError();
+}
+// pass 2 over what pass 1 left.  part: [nrows][hx_sobol_chunks(nb)][4 + 4 k] scratch; sums: [nrows][4 + 4 k];
+// shift, npart: [nrows]
+hipError_t hx_launch_sobol_sums(const double *var, int npad, int iy0, int nrows, const int *tab, int nb, int k,
+                                const void *st, const unsigned char *on, double *part, double *sums, double *shift,
+                                long long *npart, hipStream_t stream) {
+  if (k < 1 || k > HX_SOBOL_MAX_FACTORS || nb < 1 || nrows < 1) return hipErrorInvalidValue;
+  const int nchunks = hx_sobol_chunks(nb), nc = 4 + 4 * k;
+  const HxSobRow *rec = static_cast<const HxSobRow *>(st);
+  if (k <= 4)
+    hipLaunchKernelGGL(hx_sobol_kernel<4>, dim3(hxsb_grid(nchunks, nrows), 1), dim3(HXSB_BLOCK), 0, stream, var,
+                       npad, iy0, tab, nb, k, rec, on, nchunks, nrows, part);
+  else
+    hipLaunchKernelGGL(hx_sobol_kernel<8>, dim3(hxsb_grid(nchunks, nrows), (k + 7) / 8), dim3(HXSB_BLOCK), 0, stream,
+                       var, npad, iy0, tab, nb, k, rec, on, nchunks, nrows, part);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  const int total = nrows * nc;
+  hipLaunchKernelGGL(hx_mom_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, part, nchunks, nc, total,
+                     sums);
+  err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(hx_sobol_finish_kernel, dim3((nrows + 255) / 256), dim3(256), 0, stream, rec, nrows, shift,
+                     npart);
+  return hipGetLastError();
+}
+
+// ===========================================================================
 // Year-by-year co-moments of two windows of rows (hx_ensemble_comoments in hector_amd.h defines the
 // sums): cross[a][b] = sum over the members of (q d_a) d_b, a Gram matrix contracted over the member
 // axis on the fp64 matrix pipe.  Four steps:

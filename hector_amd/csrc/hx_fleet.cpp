@@ -669,6 +669,33 @@ void Fleet::moments(const std::string &cap, int year0, int year1, const hx_metri
   }
 }
 
+void Fleet::sobol(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs, int k,
+                  int n_base, const unsigned char *use_group, double *shift, double *sums, long long *n_part) {
+  check_poison();
+  const char *fn = specs ? "hx_metric_sobol" : "hx_ensemble_sobol";
+  const std::string f(fn);
+  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
+    throw std::runtime_error(f + ": nspecs must lie in 1..32");
+  if (k < 1 || k > HX_SOBOL_MAX_FACTORS)
+    throw std::runtime_error(f + ": k must lie in 1..16");
+  if (n_base < 1) throw std::runtime_error(f + ": n_base must be at least 1");
+  if ((long long)n_base * (long long)(k + 2) > (long long)n_)
+    throw std::runtime_error(f + ": n_base * (k + 2) = " + std::to_string((long long)n_base * (k + 2)) +
+                             " exceeds the " + std::to_string(n_) + " members of the core");
+  refuse_processes(fn, "Sobol sums");
+  // the first shard answers for capability, dates and a core that has not run (the host-emulation
+  // build refuses by name there); k and n_base were held to the whole core above
+  Shard &s = shards_.front();
+  use(s);
+  s.core->sobol_check(cap, year0, year1, specs, nspecs, fn);
+  if (shards_.size() > 1)
+    throw std::runtime_error(f + ": this core has several shards (" + std::to_string(shards_.size()) +
+                             "): the members of a group lie on different GPUs under the fleet's split, "
+                             "which the Sobol verbs do not serve");
+  s.core->sobol_begin(cap, year0, year1, specs, nspecs, k, n_base, use_group, fn);
+  s.core->sobol_finish(shift, sums, n_part);
+}
+
 void Fleet::comoments(const std::string &cap_a, int a0, int a1, const char *cap_b, int b0, int b1,
                       const double *weights, double *shift_a, double *sums_a, double *shift_b, double *sums_b,
                       double *cross, unsigned long long *wsum, long long *n_part) {

@@ -39,3 +39,23 @@ def biome4(n, offset=0, seed=SEED, wf_base=1.0):
     q10 = [1.0 + 2.0 * uniform01(idx, 10 + b, seed) for b in range(4)]
     wf = [np.full(n, wf_base * (1 + 0.5 * b)) for b in range(4)]
     return S, q10, wf
+
+
+def saltelli(n_base, k, offset=0, seed=SEED):
+    """A Saltelli (A, B, AB_i) design for variance-based sensitivity indices -> U[(k + 2) * n_base, k]
+    in [0, 1), in the interleaved layout Core.sobol reads: the group of base point j is the k + 2
+    consecutive rows j * (k + 2) + r, with r = 0 the point A_j, r = 1 the point B_j and r = 2 + i the
+    point A_j with column i taken from B_j.  Counter-based like ecs_q10: base point offset + j has
+    A[:, i] = uniform01(offset + j, i) and B[:, i] = uniform01(offset + j, k + i), so a larger call
+    or another offset gives the same rows.  The caller maps the columns to parameter ranges."""
+    n_base, k = int(n_base), int(k)
+    if n_base < 1 or k < 1:
+        raise ValueError("saltelli: n_base and k must be at least 1")
+    idx = np.arange(offset, offset + n_base, dtype=np.uint64)
+    A = np.stack([uniform01(idx, i, seed) for i in range(k)], axis=1)
+    B = np.stack([uniform01(idx, k + i, seed) for i in range(k)], axis=1)
+    U = np.repeat(A[:, None, :], k + 2, axis=1)          # [n_base, k + 2, k]
+    U[:, 1, :] = B
+    for i in range(k):
+        U[:, 2 + i, i] = B[:, i]
+    return U.reshape(n_base * (k + 2), k)

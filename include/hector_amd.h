@@ -534,6 +534,60 @@ int hx_metric_moments(hx_core *core, const char *capability, const hx_metric *sp
                       const double *weights, const double *predictors, int npred, double *shift,
                       double *sums, unsigned long long *wsum, long long *n_part);
 
+/* Variance-based (Sobol) sensitivity sums of every recorded year from a Saltelli design: what the
+ * first-order and total indices of an output with respect to k factors need, year by year, without
+ * the trajectories leaving the device.  No counterpart in the reference.
+ * The design (hector_amd.ensemble.saltelli lays it out) is n_base groups of k + 2 CONSECUTIVE members:
+ * member j(k+2) ran the parameters A_j, member j(k+2)+1 ran B_j, and member j(k+2)+2+i ran A_j with
+ * factor i taken from B_j.  1 <= k <= 16, n_base >= 1, n_base (k + 2) <= n_members; members past
+ * n_base (k + 2) are ignored.  use[n_base] or NULL.
+ * Group j, row y: x_A, x_B and x_i (i < k) are the row's values of those members.  A group takes
+ * part in a row if use is NULL or use[j] != 0, and none of its k + 2 values is NaN: a NaN anywhere
+ * removes the whole group from that row.
+ * Shift: c_y = the smallest x_A or x_B over the participating groups (an exact value some member
+ * has).  Every difference below is ONE IEEE subtraction -- that rounding is part of the definition
+ * -- and everything else is products of the differences, so every term is >= 0.  Over the
+ * participating groups of the row:
+ *   dA = x_A - c_y;  dB = x_B - c_y
+ *   SA1 = sum dA     SA2 = sum dA dA     SB1 = sum dB     SB2 = sum dB dB
+ *   e = x_A - x_i;  t = e e;   T_i = sum t     TT_i = sum t t
+ *   g = x_B - x_i;  u = g g;   F_i = sum u     FF_i = sum u u
+ *   shift[y] = c_y;  n_part[y] = participating groups;
+ *   sums[y * (4 + 4 k) + ...] = SA1, SA2, SB1, SB2, then T_i, TT_i, F_i, FF_i for i = 0 .. k - 1.
+ * A row in which no group takes part: shift NaN, sums 0, n_part 0.  Every sum, in any order, is
+ * within (n_part + 8) 2^-53 of the exact sum of the terms as defined, relatively.  In double, with
+ * n = n_part[y]:
+ *   m = (SA1 + SB1) / (2 n)      mean = c_y + m
+ *   V = (SA2 + SB2) / (2 n) - m m      (the population variance of the 2 n pooled A and B values)
+ *   total_i = T_i / (2 n V)            (Jansen's estimator of the total index)
+ *   first_i = 1 - F_i / (2 n V)        (Jansen's form of the first-order index)
+ *   total_se_i = sqrt((TT_i / n - (T_i / n)^2) / n) / (2 V);  first_se_i the same from F_i, FF_i
+ * The two standard errors are those of the numerators T_i / (2 n) and F_i / (2 n) with V taken as
+ * known: the sampling error of V itself is not in them.  Where V == 0 or n == 0 the indices and
+ * their standard errors are undefined.
+ * Reproducibility: n_part and c_y are exact under any lane order.  The floating sums are NOT
+ * bit-identical across lane orders; they ARE bit-identical from call to call for the same core and
+ * lane order: no floating atomics, a fixed reduction tree inside a workgroup, workgroup partials
+ * added in ascending chunk order.
+ * Cost: one lane-local kernel turns the lane order into a group-major lane table; one pass of
+ * gathered 8-byte loads over every row for participation, the minimum and the count, and one for
+ * all sums (k > 8: two, A and B re-read from the cache); 4 + 4 k (+ 2) values a row back to the host.
+ * The core is not prepared, spun up or dirtied.
+ * Errors (every message names the function; a refused call changes nothing): those of
+ * hx_ensemble_moments for capability and dates; k outside 1..16; n_base < 1 or n_base (k + 2) >
+ * n_members; a core that has not run; a core of several shards (a group's members lie on different
+ * GPUs under the fleet's split: not served); a communicator of several processes.  Not available in
+ * the host-emulation build of the test suite. */
+#define HX_SOBOL_MAX_FACTORS 16
+int hx_ensemble_sobol(hx_core *core, const char *capability, int year0, int year1, int k, int n_base,
+                      const unsigned char *use, double *shift, double *sums, long long *n_part);
+
+/* The same over metrics: row s is metric s of every member (as hx_member_metrics defines it,
+ * computed on the device; the metric block does not reach the host), 1 <= nspecs <= 32; shift[s],
+ * sums[s * (4 + 4 k) + ...], n_part[s]. */
+int hx_metric_sobol(hx_core *core, const char *capability, const hx_metric *specs, int nspecs, int k,
+                    int n_base, const unsigned char *use, double *shift, double *sums, long long *n_part);
+
 /* ---- Two series of the same member: regress or sample one output on another ----------------------
  * A pair-metric specification reduces the window year0..year1 of TWO series of a member, a (reported
  * / dependent) and b (condition / independent), to one double per member: TCRE (the slope of
