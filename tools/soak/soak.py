@@ -99,7 +99,7 @@ def diagnostics(gpu, argv):
     import hector_amd
     import oracle_binding
     from test_random_sweep import RANGES, ORACLE_FIELD
-    from test_diagnostics import KERNEL_VARS, DERIVED_VARS, HOST_VARS, ORACLE_NAME
+    from outputs_matrix import ALL, ORACLE_NAME   # (the set tests/test_*outputs_matrix.py hold per flavour)
     kw = dict(device=0) if gpu else dict(lib_path=EMUL, allow_emulation=True)
     n = 256 if gpu else 6
     step = 8 if gpu else 1
@@ -113,11 +113,10 @@ def diagnostics(gpu, argv):
         for k, (lo, hi, unit) in RANGES.items():
             c.setvar(k, vals[k], unit)
         c.setvar("lo_warming_ratio", lo_ratio)
-        allv = KERNEL_VARS + DERIVED_VARS
-        c.set_outputs(allv + ["RF_tot", "RF_CO2", "global_tas", "CO2_concentration", "land_tas", "sst"])
+        c.set_outputs(ALL)
         c.run(2300)
         st = c.status()
-        got = {v: c.fetchvars(v, (1746, 2300)) for v in allv + HOST_VARS + ["land_tas", "sst", "CO2_concentration"]}
+        got = {v: c.fetchvars(v, (1746, 2300)) for v in ALL}
         o = oracle_binding.Oracle(path)
         for i in range(0, n, step):
             p = o.default_params(); p.lo_warming_ratio = lo_ratio[i]
