@@ -2,7 +2,7 @@
 carbon-cycle / climate year loop.  HIP kernels + C ABI in
 hector_amd/csrc; this package only binds them."""
 from ._lib import HectorAmdError, DEFAULT_SCENARIO, DEFAULT_LIB  # noqa: F401
-from .core import (Core, Metric, PairMetric, Moments, CoMoments, Sobol, whiten, newcore, run, reset, shutdown, setvar, fetchvars,  # noqa: F401
+from .core import (Core, Metric, PairMetric, Moments, GroupedMoments, CoMoments, Sobol, whiten, newcore, run, reset, shutdown, setvar, fetchvars,  # noqa: F401
                    split_biome, get_tracking_data, create_biome, rename_biome,
                    get_biome_inits, sendmessage, GETDATA, SETDATA, isactive, startdate,
                    enddate, getdate, getname, get_biome_list, getunits, getfxn, runscenario)

@@ -186,6 +186,13 @@ def _declare(lib):
                                 c.POINTER(c.c_ulonglong), c.POINTER(c.c_longlong)],
         "hx_metric_moments": [P, c.c_char_p, c.c_void_p, c.c_int, dp, dp, c.c_int, dp, dp,
                               c.POINTER(c.c_ulonglong), c.POINTER(c.c_longlong)],
+        "hx_group_quantiles": [P, c.c_char_p, c.c_int, c.c_int, c.c_void_p, c.c_int, c.POINTER(c.c_int), c.c_int,
+                               dp, dp, c.c_int, dp, c.POINTER(c.c_longlong)],
+        "hx_group_probabilities": [P, c.c_char_p, c.c_int, c.c_int, c.c_void_p, c.c_int, c.POINTER(c.c_int),
+                                   c.c_int, dp, dp, c.c_int, dp, c.POINTER(c.c_ulonglong),
+                                   c.POINTER(c.c_longlong)],
+        "hx_group_moments": [P, c.c_char_p, c.c_int, c.c_int, c.c_void_p, c.c_int, c.POINTER(c.c_int), c.c_int,
+                             dp, dp, c.c_int, dp, dp, dp, c.POINTER(c.c_ulonglong), c.POINTER(c.c_longlong)],
         "hx_member_pair_metrics": [P, c.c_char_p, c.c_char_p, dp, c.c_int, c.c_int, c.c_void_p, c.c_int, dp],
         "hx_pair_metric_quantiles": [P, c.c_char_p, c.c_char_p, dp, c.c_int, c.c_int, c.c_void_p, c.c_int, dp, dp,
                                      c.c_int, dp, c.POINTER(c.c_longlong)],
@@ -238,6 +245,7 @@ ABI_SYMBOLS = ["hx_backend", "hx_build_info", "hx_last_error", "hx_newcore", "hx
                "hx_member_score", "hx_member_score_whitened", "hx_member_project", "hx_ensemble_quantiles", "hx_member_metrics", "hx_metric_quantiles",
                "hx_ensemble_probabilities", "hx_metric_probabilities",
                "hx_ensemble_moments", "hx_metric_moments", "hx_ensemble_comoments",
+               "hx_group_quantiles", "hx_group_probabilities", "hx_group_moments",
                "hx_member_pair_metrics", "hx_pair_metric_quantiles", "hx_pair_metric_probabilities",
                "hx_pair_metric_moments", "hx_ensemble_sobol", "hx_metric_sobol",
                "hx_series_define", "hx_series_drop", "hx_series_list"]

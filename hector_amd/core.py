@@ -246,6 +246,110 @@ class Moments:
         return "Moments(rows=%d, against=%r)" % (self.shift.size, self.names)
 
 
+GROUP_MAX = 16   # HX_GROUP_MAX
+
+
+class GroupedMoments:
+    """What hx_group_moments returns (include/hector_amd.h): the raw fields of Moments with a leading
+    group axis -- shift[G, R], sums[G, R, 2 + 3 K], wsum[G, R] (uint64), n_part[G, R], pshift[G, K] --
+    and the partition of the rows' variance over the groups.  gm[g] is the Moments of group g; it
+    carries the group's pshift, integer weights (0 outside the group) and the predictors, so that
+    gm[g].src() works.  Over the groups that take part in a row (W_g > 0), all in float64:
+      weight_share[G, R] = W_g / sum_g W_g
+      pooled_mean[R] = sum_g share_g mean_g
+      between[R] = sum_g share_g (mean_g - pooled_mean)**2      (the variance of the group means)
+      within[R]  = sum_g share_g var_g                          (the mean of the group variances)
+      pooled_var[R] = between + within        (the law of total variance: the variance of the union)
+      eta2[R] = between / (between + within)  (the correlation ratio: with labels = bins of a
+                parameter, the given-data estimate of its first-order sensitivity index)
+    A row nobody takes part in is NaN throughout; eta2 is NaN where the total variance is 0."""
+
+    def __init__(self, shift, sums, wsum, n_part, names=(), pshift=None, q=None, predictors=None, labels=None):
+        self.shift = np.asarray(shift, dtype=np.float64)
+        if self.shift.ndim != 2:
+            raise HectorAmdError("GroupedMoments: shift must be [groups, rows]")
+        g, r = self.shift.shape
+        self.names = list(names)
+        k = len(self.names)
+        self.sums = np.asarray(sums, dtype=np.float64).reshape(g, r, -1)
+        if self.sums.shape[2] != 2 + 3 * k:
+            raise HectorAmdError("GroupedMoments: sums must have 2 + 3 * len(names) columns")
+        self.wsum = np.asarray(wsum, dtype=np.uint64).reshape(g, r)
+        self.n_part = np.asarray(n_part, dtype=np.int64).reshape(g, r)
+        self.pshift = np.zeros((g, k)) if pshift is None else np.asarray(pshift, dtype=np.float64).reshape(g, k)
+        self._q = None if q is None else np.asarray(q, dtype=np.uint64)
+        self._pred = None if predictors is None else np.asarray(predictors, dtype=np.float64).reshape(k, -1)
+        self._labels = None if labels is None else np.asarray(labels)
+
+    @property
+    def n_groups(self):
+        return self.shift.shape[0]
+
+    def __len__(self):
+        return self.n_groups
+
+    def __getitem__(self, g):
+        g = int(g)
+        if not 0 <= g < self.n_groups:
+            raise IndexError("GroupedMoments: group %d of %d" % (g, self.n_groups))
+        q = None
+        if self._q is not None and self._labels is not None:
+            q = np.where(self._labels == g, self._q, np.uint64(0)).astype(np.uint64)
+        return Moments(self.shift[g], self.sums[g], self.wsum[g], self.n_part[g], self.names, self.pshift[g], q,
+                       self._pred)
+
+    def _group_stats(self):
+        """-> share[G, R] (0 where a group takes no part, NaN where nobody does), c[R] = the smallest
+        shift of the row, the group means LESS c and the group variances [G, R] with 0 in place of
+        NaN.  Means relative to c: a row whose participants are all equal has every one exactly 0, so
+        that its between-group variance is exactly 0 whatever the rounding of the shares."""
+        w = self.wsum.astype(np.float64)
+        on = w > 0
+        tot = w.sum(axis=0)
+        tot = np.where(tot > 0, tot, np.nan)
+        wg = np.where(on, w, 1.0)
+        a = self.sums[:, :, 0] / wg
+        c = np.where(on, self.shift, np.inf).min(axis=0)
+        c = np.where(np.isfinite(c), c, np.nan)
+        with np.errstate(invalid="ignore"):
+            dmean = np.where(on, (self.shift - c[None, :]) + a, 0.0)
+        var = np.where(on, self.sums[:, :, 1] / wg - a * a, 0.0)
+        return w / tot[None, :], c, dmean, var
+
+    @property
+    def weight_share(self):
+        return self._group_stats()[0]
+
+    @property
+    def pooled_mean(self):
+        share, c, dmean, _ = self._group_stats()
+        return c + (share * dmean).sum(axis=0)
+
+    @property
+    def between(self):
+        share, _, dmean, _ = self._group_stats()
+        pm = (share * dmean).sum(axis=0)
+        return (share * (dmean - pm[None, :]) ** 2).sum(axis=0)
+
+    @property
+    def within(self):
+        share, _, _, var = self._group_stats()
+        return (share * var).sum(axis=0)
+
+    @property
+    def pooled_var(self):
+        return self.between + self.within
+
+    @property
+    def eta2(self):
+        b, t = self.between, self.pooled_var
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(t > 0, b / np.where(t > 0, t, 1.0), np.nan)
+
+    def __repr__(self):
+        return "GroupedMoments(groups=%d, rows=%d, against=%r)" % (self.shift.shape + (self.names,))
+
+
 SOBOL_MAX_FACTORS = 16   # HX_SOBOL_MAX_FACTORS
 
 
@@ -890,13 +994,61 @@ class Core:
             n, m, b0, b1, out.ctypes.data_as(dp)))
         return out[0] if one else out
 
-    def quantiles(self, var, probs, dates=None, weights=None, counts=False):
+    def _groups(self, groups, what):
+        """groups= of the summary verbs: labels[n_members] (integers, -1 = in no group), or
+        (labels, G); G defaults to max(label) + 1 -> (labels as contiguous int32, G)."""
+        g = None
+        if isinstance(groups, tuple) and len(groups) == 2 and np.ndim(groups[1]) == 0 and np.ndim(groups[0]) > 0:
+            groups, g = groups
+            if isinstance(g, (bool, np.bool_)) or not isinstance(g, (int, np.integer)):
+                raise HectorAmdError("%s: the number of groups must be an integer" % what)
+            g = int(g)
+        lab = np.asarray(groups)
+        if lab.shape != (self.n_members,):
+            raise HectorAmdError("%s: groups must have n_members labels" % what)
+        if lab.dtype == np.bool_ or not np.issubdtype(lab.dtype, np.integer):
+            raise HectorAmdError("%s: the labels of groups must be integers (dtype %s)" % (what, lab.dtype))
+        if g is None:
+            g = int(lab.max()) + 1
+        if not 1 <= g <= GROUP_MAX:
+            raise HectorAmdError("%s: the number of groups must lie in 1..%d (it is %d)" % (what, GROUP_MAX, g))
+        if int(lab.min()) < -1 or int(lab.max()) >= g:
+            bad = int(lab.min()) if int(lab.min()) < -1 else int(lab.max())
+            raise HectorAmdError("%s: label %d lies outside -1..%d" % (what, bad, g - 1))
+        return np.ascontiguousarray(lab.astype(np.int32)), g
+
+    def _group_quantiles(self, what, var, y0, y1, arr, ns, nrows, groups, probs, weights, counts):
+        dp = ctypes.POINTER(ctypes.c_double)
+        lab, g = self._groups(groups, what)
+        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if pr.ndim != 1:
+            raise HectorAmdError("%s: probs must be one-dimensional" % what)
+        w = self._weights(weights, what)
+        out = np.empty((g, nrows, pr.size))
+        npart = np.zeros((g, nrows), dtype=np.int64)
+        self._ck(self._lib.hx_group_quantiles(
+            self._h, var.encode(), y0, y1, ctypes.byref(arr) if arr is not None else None, ns,
+            lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), g, w.ctypes.data_as(dp) if w is not None else None,
+            pr.ctypes.data_as(dp), int(pr.size), out.ctypes.data_as(dp),
+            npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return (out, npart) if counts else out
+
+    def quantiles(self, var, probs, dates=None, weights=None, counts=False, groups=None):
         """Per-year weighted quantiles over every member, on the device (hx_ensemble_quantiles:
         exact inverted-CDF quantiles, numpy's method="inverted_cdf") -> ndarray [n_years, n_probs];
-        counts=True: also the members that took part in every year [n_years]."""
+        counts=True: also the members that took part in every year [n_years].
+        groups: labels[n_members] in 0..G-1 (-1: in no group), or (labels, G) with G <= 16: the
+        quantiles of every group from ONE call (hx_group_quantiles; the weights are quantised over
+        the whole ensemble) -> [G, n_years, n_probs], counts [G, n_years].  Measured
+        (profiles/post_summaries.md, 65 536 members, 556 years, 5 probabilities): 0.46 of the time of
+        the G masked calls at G = 8 and 0.40 at G = 16, but 1.57 times the two masked calls at G = 2,
+        where the grouped select's fixed cost is not yet repaid."""
         dp = ctypes.POINTER(ctypes.c_double)
         y0, y1 = (self.strtdate, self.current_date) if dates is None else \
             (int(min(dates)), int(max(dates)))
+        if groups is not None:
+            return self._group_quantiles("quantiles", var, y0, y1, None, 0, max(y1 - y0 + 1, 0), groups, probs,
+                                         weights, counts)
         pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
         w = None
         if weights is not None:
@@ -942,12 +1094,15 @@ class Core:
                                              out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
         return out
 
-    def metric_quantiles(self, var, specs, probs, weights=None, counts=False):
+    def metric_quantiles(self, var, specs, probs, weights=None, counts=False, groups=None):
         """Weighted quantiles of every metric over the ensemble (hx_metric_quantiles: the metrics
         are computed and selected on the device, definition as quantiles()) -> ndarray
-        [n_specs, n_probs]; counts=True: also the members that took part [n_specs]."""
+        [n_specs, n_probs]; counts=True: also the members that took part [n_specs].  groups: as in
+        quantiles() -> [G, n_specs, n_probs], counts [G, n_specs]."""
         dp = ctypes.POINTER(ctypes.c_double)
         arr, ns = self._metric_array(specs, "metric_quantiles")
+        if groups is not None:
+            return self._group_quantiles("metric_quantiles", var, 0, 0, arr, ns, ns, groups, probs, weights, counts)
         pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
         if pr.ndim != 1:
             raise HectorAmdError("metric_quantiles: probs must be one-dimensional")
@@ -960,37 +1115,60 @@ class Core:
             npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         return (out, npart) if counts else out
 
-    def _probabilities(self, what, call, nrows, edges, weights, counts, sums):
+    def _probabilities(self, what, call, nrows, edges, weights, counts, sums, ngroups=0):
         dp = ctypes.POINTER(ctypes.c_double)
         ed = np.ascontiguousarray(np.atleast_1d(np.asarray(edges, dtype=np.float64)))
         if ed.ndim != 1:
             raise HectorAmdError("%s: edges must be one-dimensional" % what)
         w = self._weights(weights, what)
-        prob = np.empty((nrows, ed.size + 1))
-        qs = np.zeros((nrows, ed.size + 1), dtype=np.uint64)
-        npart = np.zeros(nrows, dtype=np.int64)
+        lead = (ngroups,) if ngroups else ()   # a grouped call: a leading group axis
+        prob = np.empty(lead + (nrows, ed.size + 1))
+        qs = np.zeros(lead + (nrows, ed.size + 1), dtype=np.uint64)
+        npart = np.zeros(lead + (nrows,), dtype=np.int64)
         self._ck(call(w.ctypes.data_as(dp) if w is not None else None, ed.ctypes.data_as(dp), int(ed.size),
                       prob.ctypes.data_as(dp), qs.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
                       npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         res = (prob,) + ((npart,) if counts else ()) + ((qs,) if sums else ())
         return res if len(res) > 1 else prob
 
-    def probabilities(self, var, edges, dates=None, weights=None, counts=False, sums=False):
+    def _group_call(self, fn, var, y0, y1, arr, ns, groups, what):
+        """-> (a call of the grouped ABI function fn with its leading arguments bound, G)."""
+        lab, g = self._groups(groups, what)
+        lp = lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        sp = ctypes.byref(arr) if arr is not None else None
+
+        def call(*a, _keep=(lab, arr)):
+            return fn(self._h, var.encode(), y0, y1, sp, ns, lp, g, *a)
+        return call, g
+
+    def probabilities(self, var, edges, dates=None, weights=None, counts=False, sums=False, groups=None):
         """Per-year weighted probabilities of the classes x < edges[0], edges[0] <= x < edges[1],
         ..., x >= edges[-1] over every member, on the device (hx_ensemble_probabilities: one pass
         over the rows, exact integer sums) -> ndarray [n_years, n_edges + 1]; counts=True: also
-        the members that took part [n_years]; sums=True: also the integer sums (uint64)."""
+        the members that took part [n_years]; sums=True: also the integer sums (uint64).
+        groups: as in quantiles() -- the classes of every group from ONE pass
+        (hx_group_probabilities) -> [G, n_years, n_edges + 1], counts [G, n_years], sums likewise:
+        for one year, the contingency table of (group x class)."""
         y0, y1 = (self.strtdate, self.current_date) if dates is None else \
             (int(min(dates)), int(max(dates)))
+        if groups is not None:
+            call, g = self._group_call(self._lib.hx_group_probabilities, var, y0, y1, None, 0, groups,
+                                       "probabilities")
+            return self._probabilities("probabilities", call, max(y1 - y0 + 1, 0), edges, weights, counts, sums, g)
         return self._probabilities(
             "probabilities",
             lambda *a: self._lib.hx_ensemble_probabilities(self._h, var.encode(), y0, y1, *a),
             max(y1 - y0 + 1, 0), edges, weights, counts, sums)
 
-    def metric_probabilities(self, var, specs, edges, weights=None, counts=False, sums=False):
+    def metric_probabilities(self, var, specs, edges, weights=None, counts=False, sums=False, groups=None):
         """The same classes over metrics (hx_metric_probabilities) -> ndarray
-        [n_specs, n_edges + 1] (+ counts [n_specs], + sums)."""
+        [n_specs, n_edges + 1] (+ counts [n_specs], + sums).  groups: as in probabilities() ->
+        [G, n_specs, n_edges + 1]."""
         arr, ns = self._metric_array(specs, "metric_probabilities")
+        if groups is not None:
+            call, g = self._group_call(self._lib.hx_group_probabilities, var, 0, 0, arr, ns, groups,
+                                       "metric_probabilities")
+            return self._probabilities("metric_probabilities", call, ns, edges, weights, counts, sums, g)
         return self._probabilities(
             "metric_probabilities",
             lambda *a: self._lib.hx_metric_probabilities(self._h, var.encode(), ctypes.byref(arr), ns, *a),
@@ -1122,6 +1300,24 @@ class Core:
                 pshift = pred[:, on].min(axis=1)
         return names, pred, w, q, pshift
 
+    def _group_moments(self, what, var, y0, y1, arr, ns, nrows, groups, weights, against):
+        dp = ctypes.POINTER(ctypes.c_double)
+        call, g = self._group_call(self._lib.hx_group_moments, var, y0, y1, arr, ns, groups, what)
+        lab = self._groups(groups, what)[0]
+        names, pred, w, q, _ = self._against(against, weights, what)
+        k = len(names)
+        shift = np.empty((g, nrows))
+        pshift = np.full((g, k), np.nan)
+        sums = np.zeros((g, nrows, 2 + 3 * k))
+        wsum = np.zeros((g, nrows), dtype=np.uint64)
+        npart = np.zeros((g, nrows), dtype=np.int64)
+        self._ck(call(w.ctypes.data_as(dp) if w is not None else None,
+                      pred.ctypes.data_as(dp) if pred is not None else None, k,
+                      shift.ctypes.data_as(dp), pshift.ctypes.data_as(dp), sums.ctypes.data_as(dp),
+                      wsum.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
+                      npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return GroupedMoments(shift, sums, wsum, npart, names, pshift, q, pred, lab)
+
     def _moments(self, what, call, nrows, weights, against):
         dp = ctypes.POINTER(ctypes.c_double)
         names, pred, w, q, pshift = self._against(against, weights, what)
@@ -1137,22 +1333,32 @@ class Core:
                       npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         return Moments(shift, sums, wsum, npart, names, pshift, q, pred)
 
-    def moments(self, var, dates=None, weights=None, against=None):
+    def moments(self, var, dates=None, weights=None, against=None, groups=None):
         """Per-year weighted mean and variance of `var` over the ensemble and its covariance,
         correlation and regression slope against per-member quantities, on the device
         (hx_ensemble_moments) -> Moments.  against: a list of parameter names (getvar), arrays
         [n_members], (var, Metric) pairs (metrics) or (var_a, b, PairMetric) triples (pair_metrics),
         at most 8.  A member takes part in a year if
-        its weight is not 0, its value is not NaN and all its `against` values are finite."""
+        its weight is not 0, its value is not NaN and all its `against` values are finite.
+        groups: as in quantiles() -- the moments of every group from one call (hx_group_moments) ->
+        GroupedMoments: gm[g] is the Moments of group g, and gm.between / gm.within / gm.eta2
+        partition every year's variance into the spread of the group means and the spread inside
+        the groups."""
         y0, y1 = (self.strtdate, self.current_date) if dates is None else \
             (int(min(dates)), int(max(dates)))
+        if groups is not None:
+            return self._group_moments("moments", var, y0, y1, None, 0, max(y1 - y0 + 1, 0), groups, weights,
+                                       against)
         return self._moments(
             "moments", lambda *a: self._lib.hx_ensemble_moments(self._h, var.encode(), y0, y1, *a),
             max(y1 - y0 + 1, 0), weights, against)
 
-    def metric_moments(self, var, specs, weights=None, against=None):
-        """The same over metrics (hx_metric_moments): one row per specification -> Moments."""
+    def metric_moments(self, var, specs, weights=None, against=None, groups=None):
+        """The same over metrics (hx_metric_moments): one row per specification -> Moments
+        (groups: -> GroupedMoments, as in moments())."""
         arr, ns = self._metric_array(specs, "metric_moments")
+        if groups is not None:
+            return self._group_moments("metric_moments", var, 0, 0, arr, ns, ns, groups, weights, against)
         return self._moments(
             "metric_moments",
             lambda *a: self._lib.hx_metric_moments(self._h, var.encode(), ctypes.byref(arr), ns, *a),

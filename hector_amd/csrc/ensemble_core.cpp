@@ -89,6 +89,23 @@ int hx_mom_chunks(int n);
 hipError_t hx_launch_moments(const double *var, int n, int npad, int iy0, int nrows, const double *qd,
                              const double *e, int npred, const double *shift, double *part, double *out,
                              hipStream_t st);
+hipError_t hx_launch_grp_prepare(const int *lab_mem, int n, int npad, const int *lane_of_member, int *lab_lane,
+                                 hipStream_t st);
+hipError_t hx_launch_gmom_prepare(const unsigned long long *q_mem, const double *pred_mem, const int *lab_mem,
+                                  int npred, int n, int npad, const int *lane_of_member, const double *c,
+                                  unsigned long long *q_lane, double *qd_lane, double *e_lane, int *lab_lane,
+                                  hipStream_t st);
+hipError_t hx_launch_gq_minmax(const double *var, int n, int npad, int iy0, int ny, const unsigned long long *q,
+                               const int *lab, int G, void *st, hipStream_t stream);
+hipError_t hx_launch_gq_hist(const double *var, int n, int npad, int iy0, int ny, const unsigned long long *q,
+                             const int *lab, int G, const int *lo, const unsigned long long *prefix, int np,
+                             unsigned long long *hist, hipStream_t stream);
+hipError_t hx_launch_gbin(const double *var, int n, int npad, int iy0, int nrows, const unsigned long long *q,
+                          const int *lab, int G, const double *edges, int K, unsigned long long *sums,
+                          hipStream_t stream);
+hipError_t hx_launch_gmoments(const double *var, int n, int npad, int iy0, int nrows, const double *qd,
+                              const double *e, const int *lab, int G, int npred, const double *shift,
+                              double *part, double *out, hipStream_t st);
 int hx_sobol_chunks(int nb);
 hipError_t hx_launch_sobol_prepare(const int *lane_of_member, int npad, int k, int nb, const unsigned char *use,
                                    int *tab, unsigned char *flag, hipStream_t st);
@@ -598,6 +615,7 @@ void EnsembleCore::free_device() {
   fr(d_spin_rec_); d_spin_rec_ = nullptr;
   fr(d_score_); fr(d_q_); fr(d_qstate_); fr(d_qhist_); fr(d_metplan_); fr(d_met_); fr(d_bin_);
   fr(d_mom_); d_mom_ = nullptr; mom_cap_ = 0; mom_src_ = nullptr;
+  fr(d_glab_); d_glab_ = nullptr;
   fr(d_comom_); d_comom_ = nullptr; comom_cap_ = 0; co_a_ = nullptr;
   fr(d_sobol_); d_sobol_ = nullptr; sobol_cap_ = 0; sob_src_ = nullptr;
   fr(d_whiten_); d_whiten_ = nullptr; whiten_cap_ = 0;
@@ -3166,7 +3184,7 @@ void EnsembleCore::q_begin_block(const double *src, int iy0, int ny, const unsig
   check(hx_launch_q_minmax(src, n_, npad_, iy0, ny, q ? d_q_ : nullptr, s.st, stream_), "quantile min/max kernel");
   check(hipMemcpyAsync(st_host, s.st, 8 * 4 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "quantile fetch");
   check(hipStreamSynchronize(stream_), "quantile sync");
-  q_src_ = src; q_iy0_ = iy0; q_ny_ = ny; q_np_ = np; q_weighted_ = q != nullptr;
+  q_src_ = src; q_iy0_ = iy0; q_ny_ = ny; q_np_ = np; q_weighted_ = q != nullptr; q_groups_ = 0;
 #endif
 }
 
@@ -3201,13 +3219,18 @@ void EnsembleCore::q_pass(const int *lo, const unsigned long long *prefix, unsig
   throw std::runtime_error("hx_ensemble_quantiles is not available in the host-emulation build");
 #else
   if (!q_src_) throw std::runtime_error("quantile pass without q_begin");
-  QState s(d_qstate_, q_ny_, q_np_);
-  const size_t yp = (size_t)q_ny_ * (size_t)q_np_;
-  check(hipMemcpyAsync(s.lo, lo, sizeof(int) * (size_t)q_ny_, hipMemcpyHostToDevice, stream_), "quantile lo");
+  const int rows = q_groups_ ? q_groups_ * q_ny_ : q_ny_;   // a grouped call: (group, row) pairs
+  QState s(d_qstate_, rows, q_np_);
+  const size_t yp = (size_t)rows * (size_t)q_np_;
+  check(hipMemcpyAsync(s.lo, lo, sizeof(int) * (size_t)rows, hipMemcpyHostToDevice, stream_), "quantile lo");
   check(hipMemcpyAsync(s.prefix, prefix, 8 * yp, hipMemcpyHostToDevice, stream_), "quantile prefix");
   check(hipMemsetAsync(d_qhist_, 0, 8 * yp * 256, stream_), "quantile histograms");
-  check(hx_launch_q_hist(q_src_, n_, npad_, q_iy0_, q_ny_, q_weighted_ ? d_q_ : nullptr, s.lo, s.prefix,
-                         q_np_, (post_flags_ & 2) ? 1 : 0, d_qhist_, stream_), "quantile histogram kernel");
+  if (q_groups_)
+    check(hx_launch_gq_hist(q_src_, n_, npad_, q_iy0_, q_ny_, q_weighted_ ? d_q_ : nullptr, d_glab_, q_groups_,
+                            s.lo, s.prefix, q_np_, d_qhist_, stream_), "grouped quantile histogram kernel");
+  else
+    check(hx_launch_q_hist(q_src_, n_, npad_, q_iy0_, q_ny_, q_weighted_ ? d_q_ : nullptr, s.lo, s.prefix,
+                           q_np_, (post_flags_ & 2) ? 1 : 0, d_qhist_, stream_), "quantile histogram kernel");
   check(hipMemcpyAsync(hist_host, d_qhist_, 8 * yp * 256, hipMemcpyDeviceToHost, stream_), "quantile fetch");
   check(hipStreamSynchronize(stream_), "quantile sync");
 #endif
@@ -3655,7 +3678,7 @@ void EnsembleCore::mom_begin_block(const double *src, int iy0, int ny, const uns
   check(hx_launch_q_minmax(src, n_, npad_, iy0, ny, b.q_lane, b.st, stream_), "moments min kernel");
   check(hipMemcpyAsync(st_host, b.st, 8 * 4 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "moments fetch");
   check(hipStreamSynchronize(stream_), "moments sync");   // (q, pred and c are the caller's until here)
-  mom_src_ = src; mom_iy0_ = iy0; mom_ny_ = ny; mom_npred_ = npred;
+  mom_src_ = src; mom_iy0_ = iy0; mom_ny_ = ny; mom_npred_ = npred; mom_groups_ = 0;
 #endif
 }
 
@@ -3697,6 +3720,218 @@ void EnsembleCore::mom_finish(const double *shift_host, double *sums_host) {
   check(hipMemcpyAsync(sums_host, b.out, 8 * (size_t)ny * nc, hipMemcpyDeviceToHost, stream_), "moments fetch");
   check(hipStreamSynchronize(stream_), "moments sync");
   mom_src_ = nullptr;
+#endif
+}
+
+// ---- grouped summaries (hx_group_quantiles, hx_group_probabilities, hx_group_moments) --------------
+// The ungrouped steps above over (group, row) pairs: the state arrays hold ngroups * nrows rows in
+// group-major order, the grouped kernels fill them from one read of every row, and the init, pick
+// and reduce kernels run over them unchanged.
+
+const double *EnsembleCore::grp_source(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                                       int nspecs, int nprobs, const char *fn, int *iy0, int *nrows) {
+  const double *src = nullptr;
+  if (specs) {
+    metric_check(capability, specs, nspecs, fn, &src);
+    if (nprobs < 1 || nprobs > 16) throw std::runtime_error(std::string(fn) + ": nprobs must lie in 1..16");
+    if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
+  } else {
+    src = q_check(capability, year0, year1, nprobs, fn);
+  }
+#ifdef HX_HOST_EMULATION
+  (void)iy0; (void)nrows;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  sync();
+  if (specs) { *iy0 = 0; *nrows = nspecs; return metric_block(src, specs, nspecs); }
+  *iy0 = year0 - scen_.start; *nrows = year1 - year0 + 1;
+  return src;
+#endif
+}
+
+void EnsembleCore::grp_upload_labels(const int *labels) {
+#ifdef HX_HOST_EMULATION
+  (void)labels;
+#else
+  if (!d_glab_) check(hipMalloc(&d_glab_, sizeof(int) * ((size_t)npad_ + (size_t)n_)), "hipMalloc group labels");
+  int *d_mem = d_glab_ + npad_;
+  check(hipMemsetAsync(d_glab_, 0xff, sizeof(int) * (size_t)npad_, stream_), "group labels");   // -1: in no group
+  check(hipMemcpyAsync(d_mem, labels, sizeof(int) * (size_t)n_, hipMemcpyHostToDevice, stream_), "group labels");
+  check(hx_launch_grp_prepare(d_mem, n_, npad_, d_lane_of_member_, d_glab_, stream_), "group label kernel");
+#endif
+}
+
+void EnsembleCore::grp_quantiles(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                                 int nspecs, const int *labels, int ngroups, const unsigned long long *q,
+                                 const double *probs, int nprobs, double *out_host, long long *n_part,
+                                 const char *fn) {
+  int iy0 = 0, ny = 0;
+  const double *src = grp_source(capability, year0, year1, specs, nspecs, nprobs, fn, &iy0, &ny);
+#ifdef HX_HOST_EMULATION
+  (void)src; (void)labels; (void)ngroups; (void)q; (void)probs; (void)out_host; (void)n_part;
+#else
+  const int np = nprobs, rows = ngroups * ny;
+  grp_upload_labels(labels);
+  q_upload(q, rows, np);
+  QState s(d_qstate_, rows, np);
+  const size_t yp = (size_t)rows * (size_t)np;
+  check(hipMemsetAsync(s.st, 0, 8 * 4 * (size_t)rows, stream_), "quantile state");
+  check(hipMemsetAsync(d_qhist_, 0, 8 * yp * 256, stream_), "quantile histograms");
+  check(hipMemcpyAsync(s.probs, probs, sizeof(double) * (size_t)np, hipMemcpyHostToDevice, stream_), "quantile probs");
+  const unsigned long long *dq = q ? d_q_ : nullptr;
+  check(hx_launch_gq_minmax(src, n_, npad_, iy0, ny, dq, d_glab_, ngroups, s.st, stream_),
+        "grouped quantile min/max kernel");
+  check(hx_launch_q_init(s.st, rows, s.probs, np, (post_flags_ & 1) ? 0 : 1, s.lo, s.prefix, s.rem, stream_),
+        "quantile init kernel");
+  // eight digits at most; a workgroup returns at once when every group of its year has finished
+  for (int pass = 0; pass < 8; ++pass) {
+    check(hx_launch_gq_hist(src, n_, npad_, iy0, ny, dq, d_glab_, ngroups, s.lo, s.prefix, np, d_qhist_, stream_),
+          "grouped quantile histogram kernel");
+    check(hx_launch_q_pick(rows, s.lo, s.prefix, s.rem, np, d_qhist_, stream_), "quantile pick kernel");
+  }
+  std::vector<unsigned long long> h((size_t)4 * rows + yp);   // records, then prefixes: adjacent
+  check(hipMemcpyAsync(h.data(), s.st, 8 * h.size(), hipMemcpyDeviceToHost, stream_), "quantile fetch");
+  check(hipStreamSynchronize(stream_), "quantile sync");
+  for (int r = 0; r < rows; ++r) {
+    const unsigned long long cnt = h[(size_t)4 * r + 3];
+    if (n_part) n_part[r] = (long long)cnt;
+    for (int j = 0; j < np; ++j)
+      out_host[(size_t)r * np + j] = cnt ? hxq_key_to_double(h[(size_t)4 * rows + (size_t)r * np + j]) : std::nan("");
+  }
+#endif
+}
+
+void EnsembleCore::grp_q_begin(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                               int nspecs, const int *labels, int ngroups, const unsigned long long *q,
+                               int nprobs, unsigned long long *st_host, const char *fn) {
+  int iy0 = 0, ny = 0;
+  const double *src = grp_source(capability, year0, year1, specs, nspecs, nprobs, fn, &iy0, &ny);
+#ifdef HX_HOST_EMULATION
+  (void)src; (void)labels; (void)ngroups; (void)q; (void)st_host;
+#else
+  const int rows = ngroups * ny;
+  grp_upload_labels(labels);
+  q_upload(q, rows, nprobs);
+  QState s(d_qstate_, rows, nprobs);
+  check(hipMemsetAsync(s.st, 0, 8 * 4 * (size_t)rows, stream_), "quantile state");
+  check(hx_launch_gq_minmax(src, n_, npad_, iy0, ny, q ? d_q_ : nullptr, d_glab_, ngroups, s.st, stream_),
+        "grouped quantile min/max kernel");
+  check(hipMemcpyAsync(st_host, s.st, 8 * 4 * (size_t)rows, hipMemcpyDeviceToHost, stream_), "quantile fetch");
+  check(hipStreamSynchronize(stream_), "quantile sync");
+  q_src_ = src; q_iy0_ = iy0; q_ny_ = ny; q_np_ = nprobs; q_weighted_ = q != nullptr; q_groups_ = ngroups;
+#endif
+}
+
+void EnsembleCore::grp_bin_sums(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                                int nspecs, const int *labels, int ngroups, const unsigned long long *q,
+                                const double *edges, int nedges, unsigned long long *sums_host, const char *fn) {
+  int iy0 = 0, ny = 0;
+  const double *src = grp_source(capability, year0, year1, specs, nspecs, 1, fn, &iy0, &ny);
+#ifdef HX_HOST_EMULATION
+  (void)src; (void)labels; (void)ngroups; (void)q; (void)edges; (void)nedges; (void)sums_host;
+#else
+  grp_upload_labels(labels);
+  q_upload(q, 1, 1);   // (the weights into lane order; the select's scratch at its smallest)
+  const size_t words = 32 + (size_t)ngroups * (size_t)ny * (size_t)(nedges + 2);
+  if (words > bin_cap_) {
+    if (d_bin_) (void)hipFree(d_bin_);
+    d_bin_ = nullptr; bin_cap_ = 0;
+    check(hipMalloc(&d_bin_, 8 * words), "hipMalloc bin sums");
+    bin_cap_ = words;
+  }
+  double *d_edges = reinterpret_cast<double *>(d_bin_);
+  unsigned long long *d_sums = d_bin_ + 32;
+  check(hipMemcpyAsync(d_edges, edges, sizeof(double) * (size_t)nedges, hipMemcpyHostToDevice, stream_), "bin edges");
+  check(hipMemsetAsync(d_sums, 0, 8 * (words - 32), stream_), "bin sums");
+  check(hx_launch_gbin(src, n_, npad_, iy0, ny, q ? d_q_ : nullptr, d_glab_, ngroups, d_edges, nedges, d_sums,
+                       stream_), "grouped bin kernel");
+  check(hipMemcpyAsync(sums_host, d_sums, 8 * (words - 32), hipMemcpyDeviceToHost, stream_), "bin fetch");
+  check(hipStreamSynchronize(stream_), "bin sync");
+#endif
+}
+
+namespace {
+// d_mom_ of a grouped call, in 8-byte words: MomBuf over ngroups * ny rows, with ngroups x 8 predictor
+// shifts and the labels in member order (two to a word) behind it
+struct GrpMomBuf {
+  unsigned long long *q_mem, *q_lane, *st;
+  double *pred_mem, *c, *qd_lane, *e_lane, *shift, *part, *out;
+  int *lab_mem;
+  size_t words, lane_words;
+  GrpMomBuf(unsigned long long *base, int n, int npad, int npred, int rows, int nchunks, int ngroups) {
+    const size_t N = (size_t)n, P = (size_t)npad, K = (size_t)npred, Y = (size_t)rows, G = (size_t)ngroups;
+    const size_t nc = 2 + 3 * K;
+    q_lane = base;                                             // [npad]  } zeroed before the prepare
+    qd_lane = reinterpret_cast<double *>(q_lane + P);          // [npad]  } kernel: padding lanes
+    e_lane = qd_lane + P;                                      // [npred][npad] } take no part
+    lane_words = (2 + K) * P;
+    q_mem = base + lane_words;                                 // [n]
+    pred_mem = reinterpret_cast<double *>(q_mem + N);          // [npred][n]
+    c = pred_mem + K * N;                                      // [ngroups][8]
+    st = reinterpret_cast<unsigned long long *>(c + 8 * G);    // [rows][4]
+    shift = reinterpret_cast<double *>(st + 4 * Y);            // [rows]
+    part = shift + Y;                                          // [rows][nchunks][nc]
+    out = part + Y * (size_t)nchunks * nc;                     // [rows][nc]
+    lab_mem = reinterpret_cast<int *>(out + Y * nc);           // [n]
+    words = lane_words + N + K * N + 8 * G + 5 * Y + Y * (size_t)nchunks * nc + Y * nc + (N + 1) / 2;
+  }
+};
+}  // namespace
+
+void EnsembleCore::grp_mom_begin(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                                 int nspecs, const int *labels, int ngroups, const unsigned long long *q,
+                                 const double *pred, int npred, const double *c, unsigned long long *st_host,
+                                 const char *fn) {
+  int iy0 = 0, ny = 0;
+  const double *src = grp_source(capability, year0, year1, specs, nspecs, 1, fn, &iy0, &ny);
+#ifdef HX_HOST_EMULATION
+  (void)src; (void)labels; (void)ngroups; (void)q; (void)pred; (void)npred; (void)c; (void)st_host;
+#else
+  const int nchunks = hx_mom_chunks(n_), rows = ngroups * ny;
+  const size_t words = GrpMomBuf(nullptr, n_, npad_, npred, rows, nchunks, ngroups).words;
+  if (words > mom_cap_) {
+    if (d_mom_) (void)hipFree(d_mom_);
+    d_mom_ = nullptr; mom_cap_ = 0;
+    check(hipMalloc(&d_mom_, 8 * words), "hipMalloc moments");
+    mom_cap_ = words;
+  }
+  GrpMomBuf b(d_mom_, n_, npad_, npred, rows, nchunks, ngroups);
+  const size_t N = (size_t)n_;
+  if (!d_glab_) check(hipMalloc(&d_glab_, sizeof(int) * ((size_t)npad_ + N)), "hipMalloc group labels");
+  check(hipMemsetAsync(b.q_lane, 0, 8 * b.lane_words, stream_), "moments lanes");
+  check(hipMemsetAsync(d_glab_, 0xff, sizeof(int) * (size_t)npad_, stream_), "group labels");
+  check(hipMemsetAsync(b.st, 0, 8 * 4 * (size_t)rows, stream_), "moments state");
+  check(hipMemcpyAsync(b.q_mem, q, 8 * N, hipMemcpyHostToDevice, stream_), "moments weights");
+  check(hipMemcpyAsync(b.lab_mem, labels, sizeof(int) * N, hipMemcpyHostToDevice, stream_), "group labels");
+  if (npred)
+    check(hipMemcpyAsync(b.pred_mem, pred, 8 * N * (size_t)npred, hipMemcpyHostToDevice, stream_),
+          "moments predictors");
+  check(hipMemcpyAsync(b.c, c, 8 * 8 * (size_t)ngroups, hipMemcpyHostToDevice, stream_), "moments predictor shifts");
+  check(hx_launch_gmom_prepare(b.q_mem, b.pred_mem, b.lab_mem, npred, n_, npad_, d_lane_of_member_, b.c, b.q_lane,
+                               b.qd_lane, b.e_lane, d_glab_, stream_), "grouped moments prepare kernel");
+  check(hx_launch_gq_minmax(src, n_, npad_, iy0, ny, b.q_lane, d_glab_, ngroups, b.st, stream_),
+        "grouped moments min kernel");
+  check(hipMemcpyAsync(st_host, b.st, 8 * 4 * (size_t)rows, hipMemcpyDeviceToHost, stream_), "moments fetch");
+  check(hipStreamSynchronize(stream_), "moments sync");   // (q, pred, c and labels are the caller's until here)
+  mom_src_ = src; mom_iy0_ = iy0; mom_ny_ = ny; mom_npred_ = npred; mom_groups_ = ngroups;
+#endif
+}
+
+void EnsembleCore::grp_mom_finish(const double *shift_host, double *sums_host) {
+#ifdef HX_HOST_EMULATION
+  (void)shift_host; (void)sums_host;
+  throw std::runtime_error(std::string("hx_group_moments") + kEmulRefusal);
+#else
+  if (!mom_src_ || !mom_groups_) throw std::runtime_error("grouped moment sums without grp_mom_begin");
+  const int ny = mom_ny_, npred = mom_npred_, G = mom_groups_, rows = G * ny;
+  GrpMomBuf b(d_mom_, n_, npad_, npred, rows, hx_mom_chunks(n_), G);
+  const size_t nc = 2 + 3 * (size_t)npred;
+  check(hipMemcpyAsync(b.shift, shift_host, 8 * (size_t)rows, hipMemcpyHostToDevice, stream_), "moments shifts");
+  check(hx_launch_gmoments(mom_src_, n_, npad_, mom_iy0_, ny, b.qd_lane, b.e_lane, d_glab_, G, npred, b.shift,
+                           b.part, b.out, stream_), "grouped moments kernel");
+  check(hipMemcpyAsync(sums_host, b.out, 8 * (size_t)rows * nc, hipMemcpyDeviceToHost, stream_), "moments fetch");
+  check(hipStreamSynchronize(stream_), "moments sync");
+  mom_src_ = nullptr; mom_groups_ = 0;
 #endif
 }
 

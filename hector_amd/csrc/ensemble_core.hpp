@@ -213,6 +213,32 @@ class EnsembleCore {
                  const unsigned long long *q, const double *pred, int npred, const double *c,
                  unsigned long long *st_host, const char *fn);
   void mom_finish(const double *shift_host, double *sums_host);
+  // ---- the grouped summaries (hx_group_quantiles / _probabilities / _moments in hector_amd.h) -------
+  // labels[n_] in member order, -1 .. ngroups-1 (checked by the fleet); rows are specs == nullptr ? the
+  // years year0..year1 : the nspecs metrics; every state and result array is group-major, (group, row)
+  // at g * nrows + row, so that hx_fleet.cpp combines shards over ngroups * nrows rows exactly as it
+  // does over rows.  fn: the ABI function named in every message; the host-emulation build refuses
+  // by that name after the checks.
+  // grp_quantiles: the whole select on this core's GPU -> out_host[ngroups * nrows][nprobs], n_part
+  void grp_quantiles(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                     const int *labels, int ngroups, const unsigned long long *q, const double *probs,
+                     int nprobs, double *out_host, long long *n_part, const char *fn);
+  // grp_q_begin is q_begin over (group, row): st_host[ngroups * nrows][4]; q_pass follows, with lo,
+  // prefix and hist_host over ngroups * nrows rows
+  void grp_q_begin(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                   const int *labels, int ngroups, const unsigned long long *q, int nprobs,
+                   unsigned long long *st_host, const char *fn);
+  // sums_host[ngroups * nrows][nedges + 2]
+  void grp_bin_sums(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                    const int *labels, int ngroups, const unsigned long long *q, const double *edges,
+                    int nedges, unsigned long long *sums_host, const char *fn);
+  // mom_begin / mom_finish over (group, row): q[n_] effective weights (0 where the label is -1 or a
+  // predictor is not finite), c[ngroups][8] the groups' predictor shifts; st_host[ngroups * nrows][4];
+  // shift_host[ngroups * nrows] -> sums_host[ngroups * nrows][2 + 3 npred]
+  void grp_mom_begin(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                     const int *labels, int ngroups, const unsigned long long *q, const double *pred,
+                     int npred, const double *c, unsigned long long *st_host, const char *fn);
+  void grp_mom_finish(const double *shift_host, double *sums_host);
   // per-member pair metrics (hx_member_pair_metrics): two operands of a member, PairCall above;
   // out_host row s at out_host + s * row_pitch (0: n_), member order.  The three block verbs are the
   // metric verbs above with the pair block in place of the metric block (fn: the ABI function named
@@ -419,6 +445,13 @@ class EnsembleCore {
   size_t mom_cap_ = 0;
   const double *mom_src_ = nullptr;           // the block mom_begin prepared for mom_finish
   int mom_iy0_ = 0, mom_ny_ = 0, mom_npred_ = 0;
+  // the grouped summaries: labels [npad_] in lane order, then [n_] in member order as uploaded
+  int *d_glab_ = nullptr;
+  int q_groups_ = 0, mom_groups_ = 0;         // 0: q_pass / the moment scratch belong to an ungrouped call
+  // the rows of a grouped call resolved (and, for metrics, queued on stream_) -> block, first row, rows
+  const double *grp_source(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                           int nspecs, int nprobs, const char *fn, int *iy0, int *nrows);
+  void grp_upload_labels(const int *labels);  // member order -> d_glab_ in lane order (padding lanes -1)
   unsigned long long *d_comom_ = nullptr;     // scratch of hx_ensemble_comoments (CoBuf in ensemble_core.cpp)
   size_t comom_cap_ = 0;
   const double *co_a_ = nullptr, *co_b_ = nullptr;   // the windows comom_begin prepared for comom_finish

@@ -435,6 +435,29 @@ int hx_metric_moments(hx_core *core, const char *capability, const hx_metric *sp
   HX_TRY(core->core->moments(capability, 0, 0, specs, nspecs, weights, predictors, npred, shift, sums, wsum,
                              n_part))
 }
+int hx_group_quantiles(hx_core *core, const char *capability, int year0, int year1, const hx_metric *specs,
+                       int nspecs, const int *labels, int ngroups, const double *weights, const double *probs,
+                       int nprobs, double *out, long long *n_part) {
+  if (!capability || !probs || !out) return fail("hx_group_quantiles: null argument");
+  HX_TRY(core->core->group_quantiles(capability, year0, year1, specs, nspecs, labels, ngroups, weights, probs,
+                                     nprobs, out, n_part))
+}
+int hx_group_probabilities(hx_core *core, const char *capability, int year0, int year1, const hx_metric *specs,
+                           int nspecs, const int *labels, int ngroups, const double *weights,
+                           const double *edges, int nedges, double *prob, unsigned long long *sums,
+                           long long *n_part) {
+  if (!capability || !prob) return fail("hx_group_probabilities: null argument");
+  HX_TRY(core->core->group_probabilities(capability, year0, year1, specs, nspecs, labels, ngroups, weights,
+                                         edges, nedges, prob, sums, n_part))
+}
+int hx_group_moments(hx_core *core, const char *capability, int year0, int year1, const hx_metric *specs,
+                     int nspecs, const int *labels, int ngroups, const double *weights,
+                     const double *predictors, int npred, double *shift, double *pshift, double *sums,
+                     unsigned long long *wsum, long long *n_part) {
+  if (!capability || !shift || !sums) return fail("hx_group_moments: null argument");
+  HX_TRY(core->core->group_moments(capability, year0, year1, specs, nspecs, labels, ngroups, weights,
+                                   predictors, npred, shift, pshift, sums, wsum, n_part))
+}
 int hx_member_pair_metrics(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
                            int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs, double *out) {
   if (!cap_a || !specs || !out) return fail("hx_member_pair_metrics: null argument");

@@ -1215,6 +1215,432 @@ hipError_t hx_launch_moments(const double *var, int n, int npad, int iy0, int nr
 }
 
 // ===========================================================================
+// The grouped flavours of the three summaries above (hx_group_quantiles, hx_group_probabilities,
+// hx_group_moments in hector_amd.h): every member carries a label 0 .. G-1 (G <= HXG_MAX) or -1, "in
+// no group", and one pass sequence answers for every group what G calls with masked weights would.
+// Lane order is a cost-sorted permutation, so a group's members are scattered in a row whatever the
+// caller's labels look like, and gathered 8-byte loads cost 3.8 times the streamed read of the same
+// bytes (profiles/post_summaries.md, the Sobol section): the kernels stay streamed -- a lane takes
+// its HXQ_PER values of the chunk into registers as above, the row is read ONCE per pass whatever G
+// is, and the lanes' labels (like q, re-read per row from the cache) say where a value counts.
+// Rows of the state arrays are (group, row) pairs, r = g * nrows + row, which is the group-major
+// layout of the results: hx_q_init_kernel, hx_q_pick_kernel and hx_mom_reduce_kernel run unchanged
+// over G * nrows rows.
+//   hx_grp_prepare_kernel   lane-local: labels from member order to lane order (padding lanes -1)
+//   hx_gmom_prepare_kernel  hx_mom_prepare_kernel with the labels and per-group predictor shifts
+//   hx_gq_minmax_kernel     per (row, group): wavefront reduction per group present in the
+//                           wavefront, combined in LDS, one global atomic per group present in the chunk
+//   hx_gq_hist_kernel       keys, weights and labels (4 bits each) stay in registers while the (group,
+//                           probability) slots go through the LDS histograms in batches of 64 slots
+//                           x 256 bins; a key is compared only against the prefixes of its own group;
+//                           groups finish at different digits and are skipped then
+//   hx_gbin_kernel          h[group][bin][copy], fewer copies per bin as G grows, flushed once
+//   hx_gmoments_kernel<NP>  inside a register batch the groups present in the wavefront (a ballot
+//                           skips the absent ones) take turns: private sums over the lanes whose label
+//                           matches, the fixed shuffle tree, added to the wavefront's slot in LDS in
+//                           batch order; one partial per (row, group, chunk)
+// ===========================================================================
+#define HXG_MAX 16
+static_assert(HXG_MAX == HX_GROUP_MAX, "the header's limit");
+
+__global__ __launch_bounds__(256) void hx_grp_prepare_kernel(const int *__restrict__ lab_mem, int n, int npad,
+                                                             const int *__restrict__ lane_of_member,
+                                                             int *__restrict__ lab_lane) {
+  const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (m >= n) return;
+  const int lane = lane_of_member[m];
+  if (lane < 0 || lane >= npad) return;
+  lab_lane[lane] = lab_mem[m];
+}
+
+// c[g * HXMOM_MAXP + k]: the predictor shifts of group g; q_mem is 0 where the label is -1
+__global__ __launch_bounds__(256) void hx_gmom_prepare_kernel(const hxq_u64 *__restrict__ q_mem,
+                                                              const double *__restrict__ pred_mem,
+                                                              const int *__restrict__ lab_mem, int npred, int n,
+                                                              int npad, const int *__restrict__ lane_of_member,
+                                                              const double *__restrict__ c,
+                                                              hxq_u64 *__restrict__ q_lane,
+                                                              double *__restrict__ qd_lane,
+                                                              double *__restrict__ e_lane,
+                                                              int *__restrict__ lab_lane) {
+  const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (m >= n) return;
+  const int lane = lane_of_member[m];
+  if (lane < 0 || lane >= npad) return;
+  const int g = lab_mem[m];
+  const hxq_u64 q = g >= 0 ? q_mem[m] : 0ull;
+  lab_lane[lane] = g;
+  q_lane[lane] = q;
+  qd_lane[lane] = (double)q;
+  for (int k = 0; k < npred; ++k)
+    e_lane[(size_t)k * (size_t)npad + (size_t)lane] =
+        q ? pred_mem[(size_t)k * (size_t)n + (size_t)m] - c[g * HXMOM_MAXP + k] : 0.0;
+}
+
+// st[g * ny + year] must be zero on entry
+template <bool WEIGHTED>
+__global__ __launch_bounds__(HXQ_BLOCK) void hx_gq_minmax_kernel(const double *var, int n, int npad, int iy0,
+                                                                 int ny, const hxq_u64 *q, const int *lab, int G,
+                                                                 HxQYear *st) {
+  __shared__ hxq_u64 s[HXG_MAX * 4];
+  const int tid = (int)threadIdx.x;
+  const int y = (int)blockIdx.y;
+  const double *row = var + (size_t)(iy0 + y) * npad;
+  const int beg = (int)blockIdx.x * HXQ_CHUNK, end = min(beg + HXQ_CHUNK, n);
+  if (tid < HXG_MAX * 4) s[tid] = 0;
+  hxq_u64 k[HXQ_PER], w[WEIGHTED ? HXQ_PER : 1];
+  int lb[HXQ_PER];   // -1: no member here, NaN, weight 0 or in no group
+  unsigned gm = 0;   // the groups this lane holds
+#pragma unroll
+  for (int e = 0; e < HXQ_PER; ++e) {
+    const int i = beg + e * HXQ_BLOCK + tid;
+    double x = __builtin_nan("");
+    int g = -1;
+    hxq_u64 we = 1ull;
+    if (i < end) { x = row[i]; g = lab[i]; if (WEIGHTED) we = q[i]; }
+    if (!(x == x) || !we || g >= G) g = -1;
+    if (WEIGHTED) w[e] = we;
+    k[e] = hxq_key(x);
+    lb[e] = g;
+    if (g >= 0) gm |= 1u << g;
+  }
+  __syncthreads();
+  for (int g = 0; g < G; ++g) {
+    if (!__ballot((gm >> g) & 1u)) continue;   // wave-uniform
+    hxq_u64 nkmin = 0, kmax = 0, W = 0, cnt = 0;
+#pragma unroll
+    for (int e = 0; e < HXQ_PER; ++e)
+      if (lb[e] == g) {
+        nkmin = max(nkmin, ~k[e]); kmax = max(kmax, k[e]); W += WEIGHTED ? w[e] : 1ull; ++cnt;
+      }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      nkmin = max(nkmin, __shfl_down(nkmin, off, 64)); kmax = max(kmax, __shfl_down(kmax, off, 64));
+      W += __shfl_down(W, off, 64); cnt += __shfl_down(cnt, off, 64);
+    }
+    if ((tid & 63) == 0) {
+      atomicMax(&s[g * 4], nkmin); atomicMax(&s[g * 4 + 1], kmax);
+      atomicAdd(&s[g * 4 + 2], W); atomicAdd(&s[g * 4 + 3], cnt);
+    }
+  }
+  __syncthreads();
+  if (tid < G && s[tid * 4 + 3]) {
+    HxQYear *o = st + (size_t)tid * ny + y;
+    atomicMax(&o->nkmin, s[tid * 4]); atomicMax(&o->kmax, s[tid * 4 + 1]);
+    atomicAdd(&o->W, s[tid * 4 + 2]); atomicAdd(&o->cnt, s[tid * 4 + 3]);
+  }
+}
+
+// grid (row chunks, years); lo[g * ny + year], prefix[(g * ny + year) * np + j], hist likewise x 256.
+// Slot s = g * np + j.  The histograms of HXGQ_SLOTS slots at a time live in LDS (128 of the CU's 160
+// KiB; the kernel's registers allow one workgroup per CU anyway), the keys stay in registers across
+// the batches, and a key goes through the np prefixes of ITS group only: the work per key is that of
+// the ungrouped kernel whatever G is.  Groups finish at different digits: every key takes the digit
+// below the lo of its own group.
+#define HXGQ_SLOTS 64
+template <bool WEIGHTED>
+__global__ __launch_bounds__(HXQ_BLOCK) void hx_gq_hist_kernel(const double *var, int n, int npad, int iy0,
+                                                               int ny, const hxq_u64 *q, const int *lab, int G,
+                                                               const int *lo, const hxq_u64 *prefix, int np,
+                                                               hxq_u64 *hist) {
+  __shared__ hxq_u64 h[HXGQ_SLOTS * 256];
+  __shared__ hxq_u64 pre[HXG_MAX * HXQ_MAXP];
+  __shared__ int own[HXG_MAX * HXQ_MAXP];   // 1: this slot fills a histogram; 0: finished, or an earlier
+                                            // probability of the group with the same prefix does
+  __shared__ int glo[HXG_MAX];
+  const int y = (int)blockIdx.y;
+  const int tid = (int)threadIdx.x;
+  const int S = G * np;   // <= 256 = HXQ_BLOCK
+  if (tid < HXG_MAX) glo[tid] = tid < G ? lo[(size_t)tid * ny + y] : 0;
+  if (tid < S) pre[tid] = prefix[((size_t)(tid / np) * ny + y) * np + (tid % np)];
+  __syncthreads();
+  bool open = false;
+  for (int g = 0; g < G; ++g) open = open || glo[g] != 0;
+  if (!open) return;   // every group of this year is finished (the same for the whole workgroup)
+  const double *row = var + (size_t)(iy0 + y) * npad;
+  const int beg = (int)blockIdx.x * HXQ_CHUNK, end = min(beg + HXQ_CHUNK, n);
+  hxq_u64 k[HXQ_PER], w[WEIGHTED ? HXQ_PER : 1];
+  unsigned part = 0;            // bit e: key e is a member's, not NaN, and in a group
+  unsigned lab4[HXQ_PER / 8];   // its label, 4 bits each
+#pragma unroll
+  for (int e = 0; e < HXQ_PER / 8; ++e) lab4[e] = 0u;
+#pragma unroll
+  for (int e = 0; e < HXQ_PER; ++e) {
+    const int i = beg + e * HXQ_BLOCK + tid;
+    double x = __builtin_nan("");
+    int g = -1;
+    if (i < end) { x = row[i]; g = lab[i]; }
+    if (WEIGHTED) w[e] = i < end ? q[i] : 0ull;
+    k[e] = hxq_key(x);
+    const bool on = x == x && g >= 0 && g < G;
+    part |= (on ? 1u : 0u) << e;
+    lab4[e >> 3] |= (on ? (unsigned)g : 0u) << ((e & 7) * 4);
+  }
+  if (tid < S) {
+    const int g = tid / np, j = tid - g * np;
+    int o = glo[g] != 0 ? 1 : 0;
+    for (int c = 0; c < j; ++c) if (pre[g * np + c] == pre[tid]) { o = 0; break; }
+    own[tid] = o;
+  }
+  // keys of groups that have finished take no part in this pass
+#pragma unroll
+  for (int e = 0; e < HXQ_PER; ++e)
+    if (glo[(lab4[e >> 3] >> ((e & 7) * 4)) & 15u] == 0) part &= ~(1u << e);
+#pragma unroll 1
+  for (int b0 = 0; b0 < S; b0 += HXGQ_SLOTS) {
+    const int nb = min(HXGQ_SLOTS, S - b0);
+    for (int i = tid; i < nb * 256; i += HXQ_BLOCK) h[i] = 0;
+    __syncthreads();   // (the first time round: own[] is complete too)
+    // (opaque to the optimiser: the 32 predicates below are then formed where they are used, one lane
+    //  mask at a time, instead of being hoisted out of the batch loop into 64 scalar registers)
+    unsigned pb = part;
+    asm volatile("" : "+v"(pb));
+#pragma unroll
+    for (int e = 0; e < HXQ_PER; ++e) {
+      const int g = (int)((lab4[e >> 3] >> ((e & 7) * 4)) & 15u);
+      const int l = glo[g];
+      const bool mine = ((pb >> e) & 1u) != 0;
+      const int shift = l >= 8 ? l - 8 : 0;
+      const hxq_u64 known = l >= 64 ? 0ull : ~0ull << l;
+      const int digit = (int)((k[e] >> shift) & 255ull);
+      const int s0 = g * np - b0;   // the group's first slot, relative to the batch
+      for (int j = 0; j < np; ++j) {
+        const int sl = s0 + j;
+        const bool in = mine && sl >= 0 && sl < nb;
+        const int s = in ? sl + b0 : 0;
+        if (in && own[s] && ((k[e] ^ pre[s]) & known) == 0)
+          atomicAdd(h + sl * 256 + digit, WEIGHTED ? w[e] : 1ull);
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < nb * 256; i += HXQ_BLOCK) {
+      const hxq_u64 v = h[i];
+      if (v) {
+        const int s = b0 + (i >> 8), g = s / np;
+        atomicAdd(hist + (((size_t)g * ny + y) * np + (s - g * np)) * 256 + (i & 255), v);
+      }
+    }
+    __syncthreads();   // the histograms are cleared for the next batch
+  }
+}
+
+// sums[(g * nrows + row)][K + 2]: the K + 1 bins, then the members that took part; zero on entry.
+// Bin slot 32 of a group counts its members; C copies per bin: 32 up to four groups, 16 up to eight, 8
+#define HXGB_WORDS (33 * 128)
+template <bool WEIGHTED>
+__global__ __launch_bounds__(HXQ_BLOCK) void hx_gbin_kernel(const double *var, int n, int npad, int iy0, int nrows,
+                                                            const hxq_u64 *q, const int *lab, int G,
+                                                            const double *edges, int K, hxq_u64 *sums) {
+  __shared__ hxq_u64 h[HXGB_WORDS];
+  __shared__ double ed[32];
+  const int tid = (int)threadIdx.x;
+  const int y = (int)blockIdx.y;
+  const double *row = var + (size_t)(iy0 + y) * npad;
+  const int beg = (int)blockIdx.x * HXQ_CHUNK, end = min(beg + HXQ_CHUNK, n);
+  const int C = G <= 4 ? 32 : G <= 8 ? 16 : 8;   // G * 33 * C <= HXGB_WORDS
+  double x[HXQ_PER];
+  hxq_u64 w[WEIGHTED ? HXQ_PER : 1];
+  int lb[HXQ_PER];
+#pragma unroll
+  for (int e = 0; e < HXQ_PER; ++e) {
+    const int i = beg + e * HXQ_BLOCK + tid;
+    x[e] = __builtin_nan("");
+    lb[e] = -1;
+    if (i < end) { x[e] = row[i]; lb[e] = lab[i]; }
+    if (WEIGHTED) w[e] = i < end ? q[i] : 0ull;
+  }
+  if (tid < 32) ed[tid] = tid < K ? edges[tid] : __builtin_nan("");
+  for (int i = tid; i < HXGB_WORDS; i += HXQ_BLOCK) h[i] = 0;
+  __syncthreads();
+  const int copy = tid & (C - 1);
+#pragma unroll
+  for (int e = 0; e < HXQ_PER; ++e) {
+    const double v = x[e];
+    const hxq_u64 we = WEIGHTED ? w[e] : 1ull;
+    const int g = lb[e];
+    int pos = 0;
+#pragma unroll
+    for (int step = 16; step > 0; step >>= 1)
+      if (ed[pos + step - 1] <= v) pos += step;
+    if (v == v && we && g >= 0 && g < G) {
+      atomicAdd(h + (g * 33 + pos) * C + copy, we);
+      atomicAdd(h + (g * 33 + 32) * C + copy, 1ull);
+    }
+  }
+  __syncthreads();
+  for (int idx = tid; idx < G * (K + 2); idx += HXQ_BLOCK) {
+    const int g = idx / (K + 2), b = idx - g * (K + 2);
+    const hxq_u64 *hb = h + (g * 33 + (b <= K ? b : 32)) * C;
+    hxq_u64 s = 0;
+    for (int c = 0; c < C; ++c) s += hb[(c + idx) & (C - 1)];
+    if (s) atomicAdd(sums + ((size_t)g * nrows + y) * (size_t)(K + 2) + b, s);
+  }
+}
+
+// part[((g * nrows + row) * nchunks + chunk) * (2 + 3 NP) + ...]; shift[g * nrows + row]; e: the lane's
+// predictors less the shifts of ITS group (hx_gmom_prepare_kernel); a group absent from the chunk
+// writes zeros
+template <int NP>
+__global__ __launch_bounds__(HXQ_BLOCK) void hx_gmoments_kernel(const double *__restrict__ var, int n, int npad,
+                                                                int iy0, int nrows, const double *__restrict__ qd,
+                                                                const double *__restrict__ e,
+                                                                const int *__restrict__ lab, int G,
+                                                                const double *__restrict__ shift,
+                                                                double *__restrict__ part) {
+  constexpr int NC = 2 + 3 * NP;
+  static_assert(HXQ_BLOCK == 256, "the combine below adds four wavefronts in a fixed order");
+  __shared__ double red[HXQ_BLOCK / 64][HXG_MAX][NC];
+  __shared__ double cg[HXG_MAX];
+  const int tid = (int)threadIdx.x, wave = tid >> 6;
+  const int y = (int)blockIdx.y;
+  const double *row = var + (size_t)(iy0 + y) * npad;
+  const int beg = (int)blockIdx.x * HXQ_CHUNK, end = min(beg + HXQ_CHUNK, n);
+  for (int i = tid; i < (HXQ_BLOCK / 64) * HXG_MAX * NC; i += HXQ_BLOCK) (&red[0][0][0])[i] = 0.0;
+  if (tid < HXG_MAX) cg[tid] = tid < G ? shift[(size_t)tid * nrows + y] : 0.0;
+  __syncthreads();
+  // (batches of 16 up to one predictor, of 8 beyond: the labels and a group's accumulators share the
+  //  registers with the batch, and the default code generation of the safe build must not spill either)
+  constexpr int B = NP <= 1 ? HXQ_PER / 2 : HXQ_PER / 4;
+#pragma unroll 1
+  for (int j0 = 0; j0 < HXQ_PER; j0 += B) {
+    const int i0 = beg + j0 * HXQ_BLOCK + tid;
+    if (i0 - tid >= end) break;   // (the same for the whole workgroup)
+    double x[B], w[B], ek[NP > 0 ? NP * B : 1];
+    int lb[B];
+    unsigned gm = 0;
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+      const int i = i0 + j * HXQ_BLOCK;
+      const bool in = i < end;
+      x[j] = __builtin_nan("");
+      w[j] = 0.0;
+      lb[j] = -1;
+      if (in) { x[j] = row[i]; w[j] = qd[i]; lb[j] = lab[i]; }
+#pragma unroll
+      for (int k = 0; k < NP; ++k) {
+        ek[k * B + j] = 0.0;
+        if (in) ek[k * B + j] = e[(size_t)k * (size_t)npad + (size_t)i];
+      }
+      if (!(x[j] == x[j] && w[j] > 0.0) || lb[j] >= G) lb[j] = -1;   // takes no part
+      if (lb[j] >= 0) gm |= 1u << lb[j];
+    }
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+      if (!__ballot((gm >> g) & 1u)) continue;   // wave-uniform: nobody of this group in the batch
+      const double c = cg[g];
+      double acc[NC];
+#pragma unroll
+      for (int a = 0; a < NC; ++a) acc[a] = 0.0;
+#pragma unroll
+      for (int j = 0; j < B; ++j) {
+        const bool on = lb[j] == g;
+        const double ww = on ? w[j] : 0.0;
+        const double d = on ? x[j] - c : 0.0;
+        const double wd = ww * d;
+        acc[0] += wd;
+        acc[1] += wd * d;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+          const double we = ww * ek[k * B + j];
+          acc[2 + 3 * k] += we;
+          acc[3 + 3 * k] += we * ek[k * B + j];
+          acc[4 + 3 * k] += wd * ek[k * B + j];
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < NC; ++a) {
+        double v = acc[a];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if ((tid & 63) == 0) red[wave][g][a] += v;   // this wavefront's slot: batches in ascending order
+      }
+    }
+  }
+  __syncthreads();
+  for (int idx = tid; idx < G * NC; idx += HXQ_BLOCK) {
+    const int g = idx / NC, a = idx - g * NC;
+    part[(((size_t)g * nrows + y) * gridDim.x + blockIdx.x) * NC + a] =
+        ((red[0][g][a] + red[1][g][a]) + red[2][g][a]) + red[3][g][a];
+  }
+}
+
+hipError_t hx_launch_grp_prepare(const int *lab_mem, int n, int npad, const int *lane_of_member, int *lab_lane,
+                                 hipStream_t st) {
+  hipLaunchKernelGGL(hx_grp_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, st, lab_mem, n, npad,
+                     lane_of_member, lab_lane);
+  return hipGetLastError();
+}
+hipError_t hx_launch_gmom_prepare(const unsigned long long *q_mem, const double *pred_mem, const int *lab_mem,
+                                  int npred, int n, int npad, const int *lane_of_member, const double *c,
+                                  unsigned long long *q_lane, double *qd_lane, double *e_lane, int *lab_lane,
+                                  hipStream_t st) {
+  hipLaunchKernelGGL(hx_gmom_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, st, q_mem, pred_mem, lab_mem,
+                     npred, n, npad, lane_of_member, c, q_lane, qd_lane, e_lane, lab_lane);
+  return hipGetLastError();
+}
+hipError_t hx_launch_gq_minmax(const double *var, int n, int npad, int iy0, int ny, const unsigned long long *q,
+                               const int *lab, int G, void *st, hipStream_t stream) {
+  if (G < 1 || G > HXG_MAX) return hipErrorInvalidValue;
+  const dim3 grid((n + HXQ_CHUNK - 1) / HXQ_CHUNK, ny);
+  if (q)
+    hipLaunchKernelGGL(hx_gq_minmax_kernel<true>, grid, dim3(HXQ_BLOCK), 0, stream, var, n, npad, iy0, ny, q, lab,
+                       G, (HxQYear *)st);
+  else
+    hipLaunchKernelGGL(hx_gq_minmax_kernel<false>, grid, dim3(HXQ_BLOCK), 0, stream, var, n, npad, iy0, ny, q, lab,
+                       G, (HxQYear *)st);
+  return hipGetLastError();
+}
+hipError_t hx_launch_gq_hist(const double *var, int n, int npad, int iy0, int ny, const unsigned long long *q,
+                             const int *lab, int G, const int *lo, const unsigned long long *prefix, int np,
+                             unsigned long long *hist, hipStream_t stream) {
+  if (G < 1 || G > HXG_MAX || np < 1 || np > HXQ_MAXP) return hipErrorInvalidValue;
+  const dim3 grid((n + HXQ_CHUNK - 1) / HXQ_CHUNK, ny);
+  if (q)
+    hipLaunchKernelGGL(hx_gq_hist_kernel<true>, grid, dim3(HXQ_BLOCK), 0, stream, var, n, npad, iy0, ny, q, lab, G,
+                       lo, prefix, np, hist);
+  else
+    hipLaunchKernelGGL(hx_gq_hist_kernel<false>, grid, dim3(HXQ_BLOCK), 0, stream, var, n, npad, iy0, ny, q, lab, G,
+                       lo, prefix, np, hist);
+  return hipGetLastError();
+}
+hipError_t hx_launch_gbin(const double *var, int n, int npad, int iy0, int nrows, const unsigned long long *q,
+                          const int *lab, int G, const double *edges, int K, unsigned long long *sums,
+                          hipStream_t stream) {
+  if (G < 1 || G > HXG_MAX || K < 1 || K > 31) return hipErrorInvalidValue;
+  const dim3 grid((n + HXQ_CHUNK - 1) / HXQ_CHUNK, nrows);
+  if (q)
+    hipLaunchKernelGGL(hx_gbin_kernel<true>, grid, dim3(HXQ_BLOCK), 0, stream, var, n, npad, iy0, nrows, q, lab, G,
+                       edges, K, sums);
+  else
+    hipLaunchKernelGGL(hx_gbin_kernel<false>, grid, dim3(HXQ_BLOCK), 0, stream, var, n, npad, iy0, nrows, q, lab, G,
+                       edges, K, sums);
+  return hipGetLastError();
+}
+// part: [G][nrows][hx_mom_chunks(n)][2 + 3 npred] scratch; out: [G][nrows][2 + 3 npred]
+hipError_t hx_launch_gmoments(const double *var, int n, int npad, int iy0, int nrows, const double *qd,
+                              const double *e, const int *lab, int G, int npred, const double *shift,
+                              double *part, double *out, hipStream_t st) {
+  if (G < 1 || G > HXG_MAX) return hipErrorInvalidValue;
+  const int nchunks = hx_mom_chunks(n), nc = 2 + 3 * npred;
+  const dim3 grid(nchunks, nrows), block(HXQ_BLOCK);
+#define HXGMOM_CASE(NP) \
+  case NP: hipLaunchKernelGGL(hx_gmoments_kernel<NP>, grid, block, 0, st, var, n, npad, iy0, nrows, qd, e, lab, G, \
+                              shift, part); break;
+  switch (npred) {
+    HXGMOM_CASE(0) HXGMOM_CASE(1) HXGMOM_CASE(2) HXGMOM_CASE(3) HXGMOM_CASE(4)
+    HXGMOM_CASE(5) HXGMOM_CASE(6) HXGMOM_CASE(7) HXGMOM_CASE(8)
+    default: return hipErrorInvalidValue;
+  }
+#undef HXGMOM_CASE
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  const int total = G * nrows * nc;
+  hipLaunchKernelGGL(hx_mom_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, part, nchunks, nc, total,
+                     out);
+  return hipGetLastError();
+}
+
+// ===========================================================================
 // Variance-based (Sobol) sensitivity sums from a Saltelli design (hx_ensemble_sobol, hx_metric_sobol
 // in hector_amd.h define the sums).  The estimators compare members in matched groups -- member A_j
 // with B_j and AB_i,j, k + 2 consecutive members -- and members sit in cost-sorted lanes, so a

@@ -669,6 +669,162 @@ void Fleet::moments(const std::string &cap, int year0, int year1, const hx_metri
   }
 }
 
+// ---- grouped summaries: the routines above over (group, row) pairs ---------------------------------
+
+void Fleet::check_groups(const char *fn, const int *labels, int ngroups) const {
+  const std::string f(fn);
+  if (!labels) throw std::runtime_error(f + ": labels is NULL");
+  if (ngroups < 1 || ngroups > HX_GROUP_MAX) throw std::runtime_error(f + ": ngroups must lie in 1..16");
+  bool any = false;
+  for (int m = 0; m < n_; ++m) {
+    if (labels[m] < -1 || labels[m] >= ngroups)
+      throw std::runtime_error(f + ": label " + std::to_string(labels[m]) + " of member " + std::to_string(m) +
+                               " lies outside -1.." + std::to_string(ngroups - 1));
+    any = any || labels[m] >= 0;
+  }
+  if (!any) throw std::runtime_error(f + ": no member has a label >= 0");
+}
+
+void Fleet::group_quantiles(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
+                            const int *labels, int ngroups, const double *weights, const double *probs,
+                            int nprobs, double *out, long long *n_part) {
+  check_poison();
+  const char *fn = "hx_group_quantiles";
+  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
+    throw std::runtime_error(std::string(fn) + ": nspecs must lie in 1..32");
+  check_probs(probs, nprobs, fn);
+  check_groups(fn, labels, ngroups);
+  refuse_processes(fn, "quantiles");
+  std::vector<unsigned long long> q;
+  quantise_weights(weights, fn, q);
+  const unsigned long long *qp = weights ? q.data() : nullptr;
+  if (shards_.size() == 1) {
+    use(shards_[0]);
+    shards_[0].core->grp_quantiles(cap, year0, year1, specs, nspecs, labels, ngroups, qp, probs, nprobs, out,
+                                   n_part, fn);
+    return;
+  }
+  const int nrows = specs ? nspecs : year1 - year0 + 1;
+  if (nrows < 1) throw std::runtime_error(std::string(fn) + ": year1 < year0");
+  select_rows(ngroups * nrows, qp, probs, nprobs, out, n_part,
+              [&](Shard &s, const unsigned long long *qs, unsigned long long *part) {
+                s.core->grp_q_begin(cap, year0, year1, specs, nspecs, labels + s.offset, ngroups, qs, nprobs,
+                                    part, fn);
+              });
+}
+
+void Fleet::group_probabilities(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
+                                const int *labels, int ngroups, const double *weights, const double *edges,
+                                int nedges, double *prob, unsigned long long *sums, long long *n_part) {
+  check_poison();
+  const char *fn = "hx_group_probabilities";
+  const std::string f(fn);
+  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
+    throw std::runtime_error(f + ": nspecs must lie in 1..32");
+  if (nedges < 1 || nedges > HX_BIN_MAX_EDGES || !edges)
+    throw std::runtime_error(f + ": nedges must lie in 1..31");
+  for (int k = 0; k < nedges; ++k) {
+    if (!std::isfinite(edges[k])) throw std::runtime_error(f + ": an edge is not finite");
+    if (k && !(edges[k] > edges[k - 1])) throw std::runtime_error(f + ": the edges are not strictly ascending");
+  }
+  check_groups(fn, labels, ngroups);
+  refuse_processes(fn, "probabilities");
+  std::vector<unsigned long long> q;
+  quantise_weights(weights, fn, q);
+  const unsigned long long *qp = weights ? q.data() : nullptr;
+  const int nrows = specs ? nspecs : year1 - year0 + 1;
+  if (nrows < 1) throw std::runtime_error(f + ": year1 < year0");
+  const size_t stride = (size_t)nedges + 2, R = (size_t)ngroups * (size_t)nrows;
+  std::vector<unsigned long long> tot(R * stride, 0ull), part(R * stride);
+  for (Shard &s : shards_) {
+    use(s);
+    s.core->grp_bin_sums(cap, year0, year1, specs, nspecs, labels + s.offset, ngroups,
+                         qp ? qp + s.offset : nullptr, edges, nedges, part.data(), fn);
+    for (size_t i = 0; i < tot.size(); ++i) tot[i] += part[i];
+  }
+  const size_t B = (size_t)nedges + 1;
+  for (size_t r = 0; r < R; ++r) {
+    const unsigned long long *t = &tot[r * stride];
+    unsigned long long W = 0;
+    for (size_t b = 0; b < B; ++b) W += t[b];
+    if (n_part) n_part[r] = (long long)t[B];
+    for (size_t b = 0; b < B; ++b) {
+      if (sums) sums[r * B + b] = t[b];
+      prob[r * B + b] = t[B] ? (double)t[b] / (double)W : std::nan("");
+    }
+  }
+}
+
+void Fleet::group_moments(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
+                          const int *labels, int ngroups, const double *weights, const double *predictors,
+                          int npred, double *shift, double *pshift, double *sums, unsigned long long *wsum,
+                          long long *n_part) {
+  check_poison();
+  const char *fn = "hx_group_moments";
+  const std::string f(fn);
+  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
+    throw std::runtime_error(f + ": nspecs must lie in 1..32");
+  if (npred < 0 || npred > HX_MOM_MAX_PRED)
+    throw std::runtime_error(f + ": npred must lie in 0..8");
+  if (npred > 0 && !predictors)
+    throw std::runtime_error(f + ": predictors is NULL with npred > 0");
+  check_groups(fn, labels, ngroups);
+  refuse_processes(fn, "moments");
+  std::vector<unsigned long long> q;
+  quantise_weights(weights, fn, q);
+  if (!weights) q.assign((size_t)n_, 1ull);
+  const int nrows = specs ? nspecs : year1 - year0 + 1;
+  if (nrows < 1) throw std::runtime_error(f + ": year1 < year0");
+  // the call's effective weights, and every group's predictor shifts over the members they leave it
+  const size_t N = (size_t)n_, K = (size_t)npred, G = (size_t)ngroups, R = G * (size_t)nrows, nc = 2 + 3 * K;
+  for (size_t m = 0; m < N; ++m) {
+    if (labels[m] < 0) q[m] = 0;
+    for (size_t k = 0; k < K; ++k)
+      if (!std::isfinite(predictors[k * N + m])) q[m] = 0;
+  }
+  std::vector<double> c(G * HX_MOM_MAX_PRED, std::nan(""));
+  for (size_t m = 0; m < N; ++m) {
+    if (!q[m]) continue;
+    double *cg = &c[(size_t)labels[m] * HX_MOM_MAX_PRED];
+    for (size_t k = 0; k < K; ++k)
+      if (!(cg[k] <= predictors[k * N + m])) cg[k] = predictors[k * N + m];
+  }
+  // 1. every shard's minimum, W and count of every (group, row); the minimum over the shards is the shift
+  std::vector<unsigned long long> st(4 * R, 0ull), part(4 * R);
+  std::vector<double> pred;
+  for (Shard &s : shards_) {
+    use(s);
+    pred.resize(K * (size_t)s.count);
+    for (size_t k = 0; k < K; ++k)
+      std::copy(predictors + k * N + (size_t)s.offset, predictors + k * N + (size_t)(s.offset + s.count),
+                pred.begin() + k * (size_t)s.count);
+    s.core->grp_mom_begin(cap, year0, year1, specs, nspecs, labels + s.offset, ngroups, q.data() + s.offset,
+                          pred.data(), npred, c.data(), part.data(), fn);
+    for (size_t y = 0; y < R; ++y) {
+      if (!part[4 * y + 3]) continue;
+      st[4 * y] = std::max(st[4 * y], part[4 * y]);
+      st[4 * y + 2] += part[4 * y + 2];
+      st[4 * y + 3] += part[4 * y + 3];
+    }
+  }
+  for (size_t y = 0; y < R; ++y) {
+    shift[y] = st[4 * y + 3] ? hxq_key_to_double(~st[4 * y]) : std::nan("");
+    if (wsum) wsum[y] = st[4 * y + 2];
+    if (n_part) n_part[y] = (long long)st[4 * y + 3];
+  }
+  if (pshift)
+    for (size_t g = 0; g < G; ++g)
+      for (size_t k = 0; k < K; ++k) pshift[g * K + k] = c[g * HX_MOM_MAX_PRED + k];
+  // 2. every shard's sums about those shifts, added in ascending shard order
+  std::fill(sums, sums + R * nc, 0.0);
+  std::vector<double> sp(R * nc);
+  for (Shard &s : shards_) {
+    use(s);
+    s.core->grp_mom_finish(shift, sp.data());
+    for (size_t i = 0; i < R * nc; ++i) sums[i] += sp[i];
+  }
+}
+
 void Fleet::sobol(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs, int k,
                   int n_base, const unsigned char *use_group, double *shift, double *sums, long long *n_part) {
   check_poison();

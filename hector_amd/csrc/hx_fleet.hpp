@@ -126,6 +126,22 @@ class Fleet {
   void moments(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
                const double *weights, const double *predictors, int npred, double *shift, double *sums,
                unsigned long long *wsum, long long *n_part, const PairCall *pair = nullptr);
+  // hx_group_quantiles / hx_group_probabilities / hx_group_moments: the three routines above over
+  // (group, row) pairs in group-major order.  labels[n_] checked here (-1 .. ngroups-1, one >= 0),
+  // the weights quantised against the largest of the WHOLE ensemble whatever the labels; every shard
+  // takes its members' labels, and its histograms, bin sums, minima and sums are combined over
+  // ngroups * nrows rows as they are over rows
+  void group_quantiles(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                       const int *labels, int ngroups, const double *weights, const double *probs, int nprobs,
+                       double *out_host, long long *n_part);
+  void group_probabilities(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                           int nspecs, const int *labels, int ngroups, const double *weights,
+                           const double *edges, int nedges, double *prob, unsigned long long *sums,
+                           long long *n_part);
+  void group_moments(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                     const int *labels, int ngroups, const double *weights, const double *predictors,
+                     int npred, double *shift, double *pshift, double *sums, unsigned long long *wsum,
+                     long long *n_part);
   // hx_ensemble_comoments (cap_b == nullptr: the symmetric call): the weights quantised once; the
   // shards' masks and row minima, then their minimum, W and count; then the shards' sums and cross
   // sums about the common shifts, added in ascending shard order
@@ -188,6 +204,7 @@ class Fleet {
   // integer weights of hx_ensemble_quantiles for fn (named in the messages): q empty = every member 1
   void quantise_weights(const double *weights, const char *fn, std::vector<unsigned long long> &q) const;
   void refuse_processes(const char *fn, const char *what) const;
+  void check_groups(const char *fn, const int *labels, int ngroups) const;
   // the select over ny rows, one shard on its GPU or the shards' histograms added per pass; begin /
   // one: what to call on a shard
   void select_rows(int ny, const unsigned long long *qp, const double *probs, int np, double *out,

@@ -534,6 +534,61 @@ int hx_metric_moments(hx_core *core, const char *capability, const hx_metric *sp
                       const double *weights, const double *predictors, int npred, double *shift,
                       double *sums, unsigned long long *wsum, long long *n_part);
 
+/* ---- Grouped summaries: quantiles, classes and moments per class of member, in one call ----------
+ * An ensemble is rarely one population: several scenarios in one launch (hx_setvar_dated_mix),
+ * blocks of a design, members binned by a parameter.  labels[n_members] (member order) gives every
+ * member its group 0 .. ngroups-1, or -1 for "in no group"; 1 <= ngroups <= HX_GROUP_MAX.  No
+ * counterpart in the reference.
+ * Rows: specs == NULL: the years year0..year1 of `capability` (nspecs is not read); specs != NULL:
+ * the nspecs metrics of every member as hx_member_metrics defines them (year0 / year1 are not read).
+ * Every output is group-major: row r of group g stands at index g * nrows + r.
+ * Weights: they become the integers q ONCE, exactly as in hx_ensemble_quantiles -- wmax is the
+ * largest weight of the WHOLE ensemble whatever the labels, NULL gives q_m = 1 -- so that the groups'
+ * W add up to the W of the ungrouped call over the labelled members.
+ * Definition: the result for group g is what the ungrouped verb computes from the weights q^g, where
+ * q^g_m = q_m if labels[m] == g and 0 otherwise: the same participation rule with W_g and n_part per
+ * (group, row), the rank target t = max(1, ceil(p * (double) W_g)), the bins of
+ * hx_ensemble_probabilities, the shifts c_{y,g} (the smallest participating value of the row in the
+ * group), the predictor shifts c_{k,g} (the smallest of predictor k over the group's members with
+ * q_m > 0 and all predictors finite) and the sums A, B, C_k, D_k, E_k of hx_ensemble_moments.  A
+ * group nobody takes part in for a row -- an empty group, all its members NaN, all its weights
+ * quantised to 0 -- gives NaN quantiles, probabilities and shift, zero sums, W 0 and n_part 0; a group
+ * without a member that has q_m > 0 and finite predictors gives NaN predictor shifts.
+ *   hx_group_quantiles:      out[(g * nrows + r) * nprobs + j], n_part[g * nrows + r] (may be NULL);
+ *                            1 <= nprobs <= 16.
+ *   hx_group_probabilities:  prob[(g * nrows + r) * (nedges + 1) + b], sums likewise (may be NULL),
+ *                            n_part[g * nrows + r] (may be NULL): with one row, the contingency table
+ *                            of (group x class).
+ *   hx_group_moments:        shift[g * nrows + r], sums[(g * nrows + r) * (2 + 3 npred) + ...],
+ *                            wsum and n_part[g * nrows + r] (may be NULL), pshift[g * npred + k] (may be
+ *                            NULL): the predictor shifts, which differ per group; 0 <= npred <= 8.
+ * Reproducibility: quantiles, bin sums, W, n_part and the shifts are exact integers or values some
+ * member has, bit-identical under any lane order or shard split.  The floating sums are bit-identical
+ * from call to call for one core, lane order and shard layout (no floating atomics, fixed trees,
+ * partials added in ascending order), and every one is within (n_part + 8) 2^-53 of the exact sum of
+ * its group, relatively.
+ * Cost: the labels go to lane order once per call; every pass reads a row ONCE whatever ngroups is
+ * (one pass for min / max / W, one per 8-bit digit of the select while any group of the row is open,
+ * one for the bins, two for the moments), against ngroups times that for masked calls.  A core of
+ * several shards combines the shards' integer histograms, sums and minima on the host over the
+ * (group, row) pairs; a communicator of several processes is refused.  The core is not prepared, spun
+ * up or dirtied.
+ * Errors (every message names the function; a refused call changes nothing): those of the ungrouped
+ * verb; labels NULL; ngroups outside 1..16; a label below -1 or >= ngroups; no member with a label
+ * >= 0.  The host-emulation build of the test suite refuses each function after the argument checks. */
+#define HX_GROUP_MAX 16
+int hx_group_quantiles(hx_core *core, const char *capability, int year0, int year1, const hx_metric *specs,
+                       int nspecs, const int *labels, int ngroups, const double *weights, const double *probs,
+                       int nprobs, double *out, long long *n_part);
+int hx_group_probabilities(hx_core *core, const char *capability, int year0, int year1, const hx_metric *specs,
+                           int nspecs, const int *labels, int ngroups, const double *weights,
+                           const double *edges, int nedges, double *prob, unsigned long long *sums,
+                           long long *n_part);
+int hx_group_moments(hx_core *core, const char *capability, int year0, int year1, const hx_metric *specs,
+                     int nspecs, const int *labels, int ngroups, const double *weights,
+                     const double *predictors, int npred, double *shift, double *pshift, double *sums,
+                     unsigned long long *wsum, long long *n_part);
+
 /* Variance-based (Sobol) sensitivity sums of every recorded year from a Saltelli design: what the
  * first-order and total indices of an output with respect to k factors need, year by year, without
  * the trajectories leaving the device.  No counterpart in the reference.
