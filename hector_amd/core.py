@@ -729,6 +729,38 @@ class Core:
         self._ck(self._lib.hx_setvar_dated_mix(self._h, var.encode(), None, 0, None, 0, None, None))
         return self
 
+    def mix_capabilities(self):
+        """The names setvar_dated_mix accepts for this core (hx_mix_capabilities): the carbon-cycle
+        and CH4 emissions, N2O_emissions, RF_albedo and the scenario's <gas>_emissions."""
+        names = ctypes.POINTER(ctypes.c_char_p)()
+        n = ctypes.c_int()
+        self._ck(self._lib.hx_mix_capabilities(self._h, ctypes.byref(names), ctypes.byref(n)))
+        return [names[i].decode() for i in range(n.value)]
+
+    def setvar_scenarios(self, paths, coeff):
+        """Whole scenarios in one core (hx_setvar_scenario_mix): every dated input series in which
+        one of the scenario files `paths` differs from this core's becomes a mix over
+        startDate..endDate with the scenarios' series as basis.  coeff[n_scenarios, n_members], or
+        one integer label 0 .. n_scenarios-1 per member (one-hot coefficients: the member's inputs
+        are then its scenario's own bits).  Returns the number of series mixed; a refused call
+        (different dates, halocarbons, scalars, an unmixable series) changes nothing."""
+        paths = [os.fspath(p) for p in paths]
+        w = np.asarray(coeff)
+        if w.ndim == 1 and w.shape == (self.n_members,) and np.issubdtype(w.dtype, np.integer):
+            if w.size and (w.min() < 0 or w.max() >= len(paths)):
+                raise HectorAmdError("setvar_scenarios: a label outside 0..n_scenarios-1")
+            w = (w[None, :] == np.arange(len(paths))[:, None]).astype(np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (len(paths), self.n_members):
+            raise HectorAmdError("setvar_scenarios: coeff must be [n_scenarios, n_members] or one "
+                                 "integer label per member")
+        arr = (ctypes.c_char_p * len(paths))(*[p.encode() for p in paths])
+        n = ctypes.c_int()
+        self._ck(self._lib.hx_setvar_scenario_mix(self._h, arr, len(paths),
+                                                  w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                  ctypes.byref(n)))
+        return n.value
+
     def set_member_sorting(self, on=True):
         self._ck(self._lib.hx_set_member_sorting(self._h, 1 if on else 0))
         return self

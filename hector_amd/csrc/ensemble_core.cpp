@@ -71,6 +71,10 @@ hipError_t hx_launch_series_permute(const double *src, const int *src_lane, int 
 hipError_t hx_launch_mseries_fill(const double *row, int ns, int npad, double *table, hipStream_t st);
 hipError_t hx_launch_mseries_mix(const double *coeff, const int *member_of_lane, int n, int npad, const int *rows,
                                  const double *basis, int nrows, int nbasis, double *table, hipStream_t st);
+hipError_t hx_launch_gas_mix(const double *par, const double *ser, const double *h0, const double *nat,
+                             const double *molar, const int *rec, const double *coeff, const long long *coff,
+                             const double *basis, const int *cover, const int *member_of_lane, int n, int nh,
+                             int ns, int npad, double *n2o_out, double *rf_other_out, hipStream_t st);
 hipError_t hx_launch_bin(const double *var, int n, int npad, int iy0, int nrows, const unsigned long long *q,
                          const double *edges, int K, unsigned long long *sums, hipStream_t stream);
 hipError_t hx_launch_q_minmax(const double *var, int n, int npad, int iy0, int ny,
@@ -609,6 +613,7 @@ void EnsembleCore::free_device() {
   fr(d_args_); fr(d_derived_); fr(d_dpart_); fr(d_gather_); fr(d_lane_of_member_); fr(d_hist_);
   fr(d_hist_status_);
   fr(d_gas_par_); fr(d_gas_ser_); d_gas_par_ = d_gas_ser_ = nullptr;
+  fr(d_gas_mix_); d_gas_mix_ = nullptr;
   fr(d_cost_); d_cost_ = nullptr; cost_from_iy_ = -1;
   fr(d_wave_clk_); d_wave_clk_ = nullptr;
   fr(d_bscratch_); d_bscratch_ = nullptr;
@@ -1237,7 +1242,8 @@ const MemberSeriesDef kMemberSeries[] = {
     {"CH4_constrain", HXM_CH4_CON, "CH4", "ppbv CH4", 0},
 };
 bool is_constraint_series(int k) { return k >= HXM_CO2_CON && k <= HXM_CH4_CON; }
-const char kMixNames[] = "ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions";
+const char kMixNames[] = "ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions, "
+                         "N2O_emissions, RF_albedo and the <gas>_emissions of the scenario's halocarbons";
 // The definition of hx_setvar_dated_mix restated for the host (fetchvars), for year column i of
 // the recipe: every product rounded before it is added, ascending k -- contraction off whatever
 // the host compiler's default is, as in hx_mseries_mix_kernel.
@@ -1257,6 +1263,22 @@ void mix_year_host(const double *basis, const double *coeff, int nbasis, size_t 
     }
     out[m] = s;
   }
+}
+// ... and for ONE member (the per-member diagnostics of fetchvars walk a member's years)
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+double mix_member_host(const double *basis, const double *coeff, int nbasis, size_t ny, size_t i, size_t n,
+                       size_t m) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double s = coeff[m] * basis[i];
+  for (int k = 1; k < nbasis; ++k) {
+    const double p = coeff[(size_t)k * n + m] * basis[(size_t)k * ny + i];
+    s = s + p;
+  }
+  return s;
 }
 bool interpolated_constraint(int k) { return k == HXM_TAS_CON || k == HXM_FTOT_CON; }
 int constraint_bit(int k) {
@@ -1303,6 +1325,15 @@ void EnsembleCore::setvar_dated(const std::string &capability, const int *years,
           throw std::runtime_error("hx_setvar_dated: " + capability + " has a mix that covers " +
                                    std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
                                    "with nbasis = 0)");
+  {
+    auto gm = gas_mix_.find(capability);
+    if (gm != gas_mix_.end())
+      for (int i = 0; i < n; ++i)
+        if (gm->second.covers(years[i]))
+          throw std::runtime_error("hx_setvar_dated: " + capability + " has a mix that covers " +
+                                   std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
+                                   "with nbasis = 0)");
+  }
   int miny = scen_.end;
   for (int i = 0; i < n; ++i) {
     for (auto &sec : sections)
@@ -1398,10 +1429,11 @@ void EnsembleCore::check_dated_mix(const std::string &capability, const int *yea
   const MemberSeriesDef *d = nullptr;
   for (const MemberSeriesDef &m : kMemberSeries)
     if (capability == m.name && !is_constraint_series(m.k)) d = &m;
-  if (!d)
+  std::string expect = d ? d->units : "";
+  if (!d && !gas_mix_capable(capability, nullptr, &expect))
     throw std::runtime_error(fn + "a mix is not supported for " + capability + " (" + kMixNames + " are)");
-  if (units && units[0] && std::string(units) != d->units)
-    throw std::runtime_error(fn + "Units: " + std::string(units) + " do not match expected: " + d->units +
+  if (units && units[0] && std::string(units) != expect)
+    throw std::runtime_error(fn + "Units: " + std::string(units) + " do not match expected: " + expect +
                              " for " + capability);
   if (nbasis < 0 || nbasis > HX_MIX_MAX_BASIS)
     throw std::runtime_error(fn + "nbasis = " + std::to_string(nbasis) + " outside 0.." +
@@ -1428,12 +1460,15 @@ void EnsembleCore::setvar_dated_mix(const std::string &capability, const int *ye
   check_dated_mix(capability, years, nyears, basis, nbasis, coeff, units);
   const MemberSeriesDef *d = nullptr;
   for (const MemberSeriesDef &m : kMemberSeries) if (capability == m.name) d = &m;
-  MemberMix &mx = mix_[d->k];
+  if (!d && nbasis == 0 && !gas_mix_.count(capability)) return;
+  const bool prepass_was = !gas_member_.empty() || !gas_mix_.empty();
+  MemberMix &mx = d ? mix_[d->k] : gas_mix_[capability];
   if (nbasis == 0 && mx.nbasis == 0) return;
   int miny = scen_.end;   // the years the replaced mix gives back change as well
   for (int y : mx.years) miny = std::min(miny, y);
   if (nbasis == 0) {
-    mx = MemberMix();
+    if (d) mx = MemberMix();
+    else gas_mix_.erase(capability);
   } else {
     mx.nbasis = nbasis;
     mx.years.assign(years, years + nyears);
@@ -1441,9 +1476,148 @@ void EnsembleCore::setvar_dated_mix(const std::string &capability, const int *ye
     mx.coeff.assign(coeff, coeff + (size_t)nbasis * (size_t)n_);
     for (int y : mx.years) miny = std::min(miny, y);
   }
-  mseries_dirty_ = true;
+  if (d) mseries_dirty_ = true;
+  else gas_dirty_ = true;   // the pre-pass evaluates the recipe: nothing else is rebuilt
+  // The pre-pass begins or ends with this call: EVERY year's N2O and forcing row changes its source
+  // (the device's exp / pow against the host's: equal to rounding, not bit for bit), so the whole
+  // run is redone -- a core whose last mix is removed gives the bits of one that never had any.
+  if (!d && prepass_was != (!gas_member_.empty() || !gas_mix_.empty())) miny = scen_.start;
   const int target = std::max(0, miny - 1 - scen_.start);
   if (target < last_iy_) dirty_from_iy_ = (dirty_from_iy_ < 0) ? target : std::min(dirty_from_iy_, target);
+}
+
+// The inputs of the gas pre-pass that may be a mix: what N2OComponent, HalocarbonComponent and the
+// albedo term of ForcingComponent read.  (SV, RF_misc, CH4N and N2O_natural_emissions vary in no
+// shipped scenario and stay shared; the aerosol and ozone / OH precursor emissions feed rows of the
+// per-year table that have no per-member form yet.)
+bool EnsembleCore::gas_mix_capable(const std::string &capability, std::string *section,
+                                   std::string *units) const {
+  auto give = [&](const std::string &sec, const char *u) {
+    if (section) *section = sec;
+    if (units) *units = u;
+    return true;
+  };
+  if (capability == "N2O_emissions") return give("N2O", "Tg N");
+  if (capability == "RF_albedo") return give("simpleNbox", "W/m2");
+  for (const Halocarbon &h : scen_.halocarbons)
+    if (capability == h.name + "_emissions") return give(h.name + "_halocarbon", "Gg");
+  return false;
+}
+
+std::vector<std::string> EnsembleCore::mix_capabilities() const {
+  std::vector<std::string> out;
+  for (const MemberSeriesDef &m : kMemberSeries)
+    if (!is_constraint_series(m.k)) out.push_back(m.name);
+  out.push_back("N2O_emissions");
+  out.push_back("RF_albedo");
+  for (const Halocarbon &h : scen_.halocarbons) out.push_back(h.name + "_emissions");
+  return out;
+}
+
+void EnsembleCore::mix_values(const MemberMix &mx, size_t i, double *out) const {
+  mix_year_host(mx.basis.data(), mx.coeff.data(), mx.nbasis, mx.years.size(), i, (size_t)n_, out);
+}
+
+// hx_setvar_scenario_mix's reading of the scenarios: everything but the mixable dated inputs has to
+// be this core's, bit for bit (the members share one parameter table, one set of constraints and
+// one spinup).  core.run_name is a label and may differ.
+std::vector<EnsembleCore::ScenarioSeries> EnsembleCore::plan_scenario_mix(
+    const std::vector<std::string> &paths) const {
+  const std::string fn = "hx_setvar_scenario_mix: ";
+  if (paths.empty() || paths.size() > (size_t)HX_MIX_MAX_BASIS)
+    throw std::runtime_error(fn + "nscen = " + std::to_string(paths.size()) + " outside 1.." +
+                             std::to_string(HX_MIX_MAX_BASIS));
+  std::vector<Scenario> sc;
+  for (const std::string &p : paths) {
+    try { sc.push_back(Scenario::load(p)); }
+    catch (const std::exception &e) { throw std::runtime_error(fn + e.what()); }
+  }
+  const size_t ns = (size_t)scen_.ns(), K = sc.size();
+  auto split = [](const std::string &name, std::string &sec, std::string &key) {
+    const size_t dot = name.find('.');
+    sec = name.substr(0, dot);
+    key = dot == std::string::npos ? "" : name.substr(dot + 1);
+  };
+  auto same_bits = [](double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0 || (std::isnan(a) && std::isnan(b)); };
+  const std::vector<std::string> capable = mix_capabilities();
+  std::map<std::string, std::vector<double>> found;   // capability -> basis [K][ns]
+  std::string sec, key;
+  for (size_t k = 0; k < K; ++k) {
+    const Scenario &o = sc[k];
+    const std::string who = " (" + o.source + ")";
+    if (o.start != scen_.start || o.end != scen_.end)
+      throw std::runtime_error(fn + "core.startDate / core.endDate differ from the core's" + who);
+    if (o.halocarbons.size() != scen_.halocarbons.size())
+      throw std::runtime_error(fn + "the list of halocarbon sections differs from the core's" + who);
+    for (size_t h = 0; h < o.halocarbons.size(); ++h)
+      if (o.halocarbons[h].name != scen_.halocarbons[h].name)
+        throw std::runtime_error(fn + "the list of halocarbon sections differs from the core's at " +
+                                 o.halocarbons[h].name + "_halocarbon" + who);
+    // scalars: the same keys with the same values (numbers compared as numbers, the rest as text)
+    const auto &mine = scen_.all_scalars(), &theirs = o.all_scalars();
+    for (int side = 0; side < 2; ++side)
+      for (auto &kv : side ? theirs : mine) {
+        if (kv.first == "core.run_name") continue;
+        split(kv.first, sec, key);
+        const auto &other = side ? mine : theirs;
+        auto it = other.find(kv.first);
+        if (it == other.end())
+          throw std::runtime_error(fn + "scalar " + key + " of section " + sec + " (" + kv.first +
+                                   ") is missing on one side" + who);
+        char *e1 = nullptr, *e2 = nullptr;
+        const double a = std::strtod(kv.second.c_str(), &e1), b = std::strtod(it->second.c_str(), &e2);
+        const bool num = e1 != kv.second.c_str() && !*e1 && e2 != it->second.c_str() && !*e2;
+        if (num ? !same_bits(a, b) : kv.second != it->second)
+          throw std::runtime_error(fn + "scalar " + key + " of section " + sec + " (" + kv.first +
+                                   ") differs from the core's" + who);
+      }
+    const auto &ms = scen_.all_series(), &ts = o.all_series();
+    std::string refused;
+    for (auto &kv : ms)
+      if (!ts.count(kv.first)) {
+        split(kv.first, sec, key);
+        throw std::runtime_error(fn + "series " + key + " of section " + sec + " (" + kv.first +
+                                 ") is missing on one side" + who);
+      }
+    for (auto &kv : ts) {
+      split(kv.first, sec, key);
+      auto it = ms.find(kv.first);
+      if (it == ms.end())
+        throw std::runtime_error(fn + "series " + key + " of section " + sec + " (" + kv.first +
+                                 ") is missing on one side" + who);
+      bool differs = kv.second.size() != it->second.size();
+      for (size_t i = 0; !differs && i < kv.second.size(); ++i) differs = !same_bits(kv.second[i], it->second[i]);
+      if (!differs) continue;
+      if (Scenario::is_constraint(key) ||
+          std::find(capable.begin(), capable.end(), key) == capable.end())
+        refused += (refused.empty() ? "" : ", ") + kv.first;
+      else
+        found[key];   // a mix over startDate..endDate, filled below
+    }
+    if (!refused.empty())   // every one of them, as section.key
+      throw std::runtime_error(fn + "series that cannot be a mix differ from the core's: " + refused + " (" +
+                               kMixNames + " can)" + who);
+  }
+  std::vector<ScenarioSeries> plan;
+  for (auto &f : found) {
+    std::string section;
+    for (const MemberSeriesDef &m : kMemberSeries) if (f.first == m.name) section = m.section;
+    if (section.empty()) gas_mix_capable(f.first, &section, nullptr);
+    ScenarioSeries p;
+    p.capability = f.first;
+    p.basis.resize(K * ns);
+    for (size_t k = 0; k < K; ++k) {
+      const std::vector<double> &v = sc[k].series(section, f.first);
+      for (size_t i = 0; i < ns; ++i) {
+        if (!std::isfinite(v[i]))
+          throw std::runtime_error(fn + "series " + f.first + " of section " + section + " is not finite (" +
+                                   sc[k].source + ")");
+        p.basis[k * ns + i] = v[i];
+      }
+    }
+    plan.push_back(std::move(p));
+  }
+  return plan;
 }
 
 // member_points_[k] -> member_series_[k]: every member's points densified by the rule of the
@@ -1558,7 +1732,7 @@ void EnsembleCore::upload_args() {
 void EnsembleCore::run_gas_kernel() {
   gas_dirty_ = false;
   auto fr = [](void *p) { if (p) (void)hipFree(p); };
-  if (gas_member_.empty()) {  // back to the host's shared series
+  if (gas_member_.empty() && gas_mix_.empty()) {  // back to the host's shared series
     if (d_mseries_[HXM_N2O]) {
       sync();
       fr(d_mseries_[HXM_N2O]); fr(d_mseries_[HXM_RF_OTHER]);
@@ -1581,17 +1755,23 @@ void EnsembleCore::run_gas_kernel() {
     return it->second[(size_t)std::min(member_of_lane_[lane], n_ - 1)];
   };
   std::vector<double> par((3 + 3 * nh) * np), ser((4 + 2 * nh) * ns), h0(nh);
-  for (size_t l = 0; l < np; ++l) {
-    par[l] = member_value("N0", s.scalar("N2O", "N0"), l);
-    par[np + l] = member_value("TN2O0", s.scalar("N2O", "TN2O0"), l);
-    par[2 * np + l] = member_value("UC_N2O", s.scalar("N2O", "UC_N2O"), l);
-    for (size_t k = 0; k < nh; ++k) {
-      const Halocarbon &H = s.halocarbons[horder[k]];
-      par[(3 + 3 * k) * np + l] = member_value("tau_" + H.name, H.tau, l);
-      par[(4 + 3 * k) * np + l] = component_disabled(H.name + "_halocarbon")
-                                      ? 0.0 : member_value("rho_" + H.name, H.rho, l);
-      par[(5 + 3 * k) * np + l] = member_value("delta_" + H.name, H.delta, l);
-    }
+  // a row of the parameter block in lane order: the members' values, or one value for every lane
+  // (looked up once per row, not per lane: 81 rows x 65 536 lanes)
+  auto fill_row = [&](size_t row, const std::string &cap, double dflt) {
+    double *dst = par.data() + row * np;
+    auto it = gas_member_.find(cap);
+    if (it == gas_member_.end()) { std::fill(dst, dst + np, dflt); return; }
+    for (size_t l = 0; l < np; ++l) dst[l] = member_value(cap, dflt, l);
+  };
+  fill_row(0, "N0", s.scalar("N2O", "N0"));
+  fill_row(1, "TN2O0", s.scalar("N2O", "TN2O0"));
+  fill_row(2, "UC_N2O", s.scalar("N2O", "UC_N2O"));
+  for (size_t k = 0; k < nh; ++k) {
+    const Halocarbon &H = s.halocarbons[horder[k]];
+    fill_row(3 + 3 * k, "tau_" + H.name, H.tau);
+    if (component_disabled(H.name + "_halocarbon")) std::fill(par.begin() + (4 + 3 * k) * np, par.begin() + (5 + 3 * k) * np, 0.0);
+    else fill_row(4 + 3 * k, "rho_" + H.name, H.rho);
+    fill_row(5 + 3 * k, "delta_" + H.name, H.delta);
   }
   const auto &n2o_em = s.series("N2O", "N2O_emissions");
   const auto &n2o_nat = s.series("N2O", "N2O_natural_emissions");
@@ -1637,10 +1817,70 @@ void EnsembleCore::run_gas_kernel() {
                        stream_), "upload gas series");
   check(hipMemcpyAsync(d_h0, h0.data(), sizeof(double) * nh, hipMemcpyHostToDevice, stream_),
         "upload gas preindustrial values");
-  check(hx_launch_gas(d_gas_par_, d_gas_ser_, d_h0, (int)nh, (int)ns, npad_,
-                      const_cast<double *>(d_mseries_[HXM_N2O]),
-                      const_cast<double *>(d_mseries_[HXM_RF_OTHER]), stream_), "gas kernel");
-  check(hipStreamSynchronize(stream_), "gas kernel sync");
+  if (gas_mix_.empty()) {
+    check(hx_launch_gas(d_gas_par_, d_gas_ser_, d_h0, (int)nh, (int)ns, npad_,
+                        const_cast<double *>(d_mseries_[HXM_N2O]),
+                        const_cast<double *>(d_mseries_[HXM_RF_OTHER]), stream_), "gas kernel");
+    check(hipStreamSynchronize(stream_), "gas kernel sync");
+    upload_args();
+    return;
+  }
+  // Some input is a mix: the recipes go up -- per mixed input nbasis x n_ coefficients in member
+  // order, its basis dense in years and the years it covers -- and hx_gas_mix_kernel evaluates them
+  // where the recurrences read the value.  Input j: 0 N2O_emissions, 1 RF_albedo, 2 + k the
+  // emissions of the k-th gas in summation order.
+  std::vector<const MemberMix *> slot(2 + nh, nullptr);
+  auto mix_of = [&](const std::string &cap) -> const MemberMix * {
+    auto it = gas_mix_.find(cap);
+    return it == gas_mix_.end() ? nullptr : &it->second;
+  };
+  slot[0] = mix_of("N2O_emissions");
+  slot[1] = mix_of("RF_albedo");
+  for (size_t k = 0; k < nh; ++k) slot[2 + k] = mix_of(s.halocarbons[horder[k]].name + "_emissions");
+  std::vector<int> rec(2 * (2 + nh), 0);
+  std::vector<long long> coff;
+  std::vector<double> dbl;   // coefficient blocks | basis [nblk][HX_MIX_MAX_BASIS][ns] | nat [ns] | molar [nh]
+  size_t nblk = 0;
+  for (size_t j = 0; j < slot.size(); ++j)
+    if (slot[j]) {
+      rec[2 * j] = slot[j]->nbasis; rec[2 * j + 1] = (int)nblk++;
+      coff.push_back((long long)dbl.size());
+      dbl.insert(dbl.end(), slot[j]->coeff.begin(), slot[j]->coeff.end());
+    }
+  const size_t o_basis = dbl.size(), o_nat = o_basis + nblk * HX_MIX_MAX_BASIS * ns, o_molar = o_nat + ns;
+  dbl.resize(o_molar + nh, 0.0);
+  std::vector<int> ints(nblk * ns + np, 0);   // cover [nblk][ns] | member_of_lane [np]
+  for (size_t j = 0, b = 0; j < slot.size(); ++j)
+    if (slot[j]) {
+      const MemberMix &mx = *slot[j];
+      const size_t ny = mx.years.size();
+      for (size_t i = 0; i < ny; ++i) {
+        const size_t iy = (size_t)(mx.years[i] - s.start);
+        ints[b * ns + iy] = 1;
+        for (size_t k = 0; k < (size_t)mx.nbasis; ++k)
+          dbl[o_basis + (b * HX_MIX_MAX_BASIS + k) * ns + iy] = mx.basis[k * ny + i];
+      }
+      ++b;
+    }
+  for (size_t iy = 0; iy < ns; ++iy) dbl[o_nat + iy] = n2o_nat[iy];
+  for (size_t k = 0; k < nh; ++k) dbl[o_molar + k] = s.halocarbons[horder[k]].molarMass;
+  std::copy(member_of_lane_.begin(), member_of_lane_.begin() + (std::ptrdiff_t)np, ints.begin() + (std::ptrdiff_t)(nblk * ns));
+  const size_t b_dbl = sizeof(double) * dbl.size(), b_ll = sizeof(long long) * coff.size(),
+               b_rec = sizeof(int) * rec.size(), b_int = sizeof(int) * ints.size();
+  fr(d_gas_mix_); d_gas_mix_ = nullptr;
+  check(hipMalloc(&d_gas_mix_, b_dbl + b_ll + b_rec + b_int), "hipMalloc gas recipes");
+  double *d_dbl = reinterpret_cast<double *>(d_gas_mix_);
+  long long *d_coff = reinterpret_cast<long long *>(d_gas_mix_ + b_dbl);
+  int *d_rec = reinterpret_cast<int *>(d_gas_mix_ + b_dbl + b_ll), *d_int = d_rec + rec.size();
+  check(hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, stream_), "upload gas recipes");
+  check(hipMemcpyAsync(d_coff, coff.data(), b_ll, hipMemcpyHostToDevice, stream_), "upload gas recipe offsets");
+  check(hipMemcpyAsync(d_rec, rec.data(), b_rec, hipMemcpyHostToDevice, stream_), "upload gas recipe records");
+  check(hipMemcpyAsync(d_int, ints.data(), b_int, hipMemcpyHostToDevice, stream_), "upload gas recipe years");
+  check(hx_launch_gas_mix(d_gas_par_, d_gas_ser_, d_h0, d_dbl + o_nat, d_dbl + o_molar, d_rec, d_dbl, d_coff,
+                          d_dbl + o_basis, d_int, d_int + nblk * ns, n_, (int)nh, (int)ns, npad_,
+                          const_cast<double *>(d_mseries_[HXM_N2O]),
+                          const_cast<double *>(d_mseries_[HXM_RF_OTHER]), stream_), "gas mix kernel");
+  check(hipStreamSynchronize(stream_), "gas mix kernel sync");   // (the staging vectors end here)
   upload_args();
 }
 
@@ -2196,7 +2436,7 @@ void EnsembleCore::prepare() {
         if (!member_series_[k].empty() || mix_[k].nbasis) mseries_dirty_ = true;  // lanes have moved
     gas_dirty_ = true;
   }
-  if (gas_dirty_ || (!gas_member_.empty() && !d_mseries_[HXM_N2O])) run_gas_kernel();
+  if (gas_dirty_ || ((!gas_member_.empty() || !gas_mix_.empty()) && !d_mseries_[HXM_N2O])) run_gas_kernel();
   if (mseries_dirty_) upload_member_series();
   clk.lap("gas kernel / member series");
   if (!need_spinup_) return;
@@ -2508,6 +2748,35 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
                         out_host + (size_t)(mx.years[i] - year0) * n_);
       return true;
     }
+  {  // an input of the gas pre-pass that has a mix: the shared series, the definition's bits on top
+    auto gm = gas_mix_.find(capability);
+    if (gm != gas_mix_.end()) {
+      if (!out_host) return true;
+      if (year0 < scen_.start || year1 > scen_.end || year1 < year0)
+        throw std::runtime_error("fetchvars: dates must lie between startDate and endDate");
+      std::string section;
+      gas_mix_capable(capability, &section, nullptr);
+      const std::vector<double> base = input(section, capability, capability == "RF_albedo" ? -0.2 : 0.0);
+      for (int y = year0; y <= year1; ++y)
+        std::fill(out_host + (size_t)(y - year0) * n_, out_host + (size_t)(y - year0 + 1) * n_,
+                  base[(size_t)(y - scen_.start)]);
+      const MemberMix &mx = gm->second;
+      for (size_t i = 0; i < mx.years.size(); ++i)
+        if (mx.years[i] >= year0 && mx.years[i] <= year1)
+          mix_values(mx, i, out_host + (size_t)(mx.years[i] - year0) * n_);
+      return true;
+    }
+  }
+  // year index -> column of a recipe (-1: the shared value), and one member's value there
+  auto cover_map = [&](const MemberMix &mx) {
+    std::vector<int> col((size_t)ns, -1);
+    for (size_t i = 0; i < mx.years.size(); ++i) col[(size_t)(mx.years[i] - scen_.start)] = (int)i;
+    return col;
+  };
+  auto member_mix = [&](const MemberMix &mx, int col, int i) {
+    return mix_member_host(mx.basis.data(), mx.coeff.data(), mx.nbasis, mx.years.size(), (size_t)col,
+                           (size_t)n_, (size_t)i);
+  };
   for (const DatedDef &d : kDated)
     if (capability == d.name && scen_.has_series(d.sections[0], capability))
       ser = scen_.series(d.sections[0], capability);
@@ -2516,8 +2785,9 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
     return capability.size() > suf.size() &&
            capability.compare(capability.size() - suf.size(), suf.size(), suf) == 0;
   };
-  if (capability == "N2O_concentration" && !gas_member_.empty() &&
-      (gas_member_.count("N0") || gas_member_.count("TN2O0") || gas_member_.count("UC_N2O")))
+  if (capability == "N2O_concentration" &&
+      (gas_member_.count("N0") || gas_member_.count("TN2O0") || gas_member_.count("UC_N2O") ||
+       gas_mix_.count("N2O_emissions")))
     return false;  // differs between members: answered from the device series (fetchvars)
   if (ser.empty() && capability == "N2O_concentration") {
     ser.resize((size_t)ns);
@@ -2531,8 +2801,9 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
       const Halocarbon &H = scen_.halocarbons[h];
       const bool conc = capability == H.name + csuf, rf = capability == "RF_" + H.name;
       if (!(conc || rf)) continue;
-      if (!(gas_member_.count("tau_" + H.name) || (rf && (gas_member_.count("rho_" + H.name) ||
-                                                           gas_member_.count("delta_" + H.name)))))
+      auto hmix = gas_mix_.find(H.name + esuf);   // ... or whose emissions do
+      if (!(gas_member_.count("tau_" + H.name) || hmix != gas_mix_.end() ||
+            (rf && (gas_member_.count("rho_" + H.name) || gas_member_.count("delta_" + H.name)))))
         break;
       if (!out_host) return true;
       if (shared_dirty_ || need_spinup_ || gas_dirty_)
@@ -2548,6 +2819,7 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
                                           ? &scen_.series(H.name + "_halocarbon", H.name + "_constrain") : nullptr;
       const int base = kc_.baseyear_idx;
       std::vector<double> v((size_t)ns);
+      const std::vector<int> col = hmix != gas_mix_.end() ? cover_map(hmix->second) : std::vector<int>((size_t)ns, -1);
       for (int i = 0; i < n_; ++i) {
         const double tau = val("tau_" + H.name, H.tau, i), rho = val("rho_" + H.name, H.rho, i),
                      delta = val("delta_" + H.name, H.delta, i);
@@ -2555,7 +2827,9 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
         double c = H.H0;
         for (int iy = 0; iy < ns; ++iy) {
           if (iy >= 1) {
-            const double dconc = (H.emissions[(size_t)iy] / H.molarMass * 1.0) / (0.1 * 1.8);
+            const double em = col[(size_t)iy] >= 0 ? member_mix(hmix->second, col[(size_t)iy], i)
+                                                   : H.emissions[(size_t)iy];
+            const double dconc = (em / H.molarMass * 1.0) / (0.1 * 1.8);
             c = c * expfac + dconc * tau * (1.0 - expfac);
             if (hc && !std::isnan((*hc)[(size_t)iy])) c = (*hc)[(size_t)iy];
           }

@@ -131,6 +131,14 @@ class EnsembleCore {
   // every check of setvar_dated_mix, changing nothing (throws what it would throw)
   void check_dated_mix(const std::string &capability, const int *years, int nyears, const double *basis,
                        int nbasis, const double *coeff, const char *units) const;
+  // the names setvar_dated_mix accepts for this core (the halocarbons are the scenario's)
+  std::vector<std::string> mix_capabilities() const;
+  // Whole scenarios as mixes (hx_setvar_scenario_mix): every dated input series in which one of
+  // the scenarios differs from this core's, as {capability, basis[nscen][ns]} over
+  // startDate..endDate.  Throws, naming section and key, if the scenarios cannot be members of
+  // this core (dates, halocarbons, a scalar, an unmixable or missing series).  Changes nothing.
+  struct ScenarioSeries { std::string capability; std::vector<double> basis; };
+  std::vector<ScenarioSeries> plan_scenario_mix(const std::vector<std::string> &paths) const;
   static const char *const *output_capabilities(int *count);
 
   void reset(double date);      // Core::reset: date < startDate => redo spinup
@@ -369,6 +377,14 @@ class EnsembleCore {
   // N2O / halocarbon parameters that differ between members: capability -> [n_] (member order)
   std::map<std::string, std::vector<double>> gas_member_;
   double *d_gas_par_ = nullptr, *d_gas_ser_ = nullptr;
+  // Mixes of the inputs the gas pre-pass reads (N2O_emissions, RF_albedo, <gas>_emissions):
+  // capability -> recipe.  They have no HXM_* row of their own and never a table: the pre-pass
+  // evaluates them where it needs the value (hx_gas_mix_kernel).
+  std::map<std::string, MemberMix> gas_mix_;
+  char *d_gas_mix_ = nullptr;          // that kernel's recipe block (coefficients, basis, cover, lane map)
+  bool gas_mix_capable(const std::string &capability, std::string *section, std::string *units) const;
+  // year column i of a recipe for every member, the definition's bits: out[n_]
+  void mix_values(const MemberMix &mx, size_t i, double *out) const;
   void run_gas_kernel();  // fills the per-member N2O and halocarbon-forcing series
   bool gas_dirty_ = false;
   int member_con_mask_ = 0;  // HXC_* bits that only per-member constraint series contribute

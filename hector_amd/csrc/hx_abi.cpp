@@ -343,6 +343,35 @@ int hx_setvar_dated_mix(hx_core *core, const char *capability, const int *years,
   if (!core || !capability) return fail("hx_setvar_dated_mix: null core or capability");
   HX_TRY(core->core->setvar_dated_mix(capability, years, nyears, basis, nbasis, coeff, units))
 }
+int hx_mix_capabilities(hx_core *core, const char *const **names, int *count) {
+  static thread_local std::vector<std::string> store;
+  static thread_local std::vector<const char *> ptrs;
+  if (!core) return fail("hx_mix_capabilities: null core");
+  HX_TRY({
+    store = core->core->mix_capabilities();
+    ptrs.clear();
+    for (auto &n : store) ptrs.push_back(n.c_str());
+    if (names) *names = ptrs.data();
+    if (count) *count = (int)ptrs.size();
+  })
+}
+int hx_setvar_scenario_mix(hx_core *core, const char *const *scenarios, int nscen, const double *coeff,
+                           int *nseries) {
+  if (!core) return fail("hx_setvar_scenario_mix: null core");
+  if (nscen < 1 || nscen > HX_MIX_MAX_BASIS)
+    return fail(("hx_setvar_scenario_mix: nscen = " + std::to_string(nscen) + " outside 1.." +
+                 std::to_string(HX_MIX_MAX_BASIS)).c_str());
+  if (!scenarios || !coeff) return fail("hx_setvar_scenario_mix: null scenarios or coeff");
+  std::vector<std::string> paths;
+  for (int k = 0; k < nscen; ++k) {
+    if (!scenarios[k]) return fail("hx_setvar_scenario_mix: null scenario path");
+    paths.push_back(scenarios[k]);
+  }
+  HX_TRY({
+    const int ns = core->core->setvar_scenario_mix(paths, coeff);
+    if (nseries) *nseries = ns;
+  })
+}
 int hx_lane_of_member(hx_core *core, int *out) {
   if (!out) return fail("null argument");
   HX_TRY(core->core->lane_of_member(out))

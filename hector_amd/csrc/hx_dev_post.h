@@ -3,7 +3,9 @@
 // window (hx_metric_kernel), of a window of two series (hx_pair_metric_kernel), exact weighted
 // quantiles over the members (hx_q_* kernels),
 // weighted bin sums against fixed edges (hx_bin_kernel) and weighted moments with per-member
-// predictors (hx_mom_* / hx_moments_kernel).  The reference has no counterpart: its
+// predictors (hx_mom_* / hx_moments_kernel) -- and, ahead of a run, the per-member input tables
+// built from mixes (hx_mseries_mix_kernel) and the gas pre-pass from recipes (hx_gas_mix_kernel).
+// The reference has no counterpart: its
 // hosts aggregate fetchvars() data frames in R.  Compiled for the GPU through hx_post.hip -- a
 // translation unit of its own, so the year-loop kernels' code generation does not see it -- and
 // for the host-emulation build through ensemble_core.cpp (score, metric, pair-metric and series kernels only: the
@@ -551,6 +553,137 @@ hipError_t hx_launch_mseries_mix(const double *coeff, const int *member_of_lane,
                      dim3(256), 0, st, coeff, member_of_lane, n, npad, rows, basis, nrows, nbasis, table);
   return hipGetLastError();
 }
+
+// ===========================================================================
+// The gas pre-pass from RECIPES: hx_gas_kernel's two rows (N2O[t]; halocarbon + albedo + misc
+// forcing) for a core in which a member's N2O_emissions, RF_albedo or <gas>_emissions is a mix
+// (hx_setvar_dated_mix).  No [ns][npad] table of emissions exists: the lane takes the coefficients of
+// ONE input at a time through member_of_lane (a padding lane: the last member's), evaluates the
+// definition in every covered year -- products rounded before they are added, ascending k, as
+// hx_mseries_mix_kernel does -- and takes the shared value elsewhere.  The value chain is the host's
+// (EnsembleCore::build_shared), operation for operation, contraction off.
+//   par [3 + 3 nh][npad], ser [4 + 2 nh][ns], h0 [nh]: as hx_gas_kernel, gases in the order their
+//       forcings are summed
+//   nat [ns]: N2O_natural_emissions;  molar [nh]: molar masses
+//   rec [2 + nh][2]: input j's {nbasis (0 = shared), index of its block}: j = 0 N2O_emissions,
+//       1 RF_albedo, 2 + h the emissions of gas h.  Block b: coeff + coff[b] is [nbasis][n] in member
+//       order, basis + b * HX_MIX_MAX_BASIS * ns is [nbasis][ns] dense in years, cover + b * ns is
+//       non-zero in the years the mix lists.  basis, cover, ser, nat and rec are indexed by the loop
+//       counters alone: scalar loads.
+// Gases OUTSIDE, years inside: a lane holds one input's (at most 8) coefficients and one recurrence;
+// the forcing row is accumulated in memory in the host's order -- 0.0 + gas 0 + gas 1 ..., then
+// (that + albedo) + misc -- so (nh + 1) read-modify-writes of a coalesced row per year.  Lane-local:
+// the host-emulation build runs it as it stands.
+// ===========================================================================
+// the definition's value in year iy from the coefficients c[] and the basis block b (K vectors)
+#define HX_GASMIX_VALUE(dst, iy)                                              \
+  do {                                                                        \
+    double s_ = c[0] * b[iy];                                                 \
+    _Pragma("unroll") for (int k_ = 1; k_ < HX_MIX_MAX_BASIS; ++k_)           \
+      if (k_ < K) {                                                           \
+        const double p_ = c[k_] * b[(size_t)k_ * (size_t)ns + (size_t)(iy)];  \
+        s_ = s_ + p_;                                                         \
+      }                                                                       \
+    dst = s_;                                                                 \
+  } while (0)
+
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__global__ __launch_bounds__(64) void hx_gas_mix_kernel(const double *__restrict__ par, const double *__restrict__ ser,
+                                                        const double *__restrict__ h0, const double *__restrict__ nat,
+                                                        const double *__restrict__ molar, const int *__restrict__ rec,
+                                                        const double *__restrict__ coeff, const long long *__restrict__ coff,
+                                                        const double *__restrict__ basis, const int *__restrict__ cover,
+                                                        const int *__restrict__ member_of_lane, int n, int nh, int ns,
+                                                        int npad, double *__restrict__ n2o_out,
+                                                        double *__restrict__ rf_other_out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= npad) return;
+  const size_t np = (size_t)npad, mem = (size_t)lane;
+  const size_t m = (size_t)min(member_of_lane[lane], n - 1);
+  double c[HX_MIX_MAX_BASIS];
+  auto take = [&](int j, const double *&b, const int *&cov) {   // input j's recipe; returns nbasis
+    const int K = rec[2 * j], blk = rec[2 * j + 1];
+#pragma unroll
+    for (int k = 0; k < HX_MIX_MAX_BASIS; ++k) c[k] = k < K ? coeff[coff[blk] + (long long)((size_t)k * (size_t)n + m)] : 0.0;
+    b = basis + (size_t)blk * HX_MIX_MAX_BASIS * (size_t)ns;
+    cov = cover + (size_t)blk * (size_t)ns;
+    return K;
+  };
+  const double *b = nullptr;
+  const int *cov = nullptr;
+  {  // N2OComponent::run (src/n2o_component.cpp:152-191)
+    const double N0 = par[mem], TN2O0 = par[np + mem], UC = par[2 * np + mem];
+    const double *em = ser, *ncon = ser + ns;
+    const int K = rec[0] ? take(0, b, cov) : 0;
+    const double N0f = isnan(ncon[0]) ? N0 : ncon[0];
+    double n2o = N0f;
+    n2o_out[mem] = n2o;
+    for (int iy = 1; iy < ns; ++iy) {
+      const double tau_n = TN2O0 * pow(n2o / N0f, -0.05);
+      double e = em[iy];
+      if (K && cov[iy]) {
+        double v;
+        HX_GASMIX_VALUE(v, iy);
+        e = v + nat[iy];
+      }
+      n2o = n2o + (e / UC - n2o / tau_n);
+      if (!isnan(ncon[iy])) n2o = ncon[iy];
+      n2o_out[(size_t)iy * np + mem] = n2o;
+    }
+  }
+  // HalocarbonComponent::run (src/halocarbon_component.cpp:181-229), one gas after the other
+  for (int h = 0; h < nh; ++h) {
+    const double tau = par[(size_t)(3 + 3 * h) * np + mem], rho = par[(size_t)(4 + 3 * h) * np + mem],
+                 delta = par[(size_t)(5 + 3 * h) * np + mem];
+    const double expfac = exp(-(1 / tau));
+    const double *dser = ser + (size_t)(4 + 2 * h) * ns, *hcon = ser + (size_t)(5 + 2 * h) * ns;
+    const double mm = molar[h];
+    const int K = rec[2 * (2 + h)] ? take(2 + h, b, cov) : 0;
+    double conc = h0[h];
+    for (int iy = 1; iy < ns; ++iy) {
+      double dconc = dser[iy];
+      if (K && cov[iy]) {
+        double v;
+        HX_GASMIX_VALUE(v, iy);
+        const double emissMol = v / mm * 1.0;
+        dconc = emissMol / (0.1 * 1.8);
+      }
+      conc = conc * expfac + dconc * tau * (1.0 - expfac);
+      if (!isnan(hcon[iy])) conc = hcon[iy];
+      const double rf_un = rho * conc;
+      const size_t o = (size_t)iy * np + mem;
+      const double before = h == 0 ? 0.0 : rf_other_out[o];
+      rf_other_out[o] = before + (rf_un + delta * rf_un);
+    }
+  }
+  {  // + RF_albedo + RF_misc (ForcingComponent::run, src/forcing_component.cpp:400-487)
+    const double *alb = ser + 2 * (size_t)ns, *misc = ser + 3 * (size_t)ns;
+    const int K = rec[2] ? take(1, b, cov) : 0;
+    for (int iy = 0; iy < ns; ++iy) {
+      const size_t o = (size_t)iy * np + mem;
+      double a = alb[iy];
+      if (K && cov[iy]) HX_GASMIX_VALUE(a, iy);
+      const double rf_h = (nh == 0 || iy == 0) ? 0.0 : rf_other_out[o];
+      rf_other_out[o] = (rf_h + a) + misc[iy];
+    }
+  }
+}
+
+hipError_t hx_launch_gas_mix(const double *par, const double *ser, const double *h0, const double *nat,
+                             const double *molar, const int *rec, const double *coeff, const long long *coff,
+                             const double *basis, const int *cover, const int *member_of_lane, int n, int nh,
+                             int ns, int npad, double *n2o_out, double *rf_other_out, hipStream_t st) {
+  if (n < 1 || nh < 0 || ns < 1 || npad < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hx_gas_mix_kernel, dim3((npad + 63) / 64), dim3(64), 0, st, par, ser, h0, nat, molar, rec,
+                     coeff, coff, basis, cover, member_of_lane, n, nh, ns, npad, n2o_out, rf_other_out);
+  return hipGetLastError();
+}
+#undef HX_GASMIX_VALUE
 
 // ===========================================================================
 // Pair metrics: one double per member from a window of TWO series of that member, a (reported /

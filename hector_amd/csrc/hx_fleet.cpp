@@ -329,6 +329,25 @@ void Fleet::setvar_dated_mix(const std::string &cap, const int *years, int nyear
                                       part[j].empty() ? nullptr : part[j].data(), units);
   }
 }
+int Fleet::setvar_scenario_mix(const std::vector<std::string> &paths, const double *coeff) {
+  if (!coeff) throw std::runtime_error("hx_setvar_scenario_mix: null coeff");
+  use(shards_[0]);
+  const auto plan = shards_[0].core->plan_scenario_mix(paths);   // (every shard holds the same scenario)
+  const int y0 = start_date(), ns = end_date() - y0 + 1, K = (int)paths.size();
+  for (size_t j = 0; j < (size_t)K * (size_t)n_; ++j)
+    if (!std::isfinite(coeff[j])) throw std::runtime_error("hx_setvar_scenario_mix: a coefficient is not finite");
+  std::vector<int> years((size_t)ns);
+  for (int i = 0; i < ns; ++i) years[(size_t)i] = y0 + i;
+  // every check of every mix first (its own shard's slice of one coefficient row suffices for the
+  // shape; the values were checked above), then the mixes: nothing can be refused half way
+  for (const auto &p : plan)
+    for (Shard &s : shards_) {
+      use(s);
+      s.core->check_dated_mix(p.capability, years.data(), ns, p.basis.data(), K, coeff, nullptr);
+    }
+  for (const auto &p : plan) setvar_dated_mix(p.capability, years.data(), ns, p.basis.data(), K, coeff, nullptr);
+  return (int)plan.size();
+}
 void Fleet::lane_of_member(int *out) {
   for (Shard &s : shards_) { use(s); s.core->lane_of_member(out + s.offset); }
 }

@@ -82,6 +82,10 @@ class Fleet {
   // coeff[k * n_members + member]: every shard takes its members' columns and the whole basis
   void setvar_dated_mix(const std::string &capability, const int *years, int nyears, const double *basis,
                         int nbasis, const double *coeff, const char *units);
+  std::vector<std::string> mix_capabilities() const { return shards_[0].core->mix_capabilities(); }
+  // hx_setvar_scenario_mix: one mix per differing input series over startDate..endDate, the
+  // scenarios' series as basis; returns the number of series.  Refused whole or applied whole.
+  int setvar_scenario_mix(const std::vector<std::string> &paths, const double *coeff);
   void lane_of_member(int *out);  // lane inside the member's shard
   void reset(double date);
   void run(double runtodate);  // queues every device, waits for none

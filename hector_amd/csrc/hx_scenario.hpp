@@ -53,6 +53,9 @@ class Scenario {
 
   std::vector<Halocarbon> halocarbons;
   std::string source;
+  // everything the file held, as "section.key" (comparing two scenarios)
+  const std::map<std::string, std::string> &all_scalars() const { return scalars_; }
+  const std::map<std::string, std::vector<double>> &all_series() const { return series_; }
 
  private:
   static Scenario load_pack(const std::string &path);

@@ -141,15 +141,45 @@ int hx_setvar_dated_members(hx_core *core, const char *capability, const int *ye
  * n_members x n_years.  The next hx_run uploads it and expands it on the device into the 8 B per
  * member-year table the run kernels read (one store-bound kernel); new coefficients for the same
  * years cost nbasis x n_members doubles of upload and that kernel again.
+ * NAMES.  ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions -- the run kernels
+ * read their table -- and the inputs of the N2O and halocarbon components and the albedo forcing:
+ * N2O_emissions ("Tg N"), RF_albedo ("W/m2") and <gas>_emissions ("Gg") of every halocarbon the
+ * scenario holds (hx_mix_capabilities lists them for a core).  These three kinds never have a table
+ * of emissions, on the host or on the device: hx_setvar_dated_members keeps refusing them, so their
+ * mix overlays the scenario's shared series, and a lane-per-member pre-pass ahead of the year loop
+ * evaluates the definition where the N2O and halocarbon recurrences read the value and writes the
+ * two rows the run kernels take (N2O; halocarbon + albedo + misc forcing: 16 B per member-year, as
+ * for per-member N0 or tau_<gas>).  N2O_concentration, RF_N2O, <gas>_concentration, RF_<gas> and
+ * RF_albedo are then per member.  The aerosol emissions (SO2, BC, OC, NH3), the ozone / OH
+ * precursors (NOX, CO, NMVOC), SV, RF_misc, CH4N and N2O_natural_emissions cannot be mixed.
  * ERRORS (every message names the function; a refused call changes nothing): a capability other
- * than ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions (the constraint
- * series, with NaN = none and interpolated points, are no linear mix); units that do not match
+ * than ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions and the names above (the
+ * constraint series, with NaN = none and interpolated points, are no linear mix); units that do not match
  * (rule of hx_setvar_dated_members); nbasis outside 0..HX_MIX_MAX_BASIS; nyears < 1; a year
  * outside startDate..endDate or listed twice; a basis value or coefficient that is not finite;
  * NULL years, basis or coeff with nbasis > 0. */
 #define HX_MIX_MAX_BASIS 8
 int hx_setvar_dated_mix(hx_core *core, const char *capability, const int *years, int nyears,
                         const double *basis, int nbasis, const double *coeff, const char *units);
+/* The names hx_setvar_dated_mix accepts for THIS core: the list holds the scenario's halocarbons.
+ * The strings live until the next call on this thread. */
+int hx_mix_capabilities(hx_core *core, const char *const **names, int *count);
+/* Whole scenarios as members of one core: scenarios[nscen] are scenario files (pack or INI),
+ * coeff[k * n_members + member] the member's weight of scenario k, 1 <= nscen <= HX_MIX_MAX_BASIS.
+ * The library reads each file with its own scenario reader, finds every dated input series in which
+ * one of them differs from the core's (bit for bit), and sets for each ONE mix over
+ * startDate..endDate whose basis is the scenarios' series and whose coefficients are coeff
+ * (*nseries, may be NULL: how many).  With one-hot coefficients a member's inputs are its scenario's
+ * own bits: 1.0 * x + (0.0 * y) + ... is exact for finite values.  Cost: that of the mixes.
+ * ERRORS (the message names the function and the section and key at fault; a refused call changes
+ * nothing): nscen outside 1..HX_MIX_MAX_BASIS; startDate or endDate that differ; a different list of
+ * halocarbons; ANY scalar that differs or is missing on one side (core.run_name, a label, excepted):
+ * the members share one parameter table and one spinup; a series that differs and cannot be a mix
+ * -- a constraint, SV, RF_misc, CH4N, N2O_natural_emissions, and the aerosol and ozone / OH precursor
+ * emissions, so the shipped SSPs, which differ in so2.SO2_emissions among others, are refused
+ * against each other -- or that is missing on one side; a coefficient that is not finite. */
+int hx_setvar_scenario_mix(hx_core *core, const char *const *scenarios, int nscen, const double *coeff,
+                           int *nseries);
 /* Keep every year's component state in HBM so hx_reset can return to any computed date --
  * what the reference's per-component tseries records provide (src/simpleNbox.cpp:708-840,
  * src/ocean_component.cpp:767-846).  272 B per member-year (one biome); default off. */
