@@ -1600,6 +1600,14 @@ class Core:
         self._ck(self._lib.hx_last_run_variant(self._h, ctypes.byref(v)))
         return v.value
 
+    def last_run_retries(self):
+        """1: the last run() took the solver's retries inside the step loop, discarded steps executed
+        and counted (solver_steps recorded, or HECTOR_AMD_FAITHFUL_RETRIES=1); 0: at the head of the
+        segment (hx_last_run_retries)."""
+        v = ctypes.c_int()
+        self._ck(self._lib.hx_last_run_retries(self._h, ctypes.byref(v)))
+        return v.value
+
     def last_spinup_ms(self):
         v = ctypes.c_double()
         self._ck(self._lib.hx_last_spinup_ms(self._h, ctypes.byref(v)))

@@ -2608,6 +2608,28 @@ void EnsembleCore::run(double runtodate) {
     check(hipMemsetAsync(d_cost_, 0, sizeof(double) * (size_t)npad_, stream_), "zero lane cost");
     cost_from_iy_ = 0;
   }
+  {  // The run kernels decide a segment's retries before its first step and then count the steps
+    // they execute (solve_year, hx_open_retry); a launch that records solver_steps -- the
+    // reference's count, discarded steps included -- takes the retries where the reference does.
+    // HECTOR_AMD_FAITHFUL_RETRIES=1: always; =0: never, solver_steps is then the count of executed
+    // steps (read at every launch; the tests hold the two paths against each other).
+    const char *e = getenv("HECTOR_AMD_FAITHFUL_RETRIES");
+    int faithful = d_out_[HXO_NSTEPS] ? 1 : 0;
+    if (e && e[0] == '1') faithful = 1;
+    else if (e && e[0] == '0') faithful = 0;
+    // The NBP-capable kernels (six solver variables: an NBP constraint somewhere, or
+    // HECTOR_AMD_EXTENDED_NBP) always take the faithful path.  Their first right-hand side of a
+    // fresh stepper exists twice in the code, ahead of the step loop and inside its retry block,
+    // and on the GPU the two copies need not round alike (contraction is per copy; not traced in the
+    // assembly): the opening retry, which goes through the first copy where the in-loop retry goes through the second,
+    // gave CO2 that differs from the faithful path's in its last bits (host emulation: none).  Held
+    // to the reference's path they compute what they always did.
+    if (((kc_.con_mask | member_con_mask_) & HXC_NBP) || getenv("HECTOR_AMD_EXTENDED_NBP")) faithful = 1;
+    if (faithful != kc_.faithful_retries) {
+      kc_.faithful_retries = faithful;
+      upload_args();
+    }
+  }
   last_run_prewarmed_ = false;
   prewarm_end();
   check(hipEventRecord(ev0_, stream_), "event");
@@ -2668,6 +2690,7 @@ void EnsembleCore::run(double runtodate) {
   const bool w2 = !pair && con <= 1 && two_wave_expected();
   last_run_w2_ = w2;
   last_run_con_ = con;
+  last_run_faithful_ = kc_.faithful_retries;
   if (pair)
     check(hx_launch_run_pair(d_args_, npad_, d_out_[HXO_HEATFLUX] != nullptr, ker_per_member_, last_iy_, target,
                              stream_, pair_cons != 0, B_), "run kernel (pair)");

@@ -305,6 +305,9 @@ class EnsembleCore {
   // hx_run_kernel): 0 plain, -2 plain + diagnostics, -1 extended, 1 extended with the NBP
   // machinery, 2 carbon tracking
   int last_run_variant() const { return last_run_con_; }
+  // 1: the last run took the solver's retries inside the step loop (the faithful path), 0: at the
+  // head of the segment (HxConst::faithful_retries as that launch saw it)
+  int last_run_retries() const { return last_run_faithful_; }
   double last_spinup_ms() const { return spin_ms_; }
   hipStream_t stream() const { return stream_; }
 
@@ -532,6 +535,7 @@ class EnsembleCore {
   int key_order_mode_ = 0;               // HECTOR_AMD_KEY_ORDER (experiments, see assign_lanes)
   bool last_run_w2_ = false;
   int last_run_con_ = 0;
+  int last_run_faithful_ = 1;
   bool two_wave_expected() const;   // run() will take hx_run_kernel<HX_B1W2> (see assign_lanes)
   int simds_ = 1024;              // SIMDs of this core's device (4 per compute unit)
   mutable double run_ms_ = 0, spin_ms_ = 0;

@@ -308,6 +308,26 @@ __device__ __forceinline__ bool pair_retry(PairCtl &c, unsigned &status) {
   return reload;
 }
 
+// A segment's retries decided before its first step (solve_year's opening retry: the argument is
+// there).  Both wavefronts run it at the head of a segment on identical inputs and reach the same
+// target; the step loop's own pair_retry then never fires.  pair_open_need: the target itself as
+// the probe; pair_open_retry: pair_retry's loop with its expressions unchanged (no step has been
+// taken: t == t_start).  The caller reloads its pools.
+__device__ __forceinline__ bool pair_open_need(const PairCtl &c) {
+#pragma clang fp contract(off)
+  return c.stepping && ((c.t + (c.t_target - c.t)) - c.ode_start) > c.max_ts;
+}
+__device__ __forceinline__ void pair_open_retry(PairCtl &c, unsigned &status) {
+#pragma clang fp contract(off)
+  do {
+    ++c.retry;
+    c.t_target = c.t_start + (c.t_target - c.t_start) / 2.0;
+    c.sdt = c.t_target - c.t;
+    c.dtl = c.sdt;
+    if (c.retry >= 8) { status |= HX_ERR_RETRIES; c.alive = false; c.stepping = false; }
+  } while (c.stepping && ((c.t + c.dtl) - c.ode_start) > c.max_ts);
+}
+
 #ifdef HX_PHASE_CLOCK
 __device__ __forceinline__ void hx_pstamp(long long *clkp, int k) {
   volatile long long *clk = clkp;
@@ -377,6 +397,12 @@ __global__ __launch_bounds__(128) HX_PAIR_OCC void hx_pair_kernel(const HxArgs *
   int par = 0;      // which half of s_st the next step hand-off uses
   int blk0 = -1;    // first year index of the current DOECLIM block
   const double eps_abs = kc.eps_abs, eps_rel = kc.eps_rel;
+  // (a constant of the launch, the same on both sides: see HxConst::faithful_retries)
+#ifndef HX_NO_OPENING_RETRY
+  const bool open_retry = kc.faithful_retries == 0;
+#else
+  constexpr bool open_retry = false;
+#endif
 #ifdef HX_PHASE_CLOCK
   __shared__ long long s_pclk[2][24];
   if (lane == 0) { for (int k = 0; k < 23; ++k) s_pclk[role][k] = 0; s_pclk[role][23] = (long long)__builtin_readcyclecounter(); }
@@ -560,6 +586,10 @@ __global__ __launch_bounds__(128) HX_PAIR_OCC void hx_pair_kernel(const HxArgs *
         c.stepping = seg;
         // (as in solve_year: the fresh stepper's first RHS ahead of the loop, the attempt as
         // straight-line code for every lane, retries behind a uniform rare branch)
+        // (the segment's retries first -- pair_open_retry; the RHS below is then the fresh stepper's)
+        if (open_retry && __any(pair_open_need(c))) {
+          if (pair_open_need(c)) { pair_open_retry(c, status); load_pools(); }
+        }
         first_rhs();
         for (bool go_ = __any(c.stepping); go_; go_ = __any(c.stepping)) {
           if (__builtin_expect(__any(pair_clip_need(c)), 0)) {
@@ -1031,6 +1061,10 @@ __global__ __launch_bounds__(128) HX_PAIR_OCC void hx_pair_kernel(const HxArgs *
         c.stepping = seg;
         double y0c = 0, y4c = 0, y3c = total(soil);  // the ocean side's atmosphere / ocean totals / soil pool after the last accepted step
         auto first_rhs = [&]() { rrs[0] = hx_div1(luc_e, tot0); rhs(y, dxdt, 0); };
+        // (the segment's retries first, as on the ocean side: the same decision from the same inputs)
+        if (open_retry && __any(pair_open_need(c))) {
+          if (pair_open_need(c)) { pair_open_retry(c, status); load_pools(); }
+        }
         first_rhs();  // (the fresh stepper's first RHS, ahead of the loop: see the ocean side)
         for (bool go_ = __any(c.stepping); go_; go_ = __any(c.stepping)) {
           double xn[2], dn[2];

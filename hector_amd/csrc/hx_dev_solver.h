@@ -44,6 +44,35 @@ template <int B, int CON> constexpr bool hx_flat_control() {
 #endif
 }
 
+// Which instantiations decide a segment's retries BEFORE its first step (solve_year, "opening
+// retry"): the ones with the flat control -- plain, diagnostics and extended kernels of one to four
+// biomes, and the two-wave flavour.  The kernels at the register file's limit (five and more
+// biomes, looped, carbon tracking) keep the retries inside the step loop only.
+// -DHX_NO_OPENING_RETRY: no kernel has the opening block (the form before it, for comparisons).
+template <int B, int CON> constexpr bool hx_open_retry() {
+#ifdef HX_NO_OPENING_RETRY
+  return false;
+#else
+  return hx_flat_control<B, CON>();
+#endif
+}
+// ... and, kernel by kernel (HF: heat-flux sum, KERPM: per-member diffusivity), without the ten of
+// those 60 instantiations that came out of the register allocator with MORE registers or scratch
+// than without the block (static comparison with -DHX_NO_OPENING_RETRY, profiles/
+// opening_retry_ab.md section 2): they keep the retries inside the step loop, their assembly is
+// unchanged.
+template <int B, bool HF, bool KERPM, int CON> constexpr bool hx_open_retry_k() {
+  if (!hx_open_retry<B, CON>()) return false;
+  if (B == HX_B1W2 && HF && KERPM && CON == 1) return false;    // 260 -> 264 B of scratch
+  if (B == HX_B1W2 && HF && !KERPM && CON == -2) return false;  // 255 -> 256 registers
+  if (B == 1 && HF && CON == 1) return false;                    // 428 -> 430 (KERPM), 430 -> 434
+  if (B == 1 && HF && KERPM && CON == 0) return false;           // 412 -> 414
+  if (B == 3 && CON == -2 && HF == KERPM) return false;          // 470 -> 472 (both), 396 -> 398 (neither)
+  if (B == 3 && !HF && !KERPM && CON == -1) return false;        // 398 -> 400
+  if (B == 4 && HF && KERPM && (CON == 1 || CON == -1)) return false;   // 498 -> 500, 484 -> 486
+  return true;
+}
+
 // rhs constants that only change at a stash (pools frozen in between,
 // src/simpleNbox-runtime.cpp:809-840)
 struct Interval {
@@ -839,7 +868,8 @@ __device__ __forceinline__ double pow_m15(double x) {
 // block for all lanes.  Lanes in reduced-timestep mode take up to 4 segments a
 // year, the others idle through the extra ones; the expensive step and stash
 // blocks are never interleaved lane by lane.
-template <int B, bool SPIN, int CON = 0>
+// OPEN: the segment's retries are decided before its first step (hx_open_retry_k; the caller's choice)
+template <int B, bool SPIN, int CON = 0, bool OPEN = false>
 __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
                                            double t0, double tnew, const YearCon &yc) {
   constexpr int NP = hx_nbp<CON>() ? 6 : 5;  // solver variables (see rhs)
@@ -981,16 +1011,60 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
     const double t_start = t;
     double t_target = tnew, dtl = m.sdt;
     double dxdt[NP];
+    constexpr bool FLAT = hx_flat_control<B, CON>();
+    // The opening retry (hx_open_retry): a segment's retries, decided before its first step.
+    //  - A retry is certain as soon as the target lies more than max_ts behind ode_start: dt is
+    //    clipped to the target, so the attempt that would reach it has t + dt == t_target and trips
+    //    the test in the step loop below -- unless an earlier attempt has tripped it already.
+    //  - Nothing computed before that retry enters the result: the retry block sets t back to
+    //    t_start, halves the target, takes dt = the new target - t_start, reloads the pools and
+    //    starts a fresh stepper; what follows depends on t_start, the halved target, the reloaded
+    //    pools and the retry count alone.  Every step accepted before it is thrown away.
+    //  - After it the block tests the new target itself, (t_start + dt) - ode_start with dt = target
+    //    - t_start, and halves again while that trips.
+    // So the same loop runs HERE with the target as the probe -- the in-loop block's own
+    // expressions, hence the same sequence of targets bit for bit (times are integers plus dyadic
+    // fractions: t + (t_target - t) is exact) -- and the step loop starts at the target it would
+    // have ended up with; its own retry block then never fires (t + dt never passes the target).
+    // The reload uses the live values (ahead of w2_park_out), and the pre-loop RHS below is the
+    // fresh stepper's first evaluation.  What it saves is the discarded passes: about one a model
+    // year in the mean wavefront, 1.9 in the costliest (profiles/opening_retry_ab.md).
+    // m.nsteps then counts the steps that were executed, not the reference's, so a launch that
+    // records solver_steps (or HECTOR_AMD_FAITHFUL_RETRIES=1: HxConst::faithful_retries, read once
+    // a launch into m.fretry) skips this block and takes the retries where the reference does.
+    // Known departure: a member that would raise HX_ERR_STEPFAIL inside steps a retry discards
+    // ends without that flag here (the reference has no step limit at all).
+    static_assert(!OPEN || FLAT, "the opening retry is written for the flat control (hx_open_retry)");
+    [[maybe_unused]] bool dead0 = false;
+    if constexpr (!SPIN && OPEN) {
+      int fr = m.fretry;
+#ifndef HX_HOST_EMULATION
+      asm volatile("" : "+s"(fr));   // (a scalar of the launch, tested here: not a flag per lane)
+#endif
+      const hx_mask need0m = hx_mask_of(seg) & hx_mask_gt((t + (t_target - t)) - m.ode_start, m.max_ts);
+      if (fr == 0 && need0m != 0) {
+        HX_COUNT(m, 23);  // segments with an opening retry
+        bool need0 = hx_lane(need0m);
+        while (need0) {
+          ++retry;
+          t_target = t_start + (t_target - t_start) / 2.0;
+          m.sdt = t_target - t;
+          dtl = m.sdt;
+          if (retry >= 8) { m.status |= HX_ERR_RETRIES; dead0 = true; }
+          need0 = !dead0 && ((t + dtl) - m.ode_start) > m.max_ts;
+        }
+        if (hx_lane(need0m)) load_pools(false);   // (a dead lane: `alive` follows from the status after the loop)
+      }
+    }
     // A freshly constructed stepper evaluates the RHS once before its first step (FSAL starts
     // empty): here, ahead of the loop, for every lane -- only the lanes of this segment use it.
     rhs<B, SPIN, CON>(m, K, K2, yc, t, y, dxdt);
     if constexpr (LAND2) dxdt[1] = hx_div1(m.luc_e, (y[1] + y[2]) + y[3]);   // (the loss rate itself: see LAND2)
     int fails = 0;
-    constexpr bool FLAT = hx_flat_control<B, CON>();
     bool stepping = seg;   // (nested form; the flat one uses it inside the retry block only)
     // The lanes that are stepping, as the wavefront's lane mask in a scalar register pair (see the
     // end of the pass): votes are scalar comparisons of it, and nothing rebuilds it from booleans.
-    [[maybe_unused]] hx_mask ST = FLAT ? hx_mask_of(seg) : 0;
+    [[maybe_unused]] hx_mask ST = FLAT ? hx_mask_of(seg && !dead0) : 0;
 #define HX_STEP_GO() (FLAT ? ST != 0 : (bool)__any(stepping))
     HX_TAB_HEAD();
     if constexpr (hx_w2<B>()) w2_park_out<B>(m);

@@ -747,6 +747,9 @@ void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
     cmk = (unsigned)args->kc.con_mask; msk = args->buf.ms_mask; omk = args->buf.out_mask0;
     m.omk = omk;
   }
+  // ... and, in the kernels that decide a segment's retries ahead of its first step, whether this
+  // launch has to take them inside the step loop instead (solve_year)
+  if constexpr (hx_open_retry_k<B, HF, KERPM, CON>()) m.fretry = args->kc.faithful_retries;
   // (... and laundered again at the head of every region that tests them: a test of an opaque
   // but loop-invariant value is itself loop-invariant, and the optimiser would compute all ~50 of
   // them ahead of the year loop and keep them in -- spilled -- scalar registers)
@@ -1212,7 +1215,7 @@ void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
         }
         yc.t_half = year - 0.5;
       }
-      solve_year<B, false, CON>(m, args->kc, year - 1.0, year, yc);
+      solve_year<B, false, CON, hx_open_retry_k<B, HF, KERPM, CON>()>(m, args->kc, year - 1.0, year, yc);
       cost_steps += m.nsteps; cost_stash += m.nstash;
     }
     HX_FENCE();

@@ -143,6 +143,11 @@ static_assert(HXM_N <= 32, "HxBuffers::ms_mask holds one bit per member series")
 // scenario scalars every lane needs (kernel argument, lives in SGPRs)
 struct HxConst {
   int start_year, ns, baseyear_idx, max_spinup, spinup_chem;
+  // Run kernels: 1 = a segment's retries are taken where the reference takes them, inside the step
+  // loop, discarded steps included (solve_year, hx_open_retry): set by EnsembleCore::run when
+  // solver_steps is recorded or HECTOR_AMD_FAITHFUL_RETRIES=1.  (In the padding behind the five
+  // ints: the tables below stay where they were, see HxArgs.)
+  int faithful_retries;
   double eps_abs, eps_rel, dt0, eps_spinup;
   double M0, lnM0, Tsoil, Tstrat, UC_CH4, TOH0, CCH4;  // M0: the INI value (OH component)
   double M0f, sqrtM0;  // preindustrial CH4 as the forcing sees it (CH4 constraint at startDate)
@@ -163,6 +168,7 @@ struct HxConst {
   // [power, descending][box * 6 + {K0, Kw, 1/Kh, K1, K2, Kb}]
   double kfit[14 * 12];
 };
+static_assert(sizeof(HxConst) == 2392, "HxConst: a new member moves the coefficient tables (see HxArgs)");
 #include "hx_chem_fit.inc"
 static_assert(HX_CHEM_FIT_DEGREE == 13, "HxConst::kfit is sized for degree 13");
 inline void hx_fill_chem_fit(double *t) {

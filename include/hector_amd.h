@@ -1017,6 +1017,16 @@ int hx_last_run_kernel(hx_core *core, const char **name);
  * 498-505, ch4_component.cpp:156-157, simpleNbox-runtime.cpp:567-603); 1 the extended kernel with
  * the NBP constraint's machinery (simpleNbox-runtime.cpp:343-383); 2 carbon tracking. */
 int hx_last_run_variant(hx_core *core, int *variant);
+/* Where the last hx_run took the carbon-cycle solver's retries: *faithful = 1 inside the step loop,
+ * as the reference does (carbon-cycle-solver.cpp:266-276), the steps a retry discards executed and
+ * counted -- what a run that records "solver_steps" gets, or any run under
+ * HECTOR_AMD_FAITHFUL_RETRIES=1; 0 at the head of the segment, before its first step (the default
+ * otherwise; the results are the same bit for bit).  Under HECTOR_AMD_FAITHFUL_RETRIES=0 a run
+ * that records "solver_steps" answers 0 too: that output then counts the executed steps, not the
+ * reference's -- a test setting, and this is how to tell.  A run with an NBP constraint
+ * always answers 1.  (The kernels that always take the retries inside the loop -- five and more
+ * biomes, carbon tracking -- ignore the setting.) */
+int hx_last_run_retries(hx_core *core, int *faithful);
 /* When every wavefront of the last hx_run's year-loop launch started and ended: ticks[2 w] and
  * ticks[2 w + 1] for wavefront w of shard `shard` (64 members in lane order; the small-ensemble
  * kernel has two wavefronts per 64 members), in ticks of the device's constant 100 MHz clock

@@ -73,6 +73,8 @@ def main():
            "passes_with_a_rejecting_lane_per_year": {"mean": float(t[20].mean() / 555), "slowest": float(t[20, slow] / 555)},
            "passes_all_accepting_per_year": {"mean": float(t[21].mean() / 555), "slowest": float(t[21, slow] / 555)},
            "passes_with_a_retry_per_year": {"mean": float(t[22].mean() / 555), "slowest": float(t[22, slow] / 555)},
+           # segments whose retries were taken at their head, before the first step (slot 23)
+           "segments_with_an_opening_retry_per_year": {"mean": float(t[23].mean() / 555), "slowest": float(t[23, slow] / 555)},
            "sections": {}}
     for k, name in SECTIONS.items():
         out["sections"][name] = {"mean_ticks_per_year": float(t[k].mean() / 555),
