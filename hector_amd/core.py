@@ -682,6 +682,15 @@ class Core:
         self._ck(self._lib.hx_enable_history(self._h, 1 if on else 0))
         return self
 
+    def enable_slcf_mixes(self, on=True):
+        """Let setvar_dated_mix, clear_mix, mix_capabilities and setvar_scenarios take the aerosol and
+        ozone / OH precursor emissions too (hx_enable_slcf_mixes): SO2, BC, OC, NH3, NOX, CO and
+        NMVOC -- what the shipped SSPs differ in besides the names that are always mixable.  Off by
+        default; costs nothing until such a mix is set (then 8 B per member-year and row: one row
+        for the aerosols, six for the precursors); switching it off under such a mix is refused."""
+        self._ck(self._lib.hx_enable_slcf_mixes(self._h, 1 if on else 0))
+        return self
+
     def setvar_dated(self, var, years, values, unit=None):
         y = np.ascontiguousarray(np.atleast_1d(np.asarray(years, dtype=np.int32)))
         v = np.ascontiguousarray(np.broadcast_to(np.asarray(values, dtype=np.float64), y.shape))

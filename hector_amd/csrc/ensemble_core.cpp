@@ -75,6 +75,10 @@ hipError_t hx_launch_gas_mix(const double *par, const double *ser, const double 
                              const double *molar, const int *rec, const double *coeff, const long long *coff,
                              const double *basis, const int *cover, const int *member_of_lane, int n, int nh,
                              int ns, int npad, double *n2o_out, double *rf_other_out, hipStream_t st);
+hipError_t hx_launch_slcf_mix(const double *ser, const double *kon, const int *rec, const double *coeff,
+                              const long long *coff, const double *basis, const int *cover,
+                              const int *member_of_lane, int n, int ns, int npad, double *const *rows7,
+                              hipStream_t st);
 hipError_t hx_launch_bin(const double *var, int n, int npad, int iy0, int nrows, const unsigned long long *q,
                          const double *edges, int K, unsigned long long *sums, hipStream_t stream);
 hipError_t hx_launch_q_minmax(const double *var, int n, int npad, int iy0, int ny,
@@ -614,6 +618,7 @@ void EnsembleCore::free_device() {
   fr(d_hist_status_);
   fr(d_gas_par_); fr(d_gas_ser_); d_gas_par_ = d_gas_ser_ = nullptr;
   fr(d_gas_mix_); d_gas_mix_ = nullptr;
+  fr(d_slcf_mix_); d_slcf_mix_ = nullptr;
   fr(d_cost_); d_cost_ = nullptr; cost_from_iy_ = -1;
   fr(d_wave_clk_); d_wave_clk_ = nullptr;
   fr(d_bscratch_); d_bscratch_ = nullptr;
@@ -740,7 +745,7 @@ HxBuffers EnsembleCore::buffers() const {
   b.dpart2 = d_dpart_ ? d_dpart_ + (size_t)npad_ * hx_doeclim_block_years() : nullptr;
   for (int v = 0; v < HXO_NVAR; ++v) b.out[v] = d_out_[v];
   b.hist = d_hist_; b.hist_status = d_hist_status_;
-  for (int k = 0; k < HXM_N; ++k) b.mseries[k] = d_mseries_[k];
+  for (int k = 0; k < HXM_N; ++k) (k < HXM_OH_B ? b.mseries[k] : HXM_SLCF(b, k)) = d_mseries_[k];
   b.uparams = d_uparams_;
   b.uderived = d_uparams_ ? d_uparams_ + HX_NPARAM(B_) : nullptr;
   b.uni_k = (row_uniform_[HXP_TT] && row_uniform_[HXP_TU] && row_uniform_[HXP_TWI] && row_uniform_[HXP_TID]) ? 1 : 0;
@@ -1193,6 +1198,34 @@ void EnsembleCore::enable_history(bool on) {
 }
 
 namespace {
+// the short-lived climate forcer inputs hx_enable_slcf_mixes adds to the mix verb, in the order
+// hx_slcf_mix_kernel numbers them: the four aerosol emissions (one group of rows, HXM_RF_AERO), the
+// three ozone / OH precursors (the other, HXM_OH_B .. HXM_O3_NMVOC)
+struct SlcfDef { const char *name; const char *sections[2]; const char *units; };
+const SlcfDef kSlcf[7] = {
+    {"SO2_emissions", {"so2", nullptr}, "Gg S"},       {"BC_emissions", {"bc", nullptr}, "Tg"},
+    {"OC_emissions", {"oc", nullptr}, "Tg"},           {"NH3_emissions", {"nh3", nullptr}, "Tg"},
+    {"NOX_emissions", {"OH", "ozone"}, "Tg N"},        {"CO_emissions", {"OH", "ozone"}, "Tg CO"},
+    {"NMVOC_emissions", {"OH", "ozone"}, "Tg NMVOC"},
+};
+int slcf_index(const std::string &capability) {
+  for (int j = 0; j < 7; ++j) if (capability == kSlcf[j].name) return j;
+  return -1;
+}
+}  // namespace
+
+void EnsembleCore::enable_slcf_mixes(bool on) {
+  if (!on && !slcf_mix_.empty()) {
+    std::string names;
+    for (const SlcfDef &d : kSlcf)
+      if (slcf_mix_.count(d.name)) names += (names.empty() ? "" : ", ") + std::string(d.name);
+    throw std::runtime_error("hx_enable_slcf_mixes: " + names + " has a mix: remove the mix first "
+                             "(hx_setvar_dated_mix with nbasis = 0)");
+  }
+  slcf_on_ = on;   // (nothing else: rows, pre-pass and kernel variant follow the mixes, not the switch)
+}
+
+namespace {
 struct DatedDef { const char *name; const char *sections[2]; const char *units; };
 // inputs with dates: capability -> INI section(s) holding the series (component_data.hpp;
 // NOX/CO/NMVOC are read by both the OH and the ozone component)
@@ -1280,6 +1313,11 @@ double mix_member_host(const double *basis, const double *coeff, int nbasis, siz
   }
   return s;
 }
+// ... and with hx_enable_slcf_mixes on
+const char kMixNamesSlcf[] = "ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions, "
+                             "N2O_emissions, RF_albedo, the <gas>_emissions of the scenario's halocarbons, "
+                             "SO2_emissions, BC_emissions, OC_emissions, NH3_emissions, NOX_emissions, "
+                             "CO_emissions and NMVOC_emissions";
 bool interpolated_constraint(int k) { return k == HXM_TAS_CON || k == HXM_FTOT_CON; }
 int constraint_bit(int k) {
   switch (k) {
@@ -1330,6 +1368,15 @@ void EnsembleCore::setvar_dated(const std::string &capability, const int *years,
     if (gm != gas_mix_.end())
       for (int i = 0; i < n; ++i)
         if (gm->second.covers(years[i]))
+          throw std::runtime_error("hx_setvar_dated: " + capability + " has a mix that covers " +
+                                   std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
+                                   "with nbasis = 0)");
+  }
+  {
+    auto sm = slcf_mix_.find(capability);
+    if (sm != slcf_mix_.end())
+      for (int i = 0; i < n; ++i)
+        if (sm->second.covers(years[i]))
           throw std::runtime_error("hx_setvar_dated: " + capability + " has a mix that covers " +
                                    std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
                                    "with nbasis = 0)");
@@ -1430,8 +1477,11 @@ void EnsembleCore::check_dated_mix(const std::string &capability, const int *yea
   for (const MemberSeriesDef &m : kMemberSeries)
     if (capability == m.name && !is_constraint_series(m.k)) d = &m;
   std::string expect = d ? d->units : "";
-  if (!d && !gas_mix_capable(capability, nullptr, &expect))
-    throw std::runtime_error(fn + "a mix is not supported for " + capability + " (" + kMixNames + " are)");
+  const int sj = slcf_on_ ? slcf_index(capability) : -1;
+  if (sj >= 0) expect = kSlcf[sj].units;
+  if (!d && sj < 0 && !gas_mix_capable(capability, nullptr, &expect))
+    throw std::runtime_error(fn + "a mix is not supported for " + capability + " (" +
+                             (slcf_on_ ? kMixNamesSlcf : kMixNames) + " are)");
   if (units && units[0] && std::string(units) != expect)
     throw std::runtime_error(fn + "Units: " + std::string(units) + " do not match expected: " + expect +
                              " for " + capability);
@@ -1460,14 +1510,18 @@ void EnsembleCore::setvar_dated_mix(const std::string &capability, const int *ye
   check_dated_mix(capability, years, nyears, basis, nbasis, coeff, units);
   const MemberSeriesDef *d = nullptr;
   for (const MemberSeriesDef &m : kMemberSeries) if (capability == m.name) d = &m;
-  if (!d && nbasis == 0 && !gas_mix_.count(capability)) return;
-  const bool prepass_was = !gas_member_.empty() || !gas_mix_.empty();
-  MemberMix &mx = d ? mix_[d->k] : gas_mix_[capability];
+  const int sj = (!d && slcf_on_) ? slcf_index(capability) : -1;
+  if (!d && nbasis == 0 && !(sj >= 0 ? slcf_mix_ : gas_mix_).count(capability)) return;
+  const bool prepass_was = !gas_member_.empty() || !gas_mix_.empty(), slcf_was = !slcf_mix_.empty();
+  MemberMix &mx = d ? mix_[d->k] : sj >= 0 ? slcf_mix_[capability] : gas_mix_[capability];
   if (nbasis == 0 && mx.nbasis == 0) return;
   int miny = scen_.end;   // the years the replaced mix gives back change as well
   for (int y : mx.years) miny = std::min(miny, y);
+  // A precursor mix that covers startDate: the member's own row 0 enters the OH term of EVERY year
+  const bool row0_was = sj >= 4 && mx.nbasis && mx.covers(scen_.start);
   if (nbasis == 0) {
     if (d) mx = MemberMix();
+    else if (sj >= 0) slcf_mix_.erase(capability);
     else gas_mix_.erase(capability);
   } else {
     mx.nbasis = nbasis;
@@ -1476,12 +1530,20 @@ void EnsembleCore::setvar_dated_mix(const std::string &capability, const int *ye
     mx.coeff.assign(coeff, coeff + (size_t)nbasis * (size_t)n_);
     for (int y : mx.years) miny = std::min(miny, y);
   }
+  if (sj >= 4 && (row0_was || (nbasis && std::find(years, years + nyears, scen_.start) != years + nyears)))
+    miny = scen_.start;
   if (d) mseries_dirty_ = true;
+  else if (sj >= 0) slcf_dirty_ = true;   // hx_slcf_mix_kernel evaluates the recipe ahead of the next run
   else gas_dirty_ = true;   // the pre-pass evaluates the recipe: nothing else is rebuilt
   // The pre-pass begins or ends with this call: EVERY year's N2O and forcing row changes its source
   // (the device's exp / pow against the host's: equal to rounding, not bit for bit), so the whole
   // run is redone -- a core whose last mix is removed gives the bits of one that never had any.
-  if (!d && prepass_was != (!gas_member_.empty() || !gas_mix_.empty())) miny = scen_.start;
+  if (!d && sj < 0 && prepass_was != (!gas_member_.empty() || !gas_mix_.empty())) miny = scen_.start;
+  // ... and the same where the first aerosol / precursor mix arrives or the last one leaves: the run may
+  // change its kernel with it (a core that only records diagnostics runs the plain kernel with them,
+  // whose last bits are not the extended kernel's), and a core whose mixes are removed has to give
+  // the bits of one that never had any.
+  if (sj >= 0 && slcf_was != !slcf_mix_.empty()) miny = scen_.start;
   const int target = std::max(0, miny - 1 - scen_.start);
   if (target < last_iy_) dirty_from_iy_ = (dirty_from_iy_ < 0) ? target : std::min(dirty_from_iy_, target);
 }
@@ -1511,6 +1573,7 @@ std::vector<std::string> EnsembleCore::mix_capabilities() const {
   out.push_back("N2O_emissions");
   out.push_back("RF_albedo");
   for (const Halocarbon &h : scen_.halocarbons) out.push_back(h.name + "_emissions");
+  if (slcf_on_) for (const SlcfDef &d : kSlcf) out.push_back(d.name);
   return out;
 }
 
@@ -1594,14 +1657,27 @@ std::vector<EnsembleCore::ScenarioSeries> EnsembleCore::plan_scenario_mix(
       else
         found[key];   // a mix over startDate..endDate, filled below
     }
+    // a precursor is ONE capability read by two components: its two series have to be one
+    if (slcf_on_)
+      for (int j = 4; j < 7; ++j) {
+        const std::string name = kSlcf[j].name;
+        if (!o.has_series("OH", name) || !o.has_series("ozone", name)) continue;
+        const std::vector<double> &a = o.series("OH", name), &b = o.series("ozone", name);
+        for (size_t i = 0; i < a.size() && i < b.size(); ++i)
+          if (!same_bits(a[i], b[i]))
+            throw std::runtime_error(fn + "series " + name + " of section OH differs from " + name +
+                                     " of section ozone (OH." + name + ", ozone." + name +
+                                     "): one capability cannot hold two series" + who);
+      }
     if (!refused.empty())   // every one of them, as section.key
       throw std::runtime_error(fn + "series that cannot be a mix differ from the core's: " + refused + " (" +
-                               kMixNames + " can)" + who);
+                               (slcf_on_ ? kMixNamesSlcf : kMixNames) + " can)" + who);
   }
   std::vector<ScenarioSeries> plan;
   for (auto &f : found) {
     std::string section;
     for (const MemberSeriesDef &m : kMemberSeries) if (f.first == m.name) section = m.section;
+    if (section.empty() && slcf_index(f.first) >= 0) section = kSlcf[slcf_index(f.first)].sections[0];
     if (section.empty()) gas_mix_capable(f.first, &section, nullptr);
     ScenarioSeries p;
     p.capability = f.first;
@@ -1899,6 +1975,116 @@ struct StageClock {
   }
 };
 }  // namespace
+
+// The aerosol and ozone / OH precursor terms per member on the device (hx_slcf_mix_kernel): the
+// recipes of the mixed inputs go up -- coefficients in member order, basis dense in years, the years
+// covered -- with the scenario's series and the scalars of EnsembleCore::build_shared, and the kernel
+// fills one or both groups of rows the extended run kernels take instead of the per-year table's
+// columns.  A group exists only while one of its inputs is a mix.
+void EnsembleCore::run_slcf_kernel() {
+  slcf_dirty_ = false;
+  auto fr = [](void *p) { if (p) (void)hipFree(p); };
+  bool want_aero = false, want_pre = false;
+  for (int j = 0; j < 7; ++j)
+    if (slcf_mix_.count(kSlcf[j].name)) (j < 4 ? want_aero : want_pre) = true;
+  const size_t np = (size_t)npad_, ns = (size_t)scen_.ns();
+  bool changed = false;
+  auto group = [&](int k0, int k1, bool want) {
+    for (int k = k0; k <= k1; ++k) {
+      if (want && !d_mseries_[k]) {
+        double *p = nullptr;
+        check(hipMalloc(&p, sizeof(double) * ns * np), "hipMalloc aerosol / precursor rows");
+        d_mseries_[k] = p;
+        changed = true;
+      } else if (!want && d_mseries_[k]) {
+        if (!changed) sync();
+        fr(const_cast<double *>(d_mseries_[k]));
+        d_mseries_[k] = nullptr;
+        changed = true;
+      }
+    }
+  };
+  group(HXM_OH_B, HXM_O3_NMVOC, want_pre);
+  group(HXM_RF_AERO, HXM_RF_AERO, want_aero);
+  if (!want_aero && !want_pre) {  // back to the shared columns
+    fr(d_slcf_mix_); d_slcf_mix_ = nullptr;
+    if (changed) upload_args();
+    return;
+  }
+  const Scenario &s = scen_;
+  auto ser_of = [&](const char *sec, const char *key) -> const std::vector<double> & { return s.series(sec, key); };
+  // ser [12][ns] | kon [8] | coefficient blocks | basis [nblk][HX_MIX_MAX_BASIS][ns]
+  std::vector<double> dbl(12 * ns + 8, 0.0);
+  for (int j = 0; j < 4; ++j) std::copy_n(ser_of(kSlcf[j].sections[0], kSlcf[j].name).begin(), ns, dbl.begin() + (std::ptrdiff_t)((size_t)j * ns));
+  for (int j = 4; j < 7; ++j) {
+    std::copy_n(ser_of("OH", kSlcf[j].name).begin(), ns, dbl.begin() + (std::ptrdiff_t)((size_t)j * ns));
+    std::copy_n(ser_of("ozone", kSlcf[j].name).begin(), ns, dbl.begin() + (std::ptrdiff_t)((size_t)(j + 3) * ns));
+  }
+  {  // the shared column's own logarithm, and its argument (build_shared's expressions)
+    const double aci_beta = 2.279759, s_BCOC = 111.05064063;
+    const double s_SO2 = (260.34644166 * 1000) * (32.065 / 64.066);
+    const double *so2 = dbl.data(), *bc = so2 + ns, *oc = bc + ns;
+    for (size_t iy = 0; iy < ns; ++iy) {
+      const double arg = 1 + (so2[iy] / s_SO2) + ((bc[iy] + oc[iy]) / s_BCOC);
+      dbl[10 * ns + iy] = arg;
+      dbl[11 * ns + iy] = -1 * aci_beta * std::log(arg);
+    }
+  }
+  {
+    double *kon = dbl.data() + 12 * ns;
+    kon[0] = s.scalar("forcing", "rho_bc"); kon[1] = s.scalar("forcing", "rho_oc");
+    kon[2] = s.scalar("forcing", "rho_so2"); kon[3] = s.scalar("forcing", "rho_nh3");
+    kon[4] = s.scalar("OH", "CNOX"); kon[5] = s.scalar("OH", "CCO"); kon[6] = s.scalar("OH", "CNMVOC");
+    kon[7] = (component_disabled("so2") || component_disabled("bc") || component_disabled("oc") ||
+              component_disabled("nh3")) ? 1.0 : 0.0;
+  }
+  const size_t o_kon = 12 * ns;
+  std::vector<int> rec(14, 0);
+  std::vector<long long> coff;
+  std::vector<const MemberMix *> blocks;
+  for (int j = 0; j < 7; ++j) {
+    auto it = slcf_mix_.find(kSlcf[j].name);
+    if (it == slcf_mix_.end()) continue;
+    rec[2 * j] = it->second.nbasis; rec[2 * j + 1] = (int)blocks.size();
+    blocks.push_back(&it->second);
+    coff.push_back((long long)dbl.size());
+    dbl.insert(dbl.end(), it->second.coeff.begin(), it->second.coeff.end());
+  }
+  const size_t nblk = blocks.size(), o_basis = dbl.size();
+  dbl.resize(o_basis + nblk * HX_MIX_MAX_BASIS * ns, 0.0);
+  std::vector<int> ints(nblk * ns + np, 0);   // cover [nblk][ns] | member_of_lane [np]
+  for (size_t b = 0; b < nblk; ++b) {
+    const MemberMix &mx = *blocks[b];
+    const size_t ny = mx.years.size();
+    for (size_t i = 0; i < ny; ++i) {
+      const size_t iy = (size_t)(mx.years[i] - s.start);
+      ints[b * ns + iy] = 1;
+      for (size_t k = 0; k < (size_t)mx.nbasis; ++k)
+        dbl[o_basis + (b * HX_MIX_MAX_BASIS + k) * ns + iy] = mx.basis[k * ny + i];
+    }
+  }
+  std::copy(member_of_lane_.begin(), member_of_lane_.begin() + (std::ptrdiff_t)np, ints.begin() + (std::ptrdiff_t)(nblk * ns));
+  const size_t b_dbl = sizeof(double) * dbl.size(), b_ll = sizeof(long long) * coff.size(),
+               b_rec = sizeof(int) * rec.size(), b_int = sizeof(int) * ints.size();
+  sync();
+  fr(d_slcf_mix_); d_slcf_mix_ = nullptr;
+  check(hipMalloc(&d_slcf_mix_, b_dbl + b_ll + b_rec + b_int), "hipMalloc aerosol / precursor recipes");
+  double *d_dbl = reinterpret_cast<double *>(d_slcf_mix_);
+  long long *d_coff = reinterpret_cast<long long *>(d_slcf_mix_ + b_dbl);
+  int *d_rec = reinterpret_cast<int *>(d_slcf_mix_ + b_dbl + b_ll), *d_int = d_rec + rec.size();
+  check(hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, stream_), "upload aerosol / precursor recipes");
+  check(hipMemcpyAsync(d_coff, coff.data(), b_ll, hipMemcpyHostToDevice, stream_), "upload recipe offsets");
+  check(hipMemcpyAsync(d_rec, rec.data(), b_rec, hipMemcpyHostToDevice, stream_), "upload recipe records");
+  check(hipMemcpyAsync(d_int, ints.data(), b_int, hipMemcpyHostToDevice, stream_), "upload recipe years");
+  double *rows7[7];
+  for (int k = 0; k < 7; ++k) rows7[k] = const_cast<double *>(d_mseries_[HXM_OH_B + k]);
+  StageClock kclk;
+  check(hx_launch_slcf_mix(d_dbl, d_dbl + o_kon, d_rec, d_dbl, d_coff, d_dbl + o_basis, d_int, d_int + nblk * ns, n_,
+                           (int)ns, npad_, rows7, stream_), "aerosol / precursor mix kernel");
+  check(hipStreamSynchronize(stream_), "aerosol / precursor mix kernel sync");   // (the staging vectors end here)
+  kclk.lap("slcf mix kernel + sync");
+  if (changed) upload_args();
+}
 
 void EnsembleCore::lane_of_member(int *out) {
   prepare();
@@ -2435,7 +2621,9 @@ void EnsembleCore::prepare() {
       for (int k = 0; k < HXM_N; ++k)
         if (!member_series_[k].empty() || mix_[k].nbasis) mseries_dirty_ = true;  // lanes have moved
     gas_dirty_ = true;
+    if (!slcf_mix_.empty()) slcf_dirty_ = true;   // (lanes may have moved, the scenario's series changed)
   }
+  if (slcf_dirty_ || (!slcf_mix_.empty() && !d_mseries_[HXM_OH_B] && !d_mseries_[HXM_RF_AERO])) run_slcf_kernel();
   if (gas_dirty_ || ((!gas_member_.empty() || !gas_mix_.empty()) && !d_mseries_[HXM_N2O])) run_gas_kernel();
   if (mseries_dirty_) upload_member_series();
   clk.lap("gas kernel / member series");
@@ -2790,6 +2978,23 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
       return true;
     }
   }
+  {  // ... and of the aerosol / precursor pre-pass
+    auto sm = slcf_mix_.find(capability);
+    if (sm != slcf_mix_.end()) {
+      if (!out_host) return true;
+      if (year0 < scen_.start || year1 > scen_.end || year1 < year0)
+        throw std::runtime_error("fetchvars: dates must lie between startDate and endDate");
+      const std::vector<double> base = input(kSlcf[slcf_index(capability)].sections[0], capability, 0.0);
+      for (int y = year0; y <= year1; ++y)
+        std::fill(out_host + (size_t)(y - year0) * n_, out_host + (size_t)(y - year0 + 1) * n_,
+                  base[(size_t)(y - scen_.start)]);
+      const MemberMix &mx = sm->second;
+      for (size_t i = 0; i < mx.years.size(); ++i)
+        if (mx.years[i] >= year0 && mx.years[i] <= year1)
+          mix_values(mx, i, out_host + (size_t)(mx.years[i] - year0) * n_);
+      return true;
+    }
+  }
   // year index -> column of a recipe (-1: the shared value), and one member's value there
   auto cover_map = [&](const MemberMix &mx) {
     std::vector<int> col((size_t)ns, -1);
@@ -2883,6 +3088,54 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
         ser[0] = 0.0;  // the component has not run at startDate
         relative = computed = true;
       }
+    }
+  }
+  {
+    // RF_BC, RF_OC, RF_SO2, RF_NH3, RF_aci of a core whose aerosol emissions are a mix: per member
+    // from the recipe, the expressions of the shared answer below (forcing_component.cpp:430-487)
+    static const char *const kAero[5] = {"RF_SO2", "RF_BC", "RF_OC", "RF_NH3", "RF_aci"};
+    int which = -1;
+    for (int j = 0; j < 5; ++j) if (capability == kAero[j]) which = j;
+    const MemberMix *amx[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool any_mix = false;
+    if (which >= 0)
+      for (int j = 0; j < 4; ++j) {
+        auto it = slcf_mix_.find(kSlcf[j].name);
+        if (it != slcf_mix_.end()) { amx[j] = &it->second; any_mix = true; }
+      }
+    if (any_mix && (which == 4 ? (amx[0] || amx[1] || amx[2]) : amx[which] != nullptr)) {
+      if (!out_host) return true;
+      if (shared_dirty_ || need_spinup_)
+        throw std::runtime_error("fetchvars: run the core after changing inputs");
+      if (year0 < scen_.start || year1 > last_date() || year1 < year0)
+        throw std::runtime_error("fetchvars: dates must lie between startDate and the current date");
+      static const char *const kRho[4] = {"rho_so2", "rho_bc", "rho_oc", "rho_nh3"};
+      const double aci_beta = 2.279759, s_BCOC = 111.05064063;
+      const double s_SO2 = (260.34644166 * 1000) * (32.065 / 64.066);
+      std::vector<double> em[4];
+      std::vector<int> col[4];
+      for (int j = 0; j < 4; ++j) {
+        em[j] = input(kSlcf[j].sections[0], kSlcf[j].name, 0);
+        col[j] = amx[j] ? cover_map(*amx[j]) : std::vector<int>((size_t)ns, -1);
+      }
+      auto emis = [&](int j, int iy, int i) {
+        return col[j][(size_t)iy] >= 0 ? member_mix(*amx[j], col[j][(size_t)iy], i) : em[j][(size_t)iy];
+      };
+      const double rho = which < 4 ? scen_.scalar("forcing", kRho[which]) : 0.0;
+      auto term = [&](int iy, int i) {
+        if (which < 4) return rho * emis(which, iy, i);
+        return -1 * aci_beta * std::log(1 + (emis(0, iy, i) / s_SO2) + ((emis(1, iy, i) + emis(2, iy, i)) / s_BCOC));
+      };
+      const int base = kc_.baseyear_idx;
+      for (int i = 0; i < n_; ++i) {
+        const double f = params_[HXP_AERO][(size_t)i];
+        const double at_base = f * term(base, i);
+        for (int y = year0; y <= year1; ++y) {
+          const int iy = y - scen_.start;
+          out_host[(size_t)(y - year0) * n_ + i] = (iy >= base) ? f * term(iy, i) - at_base : 0.0;
+        }
+      }
+      return true;
     }
   }
   if (ser.empty() && capability.compare(0, 3, "RF_") == 0) {

@@ -108,6 +108,11 @@ class EnsembleCore {
   // keep what the reference's output stream sees after every spinup step (its "spinup = 1" rows,
   // csv_outputstream_visitor.cpp:86-95): the carbon-cycle variables, max_spinup x 21 x 8 B per member
   void enable_spinup_record(bool on);
+  // Let the mix verb, mix_capabilities() and plan_scenario_mix() take the aerosol and ozone / OH
+  // precursor emissions as well (SO2, BC, OC, NH3, NOX, CO, NMVOC: hx_enable_slcf_mixes).  Off by
+  // default, and free until such a mix is set; refused while one is.
+  void enable_slcf_mixes(bool on);
+  bool slcf_mixes_enabled() const { return slcf_on_; }
   static const std::vector<std::string> &spinup_record_vars();
   // values[step * nvars + v] for steps 1..spinup_steps(member); returns the step count
   int spinup_record(int member, double *values, int max_steps);
@@ -385,6 +390,12 @@ class EnsembleCore {
   // evaluates them where it needs the value (hx_gas_mix_kernel).
   std::map<std::string, MemberMix> gas_mix_;
   char *d_gas_mix_ = nullptr;          // that kernel's recipe block (coefficients, basis, cover, lane map)
+  // ... and of the aerosol / precursor inputs (hx_enable_slcf_mixes): recipes as well, evaluated by
+  // hx_slcf_mix_kernel into the HXM_OH_B .. HXM_RF_AERO rows
+  std::map<std::string, MemberMix> slcf_mix_;
+  char *d_slcf_mix_ = nullptr;
+  bool slcf_on_ = false, slcf_dirty_ = false;
+  void run_slcf_kernel();
   bool gas_mix_capable(const std::string &capability, std::string *section, std::string *units) const;
   // year column i of a recipe for every member, the definition's bits: out[n_]
   void mix_values(const MemberMix &mx, size_t i, double *out) const;

@@ -314,6 +314,10 @@ int hx_run_name(hx_core *core, const char **name) {
 }
 int hx_enable_history(hx_core *core, int on) { HX_TRY(core->core->enable_history(on != 0)) }
 int hx_enable_spinup_record(hx_core *core, int on) { HX_TRY(core->core->enable_spinup_record(on != 0)) }
+int hx_enable_slcf_mixes(hx_core *core, int on) {
+  if (!core) return fail("hx_enable_slcf_mixes: null core");
+  HX_TRY(core->core->enable_slcf_mixes(on != 0))
+}
 int hx_spinup_record(hx_core *core, int member, const char *const **names, int *nvars, double *values,
                      int max_steps, int *steps) {
   static const std::vector<const char *> cnames = [] {

@@ -683,6 +683,135 @@ hipError_t hx_launch_gas_mix(const double *par, const double *ser, const double 
                      coeff, coff, basis, cover, member_of_lane, n, nh, ns, npad, n2o_out, rf_other_out);
   return hipGetLastError();
 }
+
+// ===========================================================================
+// The aerosol and ozone / OH precursor terms from RECIPES: the per-member counterparts of seven
+// columns of the per-year table (HXM_OH_B .. HXM_RF_AERO in hx_layout.h) for a core in which a
+// member's SO2 / BC / OC / NH3 or NOX / CO / NMVOC emissions are a mix (hx_setvar_dated_mix).  Like
+// hx_gas_mix_kernel there is no table of emissions: the lane takes its coefficients through
+// member_of_lane (a padding lane: the last member's), evaluates the definition in every covered
+// year -- products rounded before they are added, ascending k -- and takes the scenario's value
+// elsewhere.  The rows are written with the expressions of EnsembleCore::build_shared, operation for
+// operation, contraction off, and they are the TERMS, not their sums: the year loop adds them.
+// Unlike the gas pre-pass nothing here is a recurrence -- a year's terms depend on that year's
+// emissions, and the OH terms on the member's own value at startDate besides -- so a block takes
+// 64 lanes x HXSLCF_YEARS years: grid (npad / 64, ceil(ns / HXSLCF_YEARS)).
+//   ser [12][ns]: the scenario's SO2, BC, OC, NH3; NOX, CO, NMVOC of the OH section; the same of the
+//       ozone section; then the argument of the aerosol-cloud logarithm for the scenario's own
+//       emissions and the host's term for it (the shared column's std::log)
+//   kon [8]: rho_bc, rho_oc, rho_so2, rho_nh3, CNOX, CCO, CNMVOC, and non-zero if one of the four aerosol
+//       components is disabled (the row is zero then, as the shared column is)
+//   rec [7][2]: input j's {nbasis (0 = shared), block}: j = 0 SO2, 1 BC, 2 OC, 3 NH3, 4 NOX, 5 CO,
+//       6 NMVOC; coeff, coff, basis, cover: as hx_gas_mix_kernel
+//   rows.r[k]: row HXM_OH_B + k, [ns][npad]; r[0..5] null: no precursor group; r[6] null: no aerosol row
+// The logarithm is the device library's.  Where a member's argument IS the scenario's, bit for bit,
+// the lane takes the host's term: a member that carries the scenario's own aerosol emissions then
+// has the bits of a core without the mix (the two logarithms differ in the last place now and then).
+// Lane-local: the host-emulation build runs it as it stands.
+// ===========================================================================
+#define HXSLCF_YEARS 64
+struct HxSlcfRows { double *r[7]; };
+
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__global__ __launch_bounds__(64) void hx_slcf_mix_kernel(const double *__restrict__ ser, const double *__restrict__ kon,
+                                                         const int *__restrict__ rec, const double *__restrict__ coeff,
+                                                         const long long *__restrict__ coff,
+                                                         const double *__restrict__ basis, const int *__restrict__ cover,
+                                                         const int *__restrict__ member_of_lane, int n, int ns, int npad,
+                                                         HxSlcfRows rows) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int lane = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (lane >= npad) return;
+  const size_t np = (size_t)npad, mem = (size_t)lane;
+  const size_t m = (size_t)min(member_of_lane[lane], n - 1);
+  const int iy0 = (int)blockIdx.y * HXSLCF_YEARS, iy1 = min(iy0 + HXSLCF_YEARS, ns);
+  if (rows.r[0]) {  // OHComponent::run (src/oh_component.cpp:157-170), OzoneComponent::run (src/o3_component.cpp:136-139)
+    const double o3f[3] = {0.125, 0.0011, 0.0033};
+    for (int p = 0; p < 3; ++p) {
+      const int K = rec[2 * (4 + p)], blk = rec[2 * (4 + p) + 1];
+      double c[HX_MIX_MAX_BASIS];
+#pragma unroll
+      for (int k = 0; k < HX_MIX_MAX_BASIS; ++k) c[k] = k < K ? coeff[coff[blk] + (long long)((size_t)k * (size_t)n + m)] : 0.0;
+      const double *b = basis + (size_t)blk * HX_MIX_MAX_BASIS * (size_t)ns;
+      const int *cov = cover + (size_t)blk * (size_t)ns;
+      const double *soh = ser + (size_t)(4 + p) * ns, *so3 = ser + (size_t)(7 + p) * ns;
+      const double C = kon[4 + p], F = o3f[p];
+      double x0 = soh[0];   // the member's own emissions of startDate when the mix covers it
+      if (K && cov[0]) HX_GASMIX_VALUE(x0, 0);
+      double *oh = rows.r[p], *o3 = rows.r[3 + p];
+      for (int iy = iy0; iy < iy1; ++iy) {
+        double xo = soh[iy], xz = so3[iy];
+        if (K && cov[iy]) {
+          double v;
+          HX_GASMIX_VALUE(v, iy);
+          xo = xz = v;
+        }
+        const size_t o = (size_t)iy * np + mem;
+        oh[o] = C * ((1.0 * xo) - x0);
+        o3[o] = F * xz;
+      }
+    }
+  }
+  if (rows.r[6]) {  // ForcingComponent::run (src/forcing_component.cpp:430-470) for aero_scalar = 1
+    const double aci_beta = 2.279759, s_BCOC = 111.05064063;
+    const double s_SO2 = (260.34644166 * 1000) * (32.065 / 64.066);
+    const double rho_bc = kon[0], rho_oc = kon[1], rho_so2 = kon[2], rho_nh3 = kon[3];
+    const double *arg_sh = ser + (size_t)10 * ns, *aci_sh = ser + (size_t)11 * ns;
+    double ca[4][HX_MIX_MAX_BASIS];
+    int Ka[4];
+    const double *ba[4];
+    const int *cva[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      Ka[j] = rec[2 * j];
+      const int blk = rec[2 * j + 1];
+#pragma unroll
+      for (int k = 0; k < HX_MIX_MAX_BASIS; ++k)
+        ca[j][k] = k < Ka[j] ? coeff[coff[blk] + (long long)((size_t)k * (size_t)n + m)] : 0.0;
+      ba[j] = basis + (size_t)blk * HX_MIX_MAX_BASIS * (size_t)ns;
+      cva[j] = cover + (size_t)blk * (size_t)ns;
+    }
+    double *out = rows.r[6];
+    for (int iy = iy0; iy < iy1; ++iy) {
+      double e[4];   // SO2, BC, OC, NH3 of the year
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        e[j] = ser[(size_t)j * ns + iy];
+        if (Ka[j] && cva[j][iy]) {
+          double s = ca[j][0] * ba[j][iy];
+#pragma unroll
+          for (int k = 1; k < HX_MIX_MAX_BASIS; ++k)
+            if (k < Ka[j]) {
+              const double p = ca[j][k] * ba[j][(size_t)k * (size_t)ns + (size_t)iy];
+              s = s + p;
+            }
+          e[j] = s;
+        }
+      }
+      const double so2 = e[0], bc = e[1], oc = e[2], nh3 = e[3];
+      const double arg = 1 + (so2 / s_SO2) + ((bc + oc) / s_BCOC);
+      const double aci = arg == arg_sh[iy] ? aci_sh[iy] : -1 * aci_beta * log(arg);
+      const double rf = (((rho_bc * bc + rho_oc * oc) + rho_so2 * so2) + rho_nh3 * nh3) + aci;
+      out[(size_t)iy * np + mem] = kon[7] != 0.0 ? 0.0 : rf;
+    }
+  }
+}
+
+hipError_t hx_launch_slcf_mix(const double *ser, const double *kon, const int *rec, const double *coeff,
+                              const long long *coff, const double *basis, const int *cover,
+                              const int *member_of_lane, int n, int ns, int npad, double *const *rows7,
+                              hipStream_t st) {
+  if (n < 1 || ns < 1 || npad < 1) return hipErrorInvalidValue;
+  HxSlcfRows rows;
+  for (int k = 0; k < 7; ++k) rows.r[k] = rows7[k];
+  hipLaunchKernelGGL(hx_slcf_mix_kernel, dim3((npad + 63) / 64, (ns + HXSLCF_YEARS - 1) / HXSLCF_YEARS), dim3(64), 0,
+                     st, ser, kon, rec, coeff, coff, basis, cover, member_of_lane, n, ns, npad, rows);
+  return hipGetLastError();
+}
 #undef HX_GASMIX_VALUE
 
 // ===========================================================================

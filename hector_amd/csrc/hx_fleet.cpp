@@ -281,6 +281,7 @@ bool Fleet::lanes_calibrated() const {
 }
 void Fleet::enable_history(bool on) { HX_EACH(enable_history(on)) }
 void Fleet::enable_spinup_record(bool on) { HX_EACH(enable_spinup_record(on)) }
+void Fleet::enable_slcf_mixes(bool on) { HX_EACH(enable_slcf_mixes(on)) }
 int Fleet::spinup_record(int member, double *values, int max_steps) {
   Shard &s = shards_[(size_t)shard_of_member(member)];
   use(s);

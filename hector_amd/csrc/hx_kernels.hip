@@ -750,6 +750,21 @@ void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
   // ... and, in the kernels that decide a segment's retries ahead of its first step, whether this
   // launch has to take them inside the step loop instead (solve_year)
   if constexpr (hx_open_retry_k<B, HF, KERPM, CON>()) m.fretry = args->kc.faithful_retries;
+  // A member's own OH / O3 precursor terms (hx_slcf_mix_kernel's six rows: one group, one bit)
+  // replace the shared table's wherever load_year_a() has just fetched those; the year clamped as
+  // there (the request a year ahead, at the last year).
+  auto member_year_a = [&](int iyn) {
+    if constexpr (hx_cons<CON>()) {
+      if (HX_RARE(msk & (1u << HXM_OH_B))) {
+        const HxBuffers &buf = args->buf;
+        const size_t o = (size_t)(iyn < args->kc.ns ? iyn : args->kc.ns - 1) * buf.npad + mem;
+        ya[0] = HX_GCD(HXM_SLCF(buf, HXM_OH_B))[o]; ya[1] = HX_GCD(HXM_SLCF(buf, HXM_OH_C))[o];
+        ya[2] = HX_GCD(HXM_SLCF(buf, HXM_OH_D))[o]; ya[5] = HX_GCD(HXM_SLCF(buf, HXM_O3_NOX))[o];
+        ya[6] = HX_GCD(HXM_SLCF(buf, HXM_O3_CO))[o]; ya[7] = HX_GCD(HXM_SLCF(buf, HXM_O3_NMVOC))[o];
+      }
+    }
+  };
+  if constexpr (!YAL) member_year_a(iy_from + 1);
   // (... and laundered again at the head of every region that tests them: a test of an opaque
   // but loop-invariant value is itself loop-invariant, and the optimiser would compute all ~50 of
   // them ahead of the year loop and keep them in -- spilled -- scalar registers)
@@ -809,11 +824,11 @@ void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
       double twin = PKM(m, PK_TWIN);
       const double tl_m2 = PKM(m, PK_TL_M2);
       const int iold = iy - 203;
-      if constexpr (YAL && !hx_w2<B>()) load_year_a(iy);
+      if constexpr (YAL && !hx_w2<B>()) { load_year_a(iy); member_year_a(iy); }
       if constexpr (hx_w2<B>()) {
         // (two resident wavefronts hide a load's latency: nothing is requested a phase ahead, so
         // nothing waits in registers through the solver)
-        load_year_a(iy);
+        load_year_a(iy); member_year_a(iy);
         if constexpr (!W2K)
         pf_tl_old = hx_ldm<true>(HX_GCD(buf.out[HXO_TLAND]) + (size_t)(iold >= 1 ? iold : 0) * buf.npad, m.moff);
       }
@@ -1186,7 +1201,7 @@ void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
         if constexpr (!YAL) {
         hx_ccd shc = HX_CCD(buf.shared) + (size_t)iy * HXSH_STRIDE;
         yc4[0] = shc[HXSH_SQRT_N2O]; yc4[1] = shc[HXSH_RF_OTHER]; yc4[2] = shc[HXSH_RF_AERO]; yc4[3] = shc[HXSH_RF_VOL];
-        load_year_a(iy + 1);
+        load_year_a(iy + 1); member_year_a(iy + 1);
         }
       }
       const double year = (double)(args->kc.start_year + iy);
@@ -1279,7 +1294,20 @@ void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
         pf_dpart = hx_ldm<true>(HX_GCD(buf.dpart) + (size_t)(iy - blk0) * buf.npad, m.moff);
         yc4[0] = sh[HXSH_SQRT_N2O]; yc4[1] = sh[HXSH_RF_OTHER]; yc4[2] = sh[HXSH_RF_AERO]; yc4[3] = sh[HXSH_RF_VOL];
         ch4 = PKM(m, PK_CH4);
-        o3 = ((5 * PKM(m, PK_LN_CH4) + sh[HXSH_O3_NOX]) + sh[HXSH_O3_CO]) + sh[HXSH_O3_NMVOC];
+        // (ONE instance of the sum, whatever the terms' source: a second one, for the member's own
+        // terms, was contracted differently -- the last bit of O3 moved)
+        double o3_nox = sh[HXSH_O3_NOX], o3_co = sh[HXSH_O3_CO], o3_nmvoc = sh[HXSH_O3_NMVOC];
+        if constexpr (hx_cons<CON>()) {  // the member's own precursor terms (see member_year_a)
+          if (HX_RARE(msk & (1u << HXM_OH_B))) {
+            const size_t o = (size_t)iy * buf.npad + mem;
+            o3_nox = HX_GCD(HXM_SLCF(buf, HXM_O3_NOX))[o]; o3_co = HX_GCD(HXM_SLCF(buf, HXM_O3_CO))[o];
+            o3_nmvoc = HX_GCD(HXM_SLCF(buf, HXM_O3_NMVOC))[o];
+          }
+        }
+        o3 = ((5 * PKM(m, PK_LN_CH4) + o3_nox) + o3_co) + o3_nmvoc;
+      }
+      if constexpr (hx_cons<CON>()) {  // aerosol emissions that differ between members
+        if (HX_RARE(msk & (1u << HXM_RF_AERO))) yc4[2] = HX_GCD(HXM_SLCF(buf, HXM_RF_AERO))[(size_t)iy * buf.npad + mem];
       }
       // every HBM value this phase needs, issued back to back
       const double tland = PKM(m, PK_TLAND), sst = PKM(m, PK_SST);

@@ -119,6 +119,12 @@ enum HxMemberSeries {
   // members: the N2O concentration and the sum of halocarbon + albedo + misc forcings of every
   // year (row 0 of the N2O series is the member's preindustrial value)
   HXM_N2O, HXM_RF_OTHER,
+  // computed on the device (hx_slcf_mix_kernel) while a member's aerosol or ozone / OH precursor
+  // emissions are a mix: the per-member counterparts of the shared columns of the same name, the
+  // finished TERMS (the year loop adds them where it adds the shared ones, in the same order).
+  // Two groups, each allocated only while a mix needs it: the six precursor rows, the aerosol row.
+  HXM_OH_B, HXM_OH_C, HXM_OH_D, HXM_O3_NOX, HXM_O3_CO, HXM_O3_NMVOC,
+  HXM_RF_AERO,
   HXM_N
 };
 static_assert(HXM_N <= 32, "HxBuffers::ms_mask holds one bit per member series");
@@ -219,7 +225,8 @@ struct HxBuffers {
   unsigned *hist_status; // ... and the members' status bits of every year [ns][npad]
   int n, npad, ker_per_member;
   int nbiome;              // the core's biome count (the looped kernels' trip count)
-  const double *mseries[HXM_N];  // per-member series (row iy as in the shared table) or nullptr
+  const double *mseries[HXM_OH_B];  // per-member series (row iy as in the shared table) or nullptr: the rows
+                                    // below HXM_OH_B; the others are mseries_slcf, at the end
   const double *uparams;   // [HX_NPARAM(B)] one value per parameter row (member 0): rows that are
   int uni_landk, uni_bio;  // uniform over members are read through scalar loads (multi-biome kernels)
   // two-wavefront flavour (HX_B1W2): lane 0's derived constants [HX_NDERIVED(B)], and which groups
@@ -259,7 +266,13 @@ struct HxBuffers {
   long long *wave_clk;
   // (last: 396 pointers, see HxArgs)
   double *out[HXO_NVAR]; // each [ns][npad] or nullptr
+  // Rows HXM_OH_B .. HXM_RF_AERO of the per-member series (hx_slcf_mix_kernel), mseries_slcf[k - HXM_OH_B].
+  // Behind everything else: in the middle they pushed one more output pointer of the first biome past
+  // the 4 KB mark (see HxArgs) and every "plain + diagnostics" kernel gained 6 instructions and 2
+  // spilled scalars.  Here no other field moves; these are read behind their ms_mask bit only.
+  const double *mseries_slcf[HXM_N - HXM_OH_B];
 };
+#define HXM_SLCF(buf, k) ((buf).mseries_slcf[(k) - HXM_OH_B])
 // rows of HxBuffers::spin_rec: the carbon-cycle variables of the stream, which are the ones that
 // move during the spinup
 enum { HXSR_NBP = 0, HXSR_NPP, HXSR_RH, HXSR_RH_DET, HXSR_RH_SOIL, HXSR_ATMOS_C, HXSR_CA_RESIDUAL,

@@ -150,8 +150,9 @@ int hx_setvar_dated_members(hx_core *core, const char *capability, const int *ye
  * evaluates the definition where the N2O and halocarbon recurrences read the value and writes the
  * two rows the run kernels take (N2O; halocarbon + albedo + misc forcing: 16 B per member-year, as
  * for per-member N0 or tau_<gas>).  N2O_concentration, RF_N2O, <gas>_concentration, RF_<gas> and
- * RF_albedo are then per member.  The aerosol emissions (SO2, BC, OC, NH3), the ozone / OH
- * precursors (NOX, CO, NMVOC), SV, RF_misc, CH4N and N2O_natural_emissions cannot be mixed.
+ * RF_albedo are then per member.  The aerosol emissions (SO2, BC, OC, NH3) and the ozone / OH
+ * precursors (NOX, CO, NMVOC) can be mixed after hx_enable_slcf_mixes (below); SV, RF_misc, CH4N
+ * and N2O_natural_emissions cannot.
  * ERRORS (every message names the function; a refused call changes nothing): a capability other
  * than ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions and the names above (the
  * constraint series, with NaN = none and interpolated points, are no linear mix); units that do not match
@@ -175,11 +176,30 @@ int hx_mix_capabilities(hx_core *core, const char *const **names, int *count);
  * nothing): nscen outside 1..HX_MIX_MAX_BASIS; startDate or endDate that differ; a different list of
  * halocarbons; ANY scalar that differs or is missing on one side (core.run_name, a label, excepted):
  * the members share one parameter table and one spinup; a series that differs and cannot be a mix
- * -- a constraint, SV, RF_misc, CH4N, N2O_natural_emissions, and the aerosol and ozone / OH precursor
- * emissions, so the shipped SSPs, which differ in so2.SO2_emissions among others, are refused
- * against each other -- or that is missing on one side; a coefficient that is not finite. */
+ * -- a constraint, SV, RF_misc, CH4N, N2O_natural_emissions, and, unless hx_enable_slcf_mixes is on,
+ * the aerosol and ozone / OH precursor emissions, so that the shipped SSPs, which differ in
+ * so2.SO2_emissions among others, are then refused against each other -- or that is missing on one
+ * side; a coefficient that is not finite. */
 int hx_setvar_scenario_mix(hx_core *core, const char *const *scenarios, int nscen, const double *coeff,
                            int *nseries);
+/* The short-lived climate forcer inputs as mixes: with on != 0, hx_setvar_dated_mix,
+ * hx_mix_capabilities (after the halocarbons) and hx_setvar_scenario_mix also take SO2_emissions
+ * ("Gg S"), BC_emissions, OC_emissions, NH3_emissions ("Tg"), NOX_emissions ("Tg N"), CO_emissions
+ * ("Tg CO") and NMVOC_emissions ("Tg NMVOC") -- with the always-mixable names everything the shipped
+ * SSPs differ in, so hx_setvar_scenario_mix puts them into ONE core.  A precursor name stands for the
+ * series of both the OH and the ozone section, as in hx_setvar_dated; a scenario file whose two
+ * series differ is refused, naming both.  Like the gas inputs these never have a table of emissions:
+ * the host keeps the recipe, and a lane-per-member pre-pass (hx_slcf_mix_kernel) writes the finished
+ * terms the year loop adds -- six rows for the precursors (the three OH-lifetime terms, relative to
+ * the MEMBER's own emissions at startDate when the mix covers it, and the three ozone terms), one
+ * for the aerosols (BC + OC + SO2 + NH3 + aerosol-cloud term for aero_scalar = 1) -- 8 B per
+ * member-year and row, each group only while one of its inputs is a mix.  hx_fetchvars returns the
+ * seven inputs with the definition's bits and RF_BC, RF_OC, RF_SO2, RF_NH3, RF_aci per member.  A new
+ * coefficient marks the core dirty from the earliest year of the mix; for a precursor mix that covers
+ * startDate from startDate.  Off by default: every message and list is then what it was before this
+ * switch existed, and it costs nothing until such a mix is set.  on == 0 while such a mix exists is
+ * refused, naming it (remove the mix first).  hx_setvar_dated_members keeps refusing the names. */
+int hx_enable_slcf_mixes(hx_core *core, int on);
 /* Keep every year's component state in HBM so hx_reset can return to any computed date --
  * what the reference's per-component tseries records provide (src/simpleNbox.cpp:708-840,
  * src/ocean_component.cpp:767-846).  272 B per member-year (one biome); default off. */
