@@ -421,6 +421,18 @@ EnsembleCore::~EnsembleCore() {
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
+namespace {
+// The aerosol-cloud interaction term of the forcing component (forcing_component.hpp:120-131,
+// forcing_component.cpp:455-470) for aero_scalar = 1, and the argument of its logarithm: the host's
+// one definition.  hx_slcf_mix_kernel compares its own argument with `==` against aci_arg's.
+constexpr double aci_beta = 2.279759, s_BCOC = 111.05064063;
+constexpr double s_SO2 = (260.34644166 * 1000) * (32.065 / 64.066);
+inline double aci_arg(double so2, double bc, double oc) { return 1 + (so2 / s_SO2) + ((bc + oc) / s_BCOC); }
+inline double aci_term(double so2, double bc, double oc) {
+  return -1 * aci_beta * std::log(1 + (so2 / s_SO2) + ((bc + oc) / s_BCOC));
+}
+}  // namespace
+
 // Member-independent per-year series: N2O, 26 halocarbons, aerosols, albedo,
 // volcanic, misc; OH/O3 emission terms; the carbon cycle's current-year fluxes.
 void EnsembleCore::build_shared() {
@@ -463,9 +475,6 @@ void EnsembleCore::build_shared() {
                TN2O0 = s.scalar("N2O", "TN2O0");
   const double rho_bc = s.scalar("forcing", "rho_bc"), rho_oc = s.scalar("forcing", "rho_oc"),
                rho_so2 = s.scalar("forcing", "rho_so2"), rho_nh3 = s.scalar("forcing", "rho_nh3");
-  // forcing_component.hpp:120-131
-  const double aci_beta = 2.279759, s_BCOC = 111.05064063;
-  const double s_SO2 = (260.34644166 * 1000) * (32.065 / 64.066);
   const bool so2_off = component_disabled("so2");
   const bool aerosols_off = so2_off || component_disabled("bc") || component_disabled("oc") ||
                             component_disabled("nh3");
@@ -556,8 +565,7 @@ void EnsembleCore::build_shared() {
     // forcing_component.cpp:430-470 for aero_scalar = 1
     row[HXSH_RF_AERO] = (((rho_bc * bc[iy] + rho_oc * oc[iy]) + rho_so2 * so2[iy]) +
                          rho_nh3 * nh3[iy]) +
-                        (-1 * aci_beta *
-                         std::log(1 + (so2[iy] / s_SO2) + ((bc[iy] + oc[iy]) / s_BCOC)));
+                        aci_term(so2[iy], bc[iy], oc[iy]);
     row[HXSH_RF_VOL] = sv[iy];
     // aerosol forcings need all four emission components, the volcanic one the SO2 component
     // (forcing_component.cpp:422-425, 478)
@@ -636,8 +644,9 @@ void EnsembleCore::free_device() {
   d_hist_ = nullptr; d_hist_status_ = nullptr;
   for (int k = 0; k < HXM_N; ++k) {
     fr(d_mseries_[k]); d_mseries_[k] = nullptr;
-    if (!member_series_[k].empty() || mix_[k].nbasis) mseries_dirty_ = true;
+    if (!member_series_[k].empty()) mseries_dirty_ = true;
   }
+  if (any_mix(MIX_TABLE)) mseries_dirty_ = true;
   fr(d_mix_); d_mix_ = nullptr; mix_cap_ = 0;
   fr(d_diag_); fr(d_slr_); d_diag_ = d_slr_ = nullptr; diag_cap_ = 0; slr_valid_to_ = -1;
   free_derived_cache();   // (the series stay: they are snapshots that outlive a new layout)
@@ -1198,126 +1207,68 @@ void EnsembleCore::enable_history(bool on) {
 }
 
 namespace {
-// the short-lived climate forcer inputs hx_enable_slcf_mixes adds to the mix verb, in the order
-// hx_slcf_mix_kernel numbers them: the four aerosol emissions (one group of rows, HXM_RF_AERO), the
-// three ozone / OH precursors (the other, HXM_OH_B .. HXM_O3_NMVOC)
-struct SlcfDef { const char *name; const char *sections[2]; const char *units; };
-const SlcfDef kSlcf[7] = {
-    {"SO2_emissions", {"so2", nullptr}, "Gg S"},       {"BC_emissions", {"bc", nullptr}, "Tg"},
-    {"OC_emissions", {"oc", nullptr}, "Tg"},           {"NH3_emissions", {"nh3", nullptr}, "Tg"},
-    {"NOX_emissions", {"OH", "ozone"}, "Tg N"},        {"CO_emissions", {"OH", "ozone"}, "Tg CO"},
-    {"NMVOC_emissions", {"OH", "ozone"}, "Tg NMVOC"},
+// Every input with dates, once (DatedInput, ensemble_core.hpp): capability, the INI section(s)
+// holding its series (component_data.hpp; NOX/CO/NMVOC are read by both the OH and the ozone
+// component), units, the value where the scenario has no series (NaN: no constraint), its
+// per-member table -- HXM_* row or -1; lag: the table holds the value of date year-1 for what
+// slowparameval reads -- and how a mix of it is evaluated, with the input's number in
+// hx_slcf_mix_kernel.  The halocarbons' <gas>_emissions and <gas>_constrain are the scenario's:
+// EnsembleCore::find_dated adds them.
+// The ORDER of the rows is read: the rows with a table are uploaded, and the mixable ones listed by
+// mix_capabilities(), in this order.
+const double kNone = std::nan("");
+const DatedInput kDatedInputs[] = {
+    {"ffi_emissions", {"simpleNbox", ""}, "Pg C/yr", 0.0, HXM_FFI, 1, MIX_TABLE, -1},
+    {"daccs_uptake", {"simpleNbox", ""}, "Pg C/yr", 0.0, HXM_DACCS, 1, MIX_TABLE, -1},
+    {"luc_emissions", {"simpleNbox", ""}, "Pg C/yr", 0.0, HXM_LUC_E, 1, MIX_TABLE, -1},
+    {"luc_uptake", {"simpleNbox", ""}, "Pg C/yr", 0.0, HXM_LUC_U, 1, MIX_TABLE, -1},
+    {"CH4_emissions", {"CH4", ""}, "Tg CH4", 0.0, HXM_CH4_EM, 0, MIX_TABLE, -1},
+    // constraints (component_data.hpp:46,263,273,379-381) that may differ between members (NaN = no
+    // constraint for that member and year)
+    {"CO2_constrain", {"simpleNbox", ""}, "ppmv CO2", kNone, HXM_CO2_CON, 0, MIX_NONE, -1},
+    {"NBP_constrain", {"simpleNbox", ""}, "Pg C/yr", kNone, HXM_NBP_CON, 0, MIX_NONE, -1},
+    {"tas_constrain", {"temperature", ""}, "degC", kNone, HXM_TAS_CON, 0, MIX_NONE, -1},
+    {"RF_tot_constrain", {"forcing", ""}, "W/m2", kNone, HXM_FTOT_CON, 0, MIX_NONE, -1},
+    {"CH4_constrain", {"CH4", ""}, "ppbv CH4", kNone, HXM_CH4_CON, 0, MIX_NONE, -1},
+    // The inputs of the gas pre-pass that may be a mix: what N2OComponent, HalocarbonComponent (the
+    // scenario's <gas>_emissions) and the albedo term of ForcingComponent read.  If no albedo data,
+    // constant -0.2 (simpleNbox-runtime.cpp:162-167)
+    {"N2O_emissions", {"N2O", ""}, "Tg N", 0.0, -1, 0, MIX_GAS, -1},
+    {"RF_albedo", {"simpleNbox", ""}, "W/m2", -0.2, -1, 0, MIX_GAS, -1},
+    // the short-lived climate forcer inputs hx_enable_slcf_mixes adds to the mix verb, numbered as
+    // hx_slcf_mix_kernel numbers them: the four aerosol emissions (one group of rows, HXM_RF_AERO),
+    // the three ozone / OH precursors (the other, HXM_OH_B .. HXM_O3_NMVOC)
+    {"SO2_emissions", {"so2", ""}, "Gg S", 0.0, -1, 0, MIX_SLCF, 0},
+    {"BC_emissions", {"bc", ""}, "Tg", 0.0, -1, 0, MIX_SLCF, 1},
+    {"OC_emissions", {"oc", ""}, "Tg", 0.0, -1, 0, MIX_SLCF, 2},
+    {"NH3_emissions", {"nh3", ""}, "Tg", 0.0, -1, 0, MIX_SLCF, 3},
+    {"NOX_emissions", {"OH", "ozone"}, "Tg N", 0.0, -1, 0, MIX_SLCF, 4},
+    {"CO_emissions", {"OH", "ozone"}, "Tg CO", 0.0, -1, 0, MIX_SLCF, 5},
+    {"NMVOC_emissions", {"OH", "ozone"}, "Tg NMVOC", 0.0, -1, 0, MIX_SLCF, 6},
+    // these vary in no shipped scenario and stay shared
+    {"SV", {"so2", ""}, "W/m2", 0.0, -1, 0, MIX_NONE, -1},
+    {"CH4N", {"CH4", ""}, "Tg CH4", 0.0, -1, 0, MIX_NONE, -1},
+    {"N2O_natural_emissions", {"N2O", ""}, "Tg N", 0.0, -1, 0, MIX_NONE, -1},
+    {"RF_misc", {"forcing", ""}, "W/m2", 0.0, -1, 0, MIX_NONE, -1},
+    {"N2O_constrain", {"N2O", ""}, "ppbv N2O", kNone, -1, 0, MIX_NONE, -1},
 };
-int slcf_index(const std::string &capability) {
-  for (int j = 0; j < 7; ++j) if (capability == kSlcf[j].name) return j;
-  return -1;
+// input j of hx_slcf_mix_kernel, 0..6
+const DatedInput &slcf_input(int j) {
+  for (const DatedInput &r : kDatedInputs) if (r.slcf == j) return r;
+  throw std::logic_error("hx_slcf_mix_kernel has no input " + std::to_string(j));
 }
-}  // namespace
-
-void EnsembleCore::enable_slcf_mixes(bool on) {
-  if (!on && !slcf_mix_.empty()) {
-    std::string names;
-    for (const SlcfDef &d : kSlcf)
-      if (slcf_mix_.count(d.name)) names += (names.empty() ? "" : ", ") + std::string(d.name);
-    throw std::runtime_error("hx_enable_slcf_mixes: " + names + " has a mix: remove the mix first "
-                             "(hx_setvar_dated_mix with nbasis = 0)");
-  }
-  slcf_on_ = on;   // (nothing else: rows, pre-pass and kernel variant follow the mixes, not the switch)
-}
-
-namespace {
-struct DatedDef { const char *name; const char *sections[2]; const char *units; };
-// inputs with dates: capability -> INI section(s) holding the series (component_data.hpp;
-// NOX/CO/NMVOC are read by both the OH and the ozone component)
-const DatedDef kDated[] = {
-    {"ffi_emissions", {"simpleNbox", nullptr}, "Pg C/yr"},
-    {"luc_emissions", {"simpleNbox", nullptr}, "Pg C/yr"},
-    {"daccs_uptake", {"simpleNbox", nullptr}, "Pg C/yr"},
-    {"luc_uptake", {"simpleNbox", nullptr}, "Pg C/yr"},
-    {"RF_albedo", {"simpleNbox", nullptr}, "W/m2"},
-    {"SO2_emissions", {"so2", nullptr}, "Gg S"},
-    {"SV", {"so2", nullptr}, "W/m2"},
-    {"CH4_emissions", {"CH4", nullptr}, "Tg CH4"},
-    {"CH4N", {"CH4", nullptr}, "Tg CH4"},
-    {"NOX_emissions", {"OH", "ozone"}, "Tg N"},
-    {"CO_emissions", {"OH", "ozone"}, "Tg CO"},
-    {"NMVOC_emissions", {"OH", "ozone"}, "Tg NMVOC"},
-    {"N2O_emissions", {"N2O", nullptr}, "Tg N"},
-    {"N2O_natural_emissions", {"N2O", nullptr}, "Tg N"},
-    {"RF_misc", {"forcing", nullptr}, "W/m2"},
-    {"BC_emissions", {"bc", nullptr}, "Tg"},
-    {"OC_emissions", {"oc", nullptr}, "Tg"},
-    {"NH3_emissions", {"nh3", nullptr}, "Tg"},
-    // constraints (component_data.hpp:46,263,273,379-381)
-    {"CO2_constrain", {"simpleNbox", nullptr}, "ppmv CO2"},
-    {"NBP_constrain", {"simpleNbox", nullptr}, "Pg C/yr"},
-    {"tas_constrain", {"temperature", nullptr}, "degC"},
-    {"RF_tot_constrain", {"forcing", nullptr}, "W/m2"},
-    {"CH4_constrain", {"CH4", nullptr}, "ppbv CH4"},
-    {"N2O_constrain", {"N2O", nullptr}, "ppbv N2O"},
-};
-}  // namespace
-
-namespace {
-struct MemberSeriesDef { const char *name; int k; const char *section; const char *units; int lag; };
-// lag: the shared table holds the value of date year-1 for what slowparameval reads
-const MemberSeriesDef kMemberSeries[] = {
-    {"ffi_emissions", HXM_FFI, "simpleNbox", "Pg C/yr", 1},
-    {"daccs_uptake", HXM_DACCS, "simpleNbox", "Pg C/yr", 1},
-    {"luc_emissions", HXM_LUC_E, "simpleNbox", "Pg C/yr", 1},
-    {"luc_uptake", HXM_LUC_U, "simpleNbox", "Pg C/yr", 1},
-    {"CH4_emissions", HXM_CH4_EM, "CH4", "Tg CH4", 0},
-    // constraints that differ between members (NaN = no constraint for that member and year)
-    {"CO2_constrain", HXM_CO2_CON, "simpleNbox", "ppmv CO2", 0},
-    {"NBP_constrain", HXM_NBP_CON, "simpleNbox", "Pg C/yr", 0},
-    {"tas_constrain", HXM_TAS_CON, "temperature", "degC", 0},
-    {"RF_tot_constrain", HXM_FTOT_CON, "forcing", "W/m2", 0},
-    {"CH4_constrain", HXM_CH4_CON, "CH4", "ppbv CH4", 0},
-};
-bool is_constraint_series(int k) { return k >= HXM_CO2_CON && k <= HXM_CH4_CON; }
+// The lists of names as the messages print them (prose, and not in the table's order: literals).
 const char kMixNames[] = "ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions, "
                          "N2O_emissions, RF_albedo and the <gas>_emissions of the scenario's halocarbons";
-// The definition of hx_setvar_dated_mix restated for the host (fetchvars), for year column i of
-// the recipe: every product rounded before it is added, ascending k -- contraction off whatever
-// the host compiler's default is, as in hx_mseries_mix_kernel.
-#if defined(__GNUC__) && !defined(__clang__)
-__attribute__((optimize("fp-contract=off")))
-#endif
-void mix_year_host(const double *basis, const double *coeff, int nbasis, size_t ny, size_t i, size_t n,
-                   double *out) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  for (size_t m = 0; m < n; ++m) {
-    double s = coeff[m] * basis[i];
-    for (int k = 1; k < nbasis; ++k) {
-      const double p = coeff[(size_t)k * n + m] * basis[(size_t)k * ny + i];
-      s = s + p;
-    }
-    out[m] = s;
-  }
-}
-// ... and for ONE member (the per-member diagnostics of fetchvars walk a member's years)
-#if defined(__GNUC__) && !defined(__clang__)
-__attribute__((optimize("fp-contract=off")))
-#endif
-double mix_member_host(const double *basis, const double *coeff, int nbasis, size_t ny, size_t i, size_t n,
-                       size_t m) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  double s = coeff[m] * basis[i];
-  for (int k = 1; k < nbasis; ++k) {
-    const double p = coeff[(size_t)k * n + m] * basis[(size_t)k * ny + i];
-    s = s + p;
-  }
-  return s;
-}
-// ... and with hx_enable_slcf_mixes on
+// ... with hx_enable_slcf_mixes on
 const char kMixNamesSlcf[] = "ffi_emissions, daccs_uptake, luc_emissions, luc_uptake, CH4_emissions, "
                              "N2O_emissions, RF_albedo, the <gas>_emissions of the scenario's halocarbons, "
                              "SO2_emissions, BC_emissions, OC_emissions, NH3_emissions, NOX_emissions, "
                              "CO_emissions and NMVOC_emissions";
+// ... and what setvar_dated_members takes
+const char kMemberSeriesNames[] = "ffi_emissions, luc_emissions, daccs_uptake, luc_uptake, "
+                                  "CH4_emissions, CO2_constrain, NBP_constrain, tas_constrain, "
+                                  "RF_tot_constrain, CH4_constrain";
 bool interpolated_constraint(int k) { return k == HXM_TAS_CON || k == HXM_FTOT_CON; }
 int constraint_bit(int k) {
   switch (k) {
@@ -1328,71 +1279,87 @@ int constraint_bit(int k) {
 }
 }  // namespace
 
+DatedInput EnsembleCore::find_dated(const std::string &capability) const {
+  for (const DatedInput &r : kDatedInputs) if (capability == r.name) return r;
+  auto ends = [&](const std::string &suf) {
+    return capability.size() > suf.size() &&
+           capability.compare(capability.size() - suf.size(), suf.size(), suf) == 0;
+  };
+  const bool emissions = ends("_emissions");
+  DatedInput d;
+  if (!emissions && !Scenario::is_constraint(capability)) return d;
+  const std::string gas = capability.substr(0, capability.size() - 10);   // either suffix
+  for (const Halocarbon &h : scen_.halocarbons)
+    if (h.name == gas) {
+      d.name = capability;
+      d.sections[0] = gas + "_halocarbon";
+      d.units = emissions ? "Gg" : "pptv";
+      d.dflt = emissions ? 0.0 : kNone;
+      d.mix = emissions ? MIX_GAS : MIX_NONE;
+      d.halocarbon = true;
+    }
+  return d;
+}
+
+const EnsembleCore::MemberMix *EnsembleCore::mix_of(const std::string &capability) const {
+  auto it = mixes_.find(capability);
+  return it == mixes_.end() ? nullptr : &it->second;
+}
+
+bool EnsembleCore::any_mix(MixFamily family) const {
+  for (auto &m : mixes_) if (m.second.family == family) return true;
+  return false;
+}
+
+void EnsembleCore::refuse_covered(const char *fn, const std::string &capability, const int *years,
+                                  int n) const {
+  const MemberMix *mx = mix_of(capability);
+  if (!mx) return;
+  for (int i = 0; i < n; ++i)
+    if (mx->covers(years[i]))
+      throw std::runtime_error(std::string(fn) + ": " + capability + " has a mix that covers " +
+                               std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
+                               "with nbasis = 0)");
+}
+
+// R/messages.R:125-133: reset_date = min(date) - 1
+void EnsembleCore::reset_from(int year) {
+  const int target = std::max(0, year - 1 - scen_.start);
+  if (target < last_iy_) dirty_from_iy_ = (dirty_from_iy_ < 0) ? target : std::min(dirty_from_iy_, target);
+}
+
+void EnsembleCore::enable_slcf_mixes(bool on) {
+  if (!on && any_mix(MIX_SLCF)) {
+    std::string names;   // in the kernel's order
+    for (int j = 0; j < 7; ++j)
+      if (mix_of(slcf_input(j).name)) names += (names.empty() ? "" : ", ") + slcf_input(j).name;
+    throw std::runtime_error("hx_enable_slcf_mixes: " + names + " has a mix: remove the mix first "
+                             "(hx_setvar_dated_mix with nbasis = 0)");
+  }
+  slcf_on_ = on;   // (nothing else: rows, pre-pass and kernel variant follow the mixes, not the switch)
+}
+
 void EnsembleCore::setvar_dated(const std::string &capability, const int *years,
                                 const double *values, int n, const char *units) {
-  std::string sections[2];
-  std::string expect;
-  for (const DatedDef &d : kDated)
-    if (capability == d.name) {
-      sections[0] = d.sections[0];
-      if (d.sections[1]) sections[1] = d.sections[1];
-      expect = d.units;
-    }
-  const std::string suf = "_emissions";
-  if (sections[0].empty() && capability.size() > suf.size() &&
-      capability.compare(capability.size() - suf.size(), suf.size(), suf) == 0) {
-    const std::string gas = capability.substr(0, capability.size() - suf.size());
-    for (auto &h : scen_.halocarbons)
-      if (h.name == gas) { sections[0] = gas + "_halocarbon"; expect = "Gg"; }
-  }
-  if (sections[0].empty() && Scenario::is_constraint(capability)) {
-    const std::string gas = capability.substr(0, capability.size() - 10);
-    for (auto &h : scen_.halocarbons)
-      if (h.name == gas) { sections[0] = gas + "_halocarbon"; expect = "pptv"; }
-  }
-  if (sections[0].empty())
+  const DatedInput d = find_dated(capability);
+  if (!d)
     throw std::runtime_error("Unknown variable name while parsing: " + capability +
                              " (dated inputs)");
-  if (units && units[0] && expect != units)
-    throw std::runtime_error("Units: " + std::string(units) + " do not match expected: " + expect +
+  if (units && units[0] && d.units != units)
+    throw std::runtime_error("Units: " + std::string(units) + " do not match expected: " + d.units +
                              " for " + capability);
-  for (const MemberSeriesDef &d : kMemberSeries)
-    if (capability == d.name && mix_[d.k].nbasis)
-      for (int i = 0; i < n; ++i)
-        if (mix_[d.k].covers(years[i]))
-          throw std::runtime_error("hx_setvar_dated: " + capability + " has a mix that covers " +
-                                   std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
-                                   "with nbasis = 0)");
-  {
-    auto gm = gas_mix_.find(capability);
-    if (gm != gas_mix_.end())
-      for (int i = 0; i < n; ++i)
-        if (gm->second.covers(years[i]))
-          throw std::runtime_error("hx_setvar_dated: " + capability + " has a mix that covers " +
-                                   std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
-                                   "with nbasis = 0)");
-  }
-  {
-    auto sm = slcf_mix_.find(capability);
-    if (sm != slcf_mix_.end())
-      for (int i = 0; i < n; ++i)
-        if (sm->second.covers(years[i]))
-          throw std::runtime_error("hx_setvar_dated: " + capability + " has a mix that covers " +
-                                   std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
-                                   "with nbasis = 0)");
-  }
+  refuse_covered("hx_setvar_dated", capability, years, n);
   int miny = scen_.end;
   for (int i = 0; i < n; ++i) {
-    for (auto &sec : sections)
+    for (auto &sec : d.sections)
       if (!sec.empty()) scen_.set_series_value(sec, capability, years[i], values[i]);
     miny = std::min(miny, years[i]);
   }
+  if (d.mix == MIX_TABLE && mix_of(capability)) mseries_dirty_ = true;  // the rows under the mix follow
   // once a variable has per-member series (setvar_dated_members) the kernels and fetchvars read
   // those: a value "for every member" goes into every member's row as well
-  for (const MemberSeriesDef &d : kMemberSeries) {
-    const int k = d.k;
-    if (capability == d.name && mix_[k].nbasis) mseries_dirty_ = true;  // the rows under the mix follow
-    if (capability != d.name || member_series_[k].empty()) continue;
+  if (d.row >= 0 && !member_series_[d.row].empty()) {
+    const int k = d.row;
     if (interpolated_constraint(k)) {  // the interpolated years move with the points
       for (int i = 0; i < n; ++i) member_points_[k][years[i]].assign((size_t)n_, values[i]);
       densify_member_constraint(k, capability);
@@ -1404,44 +1371,33 @@ void EnsembleCore::setvar_dated(const std::string &capability, const int *years,
     mseries_dirty_ = true;
   }
   shared_dirty_ = true;
-  // R/messages.R:125-133: reset_date = min(date) - 1
-  const int target = std::max(0, miny - 1 - scen_.start);
-  if (target < last_iy_) dirty_from_iy_ = (dirty_from_iy_ < 0) ? target : std::min(dirty_from_iy_, target);
+  reset_from(miny);
 }
 
 
 void EnsembleCore::setvar_dated_members(const std::string &capability, const int *years,
                                         const double *values, int nyears, const char *units) {
-  const MemberSeriesDef *d = nullptr;
-  for (const MemberSeriesDef &m : kMemberSeries) if (capability == m.name) d = &m;
-  if (!d)
-    throw std::runtime_error("per-member dated input not supported for " + capability +
-                             " (ffi_emissions, luc_emissions, daccs_uptake, luc_uptake, "
-                             "CH4_emissions, CO2_constrain, NBP_constrain, tas_constrain, "
-                             "RF_tot_constrain, CH4_constrain are)");
-  if (units && units[0] && std::string(units) != d->units)
+  const DatedInput d = find_dated(capability);
+  if (d.row < 0)
+    throw std::runtime_error("per-member dated input not supported for " + capability + " (" +
+                             kMemberSeriesNames + " are)");
+  if (units && units[0] && std::string(units) != d.units)
     throw std::runtime_error("Units: " + std::string(units) + " do not match expected: " +
-                             d->units + " for " + capability);
-  if (mix_[d->k].nbasis)
-    for (int i = 0; i < nyears; ++i)
-      if (mix_[d->k].covers(years[i]))
-        throw std::runtime_error("hx_setvar_dated_members: " + capability + " has a mix that covers " +
-                                 std::to_string(years[i]) + ": remove the mix first (hx_setvar_dated_mix "
-                                 "with nbasis = 0)");
-  const int ns = scen_.ns();
-  std::vector<double> &ms = member_series_[d->k];
+                             d.units + " for " + capability);
+  refuse_covered("hx_setvar_dated_members", capability, years, nyears);
+  const int ns = scen_.ns(), k = d.row;
+  std::vector<double> &ms = member_series_[k];
   if (ms.empty()) {  // start from the scenario's series, the same for every member
     ms.resize((size_t)ns * n_);
-    const std::vector<double> base =
-        scen_.has_series(d->section, capability)
-            ? scen_.series(d->section, capability)
-            : std::vector<double>((size_t)ns, is_constraint_series(d->k) ? std::nan("") : 0.0);
+    const std::vector<double> base = scen_.has_series(d.sections[0], capability)
+                                         ? scen_.series(d.sections[0], capability)
+                                         : std::vector<double>((size_t)ns, d.dflt);
     for (int iy = 0; iy < ns; ++iy)
       std::fill(ms.begin() + (size_t)iy * n_, ms.begin() + (size_t)(iy + 1) * n_, base[(size_t)iy]);
-    if (interpolated_constraint(d->k)) {  // ... and from the shared series' points
-      member_points_[d->k].clear();
-      for (auto &pt : scen_.constraint_points(d->section, capability))
-        member_points_[d->k][pt.first].assign((size_t)n_, pt.second);
+    if (interpolated_constraint(k)) {  // ... and from the shared series' points
+      member_points_[k].clear();
+      for (auto &pt : scen_.constraint_points(d.sections[0], capability))
+        member_points_[k][pt.first].assign((size_t)n_, pt.second);
     }
   }
   int miny = scen_.end;
@@ -1450,40 +1406,81 @@ void EnsembleCore::setvar_dated_members(const std::string &capability, const int
       throw std::runtime_error("date outside startDate..endDate");
     // a CH4 constraint at startDate replaces the preindustrial concentration of the whole core
     // (ch4_component.cpp:137-147): that one cannot differ between members
-    if (d->k == HXM_CH4_CON && years[i] == scen_.start)
+    if (k == HXM_CH4_CON && years[i] == scen_.start)
       throw std::runtime_error("CH4_constrain at startDate: one value for the whole core (setvar_dated)");
-    if (interpolated_constraint(d->k))
-      member_points_[d->k][years[i]].assign(values + (size_t)i * n_, values + (size_t)(i + 1) * n_);
+    if (interpolated_constraint(k))
+      member_points_[k][years[i]].assign(values + (size_t)i * n_, values + (size_t)(i + 1) * n_);
     else
       std::copy(values + (size_t)i * n_, values + (size_t)(i + 1) * n_,
                 ms.begin() + (size_t)(years[i] - scen_.start) * n_);
     miny = std::min(miny, years[i]);
   }
-  if (interpolated_constraint(d->k)) densify_member_constraint(d->k, capability);
+  if (interpolated_constraint(k)) densify_member_constraint(k, capability);
   mseries_dirty_ = true;
-  const int target = std::max(0, miny - 1 - scen_.start);
-  if (target < last_iy_) dirty_from_iy_ = (dirty_from_iy_ < 0) ? target : std::min(dirty_from_iy_, target);
+  reset_from(miny);
 }
 
 bool EnsembleCore::MemberMix::covers(int year) const {
   return std::find(years.begin(), years.end(), year) != years.end();
 }
 
+std::vector<int> EnsembleCore::MemberMix::cover_map(int start, int ns) const {
+  std::vector<int> col((size_t)ns, -1);
+  for (size_t i = 0; i < years.size(); ++i) col[(size_t)(years[i] - start)] = (int)i;
+  return col;
+}
+
+// The definition of hx_setvar_dated_mix restated for the host (fetchvars), for year column i of
+// the recipe: every product rounded before it is added, ascending k -- contraction off whatever
+// the host compiler's default is, as in hx_mseries_mix_kernel.  Two loops over one formula, kept
+// apart on purpose: year_values written as a loop over member_value took 201 ms where this takes
+// 111 ms (host build, fetchvars of ffi_emissions over 556 years, 65 536 members, K = 3).  A whole
+// year, for the inputs themselves ...
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+void EnsembleCore::MemberMix::year_values(size_t i, double *out) const {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const size_t ny = years.size(), n = coeff.size() / (size_t)nbasis;
+  const double *b = basis.data(), *c = coeff.data();
+  for (size_t m = 0; m < n; ++m) {
+    double s = c[m] * b[i];
+    for (int k = 1; k < nbasis; ++k) {
+      const double p = c[(size_t)k * n + m] * b[(size_t)k * ny + i];
+      s = s + p;
+    }
+    out[m] = s;
+  }
+}
+// ... and ONE member (the per-member diagnostics of fetchvars walk a member's years)
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+double EnsembleCore::MemberMix::member_value(size_t i, size_t m) const {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const size_t ny = years.size(), n = coeff.size() / (size_t)nbasis;
+  double s = coeff[m] * basis[i];
+  for (int k = 1; k < nbasis; ++k) {
+    const double p = coeff[(size_t)k * n + m] * basis[(size_t)k * ny + i];
+    s = s + p;
+  }
+  return s;
+}
+
 void EnsembleCore::check_dated_mix(const std::string &capability, const int *years, int nyears,
                                    const double *basis, int nbasis, const double *coeff,
                                    const char *units) const {
   const std::string fn = "hx_setvar_dated_mix: ";
-  const MemberSeriesDef *d = nullptr;
-  for (const MemberSeriesDef &m : kMemberSeries)
-    if (capability == m.name && !is_constraint_series(m.k)) d = &m;
-  std::string expect = d ? d->units : "";
-  const int sj = slcf_on_ ? slcf_index(capability) : -1;
-  if (sj >= 0) expect = kSlcf[sj].units;
-  if (!d && sj < 0 && !gas_mix_capable(capability, nullptr, &expect))
+  const DatedInput d = find_dated(capability);
+  if (d.mix == MIX_NONE || (d.mix == MIX_SLCF && !slcf_on_))
     throw std::runtime_error(fn + "a mix is not supported for " + capability + " (" +
                              (slcf_on_ ? kMixNamesSlcf : kMixNames) + " are)");
-  if (units && units[0] && std::string(units) != expect)
-    throw std::runtime_error(fn + "Units: " + std::string(units) + " do not match expected: " + expect +
+  if (units && units[0] && std::string(units) != d.units)
+    throw std::runtime_error(fn + "Units: " + std::string(units) + " do not match expected: " + d.units +
                              " for " + capability);
   if (nbasis < 0 || nbasis > HX_MIX_MAX_BASIS)
     throw std::runtime_error(fn + "nbasis = " + std::to_string(nbasis) + " outside 0.." +
@@ -1508,77 +1505,53 @@ void EnsembleCore::setvar_dated_mix(const std::string &capability, const int *ye
                                     const double *basis, int nbasis, const double *coeff,
                                     const char *units) {
   check_dated_mix(capability, years, nyears, basis, nbasis, coeff, units);
-  const MemberSeriesDef *d = nullptr;
-  for (const MemberSeriesDef &m : kMemberSeries) if (capability == m.name) d = &m;
-  const int sj = (!d && slcf_on_) ? slcf_index(capability) : -1;
-  if (!d && nbasis == 0 && !(sj >= 0 ? slcf_mix_ : gas_mix_).count(capability)) return;
-  const bool prepass_was = !gas_member_.empty() || !gas_mix_.empty(), slcf_was = !slcf_mix_.empty();
-  MemberMix &mx = d ? mix_[d->k] : sj >= 0 ? slcf_mix_[capability] : gas_mix_[capability];
-  if (nbasis == 0 && mx.nbasis == 0) return;
+  const DatedInput d = find_dated(capability);   // (a mixable one: check_dated_mix has thrown otherwise)
+  const MemberMix *old = mix_of(capability);
+  if (nbasis == 0 && !old) return;   // removing a mix that is not there
+  const bool prepass_was = gas_prepass(), slcf_was = any_mix(MIX_SLCF);
   int miny = scen_.end;   // the years the replaced mix gives back change as well
-  for (int y : mx.years) miny = std::min(miny, y);
+  if (old) for (int y : old->years) miny = std::min(miny, y);
   // A precursor mix that covers startDate: the member's own row 0 enters the OH term of EVERY year
-  const bool row0_was = sj >= 4 && mx.nbasis && mx.covers(scen_.start);
+  const bool precursor = d.mix == MIX_SLCF && d.slcf >= 4;
+  bool row0 = precursor && old && old->covers(scen_.start);
   if (nbasis == 0) {
-    if (d) mx = MemberMix();
-    else if (sj >= 0) slcf_mix_.erase(capability);
-    else gas_mix_.erase(capability);
+    mixes_.erase(capability);
   } else {
+    MemberMix &mx = mixes_[capability];
+    mx.family = d.mix;
     mx.nbasis = nbasis;
     mx.years.assign(years, years + nyears);
     mx.basis.assign(basis, basis + (size_t)nbasis * (size_t)nyears);
     mx.coeff.assign(coeff, coeff + (size_t)nbasis * (size_t)n_);
     for (int y : mx.years) miny = std::min(miny, y);
+    if (precursor && mx.covers(scen_.start)) row0 = true;
   }
-  if (sj >= 4 && (row0_was || (nbasis && std::find(years, years + nyears, scen_.start) != years + nyears)))
-    miny = scen_.start;
-  if (d) mseries_dirty_ = true;
-  else if (sj >= 0) slcf_dirty_ = true;   // hx_slcf_mix_kernel evaluates the recipe ahead of the next run
-  else gas_dirty_ = true;   // the pre-pass evaluates the recipe: nothing else is rebuilt
+  if (row0) miny = scen_.start;
+  switch (d.mix) {
+    case MIX_TABLE: mseries_dirty_ = true; break;
+    case MIX_SLCF: slcf_dirty_ = true; break;   // hx_slcf_mix_kernel evaluates the recipe ahead of the next run
+    default: gas_dirty_ = true;   // the pre-pass evaluates the recipe: nothing else is rebuilt
+  }
   // The pre-pass begins or ends with this call: EVERY year's N2O and forcing row changes its source
   // (the device's exp / pow against the host's: equal to rounding, not bit for bit), so the whole
   // run is redone -- a core whose last mix is removed gives the bits of one that never had any.
-  if (!d && sj < 0 && prepass_was != (!gas_member_.empty() || !gas_mix_.empty())) miny = scen_.start;
+  if (d.mix == MIX_GAS && prepass_was != gas_prepass()) miny = scen_.start;
   // ... and the same where the first aerosol / precursor mix arrives or the last one leaves: the run may
   // change its kernel with it (a core that only records diagnostics runs the plain kernel with them,
   // whose last bits are not the extended kernel's), and a core whose mixes are removed has to give
   // the bits of one that never had any.
-  if (sj >= 0 && slcf_was != !slcf_mix_.empty()) miny = scen_.start;
-  const int target = std::max(0, miny - 1 - scen_.start);
-  if (target < last_iy_) dirty_from_iy_ = (dirty_from_iy_ < 0) ? target : std::min(dirty_from_iy_, target);
-}
-
-// The inputs of the gas pre-pass that may be a mix: what N2OComponent, HalocarbonComponent and the
-// albedo term of ForcingComponent read.  (SV, RF_misc, CH4N and N2O_natural_emissions vary in no
-// shipped scenario and stay shared; the aerosol and ozone / OH precursor emissions feed rows of the
-// per-year table that have no per-member form yet.)
-bool EnsembleCore::gas_mix_capable(const std::string &capability, std::string *section,
-                                   std::string *units) const {
-  auto give = [&](const std::string &sec, const char *u) {
-    if (section) *section = sec;
-    if (units) *units = u;
-    return true;
-  };
-  if (capability == "N2O_emissions") return give("N2O", "Tg N");
-  if (capability == "RF_albedo") return give("simpleNbox", "W/m2");
-  for (const Halocarbon &h : scen_.halocarbons)
-    if (capability == h.name + "_emissions") return give(h.name + "_halocarbon", "Gg");
-  return false;
+  if (d.mix == MIX_SLCF && slcf_was != any_mix(MIX_SLCF)) miny = scen_.start;
+  reset_from(miny);
 }
 
 std::vector<std::string> EnsembleCore::mix_capabilities() const {
   std::vector<std::string> out;
-  for (const MemberSeriesDef &m : kMemberSeries)
-    if (!is_constraint_series(m.k)) out.push_back(m.name);
-  out.push_back("N2O_emissions");
-  out.push_back("RF_albedo");
+  auto rows = [&](MixFamily f) { for (const DatedInput &r : kDatedInputs) if (r.mix == f) out.push_back(r.name); };
+  rows(MIX_TABLE);
+  rows(MIX_GAS);   // N2O_emissions, RF_albedo, then the scenario's gases
   for (const Halocarbon &h : scen_.halocarbons) out.push_back(h.name + "_emissions");
-  if (slcf_on_) for (const SlcfDef &d : kSlcf) out.push_back(d.name);
+  if (slcf_on_) rows(MIX_SLCF);
   return out;
-}
-
-void EnsembleCore::mix_values(const MemberMix &mx, size_t i, double *out) const {
-  mix_year_host(mx.basis.data(), mx.coeff.data(), mx.nbasis, mx.years.size(), i, (size_t)n_, out);
 }
 
 // hx_setvar_scenario_mix's reading of the scenarios: everything but the mixable dated inputs has to
@@ -1660,7 +1633,7 @@ std::vector<EnsembleCore::ScenarioSeries> EnsembleCore::plan_scenario_mix(
     // a precursor is ONE capability read by two components: its two series have to be one
     if (slcf_on_)
       for (int j = 4; j < 7; ++j) {
-        const std::string name = kSlcf[j].name;
+        const std::string &name = slcf_input(j).name;
         if (!o.has_series("OH", name) || !o.has_series("ozone", name)) continue;
         const std::vector<double> &a = o.series("OH", name), &b = o.series("ozone", name);
         for (size_t i = 0; i < a.size() && i < b.size(); ++i)
@@ -1675,10 +1648,7 @@ std::vector<EnsembleCore::ScenarioSeries> EnsembleCore::plan_scenario_mix(
   }
   std::vector<ScenarioSeries> plan;
   for (auto &f : found) {
-    std::string section;
-    for (const MemberSeriesDef &m : kMemberSeries) if (f.first == m.name) section = m.section;
-    if (section.empty() && slcf_index(f.first) >= 0) section = kSlcf[slcf_index(f.first)].sections[0];
-    if (section.empty()) gas_mix_capable(f.first, &section, nullptr);
+    const std::string section = find_dated(f.first).sections[0];
     ScenarioSeries p;
     p.capability = f.first;
     p.basis.resize(K * ns);
@@ -1719,27 +1689,30 @@ void EnsembleCore::densify_member_constraint(int k, const std::string &capabilit
 void EnsembleCore::upload_member_series() {
   const size_t np = (size_t)npad_, ns = (size_t)scen_.ns();
   std::vector<double> flat;
-  for (const MemberSeriesDef &d : kMemberSeries) {
-    const std::vector<double> &ms = member_series_[d.k];
-    if (ms.empty() && !mix_[d.k].nbasis) {
-      if (d_mseries_[d.k]) {  // its mix was removed and nothing lies beneath: shared again
+  for (const DatedInput &r : kDatedInputs) {
+    if (r.row < 0) continue;
+    const int k = r.row;
+    const std::vector<double> &ms = member_series_[k];
+    const MemberMix *mx = mix_of(r.name);
+    if (ms.empty() && !mx) {
+      if (d_mseries_[k]) {  // its mix was removed and nothing lies beneath: shared again
         check(hipStreamSynchronize(stream_), "sync member series");
-        (void)hipFree(d_mseries_[d.k]);
-        d_mseries_[d.k] = nullptr;
+        (void)hipFree(d_mseries_[k]);
+        d_mseries_[k] = nullptr;
       }
       continue;
     }
-    if (!d_mseries_[d.k]) check(hipMalloc(&d_mseries_[d.k], sizeof(double) * ns * np), "hipMalloc member series");
+    if (!d_mseries_[k]) check(hipMalloc(&d_mseries_[k], sizeof(double) * ns * np), "hipMalloc member series");
     if (!ms.empty()) {
       flat.assign(ns * np, 0.0);
-      for (size_t iy = (size_t)d.lag; iy < ns; ++iy)
+      for (size_t iy = (size_t)r.lag; iy < ns; ++iy)
         for (size_t l = 0; l < np; ++l)
-          flat[iy * np + l] = ms[(iy - (size_t)d.lag) * n_ + (size_t)std::min(member_of_lane_[l], n_ - 1)];
-      check(hipMemcpyAsync(d_mseries_[d.k], flat.data(), sizeof(double) * flat.size(),
+          flat[iy * np + l] = ms[(iy - (size_t)r.lag) * n_ + (size_t)std::min(member_of_lane_[l], n_ - 1)];
+      check(hipMemcpyAsync(d_mseries_[k], flat.data(), sizeof(double) * flat.size(),
                            hipMemcpyHostToDevice, stream_), "upload member series");
       check(hipStreamSynchronize(stream_), "sync member series");
     }
-    if (mix_[d.k].nbasis) build_mix_table(d.k, d.lag, d.section, d.name, !ms.empty());
+    if (mx) build_mix_table(r, *mx, !ms.empty());
   }
   upload_args();
   mseries_dirty_ = false;
@@ -1750,9 +1723,9 @@ void EnsembleCore::upload_member_series() {
 // iy - lag, as upload_member_series() lays a dense table out -- then the mix kernel over the rows
 // of the covered years.  What goes up is the recipe: the lane map, the rows, nbasis x covered
 // years of basis and nbasis x n_ coefficients in member order.
-void EnsembleCore::build_mix_table(int k, int lag, const std::string &section, const std::string &capability,
-                                   bool dense) {
-  const MemberMix &mx = mix_[k];
+void EnsembleCore::build_mix_table(const DatedInput &d, const MemberMix &mx, bool dense) {
+  const int k = d.row, lag = d.lag;
+  const std::string &section = d.sections[0], &capability = d.name;
   const size_t np = (size_t)npad_, ns = (size_t)scen_.ns(), ny = mx.years.size(), K = (size_t)mx.nbasis;
   std::vector<int> ints(member_of_lane_.begin(), member_of_lane_.begin() + (std::ptrdiff_t)np);
   std::vector<size_t> col;   // the covered years that have a row (a lag-1 series never reads endDate's)
@@ -1802,13 +1775,75 @@ void EnsembleCore::upload_args() {
   check(hipStreamSynchronize(stream_), "sync args");
 }
 
+// The recipes of a pre-pass as its kernel reads them.  slot[j]: the mix of the kernel's input j or
+// null, in the KERNEL's order (the caller's business).  Appended to dbl, behind whatever the
+// caller has put there: per mixed input nbasis x n_ coefficients in member order (coff: where),
+// then the bases dense in years [nblk][HX_MIX_MAX_BASIS][ns], zero where not covered; the ints are
+// the years covered [nblk][ns] and the lane map.
+EnsembleCore::RecipePack EnsembleCore::pack_recipes(const std::vector<const MemberMix *> &slot,
+                                                    std::vector<double> &dbl) const {
+  const size_t np = (size_t)npad_, ns = (size_t)scen_.ns();
+  RecipePack p;
+  p.rec.assign(2 * slot.size(), 0);
+  std::vector<const MemberMix *> blocks;
+  for (size_t j = 0; j < slot.size(); ++j)
+    if (slot[j]) {
+      p.rec[2 * j] = slot[j]->nbasis; p.rec[2 * j + 1] = (int)blocks.size();
+      blocks.push_back(slot[j]);
+      p.coff.push_back((long long)dbl.size());
+      dbl.insert(dbl.end(), slot[j]->coeff.begin(), slot[j]->coeff.end());
+    }
+  p.nblk = blocks.size();
+  p.o_basis = dbl.size();
+  dbl.resize(p.o_basis + p.nblk * HX_MIX_MAX_BASIS * ns, 0.0);
+  p.ints.assign(p.nblk * ns + np, 0);
+  for (size_t b = 0; b < p.nblk; ++b) {
+    const MemberMix &mx = *blocks[b];
+    const size_t ny = mx.years.size();
+    for (size_t i = 0; i < ny; ++i) {
+      const size_t iy = (size_t)(mx.years[i] - scen_.start);
+      p.ints[b * ns + iy] = 1;
+      for (size_t k = 0; k < (size_t)mx.nbasis; ++k)
+        dbl[p.o_basis + (b * HX_MIX_MAX_BASIS + k) * ns + iy] = mx.basis[k * ny + i];
+    }
+  }
+  std::copy(member_of_lane_.begin(), member_of_lane_.begin() + (std::ptrdiff_t)np,
+            p.ints.begin() + (std::ptrdiff_t)(p.nblk * ns));
+  return p;
+}
+
+// ... and on the device: doubles | offsets | records | ints in one allocation that replaces *block
+// (a kernel of the stream may still read the old one: waited for first), copies queued on stream_.
+// what: "gas", "aerosol / precursor" in the messages of a failing HIP call
+EnsembleCore::RecipeBlock EnsembleCore::upload_recipes(char **block, const std::vector<double> &dbl,
+                                                       const RecipePack &p, const char *what) {
+  const size_t b_dbl = sizeof(double) * dbl.size(), b_ll = sizeof(long long) * p.coff.size(),
+               b_rec = sizeof(int) * p.rec.size(), b_int = sizeof(int) * p.ints.size();
+  const std::string recipes = std::string(what) + " recipes";
+  sync();
+  if (*block) (void)hipFree(*block);
+  *block = nullptr;
+  check(hipMalloc(block, b_dbl + b_ll + b_rec + b_int), ("hipMalloc " + recipes).c_str());
+  RecipeBlock d;
+  d.dbl = reinterpret_cast<double *>(*block);
+  d.coff = reinterpret_cast<long long *>(*block + b_dbl);
+  d.rec = reinterpret_cast<int *>(*block + b_dbl + b_ll);
+  d.cover = d.rec + p.rec.size();
+  d.member_of_lane = d.cover + p.nblk * (size_t)scen_.ns();
+  check(hipMemcpyAsync(d.dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, stream_), ("upload " + recipes).c_str());
+  check(hipMemcpyAsync(d.coff, p.coff.data(), b_ll, hipMemcpyHostToDevice, stream_), ("upload offsets of the " + recipes).c_str());
+  check(hipMemcpyAsync(d.rec, p.rec.data(), b_rec, hipMemcpyHostToDevice, stream_), ("upload records of the " + recipes).c_str());
+  check(hipMemcpyAsync(d.cover, p.ints.data(), b_int, hipMemcpyHostToDevice, stream_), ("upload years of the " + recipes).c_str());
+  return d;
+}
+
 // N2O and halocarbon recurrences per member on the device (hx_gas_kernel): parameter rows in
 // lane order, the member-independent series the recurrences read, and the two result series
 // the extended run kernel picks up instead of the per-year table's columns.
 void EnsembleCore::run_gas_kernel() {
   gas_dirty_ = false;
   auto fr = [](void *p) { if (p) (void)hipFree(p); };
-  if (gas_member_.empty() && gas_mix_.empty()) {  // back to the host's shared series
+  if (!gas_prepass()) {  // back to the host's shared series
     if (d_mseries_[HXM_N2O]) {
       sync();
       fr(d_mseries_[HXM_N2O]); fr(d_mseries_[HXM_RF_OTHER]);
@@ -1893,7 +1928,7 @@ void EnsembleCore::run_gas_kernel() {
                        stream_), "upload gas series");
   check(hipMemcpyAsync(d_h0, h0.data(), sizeof(double) * nh, hipMemcpyHostToDevice, stream_),
         "upload gas preindustrial values");
-  if (gas_mix_.empty()) {
+  if (!any_mix(MIX_GAS)) {
     check(hx_launch_gas(d_gas_par_, d_gas_ser_, d_h0, (int)nh, (int)ns, npad_,
                         const_cast<double *>(d_mseries_[HXM_N2O]),
                         const_cast<double *>(d_mseries_[HXM_RF_OTHER]), stream_), "gas kernel");
@@ -1906,54 +1941,18 @@ void EnsembleCore::run_gas_kernel() {
   // where the recurrences read the value.  Input j: 0 N2O_emissions, 1 RF_albedo, 2 + k the
   // emissions of the k-th gas in summation order.
   std::vector<const MemberMix *> slot(2 + nh, nullptr);
-  auto mix_of = [&](const std::string &cap) -> const MemberMix * {
-    auto it = gas_mix_.find(cap);
-    return it == gas_mix_.end() ? nullptr : &it->second;
-  };
   slot[0] = mix_of("N2O_emissions");
   slot[1] = mix_of("RF_albedo");
   for (size_t k = 0; k < nh; ++k) slot[2 + k] = mix_of(s.halocarbons[horder[k]].name + "_emissions");
-  std::vector<int> rec(2 * (2 + nh), 0);
-  std::vector<long long> coff;
   std::vector<double> dbl;   // coefficient blocks | basis [nblk][HX_MIX_MAX_BASIS][ns] | nat [ns] | molar [nh]
-  size_t nblk = 0;
-  for (size_t j = 0; j < slot.size(); ++j)
-    if (slot[j]) {
-      rec[2 * j] = slot[j]->nbasis; rec[2 * j + 1] = (int)nblk++;
-      coff.push_back((long long)dbl.size());
-      dbl.insert(dbl.end(), slot[j]->coeff.begin(), slot[j]->coeff.end());
-    }
-  const size_t o_basis = dbl.size(), o_nat = o_basis + nblk * HX_MIX_MAX_BASIS * ns, o_molar = o_nat + ns;
+  const RecipePack p = pack_recipes(slot, dbl);
+  const size_t o_nat = dbl.size(), o_molar = o_nat + ns;
   dbl.resize(o_molar + nh, 0.0);
-  std::vector<int> ints(nblk * ns + np, 0);   // cover [nblk][ns] | member_of_lane [np]
-  for (size_t j = 0, b = 0; j < slot.size(); ++j)
-    if (slot[j]) {
-      const MemberMix &mx = *slot[j];
-      const size_t ny = mx.years.size();
-      for (size_t i = 0; i < ny; ++i) {
-        const size_t iy = (size_t)(mx.years[i] - s.start);
-        ints[b * ns + iy] = 1;
-        for (size_t k = 0; k < (size_t)mx.nbasis; ++k)
-          dbl[o_basis + (b * HX_MIX_MAX_BASIS + k) * ns + iy] = mx.basis[k * ny + i];
-      }
-      ++b;
-    }
   for (size_t iy = 0; iy < ns; ++iy) dbl[o_nat + iy] = n2o_nat[iy];
   for (size_t k = 0; k < nh; ++k) dbl[o_molar + k] = s.halocarbons[horder[k]].molarMass;
-  std::copy(member_of_lane_.begin(), member_of_lane_.begin() + (std::ptrdiff_t)np, ints.begin() + (std::ptrdiff_t)(nblk * ns));
-  const size_t b_dbl = sizeof(double) * dbl.size(), b_ll = sizeof(long long) * coff.size(),
-               b_rec = sizeof(int) * rec.size(), b_int = sizeof(int) * ints.size();
-  fr(d_gas_mix_); d_gas_mix_ = nullptr;
-  check(hipMalloc(&d_gas_mix_, b_dbl + b_ll + b_rec + b_int), "hipMalloc gas recipes");
-  double *d_dbl = reinterpret_cast<double *>(d_gas_mix_);
-  long long *d_coff = reinterpret_cast<long long *>(d_gas_mix_ + b_dbl);
-  int *d_rec = reinterpret_cast<int *>(d_gas_mix_ + b_dbl + b_ll), *d_int = d_rec + rec.size();
-  check(hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, stream_), "upload gas recipes");
-  check(hipMemcpyAsync(d_coff, coff.data(), b_ll, hipMemcpyHostToDevice, stream_), "upload gas recipe offsets");
-  check(hipMemcpyAsync(d_rec, rec.data(), b_rec, hipMemcpyHostToDevice, stream_), "upload gas recipe records");
-  check(hipMemcpyAsync(d_int, ints.data(), b_int, hipMemcpyHostToDevice, stream_), "upload gas recipe years");
-  check(hx_launch_gas_mix(d_gas_par_, d_gas_ser_, d_h0, d_dbl + o_nat, d_dbl + o_molar, d_rec, d_dbl, d_coff,
-                          d_dbl + o_basis, d_int, d_int + nblk * ns, n_, (int)nh, (int)ns, npad_,
+  const RecipeBlock d = upload_recipes(&d_gas_mix_, dbl, p, "gas");
+  check(hx_launch_gas_mix(d_gas_par_, d_gas_ser_, d_h0, d.dbl + o_nat, d.dbl + o_molar, d.rec, d.dbl, d.coff,
+                          d.dbl + p.o_basis, d.cover, d.member_of_lane, n_, (int)nh, (int)ns, npad_,
                           const_cast<double *>(d_mseries_[HXM_N2O]),
                           const_cast<double *>(d_mseries_[HXM_RF_OTHER]), stream_), "gas mix kernel");
   check(hipStreamSynchronize(stream_), "gas mix kernel sync");   // (the staging vectors end here)
@@ -1984,9 +1983,10 @@ struct StageClock {
 void EnsembleCore::run_slcf_kernel() {
   slcf_dirty_ = false;
   auto fr = [](void *p) { if (p) (void)hipFree(p); };
+  std::vector<const MemberMix *> slot(7, nullptr);   // in the kernel's order
   bool want_aero = false, want_pre = false;
   for (int j = 0; j < 7; ++j)
-    if (slcf_mix_.count(kSlcf[j].name)) (j < 4 ? want_aero : want_pre) = true;
+    if ((slot[(size_t)j] = mix_of(slcf_input(j).name))) (j < 4 ? want_aero : want_pre) = true;
   const size_t np = (size_t)npad_, ns = (size_t)scen_.ns();
   bool changed = false;
   auto group = [&](int k0, int k1, bool want) {
@@ -2012,22 +2012,20 @@ void EnsembleCore::run_slcf_kernel() {
     return;
   }
   const Scenario &s = scen_;
-  auto ser_of = [&](const char *sec, const char *key) -> const std::vector<double> & { return s.series(sec, key); };
+  auto ser_of = [&](const std::string &sec, const std::string &key) -> const std::vector<double> & { return s.series(sec, key); };
   // ser [12][ns] | kon [8] | coefficient blocks | basis [nblk][HX_MIX_MAX_BASIS][ns]
   std::vector<double> dbl(12 * ns + 8, 0.0);
-  for (int j = 0; j < 4; ++j) std::copy_n(ser_of(kSlcf[j].sections[0], kSlcf[j].name).begin(), ns, dbl.begin() + (std::ptrdiff_t)((size_t)j * ns));
-  for (int j = 4; j < 7; ++j) {
-    std::copy_n(ser_of("OH", kSlcf[j].name).begin(), ns, dbl.begin() + (std::ptrdiff_t)((size_t)j * ns));
-    std::copy_n(ser_of("ozone", kSlcf[j].name).begin(), ns, dbl.begin() + (std::ptrdiff_t)((size_t)(j + 3) * ns));
+  for (int j = 0; j < 7; ++j) {   // a precursor has two series: the OH section's, then the ozone section's
+    const DatedInput &in = slcf_input(j);
+    std::copy_n(ser_of(in.sections[0], in.name).begin(), ns, dbl.begin() + (std::ptrdiff_t)((size_t)j * ns));
+    if (j >= 4)
+      std::copy_n(ser_of(in.sections[1], in.name).begin(), ns, dbl.begin() + (std::ptrdiff_t)((size_t)(j + 3) * ns));
   }
   {  // the shared column's own logarithm, and its argument (build_shared's expressions)
-    const double aci_beta = 2.279759, s_BCOC = 111.05064063;
-    const double s_SO2 = (260.34644166 * 1000) * (32.065 / 64.066);
     const double *so2 = dbl.data(), *bc = so2 + ns, *oc = bc + ns;
     for (size_t iy = 0; iy < ns; ++iy) {
-      const double arg = 1 + (so2[iy] / s_SO2) + ((bc[iy] + oc[iy]) / s_BCOC);
-      dbl[10 * ns + iy] = arg;
-      dbl[11 * ns + iy] = -1 * aci_beta * std::log(arg);
+      dbl[10 * ns + iy] = aci_arg(so2[iy], bc[iy], oc[iy]);
+      dbl[11 * ns + iy] = aci_term(so2[iy], bc[iy], oc[iy]);
     }
   }
   {
@@ -2039,47 +2037,12 @@ void EnsembleCore::run_slcf_kernel() {
               component_disabled("nh3")) ? 1.0 : 0.0;
   }
   const size_t o_kon = 12 * ns;
-  std::vector<int> rec(14, 0);
-  std::vector<long long> coff;
-  std::vector<const MemberMix *> blocks;
-  for (int j = 0; j < 7; ++j) {
-    auto it = slcf_mix_.find(kSlcf[j].name);
-    if (it == slcf_mix_.end()) continue;
-    rec[2 * j] = it->second.nbasis; rec[2 * j + 1] = (int)blocks.size();
-    blocks.push_back(&it->second);
-    coff.push_back((long long)dbl.size());
-    dbl.insert(dbl.end(), it->second.coeff.begin(), it->second.coeff.end());
-  }
-  const size_t nblk = blocks.size(), o_basis = dbl.size();
-  dbl.resize(o_basis + nblk * HX_MIX_MAX_BASIS * ns, 0.0);
-  std::vector<int> ints(nblk * ns + np, 0);   // cover [nblk][ns] | member_of_lane [np]
-  for (size_t b = 0; b < nblk; ++b) {
-    const MemberMix &mx = *blocks[b];
-    const size_t ny = mx.years.size();
-    for (size_t i = 0; i < ny; ++i) {
-      const size_t iy = (size_t)(mx.years[i] - s.start);
-      ints[b * ns + iy] = 1;
-      for (size_t k = 0; k < (size_t)mx.nbasis; ++k)
-        dbl[o_basis + (b * HX_MIX_MAX_BASIS + k) * ns + iy] = mx.basis[k * ny + i];
-    }
-  }
-  std::copy(member_of_lane_.begin(), member_of_lane_.begin() + (std::ptrdiff_t)np, ints.begin() + (std::ptrdiff_t)(nblk * ns));
-  const size_t b_dbl = sizeof(double) * dbl.size(), b_ll = sizeof(long long) * coff.size(),
-               b_rec = sizeof(int) * rec.size(), b_int = sizeof(int) * ints.size();
-  sync();
-  fr(d_slcf_mix_); d_slcf_mix_ = nullptr;
-  check(hipMalloc(&d_slcf_mix_, b_dbl + b_ll + b_rec + b_int), "hipMalloc aerosol / precursor recipes");
-  double *d_dbl = reinterpret_cast<double *>(d_slcf_mix_);
-  long long *d_coff = reinterpret_cast<long long *>(d_slcf_mix_ + b_dbl);
-  int *d_rec = reinterpret_cast<int *>(d_slcf_mix_ + b_dbl + b_ll), *d_int = d_rec + rec.size();
-  check(hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, stream_), "upload aerosol / precursor recipes");
-  check(hipMemcpyAsync(d_coff, coff.data(), b_ll, hipMemcpyHostToDevice, stream_), "upload recipe offsets");
-  check(hipMemcpyAsync(d_rec, rec.data(), b_rec, hipMemcpyHostToDevice, stream_), "upload recipe records");
-  check(hipMemcpyAsync(d_int, ints.data(), b_int, hipMemcpyHostToDevice, stream_), "upload recipe years");
+  const RecipePack p = pack_recipes(slot, dbl);
+  const RecipeBlock d = upload_recipes(&d_slcf_mix_, dbl, p, "aerosol / precursor");
   double *rows7[7];
   for (int k = 0; k < 7; ++k) rows7[k] = const_cast<double *>(d_mseries_[HXM_OH_B + k]);
   StageClock kclk;
-  check(hx_launch_slcf_mix(d_dbl, d_dbl + o_kon, d_rec, d_dbl, d_coff, d_dbl + o_basis, d_int, d_int + nblk * ns, n_,
+  check(hx_launch_slcf_mix(d.dbl, d.dbl + o_kon, d.rec, d.dbl, d.coff, d.dbl + p.o_basis, d.cover, d.member_of_lane, n_,
                            (int)ns, npad_, rows7, stream_), "aerosol / precursor mix kernel");
   check(hipStreamSynchronize(stream_), "aerosol / precursor mix kernel sync");   // (the staging vectors end here)
   kclk.lap("slcf mix kernel + sync");
@@ -2617,14 +2580,16 @@ void EnsembleCore::prepare() {
     clk.lap("check_parameters");
     upload_params();
     clk.lap("upload_params");
-    if (order_changed_)
+    if (order_changed_) {  // lanes have moved
       for (int k = 0; k < HXM_N; ++k)
-        if (!member_series_[k].empty() || mix_[k].nbasis) mseries_dirty_ = true;  // lanes have moved
+        if (!member_series_[k].empty()) mseries_dirty_ = true;
+      if (any_mix(MIX_TABLE)) mseries_dirty_ = true;
+    }
     gas_dirty_ = true;
-    if (!slcf_mix_.empty()) slcf_dirty_ = true;   // (lanes may have moved, the scenario's series changed)
+    if (any_mix(MIX_SLCF)) slcf_dirty_ = true;   // (lanes may have moved, the scenario's series changed)
   }
-  if (slcf_dirty_ || (!slcf_mix_.empty() && !d_mseries_[HXM_OH_B] && !d_mseries_[HXM_RF_AERO])) run_slcf_kernel();
-  if (gas_dirty_ || ((!gas_member_.empty() || !gas_mix_.empty()) && !d_mseries_[HXM_N2O])) run_gas_kernel();
+  if (slcf_dirty_ || (any_mix(MIX_SLCF) && !d_mseries_[HXM_OH_B] && !d_mseries_[HXM_RF_AERO])) run_slcf_kernel();
+  if (gas_dirty_ || (gas_prepass() && !d_mseries_[HXM_N2O])) run_gas_kernel();
   if (mseries_dirty_) upload_member_series();
   clk.lap("gas kernel / member series");
   if (!need_spinup_) return;
@@ -2938,76 +2903,34 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
   auto input = [&](const std::string &sec, const std::string &key, double dflt) {
     return scen_.has_series(sec, key) ? scen_.series(sec, key) : std::vector<double>((size_t)ns, dflt);
   };
-  for (const MemberSeriesDef &d : kMemberSeries)
-    if (capability == d.name && (!member_series_[d.k].empty() || mix_[d.k].nbasis)) {
+  const DatedInput d = find_dated(capability);
+  {  // an input that differs between members: a dense per-member series, or the shared one, and in
+     // the years a mix covers the definition's bits on top
+    const bool dense = d.row >= 0 && !member_series_[d.row].empty();
+    const MemberMix *mx = mix_of(capability);
+    if (dense || mx) {
       if (!out_host) return true;
       if (year0 < scen_.start || year1 > scen_.end || year1 < year0)
         throw std::runtime_error("fetchvars: dates must lie between startDate and endDate");
-      if (!member_series_[d.k].empty()) {
-        std::copy(member_series_[d.k].begin() + (size_t)(year0 - scen_.start) * n_,
-                  member_series_[d.k].begin() + (size_t)(year1 - scen_.start + 1) * n_, out_host);
-      } else {  // a mix over the shared series
-        const std::vector<double> base = input(d.section, capability, 0.0);
+      if (dense) {
+        std::copy(member_series_[d.row].begin() + (size_t)(year0 - scen_.start) * n_,
+                  member_series_[d.row].begin() + (size_t)(year1 - scen_.start + 1) * n_, out_host);
+      } else {
+        const std::vector<double> base = input(d.sections[0], capability, d.dflt);
         for (int y = year0; y <= year1; ++y)
           std::fill(out_host + (size_t)(y - year0) * n_, out_host + (size_t)(y - year0 + 1) * n_,
                     base[(size_t)(y - scen_.start)]);
       }
-      const MemberMix &mx = mix_[d.k];   // the covered years: the definition's bits
-      for (size_t i = 0; i < mx.years.size(); ++i)
-        if (mx.years[i] >= year0 && mx.years[i] <= year1)
-          mix_year_host(mx.basis.data(), mx.coeff.data(), mx.nbasis, mx.years.size(), i, (size_t)n_,
-                        out_host + (size_t)(mx.years[i] - year0) * n_);
-      return true;
-    }
-  {  // an input of the gas pre-pass that has a mix: the shared series, the definition's bits on top
-    auto gm = gas_mix_.find(capability);
-    if (gm != gas_mix_.end()) {
-      if (!out_host) return true;
-      if (year0 < scen_.start || year1 > scen_.end || year1 < year0)
-        throw std::runtime_error("fetchvars: dates must lie between startDate and endDate");
-      std::string section;
-      gas_mix_capable(capability, &section, nullptr);
-      const std::vector<double> base = input(section, capability, capability == "RF_albedo" ? -0.2 : 0.0);
-      for (int y = year0; y <= year1; ++y)
-        std::fill(out_host + (size_t)(y - year0) * n_, out_host + (size_t)(y - year0 + 1) * n_,
-                  base[(size_t)(y - scen_.start)]);
-      const MemberMix &mx = gm->second;
-      for (size_t i = 0; i < mx.years.size(); ++i)
-        if (mx.years[i] >= year0 && mx.years[i] <= year1)
-          mix_values(mx, i, out_host + (size_t)(mx.years[i] - year0) * n_);
+      if (mx)
+        for (size_t i = 0; i < mx->years.size(); ++i)
+          if (mx->years[i] >= year0 && mx->years[i] <= year1)
+            mx->year_values(i, out_host + (size_t)(mx->years[i] - year0) * n_);
       return true;
     }
   }
-  {  // ... and of the aerosol / precursor pre-pass
-    auto sm = slcf_mix_.find(capability);
-    if (sm != slcf_mix_.end()) {
-      if (!out_host) return true;
-      if (year0 < scen_.start || year1 > scen_.end || year1 < year0)
-        throw std::runtime_error("fetchvars: dates must lie between startDate and endDate");
-      const std::vector<double> base = input(kSlcf[slcf_index(capability)].sections[0], capability, 0.0);
-      for (int y = year0; y <= year1; ++y)
-        std::fill(out_host + (size_t)(y - year0) * n_, out_host + (size_t)(y - year0 + 1) * n_,
-                  base[(size_t)(y - scen_.start)]);
-      const MemberMix &mx = sm->second;
-      for (size_t i = 0; i < mx.years.size(); ++i)
-        if (mx.years[i] >= year0 && mx.years[i] <= year1)
-          mix_values(mx, i, out_host + (size_t)(mx.years[i] - year0) * n_);
-      return true;
-    }
-  }
-  // year index -> column of a recipe (-1: the shared value), and one member's value there
-  auto cover_map = [&](const MemberMix &mx) {
-    std::vector<int> col((size_t)ns, -1);
-    for (size_t i = 0; i < mx.years.size(); ++i) col[(size_t)(mx.years[i] - scen_.start)] = (int)i;
-    return col;
-  };
-  auto member_mix = [&](const MemberMix &mx, int col, int i) {
-    return mix_member_host(mx.basis.data(), mx.coeff.data(), mx.nbasis, mx.years.size(), (size_t)col,
-                           (size_t)n_, (size_t)i);
-  };
-  for (const DatedDef &d : kDated)
-    if (capability == d.name && scen_.has_series(d.sections[0], capability))
-      ser = scen_.series(d.sections[0], capability);
+  // (a halocarbon's emissions are answered from the scenario's list below)
+  if (d && !d.halocarbon && scen_.has_series(d.sections[0], capability))
+    ser = scen_.series(d.sections[0], capability);
   const std::string csuf = "_concentration", esuf = "_emissions";
   auto ends = [&](const std::string &suf) {
     return capability.size() > suf.size() &&
@@ -3015,7 +2938,7 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
   };
   if (capability == "N2O_concentration" &&
       (gas_member_.count("N0") || gas_member_.count("TN2O0") || gas_member_.count("UC_N2O") ||
-       gas_mix_.count("N2O_emissions")))
+       mix_of("N2O_emissions")))
     return false;  // differs between members: answered from the device series (fetchvars)
   if (ser.empty() && capability == "N2O_concentration") {
     ser.resize((size_t)ns);
@@ -3029,8 +2952,8 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
       const Halocarbon &H = scen_.halocarbons[h];
       const bool conc = capability == H.name + csuf, rf = capability == "RF_" + H.name;
       if (!(conc || rf)) continue;
-      auto hmix = gas_mix_.find(H.name + esuf);   // ... or whose emissions do
-      if (!(gas_member_.count("tau_" + H.name) || hmix != gas_mix_.end() ||
+      const MemberMix *hmix = mix_of(H.name + esuf);   // ... or whose emissions do
+      if (!(gas_member_.count("tau_" + H.name) || hmix ||
             (rf && (gas_member_.count("rho_" + H.name) || gas_member_.count("delta_" + H.name)))))
         break;
       if (!out_host) return true;
@@ -3047,7 +2970,7 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
                                           ? &scen_.series(H.name + "_halocarbon", H.name + "_constrain") : nullptr;
       const int base = kc_.baseyear_idx;
       std::vector<double> v((size_t)ns);
-      const std::vector<int> col = hmix != gas_mix_.end() ? cover_map(hmix->second) : std::vector<int>((size_t)ns, -1);
+      const std::vector<int> col = hmix ? hmix->cover_map(scen_.start, ns) : std::vector<int>((size_t)ns, -1);
       for (int i = 0; i < n_; ++i) {
         const double tau = val("tau_" + H.name, H.tau, i), rho = val("rho_" + H.name, H.rho, i),
                      delta = val("delta_" + H.name, H.delta, i);
@@ -3055,7 +2978,7 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
         double c = H.H0;
         for (int iy = 0; iy < ns; ++iy) {
           if (iy >= 1) {
-            const double em = col[(size_t)iy] >= 0 ? member_mix(hmix->second, col[(size_t)iy], i)
+            const double em = col[(size_t)iy] >= 0 ? hmix->member_value((size_t)col[(size_t)iy], (size_t)i)
                                                    : H.emissions[(size_t)iy];
             const double dconc = (em / H.molarMass * 1.0) / (0.1 * 1.8);
             c = c * expfac + dconc * tau * (1.0 - expfac);
@@ -3099,10 +3022,8 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
     const MemberMix *amx[4] = {nullptr, nullptr, nullptr, nullptr};
     bool any_mix = false;
     if (which >= 0)
-      for (int j = 0; j < 4; ++j) {
-        auto it = slcf_mix_.find(kSlcf[j].name);
-        if (it != slcf_mix_.end()) { amx[j] = &it->second; any_mix = true; }
-      }
+      for (int j = 0; j < 4; ++j)
+        if ((amx[j] = mix_of(slcf_input(j).name))) any_mix = true;
     if (any_mix && (which == 4 ? (amx[0] || amx[1] || amx[2]) : amx[which] != nullptr)) {
       if (!out_host) return true;
       if (shared_dirty_ || need_spinup_)
@@ -3110,21 +3031,20 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
       if (year0 < scen_.start || year1 > last_date() || year1 < year0)
         throw std::runtime_error("fetchvars: dates must lie between startDate and the current date");
       static const char *const kRho[4] = {"rho_so2", "rho_bc", "rho_oc", "rho_nh3"};
-      const double aci_beta = 2.279759, s_BCOC = 111.05064063;
-      const double s_SO2 = (260.34644166 * 1000) * (32.065 / 64.066);
       std::vector<double> em[4];
       std::vector<int> col[4];
       for (int j = 0; j < 4; ++j) {
-        em[j] = input(kSlcf[j].sections[0], kSlcf[j].name, 0);
-        col[j] = amx[j] ? cover_map(*amx[j]) : std::vector<int>((size_t)ns, -1);
+        const DatedInput &in = slcf_input(j);
+        em[j] = input(in.sections[0], in.name, in.dflt);
+        col[j] = amx[j] ? amx[j]->cover_map(scen_.start, ns) : std::vector<int>((size_t)ns, -1);
       }
       auto emis = [&](int j, int iy, int i) {
-        return col[j][(size_t)iy] >= 0 ? member_mix(*amx[j], col[j][(size_t)iy], i) : em[j][(size_t)iy];
+        return col[j][(size_t)iy] >= 0 ? amx[j]->member_value((size_t)col[j][(size_t)iy], (size_t)i) : em[j][(size_t)iy];
       };
       const double rho = which < 4 ? scen_.scalar("forcing", kRho[which]) : 0.0;
       auto term = [&](int iy, int i) {
         if (which < 4) return rho * emis(which, iy, i);
-        return -1 * aci_beta * std::log(1 + (emis(0, iy, i) / s_SO2) + ((emis(1, iy, i) + emis(2, iy, i)) / s_BCOC));
+        return aci_term(emis(0, iy, i), emis(1, iy, i), emis(2, iy, i));
       };
       const int base = kc_.baseyear_idx;
       for (int i = 0; i < n_; ++i) {
@@ -3142,8 +3062,6 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
     // forcing_component.cpp:430-487; alpha = aero_scalar, volscl = vol_scalar
     const auto bc = input("bc", "BC_emissions", 0), oc = input("oc", "OC_emissions", 0),
                so2 = input("so2", "SO2_emissions", 0), nh3 = input("nh3", "NH3_emissions", 0);
-    const double aci_beta = 2.279759, s_BCOC = 111.05064063;
-    const double s_SO2 = (260.34644166 * 1000) * (32.065 / 64.066);
     auto scaled = [&](const std::vector<double> &e, const char *rho_key) {
       const double rho = scen_.scalar("forcing", rho_key);
       ser.resize((size_t)ns);
@@ -3157,8 +3075,7 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
     else if (capability == "RF_aci") {
       ser.resize((size_t)ns);
       for (int iy = 0; iy < ns; ++iy)
-        ser[(size_t)iy] = -1 * aci_beta * std::log(1 + (so2[(size_t)iy] / s_SO2) +
-                                                   ((bc[(size_t)iy] + oc[(size_t)iy]) / s_BCOC));
+        ser[(size_t)iy] = aci_term(so2[(size_t)iy], bc[(size_t)iy], oc[(size_t)iy]);
       scale = &params_[HXP_AERO];
     } else if (capability == "RF_vol") {
       ser = input("so2", "SV", 0);
@@ -3255,12 +3172,9 @@ void EnsembleCore::var_info(const std::string &capability_in, std::string *compo
     const std::string sec = shared_param_section(scen_, cap, &u);
     if (!sec.empty()) return set(sec, u);
   }
-  for (const DatedDef &d : kDated) if (cap == d.name) return set(d.sections[0], d.units);
-  for (const Halocarbon &h : scen_.halocarbons) {
-    if (cap == h.name + "_emissions") return set(h.name + "_halocarbon", "Gg");
-    if (cap == h.name + "_concentration" || cap == h.name + "_constrain")
-      return set(h.name + "_halocarbon", "pptv");
-  }
+  if (const DatedInput d = find_dated(cap)) return set(d.sections[0], d.units);
+  for (const Halocarbon &h : scen_.halocarbons)
+    if (cap == h.name + "_concentration") return set(h.name + "_halocarbon", "pptv");
   throw std::runtime_error("Caller is requesting unknown variable: " + capability_in);
 }
 

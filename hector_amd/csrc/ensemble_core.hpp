@@ -34,6 +34,22 @@ struct PairCall {
   int nspecs;
 };
 
+// How a mix of a dated input is evaluated: not at all, into the variable's table
+// (hx_mseries_mix_kernel), by the gas pre-pass (hx_gas_mix_kernel) or by the aerosol / precursor
+// pre-pass (hx_slcf_mix_kernel; taken only behind hx_enable_slcf_mixes)
+enum MixFamily { MIX_NONE, MIX_TABLE, MIX_GAS, MIX_SLCF };
+// A dated input as EnsembleCore::find_dated describes it; name empty = no such input
+struct DatedInput {
+  std::string name, sections[2];     // the one or two INI sections that hold the series
+  std::string units;
+  double dflt = 0.0;                 // the value where the scenario has no series
+  int row = -1, lag = 0;             // HXM_* row of its per-member table (-1: none) and that table's lag
+  MixFamily mix = MIX_NONE;
+  int slcf = -1;                     // MIX_SLCF: the input's index in hx_slcf_mix_kernel, 0..6
+  bool halocarbon = false;           // resolved from the scenario's halocarbons, not a row of the table
+  explicit operator bool() const { return !name.empty(); }
+};
+
 class EnsembleCore {
  public:
   EnsembleCore(const std::string &scenario_path, int n_members, int device);
@@ -367,38 +383,65 @@ class EnsembleCore {
   double *d_mseries_[HXM_N] = {};
   bool mseries_dirty_ = false;
   void upload_member_series();
+  // the one lookup of a dated input: a row of kDatedInputs (ensemble_core.cpp), or the scenario's
+  // <gas>_emissions / <gas>_constrain
+  DatedInput find_dated(const std::string &capability) const;
   // A variable's mix (setvar_dated_mix): the recipe, never the n_ x years table.  It overlays
-  // member_series_[k] if that exists, else the scenario's shared series, in `years`.
+  // member_series_[row] if that exists, else the scenario's shared series, in `years`.
   struct MemberMix {
-    int nbasis = 0;                    // 0 = none
+    MixFamily family = MIX_NONE;       // the descriptor's
+    int nbasis = 0;
     std::vector<int> years;            // [ny], as given
     std::vector<double> basis, coeff;  // [nbasis][ny], [nbasis][n_] in member order
     bool covers(int year) const;
+    // year index (from `start`) -> column of the recipe, -1: not covered
+    std::vector<int> cover_map(int start, int ns) const;
+    // the definition's bits in year column i: every member (out[n_]), one member
+    void year_values(size_t i, double *out) const;
+    double member_value(size_t i, size_t member) const;
   };
-  MemberMix mix_[HXM_N];
+  // Every mix of the core by capability, whatever its family.  Nothing that reaches the device or
+  // a message iterates this map: the pre-passes fill their slots in their own order.
+  std::map<std::string, MemberMix> mixes_;
+  const MemberMix *mix_of(const std::string &capability) const;
+  bool any_mix(MixFamily family) const;
+  // the gas pre-pass runs: a gas parameter or an input of it differs between members
+  bool gas_prepass() const { return !gas_member_.empty() || any_mix(MIX_GAS); }
+  // throws "<fn>: <capability> has a mix that covers <year>: remove the mix first ..."
+  void refuse_covered(const char *fn, const std::string &capability, const int *years, int n) const;
+  // inputs changed from `year` on: the next run() goes back to year - 1 (R/messages.R:125-133)
+  void reset_from(int year);
   char *d_mix_ = nullptr;              // scratch of the mix kernel: lane map, rows, basis, coefficients
   size_t mix_cap_ = 0;
-  void build_mix_table(int k, int lag, const std::string &section, const std::string &capability, bool dense);
+  void build_mix_table(const DatedInput &d, const MemberMix &mx, bool dense);
+  // The recipe block of a pre-pass (hx_gas_mix_kernel, hx_slcf_mix_kernel): pack_recipes appends
+  // to the caller's doubles the coefficient blocks of the slots that hold a mix and their bases
+  // dense in years; upload_recipes puts the four parts into one fresh allocation.
+  struct RecipePack {
+    std::vector<long long> coff;       // [nblk] offset of a block's coefficients in the doubles
+    std::vector<int> rec;              // [slots][2]: nbasis (0: no mix), block
+    std::vector<int> ints;             // cover [nblk][ns] | member_of_lane [npad]
+    size_t nblk = 0, o_basis = 0;      // basis [nblk][HX_MIX_MAX_BASIS][ns] at dbl[o_basis]
+  };
+  struct RecipeBlock { double *dbl; long long *coff; int *rec, *cover, *member_of_lane; };
+  RecipePack pack_recipes(const std::vector<const MemberMix *> &slot, std::vector<double> &dbl) const;
+  RecipeBlock upload_recipes(char **block, const std::vector<double> &dbl, const RecipePack &p,
+                             const char *what);
   void upload_args();
   bool component_disabled(const std::string &section) const;  // "enabled=0" in the INI section
   void check_component_enabled(const std::string &capability) const;
   // N2O / halocarbon parameters that differ between members: capability -> [n_] (member order)
   std::map<std::string, std::vector<double>> gas_member_;
   double *d_gas_par_ = nullptr, *d_gas_ser_ = nullptr;
-  // Mixes of the inputs the gas pre-pass reads (N2O_emissions, RF_albedo, <gas>_emissions):
-  // capability -> recipe.  They have no HXM_* row of their own and never a table: the pre-pass
-  // evaluates them where it needs the value (hx_gas_mix_kernel).
-  std::map<std::string, MemberMix> gas_mix_;
+  // Mixes of the inputs the gas pre-pass reads (N2O_emissions, RF_albedo, <gas>_emissions) have no
+  // HXM_* row of their own and never a table: the pre-pass evaluates them where it needs the value
+  // (hx_gas_mix_kernel).
   char *d_gas_mix_ = nullptr;          // that kernel's recipe block (coefficients, basis, cover, lane map)
-  // ... and of the aerosol / precursor inputs (hx_enable_slcf_mixes): recipes as well, evaluated by
+  // ... and those of the aerosol / precursor inputs (hx_enable_slcf_mixes) are evaluated by
   // hx_slcf_mix_kernel into the HXM_OH_B .. HXM_RF_AERO rows
-  std::map<std::string, MemberMix> slcf_mix_;
   char *d_slcf_mix_ = nullptr;
   bool slcf_on_ = false, slcf_dirty_ = false;
   void run_slcf_kernel();
-  bool gas_mix_capable(const std::string &capability, std::string *section, std::string *units) const;
-  // year column i of a recipe for every member, the definition's bits: out[n_]
-  void mix_values(const MemberMix &mx, size_t i, double *out) const;
   void run_gas_kernel();  // fills the per-member N2O and halocarbon-forcing series
   bool gas_dirty_ = false;
   int member_con_mask_ = 0;  // HXC_* bits that only per-member constraint series contribute

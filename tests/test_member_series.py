@@ -1,6 +1,6 @@
 """Per-member input series (hx_setvar_dated_members) on every kernel flavour, against the oracle.
 
-All ten series of kMemberSeries (ensemble_core.cpp) set per member: the five emission series at
+All ten series that have a row in kDatedInputs (ensemble_core.cpp) set per member: the five emission series at
 once on every flavour of the run kernels, the five constraints with members that hold different
 ones (or none), values at the ends of the scenario, and the workflows that move a member's series
 to another lane or another year.  S is drawn unsorted, so with member sorting on the lane order is
