@@ -23,6 +23,9 @@ SERIES_OPS = {"copy": 0, "add": 1, "sub": 2, "mul": 3, "div": 4, "anomaly": 5, "
               "runmean": 7, "delta": 8}     # HX_SER_* of include/hector_amd.h
 
 
+RANK_KINDS = {"pit": 0, "numerator": 1}     # HX_RANK_* of include/hector_amd.h
+
+
 _SCORE_WHITENED_MAX = 256   # HX_SCORE_WHITENED_MAX
 _PROJECT_MAX_OUT, _PROJECT_MAX_YEARS = 64, 1024   # HX_PROJECT_MAX_OUT, HX_PROJECT_MAX_YEARS
 
@@ -1537,6 +1540,82 @@ class Core:
         n = ctypes.c_int()
         self._ck(self._lib.hx_series_list(self._h, ctypes.byref(names), ctypes.byref(years), ctypes.byref(n)))
         return {names[i].decode(): int(years[i]) for i in range(n.value)}
+
+    def rank_series(self, name, var, dates=None, weights=None, kind="pit"):
+        """Define the series `name` as every member's weighted mid-rank of `var` within its year, by
+        a sort of every row on the device (hx_series_rank; hector_amd.ensemble.midpit is the same
+        definition in numpy, bit for bit).  kind "pit": (2 L + E) / (2 W) in (0, 1], the share of the
+        ensemble's weight below the member, ties counted half; "numerator": the exact integer
+        2 L + E.  The rows of `dates` (default: all years run) hold the ranks, every other row NaN.
+        As a series the ranks feed the other verbs: moments(name, against=ranked predictors) is a
+        Spearman correlation (spearman() does that), probabilities(name, edges) a rank histogram,
+        derive and metrics a trajectory's depth."""
+        if kind not in RANK_KINDS:
+            raise HectorAmdError("rank_series: kind must be 'pit' or 'numerator'")
+        w = self._weights(weights, "rank_series")
+        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
+            (int(min(dates)), int(max(dates)))
+        self._ck(self._lib.hx_series_rank(
+            self._h, name.encode(), var.encode(), y0, y1,
+            w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if w is not None else None, RANK_KINDS[kind]))
+        return self
+
+    def metric_ranks(self, var, specs, weights=None, kind="pit"):
+        """Every member's weighted mid-rank among the members, metric by metric (hx_metric_ranks: the
+        metrics of hx_member_metrics are computed and sorted on the device) -> ndarray
+        [n_specs, n_members]; NaN where a member's metric is NaN.  kind as in rank_series()."""
+        if kind not in RANK_KINDS:
+            raise HectorAmdError("metric_ranks: kind must be 'pit' or 'numerator'")
+        arr, ns = self._metric_array(specs, "metric_ranks")
+        w = self._weights(weights, "metric_ranks")
+        dp = ctypes.POINTER(ctypes.c_double)
+        out = np.empty((ns, self.n_members))
+        self._ck(self._lib.hx_metric_ranks(self._h, var.encode(), ctypes.byref(arr), ns,
+                                           w.ctypes.data_as(dp) if w is not None else None, RANK_KINDS[kind],
+                                           out.ctypes.data_as(dp)))
+        return out
+
+    def crps(self, var, years, obs, weights=None, return_pit=False, counts=False):
+        """The continuous ranked probability score of the weighted ensemble against the observation
+        obs[i] of the year years[i], on the device (hx_ensemble_crps; hector_amd.ensemble.crps is the
+        definition in numpy) -> ndarray [n_years].  The years need not be ascending or contiguous; a
+        NaN observation, or a year in which no member takes part, gives NaN.  return_pit=True: also
+        the mid-PIT of every observation within its year's ensemble (their histogram is the rank
+        histogram); counts=True: also the members that took part."""
+        yr = np.ascontiguousarray(np.atleast_1d(np.asarray(years)).astype(np.int32))
+        ob = np.ascontiguousarray(np.atleast_1d(np.asarray(obs, dtype=np.float64)))
+        if yr.ndim != 1 or ob.shape != yr.shape:
+            raise HectorAmdError("crps: years and obs must be one-dimensional and of one length")
+        w = self._weights(weights, "crps")
+        dp = ctypes.POINTER(ctypes.c_double)
+        out, pit = np.empty(yr.size), np.empty(yr.size)
+        npart = np.zeros(yr.size, dtype=np.int64)
+        self._ck(self._lib.hx_ensemble_crps(
+            self._h, var.encode(), yr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ob.ctypes.data_as(dp),
+            int(yr.size), w.ctypes.data_as(dp) if w is not None else None, out.ctypes.data_as(dp),
+            pit.ctypes.data_as(dp), npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        res = (out,) + ((pit,) if return_pit else ()) + ((npart,) if counts else ())
+        return res if len(res) > 1 else out
+
+    def spearman(self, var, against, dates=None, weights=None):
+        """Per-year weighted Spearman rank correlation of `var` with per-member quantities ->
+        ndarray [n_years, K]: the Pearson correlation (moments().corr) of the members' mid-ranks
+        within the year (a temporary rank series, dropped again) with the mid-ranks of every
+        predictor (hector_amd.ensemble.midpit, same weights).  against: as in moments() -- parameter
+        names, arrays [n_members], (var, Metric) pairs.  The core must have room for one more
+        series (16 at most)."""
+        from . import ensemble
+        names, pred, w, _, _ = self._against(against, weights, "spearman")
+        if pred is None:
+            raise HectorAmdError("spearman: against is empty")
+        ranked = [ensemble.midpit(p, w) for p in pred]
+        have = self.series()
+        temp = next(t for t in ("_spearman_%d" % i for i in range(len(have) + 1)) if t not in have)
+        self.rank_series(temp, var, dates, weights)
+        try:
+            return self.moments(temp, dates, weights, against=ranked).corr
+        finally:
+            self.drop_series(temp)
 
     def status(self):
         out = np.zeros(self.n_members, dtype=np.uint32)

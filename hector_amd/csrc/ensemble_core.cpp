@@ -128,6 +128,11 @@ int hx_co_chunks(int n, int na, int nb);
 hipError_t hx_launch_co_gram(const double *va, int ia0, int na, const double *vb, int ib0, int nb, int n,
                              int npad, int sym, const double *qd, const double *shift_a,
                              const double *shift_b, double *part, double *cross, hipStream_t st);
+size_t hx_rank_row_words(int n);
+size_t hx_rank_scratch_bytes();
+hipError_t hx_launch_rank(const double *src, int n, int npad, int row0, const int *rows, int nrows,
+                          const unsigned long long *q, int mode, const double *obs, unsigned long long *scratch,
+                          double *dst, int dst_row0, void *res, hipStream_t stream);
 int hx_sw_padded(int n);
 void hx_sw_pack(const double *whiten, int n, double *wf);
 hipError_t hx_launch_score_whiten(const double *var, int nmem, int npad, const int *iy, const double *obs,
@@ -636,6 +641,7 @@ void EnsembleCore::free_device() {
   fr(d_glab_); d_glab_ = nullptr;
   fr(d_comom_); d_comom_ = nullptr; comom_cap_ = 0; co_a_ = nullptr;
   fr(d_sobol_); d_sobol_ = nullptr; sobol_cap_ = 0; sob_src_ = nullptr;
+  fr(d_rank_); d_rank_ = nullptr; rank_cap_ = 0;
   fr(d_whiten_); d_whiten_ = nullptr; whiten_cap_ = 0;
   fr(d_project_); d_project_ = nullptr; project_cap_ = 0;
   d_score_ = nullptr; d_q_ = d_qstate_ = d_qhist_ = nullptr;
@@ -4915,8 +4921,8 @@ void EnsembleCore::series_drop(const std::string &name) {
   series_.erase(series_.begin() + si);
 }
 
-void EnsembleCore::series_define(const std::string &name, const std::string &a_name, const hx_series_op &op) {
-  const std::string f = "hx_series_define";
+// a new series' name, or the one it replaces, by the rules of hx_series_define (f: the function named)
+int EnsembleCore::series_name_check(const std::string &f, const std::string &name) {
   {  // [A-Za-z_][A-Za-z0-9_]{0,62}
     bool ok = !name.empty() && name.size() <= 63;
     for (size_t i = 0; ok && i < name.size(); ++i) {
@@ -4938,6 +4944,12 @@ void EnsembleCore::series_define(const std::string &name, const std::string &a_n
       throw std::runtime_error(f + ": the core holds " + std::to_string(HX_SER_MAX) + " series already "
                                "(hx_series_drop frees one)");
   }
+  return existing;
+}
+
+void EnsembleCore::series_define(const std::string &name, const std::string &a_name, const hx_series_op &op) {
+  const std::string f = "hx_series_define";
+  const int existing = series_name_check(f, name);
   if (op.op < 0 || op.op >= HX_SER_NOPS) throw std::runtime_error(f + ": unknown op " + std::to_string(op.op));
   const bool binary = op.op >= HX_SER_ADD && op.op <= HX_SER_DIV;
   const int ns = scen_.ns();
@@ -5036,6 +5048,186 @@ void EnsembleCore::series_define(const std::string &name, const std::string &a_n
   } else {
     series_.push_back(std::move(s));
   }
+}
+
+// ---- member ranks and the CRPS (hx_series_rank, hx_metric_ranks, hx_ensemble_crps) ----------------
+
+#ifndef HX_HOST_EMULATION
+namespace {
+// d_rank_ in 8-byte words: the rows' records [nrows][4], the observations [nrows], the row list
+// [nrows] (int), then the sort's buffers for one batch of `per` rows: the rows are split into equal
+// batches that keep those buffers under hx_rank_scratch_bytes() (one row, if a row alone is more)
+struct RankBuf {
+  unsigned long long *res, *sort;
+  double *obs;
+  int *rows;
+  int per;
+  size_t words;
+  RankBuf(unsigned long long *base, int n, int nrows) {
+    const size_t R = (size_t)nrows, rw = hx_rank_row_words(n);
+    const size_t most = std::max<size_t>(1, hx_rank_scratch_bytes() / 8 / rw);
+    const size_t nb = (R + most - 1) / most;
+    per = (int)((R + nb - 1) / nb);
+    res = base;
+    obs = reinterpret_cast<double *>(res + 4 * R);
+    rows = reinterpret_cast<int *>(res + 5 * R);
+    sort = res + 5 * R + (R + 1) / 2;
+    words = 5 * R + (R + 1) / 2 + (size_t)per * rw;
+  }
+};
+}  // namespace
+#endif
+
+void EnsembleCore::rank_check(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                              int nspecs, const char *fn) {
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)year0; (void)year1; (void)specs; (void)nspecs;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  const double *src = nullptr;
+  if (specs) metric_check(capability, specs, nspecs, fn, &src);
+  else (void)q_check(capability, year0, year1, 1, fn);
+#endif
+}
+
+std::vector<unsigned long long> EnsembleCore::rank_rows(const char *fn, const double *src, int row0,
+                                                        const int *rows, int nrows, const unsigned long long *q,
+                                                        int mode, const double *obs, double *dst, int dst_row0) {
+  std::vector<unsigned long long> rec;
+#ifdef HX_HOST_EMULATION
+  (void)src; (void)row0; (void)rows; (void)nrows; (void)q; (void)mode; (void)obs; (void)dst; (void)dst_row0;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  const size_t words = RankBuf(nullptr, n_, nrows).words;
+  if (words > rank_cap_) {
+    if (d_rank_) (void)hipFree(d_rank_);
+    d_rank_ = nullptr; rank_cap_ = 0;
+    if (hipMalloc(&d_rank_, 8 * words) != hipSuccess || !d_rank_) {
+      (void)hipGetLastError();
+      d_rank_ = nullptr;
+      throw std::runtime_error(std::string(fn) + ": no device memory for the scratch of the sort (" +
+                               std::to_string((8 * words) >> 20) + " MiB)");
+    }
+    rank_cap_ = words;
+  }
+  RankBuf b(d_rank_, n_, nrows);
+  const unsigned long long *dq = nullptr;
+  if (q) {   // member order -> lane order (padding lanes: 0; the sort never reads them)
+    if (!d_q_) check(hipMalloc(&d_q_, 8 * (size_t)npad_), "hipMalloc quantile weights");
+    std::vector<unsigned long long> ql((size_t)npad_, 0ull);
+    for (int m = 0; m < n_; ++m) ql[(size_t)lane_of_member_[(size_t)m]] = q[m];
+    check(hipMemcpy(d_q_, ql.data(), 8 * (size_t)npad_, hipMemcpyHostToDevice), "rank weights");
+    dq = d_q_;
+  }
+  if (rows) check(hipMemcpy(b.rows, rows, sizeof(int) * (size_t)nrows, hipMemcpyHostToDevice), "rank rows");
+  if (obs) check(hipMemcpy(b.obs, obs, sizeof(double) * (size_t)nrows, hipMemcpyHostToDevice), "rank observations");
+  for (int r0 = 0; r0 < nrows; r0 += b.per) {   // (stream order: a batch has finished with the buffers before the next)
+    const int nr = std::min(b.per, nrows - r0);
+    check(hx_launch_rank(src, n_, npad_, row0 + r0, rows ? b.rows + r0 : nullptr, nr, dq, mode,
+                         obs ? b.obs + r0 : nullptr, b.sort, dst, dst_row0 + r0, b.res + 4 * (size_t)r0, stream_),
+          "rank kernel");
+  }
+  if (mode == 2) {
+    rec.resize(4 * (size_t)nrows);
+    check(hipMemcpyAsync(rec.data(), b.res, 8 * rec.size(), hipMemcpyDeviceToHost, stream_), "rank fetch");
+  }
+  check(hipStreamSynchronize(stream_), "rank sync");
+#endif
+  return rec;
+}
+
+void EnsembleCore::series_rank(const std::string &name, const std::string &capability, int year0, int year1,
+                               const unsigned long long *q, int kind) {
+  const char *fn = "hx_series_rank";
+#ifdef HX_HOST_EMULATION
+  (void)name; (void)capability; (void)year0; (void)year1; (void)q; (void)kind;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  const std::string f(fn);
+  const int existing = series_name_check(f, name);
+  if (kind != HX_RANK_PIT && kind != HX_RANK_NUMERATOR)
+    throw std::runtime_error(f + ": unknown kind " + std::to_string(kind) + " (HX_RANK_PIT or HX_RANK_NUMERATOR)");
+  const double *src = q_check(capability, year0, year1, 1, fn);
+  if (lane_of_member_.empty()) throw std::runtime_error(f + ": run the core first");
+  sync();
+  const size_t bytes = sizeof(double) * (size_t)scen_.ns() * (size_t)npad_;
+  double *z = nullptr;
+  if (hipMalloc(&z, bytes) != hipSuccess || !z) {
+    (void)hipGetLastError();
+    throw std::runtime_error(f + ": no device memory for the block of series " + name + " (" +
+                             std::to_string(bytes >> 20) + " MiB)");
+  }
+  const int iy0 = year0 - scen_.start, ny = year1 - year0 + 1;
+  try {
+    check(hipMemsetAsync(z, 0xff, bytes, stream_), "rank series fill");   // every double a NaN
+    (void)rank_rows(fn, src, iy0, nullptr, ny, q, kind, nullptr, z, iy0);
+  } catch (...) { (void)hipFree(z); throw; }
+  Series s;
+  s.name = name; s.block = z; s.valid_iy = year1 - scen_.start; s.lane_of_member = lane_of_member_;
+  if (existing >= 0) {
+    (void)hipFree(series_[(size_t)existing].block);
+    series_[(size_t)existing] = std::move(s);
+  } else {
+    series_.push_back(std::move(s));
+  }
+#endif
+}
+
+void EnsembleCore::metric_ranks(const std::string &capability, const hx_metric *specs, int nspecs,
+                                const unsigned long long *q, int kind, double *out_host) {
+  const char *fn = "hx_metric_ranks";
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)specs; (void)nspecs; (void)q; (void)kind; (void)out_host;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  const std::string f(fn);
+  const double *src = nullptr;
+  metric_check(capability, specs, nspecs, fn, &src);
+  if (kind != HX_RANK_PIT && kind != HX_RANK_NUMERATOR)
+    throw std::runtime_error(f + ": unknown kind " + std::to_string(kind) + " (HX_RANK_PIT or HX_RANK_NUMERATOR)");
+  if (!out_host) throw std::runtime_error(f + ": null argument");
+  sync();
+  const double *blk = metric_block(src, specs, nspecs);
+  // the ranks in lane order [nspecs][npad_], then in member order [nspecs][n_], in the score scratch
+  const size_t lane_bytes = sizeof(double) * (size_t)nspecs * (size_t)npad_;
+  const size_t mem_bytes = sizeof(double) * (size_t)nspecs * (size_t)n_;
+  if (lane_bytes + mem_bytes > score_cap_) {
+    if (d_score_) (void)hipFree(d_score_);
+    d_score_ = nullptr; score_cap_ = 0;
+    check(hipMalloc(&d_score_, lane_bytes + mem_bytes), "hipMalloc score");
+    score_cap_ = lane_bytes + mem_bytes;
+  }
+  double *d_lane = d_score_, *d_mem = d_score_ + (size_t)nspecs * (size_t)npad_;
+  check(hipMemsetAsync(d_lane, 0xff, lane_bytes, stream_), "metric rank fill");
+  (void)rank_rows(fn, blk, 0, nullptr, nspecs, q, kind, nullptr, d_lane, 0);
+  check(hx_launch_gather(d_lane, d_lane_of_member_, d_mem, n_, npad_, nspecs, stream_), "metric rank gather");
+  check(hipMemcpyAsync(out_host, d_mem, mem_bytes, hipMemcpyDeviceToHost, stream_), "metric rank fetch");
+  check(hipStreamSynchronize(stream_), "metric rank sync");
+#endif
+}
+
+void EnsembleCore::crps(const std::string &capability, const int *years, const double *obs, int nyears,
+                        const unsigned long long *q, double *crps_host, double *pit_host,
+                        long long *n_part_host) {
+  const char *fn = "hx_ensemble_crps";
+#ifdef HX_HOST_EMULATION
+  (void)capability; (void)years; (void)obs; (void)nyears; (void)q; (void)crps_host; (void)pit_host; (void)n_part_host;
+  throw std::runtime_error(std::string(fn) + kEmulRefusal);
+#else
+  const std::string f(fn);
+  if (nyears < 1 || !years || !obs || !crps_host) throw std::runtime_error(f + ": nyears < 1");
+  const int y0 = *std::min_element(years, years + nyears), y1 = *std::max_element(years, years + nyears);
+  const double *src = q_check(capability, y0, y1, 1, fn);
+  sync();
+  std::vector<int> rows((size_t)nyears);
+  for (int i = 0; i < nyears; ++i) rows[(size_t)i] = years[i] - scen_.start;
+  const std::vector<unsigned long long> rec = rank_rows(fn, src, 0, rows.data(), nyears, q, 2, obs, nullptr, 0);
+  for (int i = 0; i < nyears; ++i) {
+    std::memcpy(&crps_host[i], &rec[4 * (size_t)i], 8);
+    if (pit_host) std::memcpy(&pit_host[i], &rec[4 * (size_t)i + 1], 8);
+    if (n_part_host) n_part_host[i] = (long long)rec[4 * (size_t)i + 2];
+  }
+#endif
 }
 
 }  // namespace hx

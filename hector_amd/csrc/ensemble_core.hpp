@@ -307,6 +307,19 @@ class EnsembleCore {
   void series_define(const std::string &name, const std::string &a, const hx_series_op &op);
   void series_drop(const std::string &name);
   void series_list(std::vector<std::string> *names, std::vector<int> *valid_to) const;
+  // ---- member ranks and the CRPS (hx_series_rank / hx_metric_ranks / hx_ensemble_crps) ------------
+  // One shard only: the sort needs the whole row on this core.  q[n_] integer weights in member order
+  // (nullptr: every member 1); kind: HX_RANK_*.  rank_check is the validation of capability and dates
+  // (specs != nullptr: of the specifications) alone, fn named in every message; the host-emulation
+  // build refuses there.  No prepare(), no spinup, not dirtied.
+  void rank_check(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
+                  const char *fn);
+  void series_rank(const std::string &name, const std::string &capability, int year0, int year1,
+                   const unsigned long long *q, int kind);
+  void metric_ranks(const std::string &capability, const hx_metric *specs, int nspecs,
+                    const unsigned long long *q, int kind, double *out_host);
+  void crps(const std::string &capability, const int *years, const double *obs, int nyears,
+            const unsigned long long *q, double *crps_host, double *pit_host, long long *n_part_host);
   int device() const { return device_; }
   void status(unsigned *out_host);
   void state_row(int row, double *out_host);
@@ -561,6 +574,18 @@ class EnsembleCore {
   };
   std::vector<Series> series_;
   int find_series(const std::string &name) const;
+  // the rules of hx_series_define for a new or replaced name, fn named in the messages -> the index of
+  // the series it replaces, -1 for a new one
+  int series_name_check(const std::string &fn, const std::string &name);
+  // scratch of the rank verbs (RankBuf in ensemble_core.cpp) and the sort of `nrows` rows of a block in
+  // lane order: rows == nullptr the rows row0.., else rows[i]; mode HX_RANK_* writes dst rows
+  // dst_row0.., mode 2 (the CRPS against obs[i]) fills the records it returns (4 words a row:
+  // crps, pit, n_part, 0).  Queued on stream_ and waited for.
+  unsigned long long *d_rank_ = nullptr;
+  size_t rank_cap_ = 0;
+  std::vector<unsigned long long> rank_rows(const char *fn, const double *src, int row0, const int *rows,
+                                            int nrows, const unsigned long long *q, int mode, const double *obs,
+                                            double *dst, int dst_row0);
   void series_to_current_lanes(Series &s);   // permutes the block on the device if the lanes have moved
   void free_series();
   // the kept blocks of derived diagnostics / combinations: valid while out_epoch_ stands

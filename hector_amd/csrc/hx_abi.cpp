@@ -562,6 +562,21 @@ int hx_series_list(hx_core *core, const char *const **names, const int **valid_t
     if (count) *count = (int)store.size();
   })
 }
+int hx_series_rank(hx_core *core, const char *name, const char *capability, int year0, int year1,
+                   const double *weights, int kind) {
+  if (!name || !capability) return fail("hx_series_rank: null argument");
+  HX_TRY(core->core->series_rank(name, capability, year0, year1, weights, kind))
+}
+int hx_metric_ranks(hx_core *core, const char *capability, const hx_metric *specs, int nspecs,
+                    const double *weights, int kind, double *out) {
+  if (!capability || !specs || !out) return fail("hx_metric_ranks: null argument");
+  HX_TRY(core->core->metric_ranks(capability, specs, nspecs, weights, kind, out))
+}
+int hx_ensemble_crps(hx_core *core, const char *capability, const int *years, const double *obs,
+                     int nyears, const double *weights, double *crps, double *pit_obs, long long *n_part) {
+  if (!capability || !years || !obs || !crps) return fail("hx_ensemble_crps: null argument");
+  HX_TRY(core->core->crps(capability, years, obs, nyears, weights, crps, pit_obs, n_part))
+}
 int hx_status(hx_core *core, unsigned *out) {
   if (!out) return fail("hx_status: null argument");
   HX_TRY(core->core->status(out))

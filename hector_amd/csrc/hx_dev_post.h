@@ -1257,6 +1257,418 @@ hipError_t hx_launch_q_pick(int ny, int *lo, unsigned long long *prefix, unsigne
 }
 
 // ===========================================================================
+// Weighted mid-ranks of a row's members and the CRPS of a row against an observation
+// (hx_series_rank, hx_metric_ranks, hx_ensemble_crps in hector_amd.h) by a stable least-significant-
+// digit radix sort of the row's (key, lane) pairs, 8 bits a pass.
+//
+// One workgroup of HXR_BLOCK threads per row; nothing is scanned or synchronised across workgroups,
+// every sum that reaches a result is an integer or a fixed-shape tree of doubles.  The steps of a row:
+//   gather  the row's lanes 0..n-1 in chunks of HXR_BLOCK: x is canonicalised (-0.0 -> +0.0) before
+//           hxq_key, the members taking part (not NaN; the CRPS: and q > 0) are compacted in lane
+//           order into (key, lane) buffer A, and min key, max key, W = sum q, the observation's sums
+//           and the histogram of digit 0 are taken on the way.  Padding lanes (>= n) are never read.
+//   sort    digits 0 .. hb / 8 only, hb the highest bit in which min and max key differ: the keys
+//           share every bit above hb, so a row of equal values runs no pass.  A pass walks its source
+//           in chunks of HXR_CHUNK, in order; a wavefront takes HXR_PER x 64 consecutive elements, 64
+//           at a time: the lanes that hold the same digit are found with eight ballots (hxr_match),
+//           the first of them adds their number to the wavefront's counter of that digit in LDS
+//           (32-bit ds_add, its return value is the digit's count so far) and a lane's place within
+//           its digit follows from the lanes below it.  One thread per digit then turns the
+//           wavefronts' counters into offsets, running over the chunks, and the pairs are scattered
+//           to the other buffer.  The histogram of the next digit is taken during the scatter.
+//   ranks   forward over the sorted pairs: the running uint64 sum of q (shuffle scans as in
+//           hx_q_pick_kernel, the wavefronts added in order) and the first index of every run of equal
+//           keys go to the buffers the sort no longer needs; backward: the running sum at the end of
+//           a run is the suffix minimum over the run ends, N = (sum before the run) + (sum at its end)
+//           = 2 L + E, and z goes to the member's lane of the destination row.
+//   CRPS    forward with the same running sum: one thread per boundary between two runs evaluates
+//           the terms of hector_amd.h, a thread adds its terms in chunk order, the threads are added
+//           by a shuffle tree per wavefront and the wavefronts in order.
+// Scratch per row: two key and two lane buffers of n entries (hx_rank_row_words); the host runs the
+// rows in batches that keep it under HXR_SCRATCH_BYTES.  Every scatter is held to the row's count
+// and every lane read back from a buffer to n before it is used as an index.
+// ===========================================================================
+#define HXR_BLOCK 512
+#define HXR_WAVES (HXR_BLOCK / 64)
+#define HXR_PER 4
+#define HXR_CHUNK (HXR_BLOCK * HXR_PER)
+#define HXR_MODE_CRPS 2   // modes 0 and 1 are HX_RANK_PIT and HX_RANK_NUMERATOR
+static_assert(HX_RANK_PIT == 0 && HX_RANK_NUMERATOR == 1, "the header's kinds are the kernel's modes");
+
+struct HxRankOut { double crps, pit; long long npart, pad; };
+
+__device__ __forceinline__ double hxr_unkey(hxq_u64 key) {
+  const hxq_u64 b = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
+  return __longlong_as_double((long long)b);
+}
+
+// the lanes with `on` that hold the same digit as this one (called by the whole wavefront together)
+__device__ __forceinline__ hxq_u64 hxr_match(int digit, bool on) {
+  hxq_u64 m = __ballot(on);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const bool bit = (digit >> b) & 1;
+    const hxq_u64 v = __ballot(bit);
+    m &= bit ? v : ~v;
+  }
+  return m;
+}
+
+// the terms of one boundary between the runs a < b of the sorted row against the observation y:
+// C = the running sum at the end of run a
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__device__ __forceinline__ double hxr_crps_terms(double acc, double a, double b, double y, hxq_u64 C, hxq_u64 W) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double F = (double)C / (double)W, G = (double)(W - C) / (double)W;
+  const double FF = F * F, GG = G * G;
+  if (y <= a) {
+    const double t = (b - a) * GG;
+    acc = acc + t;
+  } else if (y >= b) {
+    const double t = (b - a) * FF;
+    acc = acc + t;
+  } else {
+    const double t = (y - a) * FF, u = (b - y) * GG;
+    acc = acc + t;
+    acc = acc + u;
+  }
+  return acc;
+}
+
+// the sum of v over the workgroup in every thread: a shuffle tree per wavefront, the wavefronts in
+// order (slot: HXR_WAVES words of LDS; two barriers)
+__device__ __forceinline__ hxq_u64 hxr_block_sum(hxq_u64 v, hxq_u64 *slot, int lane, int wv) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  __syncthreads();
+  if (lane == 0) slot[wv] = v;
+  __syncthreads();
+  hxq_u64 s = 0;
+  for (int w = 0; w < HXR_WAVES; ++w) s += slot[w];
+  return s;
+}
+__device__ __forceinline__ hxq_u64 hxr_block_max(hxq_u64 v, hxq_u64 *slot, int lane, int wv) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
+  __syncthreads();
+  if (lane == 0) slot[wv] = v;
+  __syncthreads();
+  hxq_u64 s = 0;
+  for (int w = 0; w < HXR_WAVES; ++w) s = max(s, slot[w]);
+  return s;
+}
+
+// grid (rows); row r reads src row (rows ? rows[r] : row0 + r) and, for the rank modes, writes dst
+// row dst_row0 + r (NaN on entry: a lane that takes no part keeps it); the CRPS writes res[r]
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+__global__ __launch_bounds__(HXR_BLOCK) void hx_rank_kernel(const double *__restrict__ src, int n, int npad, int row0,
+                                                            const int *__restrict__ rows,
+                                                            const hxq_u64 *__restrict__ q, int mode,
+                                                            const double *__restrict__ obs, hxq_u64 *scratch,
+                                                            double *dst, int dst_row0, HxRankOut *res) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  __shared__ unsigned cnt[2][HXR_WAVES][256];
+  __shared__ unsigned hist[2][256];
+  __shared__ unsigned base[256];
+  __shared__ hxq_u64 wtot[HXR_WAVES], wsec[HXR_WAVES];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r = (int)blockIdx.x;
+  const bool crps = mode == HXR_MODE_CRPS;
+  const double *row = src + (size_t)(rows ? rows[r] : row0 + r) * (size_t)npad;
+  const size_t cap = ((size_t)n + 1) & ~(size_t)1;
+  hxq_u64 *ksrc = scratch + (size_t)r * 3 * cap, *kdst = ksrc + cap;
+  int *lsrc = reinterpret_cast<int *>(kdst + cap), *ldst = lsrc + cap;
+  const hxq_u64 below = lane ? ~0ull >> (64 - lane) : 0ull;   // the lanes under this one
+
+  double yobs = crps ? obs[r] : 0.0;
+  if (yobs == 0.0) yobs = 0.0;
+  if (crps && yobs != yobs) {   // (the same for the whole workgroup)
+    if (tid == 0) { res[r].crps = __builtin_nan(""); res[r].pit = __builtin_nan(""); res[r].npart = 0; res[r].pad = 0; }
+    return;
+  }
+  const hxq_u64 ky = hxq_key(yobs);
+
+  // ---- gather ----------------------------------------------------------------------------------
+  if (tid < 256) { hist[0][tid] = 0; hist[1][tid] = 0; }
+  __syncthreads();
+  hxq_u64 nkmin = 0, kmax = 0, W = 0, lt = 0, eq = 0;
+  int m = 0;   // members gathered so far (the same in every thread)
+  for (int cb = 0; cb < n; cb += HXR_BLOCK) {
+    const int i = cb + tid;
+    const bool in = i < n;
+    double x = __builtin_nan("");
+    if (in) x = row[i];
+    if (x == 0.0) x = 0.0;
+    const hxq_u64 w = (in && q) ? q[i] : 1ull;
+    const bool part = in && x == x && (!crps || w != 0);
+    const hxq_u64 k = hxq_key(x);
+    if (part) {
+      nkmin = max(nkmin, ~k); kmax = max(kmax, k); W += w;
+      if (k < ky) lt += w;
+      if (k == ky) eq += w;
+    }
+    const hxq_u64 pm = __ballot(part);
+    if (lane == 0) wtot[wv] = (hxq_u64)__popcll(pm);
+    const int d = (int)(k & 255ull);
+    const hxq_u64 mm = hxr_match(d, part);
+    if (part && lane == __ffsll((long long)mm) - 1) atomicAdd(&hist[0][d], (unsigned)__popcll(mm));
+    __syncthreads();
+    int off = m, tot = 0;
+    for (int w2 = 0; w2 < HXR_WAVES; ++w2) {
+      const int c = (int)wtot[w2];
+      if (w2 < wv) off += c;
+      tot += c;
+    }
+    if (part) {
+      const int pos = off + __popcll(pm & below);
+      if (pos < n) { ksrc[pos] = k; lsrc[pos] = i; }
+    }
+    m += tot;
+    __syncthreads();
+  }
+  nkmin = hxr_block_max(nkmin, wtot, lane, wv);
+  kmax = hxr_block_max(kmax, wsec, lane, wv);
+  W = hxr_block_sum(W, wtot, lane, wv);
+  lt = hxr_block_sum(lt, wsec, lane, wv);
+  eq = hxr_block_sum(eq, wtot, lane, wv);
+  __syncthreads();
+  if (m == 0 || W == 0) {   // nobody takes part: the rank row stays NaN
+    if (crps && tid == 0) { res[r].crps = __builtin_nan(""); res[r].pit = __builtin_nan(""); res[r].npart = 0; res[r].pad = 0; }
+    return;
+  }
+
+  // ---- sort ------------------------------------------------------------------------------------
+  const hxq_u64 diff = ~nkmin ^ kmax;
+  const int npass = diff ? (63 - __clzll((long long)diff)) / 8 + 1 : 0;
+  for (int p = 0; p < npass; ++p) {
+    const int shift = 8 * p, hc = p & 1, hn = hc ^ 1;
+    const bool next = p + 1 < npass;
+    if (wv == 0) {   // base[d] = the keys with a smaller digit
+      const unsigned c0 = hist[hc][4 * lane], c1 = hist[hc][4 * lane + 1], c2 = hist[hc][4 * lane + 2],
+                     c3 = hist[hc][4 * lane + 3];
+      const unsigned s = c0 + c1 + c2 + c3;
+      unsigned incl = s;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+      }
+      const unsigned ex = incl - s;
+      base[4 * lane] = ex; base[4 * lane + 1] = ex + c0; base[4 * lane + 2] = ex + c0 + c1;
+      base[4 * lane + 3] = ex + c0 + c1 + c2;
+    }
+    for (int j = lane; j < 256; j += 64) { cnt[0][wv][j] = 0; cnt[1][wv][j] = 0; }
+    if (tid < 256) hist[hn][tid] = 0;   // (last read a pass ago, as that pass's hist[hc])
+    __syncthreads();
+    int buf = 0;
+    for (int cb = 0; cb < m; cb += HXR_CHUNK, buf ^= 1) {
+      hxq_u64 k[HXR_PER];
+      int ln[HXR_PER];
+      unsigned rk[HXR_PER];
+#pragma unroll
+      for (int e = 0; e < HXR_PER; ++e) {
+        const int i = cb + wv * (64 * HXR_PER) + e * 64 + lane;
+        k[e] = 0; ln[e] = 0;
+        if (i < m) { k[e] = ksrc[i]; ln[e] = lsrc[i]; }
+      }
+#pragma unroll
+      for (int e = 0; e < HXR_PER; ++e) {
+        const int i = cb + wv * (64 * HXR_PER) + e * 64 + lane;
+        const bool on = i < m;
+        const int d = (int)((k[e] >> shift) & 255ull);
+        const hxq_u64 mm = hxr_match(d, on);
+        const int leader = on ? __ffsll((long long)mm) - 1 : lane;
+        unsigned old = 0;
+        if (on && lane == leader) old = atomicAdd(&cnt[buf][wv][d], (unsigned)__popcll(mm));
+        old = __shfl(old, leader, 64);
+        rk[e] = old + (unsigned)__popcll(mm & below);
+        if (next) {
+          const int d2 = (int)((k[e] >> (shift + 8)) & 255ull);
+          const hxq_u64 m2 = hxr_match(d2, on);
+          if (on && lane == __ffsll((long long)m2) - 1) atomicAdd(&hist[hn][d2], (unsigned)__popcll(m2));
+        }
+      }
+      __syncthreads();
+      if (tid < 256) {   // the wavefronts' counts of digit tid -> where each of them starts
+        unsigned run = base[tid];
+        for (int w2 = 0; w2 < HXR_WAVES; ++w2) {
+          const unsigned c = cnt[buf][w2][tid];
+          cnt[buf][w2][tid] = run;
+          run += c;
+        }
+        base[tid] = run;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int e = 0; e < HXR_PER; ++e) {
+        const int i = cb + wv * (64 * HXR_PER) + e * 64 + lane;
+        if (i < m) {
+          const int d = (int)((k[e] >> shift) & 255ull);
+          const unsigned pos = cnt[buf][wv][d] + rk[e];
+          if (pos < (unsigned)m) { kdst[pos] = k[e]; ldst[pos] = ln[e]; }
+        }
+      }
+      // this wavefront's counters of the next chunk (last read by it a chunk ago)
+      for (int j = lane; j < 256; j += 64) cnt[buf ^ 1][wv][j] = 0;
+    }
+    __syncthreads();
+    { hxq_u64 *t = ksrc; ksrc = kdst; kdst = t; }
+    { int *t = lsrc; lsrc = ldst; ldst = t; }
+  }
+
+  const int nch = (m + HXR_BLOCK - 1) / HXR_BLOCK;
+  if (crps) {
+    // ---- CRPS --------------------------------------------------------------------------------
+    hxq_u64 carry = 0;
+    double acc = 0.0;
+    if (tid == 0) {
+      const double v1 = hxr_unkey(ksrc[0]), vm = hxr_unkey(ksrc[m - 1]);
+      if (yobs < v1) acc = v1 - yobs;
+      if (yobs > vm) acc = yobs - vm;
+    }
+    for (int c = 0; c < nch; ++c) {
+      const int i = c * HXR_BLOCK + tid;
+      const bool on = i < m;
+      hxq_u64 k = 0, w = 0;
+      if (on) {
+        k = ksrc[i];
+        const int l = lsrc[i];
+        w = q ? ((unsigned)l < (unsigned)n ? q[l] : 0ull) : 1ull;
+      }
+      hxq_u64 incl = w;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const hxq_u64 v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+      }
+      if (lane == 63) wtot[wv] = incl;
+      __syncthreads();
+      hxq_u64 off = carry, tot = 0;
+      for (int w2 = 0; w2 < HXR_WAVES; ++w2) {
+        const hxq_u64 t = wtot[w2];
+        if (w2 < wv) off += t;
+        tot += t;
+      }
+      carry += tot;
+      if (on && i + 1 < m) {
+        const hxq_u64 kn = ksrc[i + 1];
+        if (kn != k) acc = hxr_crps_terms(acc, hxr_unkey(k), hxr_unkey(kn), yobs, off + incl, W);
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_down(acc, o, 64);
+    double *dsum = reinterpret_cast<double *>(wsec);
+    if (lane == 0) dsum[wv] = acc;
+    __syncthreads();
+    if (tid == 0) {
+      double s = dsum[0];
+      for (int w2 = 1; w2 < HXR_WAVES; ++w2) s = s + dsum[w2];
+      res[r].crps = s;
+      res[r].pit = (double)(2 * lt + eq) / (double)(2 * W);
+      res[r].npart = (long long)m;
+      res[r].pad = 0;
+    }
+    return;
+  }
+
+  // ---- ranks, forward: kdst[i] = the running sum of q up to and including i, ldst[i] = the first
+  // index of i's run ---------------------------------------------------------------------------
+  {
+    hxq_u64 carry = 0;
+    int cstart = 0;
+    for (int c = 0; c < nch; ++c) {
+      const int i = c * HXR_BLOCK + tid;
+      const bool on = i < m;
+      hxq_u64 k = 0, w = 0;
+      int st = 0;
+      if (on) {
+        k = ksrc[i];
+        const int l = lsrc[i];
+        w = q ? ((unsigned)l < (unsigned)n ? q[l] : 0ull) : 1ull;
+        if (i > 0 && ksrc[i - 1] != k) st = i;
+      }
+      hxq_u64 incl = w;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const hxq_u64 v = __shfl_up(incl, o, 64);
+        const int s2 = __shfl_up(st, o, 64);
+        if (lane >= o) { incl += v; st = max(st, s2); }
+      }
+      if (lane == 63) { wtot[wv] = incl; wsec[wv] = (hxq_u64)st; }
+      __syncthreads();
+      hxq_u64 off = carry, tot = 0;
+      int sbefore = cstart, sall = cstart;
+      for (int w2 = 0; w2 < HXR_WAVES; ++w2) {
+        const hxq_u64 t = wtot[w2];
+        const int s2 = (int)wsec[w2];
+        if (w2 < wv) { off += t; sbefore = max(sbefore, s2); }
+        tot += t; sall = max(sall, s2);
+      }
+      carry += tot; cstart = sall;
+      if (on) { kdst[i] = off + incl; ldst[i] = max(st, sbefore); }
+      __syncthreads();
+    }
+  }
+  // ---- ranks, backward: the running sum at the end of i's run is the smallest one over the run
+  // ends at or after i -----------------------------------------------------------------------------
+  {
+    double *out = dst + (size_t)(dst_row0 + r) * (size_t)npad;
+    const double twoW = (double)(2 * W);
+    hxq_u64 carry = ~0ull;
+    for (int c = nch - 1; c >= 0; --c) {
+      const int i = c * HXR_BLOCK + tid;
+      const bool on = i < m;
+      hxq_u64 v = ~0ull;
+      if (on && (i == m - 1 || ksrc[i + 1] != ksrc[i])) v = kdst[i];
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const hxq_u64 t = __shfl_down(v, o, 64);
+        if (lane + o < 64) v = min(v, t);
+      }
+      if (lane == 0) wtot[wv] = v;
+      __syncthreads();
+      hxq_u64 after = carry, all = carry;
+      for (int w2 = 0; w2 < HXR_WAVES; ++w2) {
+        const hxq_u64 t = wtot[w2];
+        if (w2 > wv) after = min(after, t);
+        all = min(all, t);
+      }
+      carry = all;
+      if (on) {
+        const hxq_u64 H = min(v, after);
+        const int st = ldst[i], l = lsrc[i];
+        const hxq_u64 L = (st > 0 && st <= i) ? kdst[st - 1] : 0ull;
+        const hxq_u64 N = L + H;
+        const double z = mode == HX_RANK_NUMERATOR ? (double)N : (double)N / twoW;
+        if ((unsigned)l < (unsigned)n) out[l] = z;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// 8-byte words of scratch a row of n members needs; the most scratch a batch of rows may take
+size_t hx_rank_row_words(int n) { return 3 * (((size_t)n + 1) & ~(size_t)1); }
+#define HXR_SCRATCH_BYTES ((size_t)HX_RANK_SCRATCH_MIB << 20)
+size_t hx_rank_scratch_bytes() { return HXR_SCRATCH_BYTES; }
+hipError_t hx_launch_rank(const double *src, int n, int npad, int row0, const int *rows, int nrows,
+                          const unsigned long long *q, int mode, const double *obs, unsigned long long *scratch,
+                          double *dst, int dst_row0, void *res, hipStream_t stream) {
+  hipLaunchKernelGGL(hx_rank_kernel, dim3(nrows), dim3(HXR_BLOCK), 0, stream, src, n, npad, row0, rows, q, mode,
+                     obs, scratch, dst, dst_row0, (HxRankOut *)res);
+  return hipGetLastError();
+}
+
+// ===========================================================================
 // Weighted bin sums of rows against fixed edges (hx_ensemble_probabilities, hx_metric_probabilities).
 // grid (row chunks, rows) like hx_q_hist_kernel; a lane takes its HXQ_PER values of the chunk into
 // registers first.  bin(x) = the number of edges <= x: a branch-free binary search over the edges in

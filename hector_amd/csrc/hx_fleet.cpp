@@ -925,6 +925,63 @@ void Fleet::series_define(const std::string &name, const std::string &a, const h
 }
 void Fleet::series_drop(const std::string &name) { HX_EACH(series_drop(name)) }
 
+// The three rank verbs share their refusals: the first shard answers for the capability, the dates or
+// specifications and a core that has not run (the host-emulation build refuses by name there), then
+// a core of several shards is refused -- the sort needs the whole row on one GPU
+EnsembleCore &Fleet::rank_shard(const char *fn, const std::string &cap, int year0, int year1,
+                                const hx_metric *specs, int nspecs) {
+  refuse_processes(fn, "ranks");
+  Shard &s = shards_.front();
+  use(s);
+  s.core->rank_check(cap, year0, year1, specs, nspecs, fn);
+  if (shards_.size() > 1)
+    throw std::runtime_error(std::string(fn) + ": this core has several shards (" +
+                             std::to_string(shards_.size()) + "): a rank needs the whole row of members on "
+                             "one GPU, which the rank verbs do not serve");
+  return *s.core;
+}
+
+static void check_rank_kind(const char *fn, int kind) {
+  if (kind != HX_RANK_PIT && kind != HX_RANK_NUMERATOR)
+    throw std::runtime_error(std::string(fn) + ": unknown kind " + std::to_string(kind) +
+                             " (HX_RANK_PIT or HX_RANK_NUMERATOR)");
+}
+
+void Fleet::series_rank(const std::string &name, const std::string &cap, int year0, int year1,
+                        const double *weights, int kind) {
+  check_poison();
+  const char *fn = "hx_series_rank";
+  check_rank_kind(fn, kind);
+  std::vector<unsigned long long> q;
+  quantise_weights(weights, fn, q);
+  rank_shard(fn, cap, year0, year1, nullptr, 0).series_rank(name, cap, year0, year1, weights ? q.data() : nullptr,
+                                                            kind);
+}
+
+void Fleet::metric_ranks(const std::string &cap, const hx_metric *specs, int nspecs, const double *weights,
+                         int kind, double *out) {
+  check_poison();
+  const char *fn = "hx_metric_ranks";
+  if (nspecs < 1 || nspecs > HX_MET_MAX_SPECS || !specs)
+    throw std::runtime_error(std::string(fn) + ": nspecs must lie in 1..32");
+  check_rank_kind(fn, kind);
+  std::vector<unsigned long long> q;
+  quantise_weights(weights, fn, q);
+  rank_shard(fn, cap, 0, 0, specs, nspecs).metric_ranks(cap, specs, nspecs, weights ? q.data() : nullptr, kind, out);
+}
+
+void Fleet::crps(const std::string &cap, const int *years, const double *obs, int nyears, const double *weights,
+                 double *crps_out, double *pit_obs, long long *n_part) {
+  check_poison();
+  const char *fn = "hx_ensemble_crps";
+  if (nyears < 1) throw std::runtime_error(std::string(fn) + ": nyears < 1");
+  std::vector<unsigned long long> q;
+  quantise_weights(weights, fn, q);
+  const int y0 = *std::min_element(years, years + nyears), y1 = *std::max_element(years, years + nyears);
+  rank_shard(fn, cap, y0, y1, nullptr, 0).crps(cap, years, obs, nyears, weights ? q.data() : nullptr, crps_out,
+                                               pit_obs, n_part);
+}
+
 void Fleet::state_row(int row, double *out) {
   for (Shard &s : shards_) { use(s); s.core->state_row(row, out + s.offset); }
 }

@@ -167,6 +167,15 @@ class Fleet {
   void series_list(std::vector<std::string> *names, std::vector<int> *valid_to) const {
     shards_[0].core->series_list(names, valid_to);
   }
+  // hx_series_rank / hx_metric_ranks / hx_ensemble_crps: the kind and nyears held to their ranges,
+  // the weights quantised as for quantiles, a communicator of several processes and a core of several
+  // shards refused (a rank needs the whole row on one GPU), then the one shard's sort
+  void series_rank(const std::string &name, const std::string &capability, int year0, int year1,
+                   const double *weights, int kind);
+  void metric_ranks(const std::string &capability, const hx_metric *specs, int nspecs, const double *weights,
+                    int kind, double *out);
+  void crps(const std::string &capability, const int *years, const double *obs, int nyears,
+            const double *weights, double *crps_out, double *pit_obs, long long *n_part);
   void state_row(int row, double *out_host);
   int spinup_steps(int member);
   void tracking_data(int member, int year0, int year1, double *values, double *fractions,
@@ -209,6 +218,9 @@ class Fleet {
   void free_stats_buffers();
   // integer weights of hx_ensemble_quantiles for fn (named in the messages): q empty = every member 1
   void quantise_weights(const double *weights, const char *fn, std::vector<unsigned long long> &q) const;
+  // the one shard a rank verb runs on, after the refusals the three of them share (hx_fleet.cpp)
+  EnsembleCore &rank_shard(const char *fn, const std::string &capability, int year0, int year1,
+                           const hx_metric *specs, int nspecs);
   void refuse_processes(const char *fn, const char *what) const;
   void check_groups(const char *fn, const int *labels, int ngroups) const;
   // the select over ny rows, one shard on its GPU or the shards' histograms added per pass; begin /

@@ -929,6 +929,72 @@ int hx_series_drop(hx_core *core, const char *name);
  * that holds values); either may be NULL.  The arrays stay valid until the next call on this thread. */
 int hx_series_list(hx_core *core, const char *const **names, const int **valid_to, int *count);
 
+/* ---- Member ranks within a year's row, and the CRPS of a row against an observation --------------
+ * Every member's weighted mid-rank within its year (its mid-PIT), and the continuous ranked
+ * probability score of the ensemble against an observed record, by a sort of every row on the
+ * device.  No counterpart in the reference.  capability: a per-member variable on the device as for
+ * the other verbs (recorded, derived or a series), so the CRPS of an anomaly is hx_series_define
+ * (ANOMALY) first and then hx_ensemble_crps of that series.
+ * Weights: quantised exactly as for hx_ensemble_quantiles, q_m = rint(w_m / wmax * 2^32), NULL: every
+ * q_m = 1; the same weights are refused.  Values are compared as IEEE doubles after x + 0.0, so -0.0
+ * and +0.0 tie.
+ * Mid-PIT of a member.  For a row, the members whose value is not NaN take part.  W = sum q over
+ * them (a q of 0 adds nothing, but such a member still gets a rank).  For member i:
+ *   L_i = sum of q_j with x_j < x_i;   E_i = sum of q_j with x_j == x_i (q_i included);
+ *   N_i = 2 L_i + E_i      an exact integer <= 2 W <= 2^53
+ *   HX_RANK_PIT:        z_i = (double) N_i / (double) (2 W)   one correctly rounded division, in (0, 1]
+ *   HX_RANK_NUMERATOR:  z_i = (double) N_i    (NULL weights: the average rank of the member, as
+ *                       scipy.stats.rankdata gives it, is (N_i + 1) / 2)
+ * A NaN value gives NaN; W = 0 gives NaN for the whole row.  The result does not depend on lane
+ * order, kernel flavour or how ties are stored: numpy reproduces it bit for bit
+ * (hector_amd.ensemble.midpit).
+ * CRPS of a row against an observation y.  The members with q > 0 and a value that is not NaN take
+ * part (n_part of them); v_1 < ... < v_m are their distinct values, C_k the running sum of q up to and
+ * including v_k, W = C_m, F_k = (double) C_k / (double) W and G_k = (double) (W - C_k) / (double) W (the
+ * integer difference: 1 - F is never formed in floating point).  The result is the sum of these
+ * non-negative terms, each evaluated in double without fused multiply-add:
+ *   v_1 - y  if y < v_1;      y - v_m  if y > v_m;      and for k = 1 .. m-1:
+ *   y <= v_k:       (v_(k+1) - v_k) * (G_k * G_k)
+ *   y >= v_(k+1):   (v_(k+1) - v_k) * (F_k * F_k)
+ *   otherwise the two terms  (y - v_k) * (F_k * F_k)  and  (v_(k+1) - y) * (G_k * G_k)
+ * The order of the additions is not fixed; no term is negative, so every result lies within
+ * (m + 8) 2^-53, relatively, of the exact sum (four roundings a term, m - 1 additions), as long as
+ * the result is a normal double: below 2^-1022 a term or a result is a multiple of 2^-1074.  It equals the
+ * energy form sum p |x - y| - 1/2 sum sum p p' |x - x'| with p = q / W.  pit_obs is the mid-PIT of
+ * the observation itself, (2 sum q[x < y] + sum q[x == y]) / (2 W), exact as above.  A NaN observation,
+ * or a year in which nobody takes part: crps NaN, pit_obs NaN, n_part 0.  With an infinite
+ * participating value the result is whatever IEEE arithmetic gives for the formula (inf or NaN).
+ * Reproducibility: ranks, pit_obs and n_part are exact; the CRPS is bit-identical from call to call
+ * and across lane orders (the terms are added in the order of the sorted values by a fixed tree).
+ * Cost: one workgroup per row sorts the row's (key, lane) pairs by a least-significant-digit radix
+ * sort, 8 bits a pass, and only the passes below the highest bit in which the row's smallest and
+ * largest key differ (a row of equal values runs none, a typical temperature row seven); two more
+ * sweeps over the sorted row give the ranks, one the CRPS.  Scratch: 24 bytes a member and row; rows are
+ * processed in batches so that it stays under HX_RANK_SCRATCH_MIB MiB (or one row, if that is more).
+ * hx_series_rank defines (or replaces) the series `name`: rows year0..year1 hold the ranks of
+ * `capability`, every other row NaN, valid_to = year1; all rules of hx_series_define for names, the
+ * 16-series limit and lane reordering hold.  With the rank as a series the other verbs do the rest:
+ * hx_ensemble_moments of it against ranked predictors is the Spearman correlation,
+ * hx_ensemble_probabilities of it a rank histogram.  hx_metric_ranks is the same for a metric block
+ * (as hx_member_metrics defines it): out[s * n_members + member], member order, back on the host.
+ * hx_ensemble_crps: crps[i], pit_obs[i], n_part[i] (either of the last two may be NULL) for the year
+ * years[i] and the observation obs[i]; the years need not be ascending, contiguous or distinct.
+ * Errors (every message names its function; a refused call changes nothing): those of
+ * hx_ensemble_quantiles for capability, dates and weights; those of hx_series_define for the name;
+ * those of hx_member_metrics for the specifications; an unknown kind; nyears < 1; a core that has not
+ * run; a core of several shards (a rank needs the whole row on one GPU: not served); a communicator
+ * of several processes; no device memory for the scratch or the block.  Not available in the
+ * host-emulation build of the test suite. */
+#define HX_RANK_PIT 0
+#define HX_RANK_NUMERATOR 1
+#define HX_RANK_SCRATCH_MIB 512
+int hx_series_rank(hx_core *core, const char *name, const char *capability, int year0, int year1,
+                   const double *weights, int kind);
+int hx_metric_ranks(hx_core *core, const char *capability, const hx_metric *specs, int nspecs,
+                    const double *weights, int kind, double *out);
+int hx_ensemble_crps(hx_core *core, const char *capability, const int *years, const double *obs,
+                     int nyears, const double *weights, double *crps, double *pit_obs, long long *n_part);
+
 /* per-member model-error bitmask (HX_ERR_* below), host array of n_members */
 int hx_status(hx_core *core, unsigned *out);
 int hx_spinup_steps(hx_core *core, int member, int *steps);
