@@ -694,6 +694,15 @@ class Core:
         self._ck(self._lib.hx_enable_slcf_mixes(self._h, 1 if on else 0))
         return self
 
+    def enable_member_forcing(self, on=True):
+        """Let setvar take one value per member for the forcing efficacies delta_co2, delta_ch4,
+        delta_n2o, rho_bc, rho_oc, rho_so2 and rho_nh3 (hx_enable_member_forcing).  Off by default;
+        a per-member rho_* costs 8 B per member-year (one aerosol row, however many of the four
+        differ), the three delta_* 24 B per member.  Switching it off while one of the seven differs
+        between members is refused."""
+        self._ck(self._lib.hx_enable_member_forcing(self._h, 1 if on else 0))
+        return self
+
     def setvar_dated(self, var, years, values, unit=None):
         y = np.ascontiguousarray(np.atleast_1d(np.asarray(years, dtype=np.int32)))
         v = np.ascontiguousarray(np.broadcast_to(np.asarray(values, dtype=np.float64), y.shape))

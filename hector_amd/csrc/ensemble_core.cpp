@@ -78,7 +78,7 @@ hipError_t hx_launch_gas_mix(const double *par, const double *ser, const double 
 hipError_t hx_launch_slcf_mix(const double *ser, const double *kon, const int *rec, const double *coeff,
                               const long long *coff, const double *basis, const int *cover,
                               const int *member_of_lane, int n, int ns, int npad, double *const *rows7,
-                              hipStream_t st);
+                              const double *const *rho4, hipStream_t st);
 hipError_t hx_launch_bin(const double *var, int n, int npad, int iy0, int nrows, const unsigned long long *q,
                          const double *edges, int K, unsigned long long *sums, hipStream_t stream);
 hipError_t hx_launch_q_minmax(const double *var, int n, int npad, int iy0, int ny,
@@ -873,6 +873,46 @@ static bool gas_member_capable(const Scenario &scen, const std::string &capabili
   return false;
 }
 
+// The forcing efficacies that may differ between members behind hx_enable_member_forcing: the
+// rho_* enter the aerosol row of the pre-pass (hx_slcf_mix_kernel), the delta_* the year loop of
+// the extended run kernels (HXM_EFFICACY).
+static const char *const kForcingMember[7] = {"delta_co2", "delta_ch4", "delta_n2o",
+                                              "rho_bc", "rho_oc", "rho_so2", "rho_nh3"};
+static bool forcing_member_capable(const std::string &capability) {
+  for (const char *k : kForcingMember) if (capability == k) return true;
+  return false;
+}
+
+void EnsembleCore::enable_member_forcing(bool on) {
+  if (on == forcing_on_) return;
+  if (!on && !forcing_member_.empty()) {
+    std::string names;
+    for (const std::string &k : member_forcing_names()) names += (names.empty() ? "" : ", ") + k;
+    throw std::runtime_error("hx_enable_member_forcing: " + names + " differs between members: set "
+                             "one value for the whole core first (hx_setvar with one value)");
+  }
+  forcing_on_ = on;   // (nothing else: rows, pre-pass and kernel variant follow the values, not the switch)
+}
+
+std::vector<std::string> EnsembleCore::member_forcing_names() const {
+  std::vector<std::string> names;
+  for (const char *k : kForcingMember) if (forcing_member_.count(k)) names.push_back(k);
+  return names;
+}
+
+bool EnsembleCore::rho_member() const {
+  for (int j = 3; j < 7; ++j) if (forcing_member_.count(kForcingMember[j])) return true;
+  return false;
+}
+
+// (with [CH4] or [N2O] disabled the forcing component leaves CO2, CH4 and N2O out: the shared -1
+//  of build_shared holds for every member, the members' values are kept for getvar only)
+bool EnsembleCore::delta_member() const {
+  if (component_disabled("CH4") || component_disabled("N2O")) return false;
+  for (int j = 0; j < 3; ++j) if (forcing_member_.count(kForcingMember[j])) return true;
+  return false;
+}
+
 void EnsembleCore::setvar(const std::string &capability, const double *values, int nvalues,
                           const char *units) {
   // R/messages.R (setvar): "<biome>.<variable>" at most
@@ -891,15 +931,18 @@ void EnsembleCore::setvar(const std::string &capability, const double *values, i
                                  expect + " for " + capability);
       bool uniform = true;
       for (int i = 1; i < nvalues; ++i) if (values[i] != values[0]) uniform = false;
+      const bool forcing = forcing_on_ && forcing_member_capable(capability);
       if (!uniform) {
         if (nvalues != n_) throw std::runtime_error("setvar: need 1 or n_members values");
-        if (!gas_member_capable(scen_, capability))
+        if (!forcing && !gas_member_capable(scen_, capability))
           throw std::runtime_error(capability + " belongs to a member-independent component: one "
                                    "value for the whole core");
-        gas_member_[capability].assign(values, values + n_);
+        (forcing ? forcing_member_ : gas_member_)[capability].assign(values, values + n_);
       } else {
         gas_member_.erase(capability);
+        forcing_member_.erase(capability);
       }
+      if (forcing_member_capable(capability)) { slcf_dirty_ = true; eff_dirty_ = true; }
       scen_.set_scalar(sec, key, values[0]);  // (member 0's value where members differ)
       gas_dirty_ = true;
       shared_dirty_ = true;
@@ -947,7 +990,9 @@ void EnsembleCore::getvar(const std::string &capability, double *out) const {
     const std::string sec = shared_param_section(scen_, capability, nullptr, &key);
     if (!sec.empty()) {
       auto it = gas_member_.find(capability);
+      auto fm = forcing_member_.find(capability);
       if (it != gas_member_.end()) std::copy(it->second.begin(), it->second.end(), out);
+      else if (fm != forcing_member_.end()) std::copy(fm->second.begin(), fm->second.end(), out);
       else std::fill(out, out + n_, scen_.scalar(sec, key));
       return;
     }
@@ -1837,7 +1882,8 @@ EnsembleCore::RecipeBlock EnsembleCore::upload_recipes(char **block, const std::
   d.cover = d.rec + p.rec.size();
   d.member_of_lane = d.cover + p.nblk * (size_t)scen_.ns();
   check(hipMemcpyAsync(d.dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, stream_), ("upload " + recipes).c_str());
-  check(hipMemcpyAsync(d.coff, p.coff.data(), b_ll, hipMemcpyHostToDevice, stream_), ("upload offsets of the " + recipes).c_str());
+  if (b_ll)   // (a pre-pass without a mix: per-member rho_* alone)
+    check(hipMemcpyAsync(d.coff, p.coff.data(), b_ll, hipMemcpyHostToDevice, stream_), ("upload offsets of the " + recipes).c_str());
   check(hipMemcpyAsync(d.rec, p.rec.data(), b_rec, hipMemcpyHostToDevice, stream_), ("upload records of the " + recipes).c_str());
   check(hipMemcpyAsync(d.cover, p.ints.data(), b_int, hipMemcpyHostToDevice, stream_), ("upload years of the " + recipes).c_str());
   return d;
@@ -1993,6 +2039,7 @@ void EnsembleCore::run_slcf_kernel() {
   bool want_aero = false, want_pre = false;
   for (int j = 0; j < 7; ++j)
     if ((slot[(size_t)j] = mix_of(slcf_input(j).name))) (j < 4 ? want_aero : want_pre) = true;
+  if (rho_member()) want_aero = true;   // (hx_enable_member_forcing: no mix needed)
   const size_t np = (size_t)npad_, ns = (size_t)scen_.ns();
   bool changed = false;
   auto group = [&](int k0, int k1, bool want) {
@@ -2043,16 +2090,60 @@ void EnsembleCore::run_slcf_kernel() {
               component_disabled("nh3")) ? 1.0 : 0.0;
   }
   const size_t o_kon = 12 * ns;
+  // rho_bc, rho_oc, rho_so2, rho_nh3 that differ between members: [n_] each, member order, behind kon
+  static const char *const kRho[4] = {"rho_bc", "rho_oc", "rho_so2", "rho_nh3"};
+  size_t o_rho[4] = {0, 0, 0, 0};
+  for (int j = 0; j < 4; ++j) {
+    auto it = forcing_member_.find(kRho[j]);
+    if (it == forcing_member_.end()) continue;
+    o_rho[j] = dbl.size();
+    dbl.insert(dbl.end(), it->second.begin(), it->second.end());
+  }
   const RecipePack p = pack_recipes(slot, dbl);
   const RecipeBlock d = upload_recipes(&d_slcf_mix_, dbl, p, "aerosol / precursor");
   double *rows7[7];
   for (int k = 0; k < 7; ++k) rows7[k] = const_cast<double *>(d_mseries_[HXM_OH_B + k]);
+  const double *rho4[4];
+  for (int j = 0; j < 4; ++j) rho4[j] = o_rho[j] ? d.dbl + o_rho[j] : nullptr;
   StageClock kclk;
   check(hx_launch_slcf_mix(d.dbl, d.dbl + o_kon, d.rec, d.dbl, d.coff, d.dbl + p.o_basis, d.cover, d.member_of_lane, n_,
-                           (int)ns, npad_, rows7, stream_), "aerosol / precursor mix kernel");
+                           (int)ns, npad_, rows7, rho4, stream_), "aerosol / precursor mix kernel");
   check(hipStreamSynchronize(stream_), "aerosol / precursor mix kernel sync");   // (the staging vectors end here)
   kclk.lap("slcf mix kernel + sync");
   if (changed) upload_args();
+}
+
+// delta_co2, delta_ch4, delta_n2o per lane (HXM_EFFICACY, [3][npad]) while one of them differs
+// between members: a row that does not holds the core's value.  Gone when none does, or when the
+// forcing component leaves the three gases out ([CH4] or [N2O] disabled: delta_member()).
+void EnsembleCore::upload_efficacies() {
+  eff_dirty_ = false;
+  if (!delta_member()) {
+    if (d_mseries_[HXM_EFFICACY]) {
+      sync();
+      (void)hipFree(d_mseries_[HXM_EFFICACY]);
+      d_mseries_[HXM_EFFICACY] = nullptr;
+      upload_args();
+    }
+    return;
+  }
+  const size_t np = (size_t)npad_;
+  static const char *const kDelta[3] = {"delta_co2", "delta_ch4", "delta_n2o"};
+  const double shared[3] = {kc_.delta_co2, kc_.delta_ch4, kc_.delta_n2o};
+  std::vector<double> eff(3 * np);
+  for (int j = 0; j < 3; ++j) {
+    double *dst = eff.data() + (size_t)j * np;
+    auto it = forcing_member_.find(kDelta[j]);
+    if (it == forcing_member_.end()) { std::fill(dst, dst + np, shared[j]); continue; }
+    for (size_t l = 0; l < np; ++l) dst[l] = it->second[(size_t)std::min(member_of_lane_[l], n_ - 1)];
+  }
+  const bool fresh = !d_mseries_[HXM_EFFICACY];
+  if (fresh) check(hipMalloc(&d_mseries_[HXM_EFFICACY], sizeof(double) * 3 * np), "hipMalloc forcing efficacies");
+  else sync();   // (a kernel of the stream may still read the rows)
+  check(hipMemcpyAsync(d_mseries_[HXM_EFFICACY], eff.data(), sizeof(double) * eff.size(), hipMemcpyHostToDevice,
+                       stream_), "upload forcing efficacies");
+  check(hipStreamSynchronize(stream_), "sync forcing efficacies");   // (the staging vector ends here)
+  if (fresh) upload_args();
 }
 
 void EnsembleCore::lane_of_member(int *out) {
@@ -2566,6 +2657,17 @@ void EnsembleCore::check_parameters() const {
   if (!(kc_.delta_ch4 >= -1 && kc_.delta_ch4 <= 1)) throw std::runtime_error("bad delta CH4 value");
   if (!(kc_.delta_n2o >= -1 && kc_.delta_n2o <= 1)) throw std::runtime_error("bad delta N2O value");
   if (!(kc_.delta_co2 >= -1 && kc_.delta_co2 <= 1)) throw std::runtime_error("bad delta CO2 value");
+  if (delta_member()) {  // ... of every member (hx_enable_member_forcing), in the reference's order
+    static const char *const kDelta[3][2] = {{"delta_ch4", "bad delta CH4 value"}, {"delta_n2o", "bad delta N2O value"},
+                                             {"delta_co2", "bad delta CO2 value"}};
+    for (const auto &d : kDelta) {
+      auto it = forcing_member_.find(d[0]);
+      if (it == forcing_member_.end()) continue;
+      for (size_t i = 0; i < (size_t)n_; ++i)
+        if (!(it->second[i] >= -1 && it->second[i] <= 1))
+          throw std::runtime_error(std::string(d[1]) + " (member " + std::to_string(i) + ")");
+    }
+  }
 }
 
 void EnsembleCore::prepare() {
@@ -2592,9 +2694,11 @@ void EnsembleCore::prepare() {
       if (any_mix(MIX_TABLE)) mseries_dirty_ = true;
     }
     gas_dirty_ = true;
-    if (any_mix(MIX_SLCF)) slcf_dirty_ = true;   // (lanes may have moved, the scenario's series changed)
+    if (slcf_prepass()) slcf_dirty_ = true;   // (lanes may have moved, the scenario's series changed)
+    eff_dirty_ = true;
   }
-  if (slcf_dirty_ || (any_mix(MIX_SLCF) && !d_mseries_[HXM_OH_B] && !d_mseries_[HXM_RF_AERO])) run_slcf_kernel();
+  if (slcf_dirty_ || (slcf_prepass() && !d_mseries_[HXM_OH_B] && !d_mseries_[HXM_RF_AERO])) run_slcf_kernel();
+  if (eff_dirty_ || (delta_member() && !d_mseries_[HXM_EFFICACY])) upload_efficacies();
   if (gas_dirty_ || (gas_prepass() && !d_mseries_[HXM_N2O])) run_gas_kernel();
   if (mseries_dirty_) upload_member_series();
   clk.lap("gas kernel / member series");
@@ -2826,9 +2930,15 @@ void EnsembleCore::run(double runtodate) {
   // land-ocean warming ratio take the extended run kernel, which is also taken for diagnostics
   // this one does not record itself)
   const int pair_cons = con_mask & (HXC_CO2 | HXC_TAS | HXC_FTOT | HXC_CH4);
+  // (per-member forcing efficacies -- the three delta_* rows, the aerosol row written with the
+  // members' rho_* -- are read by the instantiations that carry the constraints)
+  // (an aerosol row that exists for a MIX keeps the core on the run kernels, as before)
+  const bool pair_aero = d_mseries_[HXM_RF_AERO] && !any_mix(MIX_SLCF);
+  const bool pair_forcing = d_mseries_[HXM_EFFICACY] || pair_aero;
   bool plain = (con_mask & ~(HXC_CO2 | HXC_TAS | HXC_FTOT | HXC_CH4)) == 0 && !d_track_out_f_ &&
-               !(pair_cons && ker_per_member_);
-  for (int k = 0; k < HXM_N; ++k) if (d_mseries_[k]) plain = false;
+               !((pair_cons || pair_forcing) && ker_per_member_);
+  for (int k = 0; k < HXM_N; ++k)
+    if (d_mseries_[k] && k != HXM_EFFICACY && !(k == HXM_RF_AERO && pair_aero)) plain = false;
   bool pair = hx_pair_available() && B_ <= 4 && plain && n_ <= pair_max_members_;
   // (two to four biomes -- the land side owns the biome loops --: with shared diffusivity and without
   // the heat-flux sum)
@@ -2852,7 +2962,7 @@ void EnsembleCore::run(double runtodate) {
   last_run_faithful_ = kc_.faithful_retries;
   if (pair)
     check(hx_launch_run_pair(d_args_, npad_, d_out_[HXO_HEATFLUX] != nullptr, ker_per_member_, last_iy_, target,
-                             stream_, pair_cons != 0, B_), "run kernel (pair)");
+                             stream_, pair_cons != 0 || pair_forcing, B_), "run kernel (pair)");
   else
   check(hx_launch_run(B_, d_args_, npad_, hf || con == 2, ker_per_member_, con, last_iy_, target,
                       stream_, w2, simds_ / 4),
@@ -3048,8 +3158,10 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
         return col[j][(size_t)iy] >= 0 ? amx[j]->member_value((size_t)col[j][(size_t)iy], (size_t)i) : em[j][(size_t)iy];
       };
       const double rho = which < 4 ? scen_.scalar("forcing", kRho[which]) : 0.0;
+      const std::vector<double> *rho_m = nullptr;   // ... that differs between members
+      if (which < 4 && forcing_member_.count(kRho[which])) rho_m = &forcing_member_.at(kRho[which]);
       auto term = [&](int iy, int i) {
-        if (which < 4) return rho * emis(which, iy, i);
+        if (which < 4) return (rho_m ? (*rho_m)[(size_t)i] : rho) * emis(which, iy, i);
         return aci_term(emis(0, iy, i), emis(1, iy, i), emis(2, iy, i));
       };
       const int base = kc_.baseyear_idx;
@@ -3074,6 +3186,31 @@ bool EnsembleCore::fetch_host(const std::string &capability_in, int year0, int y
       for (int iy = 0; iy < ns; ++iy) ser[(size_t)iy] = rho * e[(size_t)iy];
       scale = &params_[HXP_AERO];
     };
+    {  // an efficacy that differs between members (hx_enable_member_forcing): per member, the
+       // expressions of the shared answer below
+      static const char *const kRf[4] = {"RF_BC", "RF_OC", "RF_SO2", "RF_NH3"};
+      static const char *const kRho[4] = {"rho_bc", "rho_oc", "rho_so2", "rho_nh3"};
+      const std::vector<double> *em[4] = {&bc, &oc, &so2, &nh3};
+      for (int j = 0; j < 4; ++j) {
+        if (capability != kRf[j] || !forcing_member_.count(kRho[j])) continue;
+        if (!out_host) return true;
+        if (shared_dirty_ || need_spinup_)
+          throw std::runtime_error("fetchvars: run the core after changing inputs");
+        if (year0 < scen_.start || year1 > last_date() || year1 < year0)
+          throw std::runtime_error("fetchvars: dates must lie between startDate and the current date");
+        const std::vector<double> &rho = forcing_member_.at(kRho[j]), &e = *em[j];
+        const int base = kc_.baseyear_idx;
+        for (int i = 0; i < n_; ++i) {
+          const double f = params_[HXP_AERO][(size_t)i], r = rho[(size_t)i];
+          for (int y = year0; y <= year1; ++y) {
+            const int iy = y - scen_.start;
+            out_host[(size_t)(y - year0) * n_ + i] =
+                (iy >= base) ? f * (r * e[(size_t)iy]) - f * (r * e[(size_t)base]) : 0.0;
+          }
+        }
+        return true;
+      }
+    }
     if (capability == "RF_BC") scaled(bc, "rho_bc");
     else if (capability == "RF_OC") scaled(oc, "rho_oc");
     else if (capability == "RF_SO2") scaled(so2, "rho_so2");
@@ -3274,6 +3411,7 @@ void EnsembleCore::compute_derived(const std::string &capability, int iy0, int n
   a.npad = npad_; a.iy0 = iy0; a.ny = ny; a.base_idx = kc_.baseyear_idx;
   a.shared = d_shared_;
   a.n2o_members = d_mseries_[HXM_N2O];
+  a.eff_members = d_mseries_[HXM_EFFICACY];
   a.lo_ratio = d_params_ + (size_t)HXP_LO_RATIO * np;
   a.sqrtN0 = kc_.sqrtN0; a.sqrtM0 = kc_.sqrtM0; a.M0f = kc_.M0f;
   a.delta_n2o = kc_.delta_n2o; a.delta_ch4 = kc_.delta_ch4;

@@ -129,6 +129,12 @@ class EnsembleCore {
   // default, and free until such a mix is set; refused while one is.
   void enable_slcf_mixes(bool on);
   bool slcf_mixes_enabled() const { return slcf_on_; }
+  // Let setvar take n_members values for the forcing efficacies delta_co2, delta_ch4, delta_n2o,
+  // rho_bc, rho_oc, rho_so2, rho_nh3 (hx_enable_member_forcing).  Off by default; switching it off
+  // is refused while one of them differs between members.
+  void enable_member_forcing(bool on);
+  bool member_forcing_enabled() const { return forcing_on_; }
+  std::vector<std::string> member_forcing_names() const;   // those that differ between members now
   static const std::vector<std::string> &spinup_record_vars();
   // values[step * nvars + v] for steps 1..spinup_steps(member); returns the step count
   int spinup_record(int member, double *values, int max_steps);
@@ -454,6 +460,15 @@ class EnsembleCore {
   // hx_slcf_mix_kernel into the HXM_OH_B .. HXM_RF_AERO rows
   char *d_slcf_mix_ = nullptr;
   bool slcf_on_ = false, slcf_dirty_ = false;
+  // Forcing efficacies that differ between members (hx_enable_member_forcing): capability -> [n_]
+  // in member order.  The four rho_* go to hx_slcf_mix_kernel, which writes the HXM_RF_AERO row
+  // with them; the three delta_* are the HXM_EFFICACY rows the extended run kernels read.
+  std::map<std::string, std::vector<double>> forcing_member_;
+  bool forcing_on_ = false, eff_dirty_ = false;
+  bool rho_member() const;     // one of rho_bc, rho_oc, rho_so2, rho_nh3 differs between members
+  bool delta_member() const;   // ... of delta_co2, delta_ch4, delta_n2o, and the run uses them
+  bool slcf_prepass() const { return any_mix(MIX_SLCF) || rho_member(); }
+  void upload_efficacies();
   void run_slcf_kernel();
   void run_gas_kernel();  // fills the per-member N2O and halocarbon-forcing series
   bool gas_dirty_ = false;

@@ -318,6 +318,10 @@ int hx_enable_slcf_mixes(hx_core *core, int on) {
   if (!core) return fail("hx_enable_slcf_mixes: null core");
   HX_TRY(core->core->enable_slcf_mixes(on != 0))
 }
+int hx_enable_member_forcing(hx_core *core, int on) {
+  if (!core) return fail("hx_enable_member_forcing: null core");
+  HX_TRY(core->core->enable_member_forcing(on != 0))
+}
 int hx_spinup_record(hx_core *core, int member, const char *const **names, int *nvars, double *values,
                      int max_steps, int *steps) {
   static const std::vector<const char *> cnames = [] {

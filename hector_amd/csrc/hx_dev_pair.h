@@ -718,6 +718,14 @@ __global__ __launch_bounds__(128) HX_PAIR_OCC void hx_pair_kernel(const HxArgs *
         const double a2 = -3.4197e-4, b2 = 2.5455e-4, c2 = -2.4357e-4, d2 = 0.12173;
         const double a3 = -8.9603e-5, b3 = -1.2462e-4, d3 = 0.045194;
         const double sqN = sh[HXSH_SQRT_N2O], sqN0 = kc.sqrtN0, rf_other = sh[HXSH_RF_OTHER];
+        // forcing efficacies that differ between members (hx_enable_member_forcing): the three delta_*
+        // [3][npad] and the aerosol row the pre-pass wrote with the members' rho_*, each taken where the
+        // core-wide value is read
+        [[maybe_unused]] bool eff_on = false, aero_on = false;
+        if constexpr (CONS) {
+          eff_on = HX_RARE(buf.ms_mask & (1u << HXM_EFFICACY));
+          aero_on = HX_RARE(buf.ms_mask & (1u << HXM_RF_AERO));
+        }
         const double sqM = hx_sqrt(ch4), sqC = hx_sqrt(co2c);
         const double C_alpha_max = C0 - (b1 / (2 * a1));
         double alpha_prime;
@@ -726,15 +734,23 @@ __global__ __launch_bounds__(128) HX_PAIR_OCC void hx_pair_kernel(const HxArgs *
           alpha_prime = d1 + a1 * ((co2c - C0) * (co2c - C0)) + b1 * (co2c - C0);
         else alpha_prime = d1;
         const double sarf_co2 = (alpha_prime + c1 * sqN) * ln_co2r;
-        const double fco2 = (sarf_co2 * kc.delta_co2) + sarf_co2;
+        double dl_co2 = kc.delta_co2;
+        if constexpr (CONS) { if (eff_on) dl_co2 = HX_GCD(HXM_SLCF(buf, HXM_EFFICACY))[mem]; }
+        const double fco2 = (sarf_co2 * dl_co2) + sarf_co2;
         const double sarf_n2o = (a2 * sqC + b2 * sqN + c2 * sqM + d2) * (sqN - sqN0);
-        const double fn2o = (kc.delta_n2o * sarf_n2o) + sarf_n2o;
+        double dl_n2o = kc.delta_n2o;
+        if constexpr (CONS) { if (eff_on) dl_n2o = HX_GCD(HXM_SLCF(buf, HXM_EFFICACY))[2 * np + mem]; }
+        const double fn2o = (dl_n2o * sarf_n2o) + sarf_n2o;
         const double sarf_ch4 = (a3 * sqM + b3 * sqN + d3) * (sqM - kc.sqrtM0);
-        const double fch4 = (kc.delta_ch4 * sarf_ch4) + sarf_ch4;
+        double dl_ch4 = kc.delta_ch4;
+        if constexpr (CONS) { if (eff_on) dl_ch4 = HX_GCD(HXM_SLCF(buf, HXM_EFFICACY))[np + mem]; }
+        const double fch4 = (dl_ch4 * sarf_ch4) + sarf_ch4;
         const double fh2o = 0.0485 * ((ch4 - kc.M0f) * kc.inv_h2o_span);
         const double fo3 = kc.o3_rf * o3;
+        double rf_aero = sh[HXSH_RF_AERO];
+        if constexpr (CONS) { if (aero_on) rf_aero = HX_GCD(HXM_SLCF(buf, HXM_RF_AERO))[(size_t)iy * np + mem]; }
         double ftot = ((((((fco2 + fn2o) + fch4) + fh2o) + fo3) + rf_other) +
-                       p_aero * sh[HXSH_RF_AERO]) + p_vol * sh[HXSH_RF_VOL];
+                       p_aero * rf_aero) + p_vol * sh[HXSH_RF_VOL];
         if constexpr (CONS) {  // forcing_component.cpp:498-505
           const double cf = sh[HXSH_FTOT_CON];
           if ((kc.con_mask & HXC_FTOT) && !isnan(cf)) ftot = cf;

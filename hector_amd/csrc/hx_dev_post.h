@@ -704,6 +704,8 @@ hipError_t hx_launch_gas_mix(const double *par, const double *ser, const double 
 //   rec [7][2]: input j's {nbasis (0 = shared), block}: j = 0 SO2, 1 BC, 2 OC, 3 NH3, 4 NOX, 5 CO,
 //       6 NMVOC; coeff, coff, basis, cover: as hx_gas_mix_kernel
 //   rows.r[k]: row HXM_OH_B + k, [ns][npad]; r[0..5] null: no precursor group; r[6] null: no aerosol row
+//   rho.r[j]: rho_bc, rho_oc, rho_so2, rho_nh3 of every member, [n] in member order (read through
+//       member_of_lane as the coefficients are), or null: the scalar in kon (hx_enable_member_forcing)
 // The logarithm is the device library's.  Where a member's argument IS the scenario's, bit for bit,
 // the lane takes the host's term: a member that carries the scenario's own aerosol emissions then
 // has the bits of a core without the mix (the two logarithms differ in the last place now and then).
@@ -711,6 +713,7 @@ hipError_t hx_launch_gas_mix(const double *par, const double *ser, const double 
 // ===========================================================================
 #define HXSLCF_YEARS 64
 struct HxSlcfRows { double *r[7]; };
+struct HxSlcfRho { const double *r[4]; };
 
 #if defined(__GNUC__) && !defined(__clang__)
 __attribute__((optimize("fp-contract=off")))
@@ -720,7 +723,7 @@ __global__ __launch_bounds__(64) void hx_slcf_mix_kernel(const double *__restric
                                                          const long long *__restrict__ coff,
                                                          const double *__restrict__ basis, const int *__restrict__ cover,
                                                          const int *__restrict__ member_of_lane, int n, int ns, int npad,
-                                                         HxSlcfRows rows) {
+                                                         HxSlcfRows rows, HxSlcfRho rho) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -759,7 +762,8 @@ __global__ __launch_bounds__(64) void hx_slcf_mix_kernel(const double *__restric
   if (rows.r[6]) {  // ForcingComponent::run (src/forcing_component.cpp:430-470) for aero_scalar = 1
     const double aci_beta = 2.279759, s_BCOC = 111.05064063;
     const double s_SO2 = (260.34644166 * 1000) * (32.065 / 64.066);
-    const double rho_bc = kon[0], rho_oc = kon[1], rho_so2 = kon[2], rho_nh3 = kon[3];
+    const double rho_bc = rho.r[0] ? rho.r[0][m] : kon[0], rho_oc = rho.r[1] ? rho.r[1][m] : kon[1];
+    const double rho_so2 = rho.r[2] ? rho.r[2][m] : kon[2], rho_nh3 = rho.r[3] ? rho.r[3][m] : kon[3];
     const double *arg_sh = ser + (size_t)10 * ns, *aci_sh = ser + (size_t)11 * ns;
     double ca[4][HX_MIX_MAX_BASIS];
     int Ka[4];
@@ -804,12 +808,14 @@ __global__ __launch_bounds__(64) void hx_slcf_mix_kernel(const double *__restric
 hipError_t hx_launch_slcf_mix(const double *ser, const double *kon, const int *rec, const double *coeff,
                               const long long *coff, const double *basis, const int *cover,
                               const int *member_of_lane, int n, int ns, int npad, double *const *rows7,
-                              hipStream_t st) {
+                              const double *const *rho4, hipStream_t st) {
   if (n < 1 || ns < 1 || npad < 1) return hipErrorInvalidValue;
   HxSlcfRows rows;
   for (int k = 0; k < 7; ++k) rows.r[k] = rows7[k];
+  HxSlcfRho rho;
+  for (int j = 0; j < 4; ++j) rho.r[j] = rho4 ? rho4[j] : nullptr;
   hipLaunchKernelGGL(hx_slcf_mix_kernel, dim3((npad + 63) / 64, (ns + HXSLCF_YEARS - 1) / HXSLCF_YEARS), dim3(64), 0,
-                     st, ser, kon, rec, coeff, coff, basis, cover, member_of_lane, n, ns, npad, rows);
+                     st, ser, kon, rec, coeff, coff, basis, cover, member_of_lane, n, ns, npad, rows, rho);
   return hipGetLastError();
 }
 #undef HX_GASMIX_VALUE

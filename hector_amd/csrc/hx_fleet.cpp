@@ -282,6 +282,23 @@ bool Fleet::lanes_calibrated() const {
 void Fleet::enable_history(bool on) { HX_EACH(enable_history(on)) }
 void Fleet::enable_spinup_record(bool on) { HX_EACH(enable_spinup_record(on)) }
 void Fleet::enable_slcf_mixes(bool on) { HX_EACH(enable_slcf_mixes(on)) }
+void Fleet::enable_member_forcing(bool on) {
+  if (!on && shards_.size() > 1) {   // every shard first: a refused call changes nothing
+    static const char *const order[7] = {"delta_co2", "delta_ch4", "delta_n2o", "rho_bc", "rho_oc", "rho_so2", "rho_nh3"};
+    std::string names;
+    for (const char *k : order)
+      for (Shard &s : shards_) {
+        const auto held = s.core->member_forcing_names();
+        if (std::find(held.begin(), held.end(), k) == held.end()) continue;
+        names += (names.empty() ? "" : ", ") + std::string(k);
+        break;
+      }
+    if (!names.empty())
+      throw std::runtime_error("hx_enable_member_forcing: " + names + " differs between members: set "
+                               "one value for the whole core first (hx_setvar with one value)");
+  }
+  HX_EACH(enable_member_forcing(on))
+}
 int Fleet::spinup_record(int member, double *values, int max_steps) {
   Shard &s = shards_[(size_t)shard_of_member(member)];
   use(s);

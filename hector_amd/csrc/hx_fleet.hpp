@@ -76,6 +76,7 @@ class Fleet {
   void enable_history(bool on);
   void enable_spinup_record(bool on);
   void enable_slcf_mixes(bool on);
+  void enable_member_forcing(bool on);
   int spinup_record(int member, double *values, int max_steps);
   void setvar_dated(const std::string &capability, const int *years, const double *values, int n,
                     const char *units);

@@ -1359,6 +1359,10 @@ void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
             rf_other = HX_GCD(buf.mseries[HXM_RF_OTHER])[(size_t)iy * buf.npad + mem];
           }
         }
+        // forcing efficacies that differ between members (HXM_EFFICACY: delta_co2 | delta_ch4 |
+        // delta_n2o, [3][npad]), each taken where the core-wide one is read
+        [[maybe_unused]] bool eff_on = false;
+        if constexpr (hx_cons<CON>()) eff_on = HX_RARE(msk & (1u << HXM_EFFICACY));
         const double sqM = hx_sqrt(ch4), sqC = hx_sqrt(co2c);
         const double C_alpha_max = m.C0 - (b1 / (2 * a1));
         double alpha_prime;
@@ -1367,11 +1371,17 @@ void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
           alpha_prime = d1 + a1 * ((co2c - m.C0) * (co2c - m.C0)) + b1 * (co2c - m.C0);
         else alpha_prime = d1;
         const double sarf_co2 = (alpha_prime + c1 * sqN) * ln_co2r;
-        const double fco2 = (sarf_co2 * kc.delta_co2) + sarf_co2;
+        double dl_co2 = kc.delta_co2;
+        if constexpr (hx_cons<CON>()) { if (eff_on) dl_co2 = HX_GCD(HXM_SLCF(buf, HXM_EFFICACY))[mem]; }
+        const double fco2 = (sarf_co2 * dl_co2) + sarf_co2;
         const double sarf_n2o = (a2 * sqC + b2 * sqN + c2 * sqM + d2) * (sqN - sqN0);
-        const double fn2o = (kc.delta_n2o * sarf_n2o) + sarf_n2o;
+        double dl_n2o = kc.delta_n2o;
+        if constexpr (hx_cons<CON>()) { if (eff_on) dl_n2o = HX_GCD(HXM_SLCF(buf, HXM_EFFICACY))[2 * (size_t)buf.npad + mem]; }
+        const double fn2o = (dl_n2o * sarf_n2o) + sarf_n2o;
         const double sarf_ch4 = (a3 * sqM + b3 * sqN + d3) * (sqM - kc.sqrtM0);
-        const double fch4 = (kc.delta_ch4 * sarf_ch4) + sarf_ch4;
+        double dl_ch4 = kc.delta_ch4;
+        if constexpr (hx_cons<CON>()) { if (eff_on) dl_ch4 = HX_GCD(HXM_SLCF(buf, HXM_EFFICACY))[(size_t)buf.npad + mem]; }
+        const double fch4 = (dl_ch4 * sarf_ch4) + sarf_ch4;
         const double fh2o = 0.0485 * ((ch4 - kc.M0f) * kc.inv_h2o_span);
         const double fo3 = kc.o3_rf * o3;  // (0 with [ozone] enabled=0, forcing_component.cpp:392)
         double ftot = ((((((fco2 + fn2o) + fch4) + fh2o) + fo3) + rf_other) +
@@ -1911,11 +1921,13 @@ __device__ __forceinline__ double diag_rf(int kind, const HxDiagArgs &a, int iy,
   if (kind == HXG_RF_H2O) return 0.0485 * ((ch4 - a.M0f) / (1831 - a.M0f));
   if (kind == HXG_RF_CH4) {
     const double sarf = (a3 * sqM + b3 * sqN + d3) * (sqM - a.sqrtM0);
-    return (a.delta_ch4 * sarf) + sarf;
+    const double delta = a.eff_members ? a.eff_members[(size_t)a.npad + mem] : a.delta_ch4;
+    return (delta * sarf) + sarf;
   }
   const double sqC = sqrt(a.co2[o]);
   const double sarf = (a2 * sqC + b2 * sqN + c2 * sqM + d2) * (sqN - sqN0);
-  return (a.delta_n2o * sarf) + sarf;
+  const double delta = a.eff_members ? a.eff_members[2 * (size_t)a.npad + mem] : a.delta_n2o;
+  return (delta * sarf) + sarf;
 }
 
 __global__ __launch_bounds__(256) void hx_diag_kernel(int kind, HxDiagArgs a, double *out) {

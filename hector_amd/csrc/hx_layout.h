@@ -125,8 +125,13 @@ enum HxMemberSeries {
   // Two groups, each allocated only while a mix needs it: the six precursor rows, the aerosol row.
   HXM_OH_B, HXM_OH_C, HXM_OH_D, HXM_O3_NOX, HXM_O3_CO, HXM_O3_NMVOC,
   HXM_RF_AERO,
+  // NOT a series: the forcing efficacies delta_co2, delta_ch4, delta_n2o of every lane, three rows
+  // [3][npad] in that order, while one of them differs between members (hx_enable_member_forcing);
+  // a row that does not holds the core's value in every lane.  Uploaded with the parameters.
+  HXM_EFFICACY,
   HXM_N
 };
+static_assert(HXM_RF_AERO == 18 && HXM_EFFICACY == 19 && HXM_N == 20, "HxMemberSeries: existing indices do not move");
 static_assert(HXM_N <= 32, "HxBuffers::ms_mask holds one bit per member series");
 
 // ---- status bits (per member) ---------------------------------------------
@@ -266,7 +271,8 @@ struct HxBuffers {
   long long *wave_clk;
   // (last: 396 pointers, see HxArgs)
   double *out[HXO_NVAR]; // each [ns][npad] or nullptr
-  // Rows HXM_OH_B .. HXM_RF_AERO of the per-member series (hx_slcf_mix_kernel), mseries_slcf[k - HXM_OH_B].
+  // Rows HXM_OH_B .. HXM_RF_AERO of the per-member series (hx_slcf_mix_kernel) and the efficacy rows
+  // HXM_EFFICACY, mseries_slcf[k - HXM_OH_B].
   // Behind everything else: in the middle they pushed one more output pointer of the first biome past
   // the 4 KB mark (see HxArgs) and every "plain + diagnostics" kernel gained 6 instructions and 2
   // spilled scalars.  Here no other field moves; these are read behind their ms_mask bit only.
@@ -292,6 +298,7 @@ struct HxDiagArgs {
   const double *lo_ratio;                  // parameter row (ocean_tas)
   const double *shared;                    // per-year table
   const double *n2o_members;               // per-member N2O series [ns][npad] or null (RF_N2O)
+  const double *eff_members;               // per-member delta_co2 | delta_ch4 | delta_n2o [3][npad] or null
   double deltaT, inv_vol;                  // of the box
   double sqrtN0, sqrtM0, M0f, delta_n2o, delta_ch4;
   int base_idx, npad, iy0, ny;

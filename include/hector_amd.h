@@ -100,7 +100,10 @@ int hx_shutdown(hx_core *core);
  * (N0, TN2O0, UC_N2O: src/n2o_component.cpp:95-130; tau_<gas> = the INI key "tau" of
  * [<gas>_halocarbon], rho_<gas>, delta_<gas>: src/halocarbon_component.cpp:118-150), which the
  * reference perturbs per run: with one value per member their recurrences run per member on
- * the device ahead of the year loop (16 B per member-year of HBM). */
+ * the device ahead of the year loop (16 B per member-year of HBM) -- and, after
+ * hx_enable_member_forcing (below), the forcing efficacies delta_co2, delta_ch4, delta_n2o, rho_bc,
+ * rho_oc, rho_so2, rho_nh3 (src/forcing_component.cpp).  M0, Tsoil, Tstrat, TOH0 and PO3 stay
+ * core-wide: they sit inside the CH4 / OH recurrence and in the CH4 initial state. */
 int hx_setvar(hx_core *core, const char *capability, const double *values, int nvalues,
               const char *units);
 /* setvar(core, dates, var, values, unit) for a scenario INPUT series (emissions, SV,
@@ -200,6 +203,32 @@ int hx_setvar_scenario_mix(hx_core *core, const char *const *scenarios, int nsce
  * switch existed, and it costs nothing until such a mix is set.  on == 0 while such a mix exists is
  * refused, naming it (remove the mix first).  hx_setvar_dated_members keeps refusing the names. */
 int hx_enable_slcf_mixes(hx_core *core, int on);
+/* The forcing efficacies per member: with on != 0, hx_setvar of delta_co2, delta_ch4, delta_n2o
+ * ("(unitless)"), rho_bc, rho_oc, rho_nh3 ("W/m2/Tg") and rho_so2 ("W/m2/Gg") accepts n_members
+ * values (units checked as before) and hx_getvar returns them -- a forcing-uncertainty ensemble in
+ * which CO2, CH4 and N2O forcing scale independently and every aerosol species has its own efficacy,
+ * in one launch.  One value, or n_members equal values, puts the name back on the shared path (the
+ * rule of N0, tau_<gas> ...); a core of several shards splits the vectors like every other
+ * per-member parameter.  Invalidation is what hx_setvar of these names always did.
+ * rho_*: the lane-per-member pre-pass that serves the aerosol mixes (hx_slcf_mix_kernel) writes
+ * the finished aerosol row with the member's own efficacies -- (((rho_bc*BC + rho_oc*OC) +
+ * rho_so2*SO2) + rho_nh3*NH3) + aerosol-cloud term, unfused, as the host writes the shared column
+ * -- and the extended run kernels take it; hx_enable_slcf_mixes is not needed.  8 B per member-year
+ * for the row, whatever the number of per-member rho_*, only while one differs or an aerosol input
+ * is a mix.  hx_fetchvars of RF_BC, RF_OC, RF_SO2, RF_NH3 answers per member.
+ * delta_*: three values per lane, 24 B per member, uploaded with the parameters; the extended run
+ * kernels read them where the core-wide ones are used -- (sarf*delta)+sarf for CO2, (delta*sarf)+sarf
+ * for CH4 and N2O -- and the derived RF_CH4 / RF_N2O follow.  The reference's range check (-1..1,
+ * ForcingComponent::prepareToRun) holds for every member: hx_run fails naming the first member at
+ * fault.  With [CH4] or [N2O] disabled the forcing component leaves the three gases out: the
+ * members' values are kept and returned, the run uses the shared -1 for every member.
+ * A core that holds such values runs the extended instantiations of the run kernels (one- and
+ * two-wave, 2-4 and looped biomes, carbon tracking) or, where the small-ensemble pair kernel would
+ * serve it, that kernel's instantiation with the constraint code; the plain instantiations are
+ * unchanged.  Off by default: every message and list is then what it was before this switch existed.  on == 0 while one of the seven differs between members is
+ * refused, naming it; a refused call changes nothing.
+ * Out of scope: M0, Tsoil, Tstrat, TOH0, PO3 (see hx_setvar). */
+int hx_enable_member_forcing(hx_core *core, int on);
 /* Keep every year's component state in HBM so hx_reset can return to any computed date --
  * what the reference's per-component tseries records provide (src/simpleNbox.cpp:708-840,
  * src/ocean_component.cpp:767-846).  272 B per member-year (one biome); default off. */
