@@ -73,6 +73,57 @@ template <int B, bool HF, bool KERPM, int CON> constexpr bool hx_open_retry_k() 
   return true;
 }
 
+// Which instantiations take the per-lane control of the STASH and of the segment loop around it as
+// lane masks and selects (stash(), solve_year(): "flat stash"): the ones with the flat control of a
+// pass, kernel by kernel like hx_open_retry_k -- an instantiation that comes out of the register
+// allocator with more registers or scratch than in the nested form keeps that form, its assembly
+// unchanged (profiles/stash_control_ab.md section 2).
+// -DHX_STASH_CONTROL_OLD: the nested form in every kernel (the build before it, for comparisons).
+template <int B, bool HF, bool KERPM, int CON> constexpr bool hx_flat_stash() {
+#ifdef HX_STASH_CONTROL_OLD
+  return false;
+#else
+  if (!hx_flat_control<B, CON>()) return false;
+  // 30 of the 60 instantiations keep the nested form: the ones tools/isa_compare.py marks against
+  // -DHX_STASH_CONTROL_OLD (vector registers or scratch gained) and the ones whose static
+  // instruction count grew -- in the CON = +-1 kernels mostly by way of spilled scalar registers
+  // (one biome, HF, CON = 1: 254 -> 448 spilled, 8640 -> 10838 instructions).
+  // How the list is made (it belongs to ONE compiler's register allocation; after a change of
+  // compiler or of the stash, make it again): put `return true;` in the place of the lines below,
+  // compile hx_kernels.hip with the product flags and -save-temps=obj twice, with
+  // -DHX_STASH_CONTROL_OLD (before.s) and without (after.s), and run
+  //   python tools/isa_compare.py before.s after.s --kernel hx_run_kernel
+  // every kernel it marks REGS+ / SCRATCH+, and every one whose last column (static instructions)
+  // grew, returns false here; rebuild and run it again: nothing marked, no count grown.
+  // Below, "N of 12": N of a biome count's 12 instantiations KEEP THE NESTED FORM (return false);
+  // the figures behind a line are before -> after of what made its kernels leave (registers =
+  // VGPR + AGPR, unless it says instructions, scratch or spilled).
+  if (B == HX_B1W2) {   // two-wave flavour: 7 of 12
+    if (CON == -2) return HF && KERPM;                  // 255 -> 256, 237 -> 239 registers
+    if (CON == 1) return HF && KERPM;                   // (HF, !KERPM): 7730 -> 7732 instructions
+    if (CON == -1) return HF && KERPM;                  // 244 -> 246 registers; 7140 -> 7173 instructions
+    return HF;                                          // CON = 0: 88 -> 92 B of scratch, 235 -> 237 registers
+  }
+  if (B == 1) return !(!KERPM && (CON == 1 || CON == -1));   // 3 of 12; spilled scalars, instructions: 8204 -> 9821, 8025 -> 9502, 8640 -> 10838
+  if (B == 2) {   // 8 of 12
+    if (CON == -2) return HF && KERPM;                  // 434 -> 438, 370 -> 374
+    if (CON == -1) return !HF;                          // 456 -> 458, 442 -> 444
+    if (CON == 1) return false;                         // 460 -> 462, 448 -> 450
+    return KERPM;                                       // CON = 0: 410 -> 418, 346 -> 354
+  }
+  if (B == 3) {   // 3 of 12
+    if (CON == -1) return HF;                           // 400 -> 402
+    if (CON == 0) return KERPM;                         // 454 -> 458, 390 -> 394
+    return true;
+  }
+  // four biomes: 9 of 12
+  if (CON == -2) return !KERPM;                         // 12873 -> 12975 instructions
+  if (CON == -1) return false;                          // 14660 -> 14725 (2 spilled vector registers), 11520 -> 13177, 11170 -> 12743
+  if (CON == 1) return HF && !KERPM;                    // 504 -> 506
+  return false;                                         // CON = 0: 476 -> 478, 440 -> 446; 11461 -> 11471, 7564 -> 7577 instructions
+#endif
+}
+
 // rhs constants that only change at a stash (pools frozen in between,
 // src/simpleNbox-runtime.cpp:809-840)
 struct Interval {
@@ -517,7 +568,12 @@ template <int CON, bool SPIN> constexpr bool hx_zchain() { return false; }
 namespace {
 
 // OceanComponent::stashCValues + SimpleNbox::stashCValues for one lane
-template <int B, bool SPIN, int CON = 0>
+// FS (hx_flat_stash; the caller's choice): the stash's per-lane decisions -- the max_timestep
+// controller, the thawed pool's clamp, the negative-pool and mass flags, the flux adjustment -- as
+// selects on lane masks: every lane computes both sides and keeps one, the values are the ones the
+// branches of the nested form assign.  Nested, the controller alone was four exec-mask regions
+// (about 12 exec-mask instructions and 5 branches around six arithmetic operations).
+template <int B, bool SPIN, int CON = 0, bool FS = false>
 __device__ __forceinline__ void stash(Member<B> &m, double t, const double *y,
                                       double c4, double c5, double c7, Interval &K,
                                       Interval &K2, const YearCon &yc, bool more) {
@@ -565,12 +621,30 @@ __device__ __forceinline__ void stash(Member<B> &m, double t, const double *y,
   const double totC = m.cDO + m.cIO + m.cLL + m.cHL;
   const double solver_flux = y[4] - totC;
   double adj = 0.0;
-  if (currentflux != 0.0) adj = (solver_flux - currentflux) / 2.0;
+  if constexpr (FS) adj = (currentflux != 0.0) ? (solver_flux - currentflux) / 2.0 : 0.0;
+  else if (currentflux != 0.0) adj = (solver_flux - currentflux) / 2.0;
   aH += adj;
   aL += adj;
   const double inv_yf = hx_recip(yf);
   const double cdiff = solver_flux * inv_yf - m.lastflux_ann;
-  if (cdiff > 0.1) {  // ocean_component.cpp:703-733
+  if constexpr (FS) {  // ocean_component.cpp:703-733, every lane both ways
+    // halve: the flux jumped.  Otherwise, at a whole date with the timeout running, count it down;
+    // at zero double back, and re-arm the timeout while max_timestep stays below 1.
+    const hx_mask halve = hx_mask_gt(cdiff, 0.1);
+    const hx_mask count = ~halve & hx_mask_of(!in_partial_year) & hx_mask_of(m.ts_timeout != 0);
+    const int tdec = max(0, m.ts_timeout - 1);
+    const hx_mask grow = count & hx_mask_of(tdec == 0);
+    const double halved = fmax(0.3, m.max_ts * 0.5);
+    const double doubled = fmin(1.0, m.max_ts / 0.5);
+    const hx_mask arm = halve | (grow & hx_mask_of(doubled < 1.0));
+    // (one select after the other, the later one wins: `halve` and `grow` exclude each other, and
+    // `arm` overrides the count)
+    double mts = hx_lane(grow) ? doubled : m.max_ts;
+    int tto = hx_lane(count) ? tdec : m.ts_timeout;
+    m.max_ts = hx_lane(halve) ? halved : mts;
+    m.ts_timeout = hx_lane(arm) ? 20 : tto;
+  } else
+  if (cdiff > 0.1) {
     m.max_ts = fmax(0.3, m.max_ts * 0.5);
     m.ts_timeout = 20;
   } else if (!in_partial_year && m.ts_timeout) {
@@ -660,9 +734,18 @@ __device__ __forceinline__ void stash(Member<B> &m, double t, const double *y,
   double alf = ((npp_t - rh_t) - m.luc_e) + m.luc_u;
   const double npp_rh = npp_t + rh_t;
   double tpf = c5;
+  // (FS: the two flags of a stash -- this one and HX_ERR_MASS below -- are lane masks, written
+  // behind ONE vote at the stash's end.  The test is on the CLAMPED thawed pool as it is here,
+  // tpf_clamped: an NBP constraint moves tpf further down, and that value is not the one tested.)
+  [[maybe_unused]] double tpf_clamped = 0.0;
+  if constexpr (FS) {
+    tpf = (fabs(c5) < 1e-10) ? 0.0 : c5;  // :337-341
+    tpf_clamped = tpf;
+  } else {
   if (fabs(tpf) < 1e-10) tpf = 0.0;  // :337-341
   if (y[0] < 0 || y[1] < 0 || y[2] < 0 || y[3] < 0 || c4 < 0 || tpf < 0)
     m.status |= HX_ERR_NEGPOOL;
+  }
   double nveg = y[1], ndet = y[2], nsoil = y[3];
   double rh_adj = 1.0;
   double npp_fin_total = npp_t;  // npp_total after any NBP constraint (final_npp weights it)
@@ -773,6 +856,13 @@ __device__ __forceinline__ void stash(Member<B> &m, double t, const double *y,
   const double sum = ((((((y[0] + y[1]) + y[2]) + y[3]) + c4) + c5) + y[4]) + c7 +
                      m.cum_pf_ch4;
   // (written so that a NaN state raises the flag too: the reference would carry it on silently)
+  if constexpr (FS) {
+    const hx_mask negm = hx_mask_gt(0.0, y[0]) | hx_mask_gt(0.0, y[1]) | hx_mask_gt(0.0, y[2]) |
+                         hx_mask_gt(0.0, y[3]) | hx_mask_gt(0.0, c4) | hx_mask_gt(0.0, tpf_clamped);
+    const hx_mask massm = hx_mask_gt(m.masstot, 0.0) & hx_mask_of(!(fabs(sum - m.masstot) <= 0.001));
+    if (__builtin_expect((negm | massm) != 0, 0))
+      m.status |= (hx_lane(negm) ? HX_ERR_NEGPOOL : 0u) | (hx_lane(massm) ? HX_ERR_MASS : 0u);
+  } else
   if (m.masstot > 0.0 && !(fabs(sum - m.masstot) <= 0.001)) m.status |= HX_ERR_MASS;
   m.masstot = sum;
   double ca_residual = 0.0;
@@ -869,7 +959,8 @@ __device__ __forceinline__ double pow_m15(double x) {
 // year, the others idle through the extra ones; the expensive step and stash
 // blocks are never interleaved lane by lane.
 // OPEN: the segment's retries are decided before its first step (hx_open_retry_k; the caller's choice)
-template <int B, bool SPIN, int CON = 0, bool OPEN = false>
+// FS: the segment loop's vote and the stash's decisions on lane masks (hx_flat_stash; the caller's choice)
+template <int B, bool SPIN, int CON = 0, bool OPEN = false, bool FS = false>
 __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
                                            double t0, double tnew, const YearCon &yc) {
   constexpr int NP = hx_nbp<CON>() ? 6 : 5;  // solver variables (see rhs)
@@ -1001,12 +1092,18 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
   // pool, runaway CO2) can drive the step size towards zero -- a lane that never finishes its
   // year would hang the whole launch.
   bool alive = m.status == 0;
+  static_assert(!FS || hx_flat_control<B, CON>(), "the flat stash is written for the flat control (hx_flat_stash)");
+  // FS: the lanes of the next segment as a lane mask, made ONCE where the segment ends (a lane is
+  // alive as long as its status word is clean) -- the vote is a scalar comparison of it and `seg`
+  // its lanes, nothing is rebuilt from booleans at the top of the loop.
+  [[maybe_unused]] hx_mask SG = FS ? (hx_mask_of(m.status == 0) & hx_mask_gt(tnew, t)) : 0;
+#define HX_SEG_GO() (FS ? SG != 0 : (bool)__any(alive && t < tnew))
 #ifndef HX_TOP_TESTED_LOOPS   // (bottom-tested like the step loop below, for the same reason)
-  for (bool go_seg = __any(alive && t < tnew); go_seg; go_seg = __any(alive && t < tnew)) {
+  for (bool go_seg = HX_SEG_GO(); go_seg; go_seg = HX_SEG_GO()) {
 #else
-  while (__any(alive && t < tnew)) {
+  while (HX_SEG_GO()) {
 #endif
-    const bool seg = alive && t < tnew;
+    const bool seg = FS ? hx_lane(SG) : (alive && t < tnew);
     // fresh integrate_adaptive call: by-value dt, fresh controlled stepper
     const double t_start = t;
     double t_target = tnew, dtl = m.sdt;
@@ -1041,7 +1138,7 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
 #ifndef HX_HOST_EMULATION
       asm volatile("" : "+s"(fr));   // (a scalar of the launch, tested here: not a flag per lane)
 #endif
-      const hx_mask need0m = hx_mask_of(seg) & hx_mask_gt((t + (t_target - t)) - m.ode_start, m.max_ts);
+      const hx_mask need0m = (FS ? SG : hx_mask_of(seg)) & hx_mask_gt((t + (t_target - t)) - m.ode_start, m.max_ts);
       if (fr == 0 && need0m != 0) {
         HX_COUNT(m, 23);  // segments with an opening retry
         bool need0 = hx_lane(need0m);
@@ -1064,7 +1161,9 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
     bool stepping = seg;   // (nested form; the flat one uses it inside the retry block only)
     // The lanes that are stepping, as the wavefront's lane mask in a scalar register pair (see the
     // end of the pass): votes are scalar comparisons of it, and nothing rebuilds it from booleans.
-    [[maybe_unused]] hx_mask ST = FLAT ? hx_mask_of(seg && !dead0) : 0;
+    // (FS: a lane of this segment with eight retries is one the opening block has just flagged --
+    // the count starts from 0 at every stash, and a lane flagged earlier is not in SG)
+    [[maybe_unused]] hx_mask ST = FS ? (SG & ~hx_mask_gt(retry, 7)) : FLAT ? hx_mask_of(seg && !dead0) : 0;
 #define HX_STEP_GO() (FLAT ? ST != 0 : (bool)__any(stepping))
     HX_TAB_HEAD();
     if constexpr (hx_w2<B>()) w2_park_out<B>(m);
@@ -1554,6 +1653,16 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
     if constexpr (FLAT) alive = m.status == 0;   // (a lane the loop has flagged -- retries, step limits -- is out of the year)
     HX_STAMP(m, 10);
     HX_COUNT(m, 17);    // segments
+    if constexpr (FS) {
+      // (the lanes of this segment that are still alive have moved on from t_start, and no other
+      // lane has: SG itself need not live through the step loop)
+      if (hx_lane(hx_mask_of(m.status == 0) & hx_mask_gt(t, t_start))) {
+        retry = 0;
+        stash<B, SPIN, CON, true>(m, t, y, l4, hx_nbp<CON>() ? y[NP - 1] : l5, l7, K, K2, yc, t < tnew);
+      }
+      // (a lane outside this segment had its year behind it or its status set: neither comes back)
+      SG = hx_mask_of(m.status == 0) & hx_mask_gt(tnew, t);
+    } else
     if (seg && alive) {
       // the solver keeps integrating its own c[] afterwards (no getCValues,
       // carbon-cycle-solver.cpp:282-287); only the frozen-pool constants move
@@ -1566,6 +1675,7 @@ __device__ __forceinline__ void solve_year(Member<B> &m, const HxConst &kc,
 
 }  // namespace
 #undef HX_STEP_GO
+#undef HX_SEG_GO
 #ifndef HX_TAB_LITERALS
 #undef b21
 #undef f2

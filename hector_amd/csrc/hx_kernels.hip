@@ -1230,7 +1230,7 @@ void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
         }
         yc.t_half = year - 0.5;
       }
-      solve_year<B, false, CON, hx_open_retry_k<B, HF, KERPM, CON>()>(m, args->kc, year - 1.0, year, yc);
+      solve_year<B, false, CON, hx_open_retry_k<B, HF, KERPM, CON>(), hx_flat_stash<B, HF, KERPM, CON>()>(m, args->kc, year - 1.0, year, yc);
       cost_steps += m.nsteps; cost_stash += m.nstash;
     }
     HX_FENCE();
