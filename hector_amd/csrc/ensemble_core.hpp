@@ -15,6 +15,7 @@
 
 #include "../../include/hector_amd.h"   // hx_metric
 #include "hx_layout.h"
+#include "hx_post_abi.h"
 #include "hx_scenario.hpp"
 
 namespace hx {
@@ -194,7 +195,7 @@ class EnsembleCore {
   void stats_device(const std::string &capability, int year0, int year1, double *d_stats);
   // the same, queued on the core's stream without waiting (the fleet's collective follows it)
   void stats_async(const std::string &capability, int year0, int year1, double *d_stats);
-  // ---- post-processing on the device (hx_dev_post.h); both read results only: no prepare(), no
+  // ---- post-processing on the device (ensemble_post.cpp, hx_dev_post.h); both read results only: no prepare(), no
   // prewarm loop, no spinup, the core is not dirtied.  Scratch is allocated on first use.
   // chi2[member] of a recorded output against obs (hx_member_score in hector_amd.h): out_host[n_]
   // in member order; -> the number of observations that counted
@@ -362,6 +363,34 @@ class EnsembleCore {
   void prepare();  // upload + spinup when dirty
   HxBuffers buffers() const;
   void check(hipError_t e, const char *what) const;
+  // A grow-only scratch buffer on the device, sized in elements of T.  reserve() frees and allocates
+  // anew only when count exceeds the capacity: the old contents are gone then, nothing is waited for
+  // and nothing rounded up.  No destructor: free_device() releases every one of them while the
+  // device is still there.
+  template <class T> class Scratch {
+   public:
+    T *get() const { return p_; }
+    template <class U> U *as() const { return reinterpret_cast<U *>(p_); }   // a buffer of mixed parts
+    size_t capacity() const { return cap_; }
+    hipError_t grow(size_t count) {   // reserve() for the caller that words the failure itself
+      if (count <= cap_) return hipSuccess;
+      release();
+      const hipError_t e = hipMalloc(&p_, sizeof(T) * count);
+      if (e == hipSuccess) cap_ = count; else p_ = nullptr;
+      return e;
+    }
+    T *reserve(size_t count, const EnsembleCore &core, const char *what) {
+      core.check(grow(count), what);
+      return p_;
+    }
+    void release() {
+      if (p_) (void)hipFree(p_);
+      p_ = nullptr; cap_ = 0;
+    }
+   private:
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+  };
 
   Scenario scen_;
   int n_, npad_, B_, device_;
@@ -430,8 +459,7 @@ class EnsembleCore {
   void refuse_covered(const char *fn, const std::string &capability, const int *years, int n) const;
   // inputs changed from `year` on: the next run() goes back to year - 1 (R/messages.R:125-133)
   void reset_from(int year);
-  char *d_mix_ = nullptr;              // scratch of the mix kernel: lane map, rows, basis, coefficients
-  size_t mix_cap_ = 0;
+  Scratch<char> d_mix_;                // scratch of the mix kernel: lane map, rows, basis, coefficients
   void build_mix_table(const DatedInput &d, const MemberMix &mx, bool dense);
   // The recipe block of a pre-pass (hx_gas_mix_kernel, hx_slcf_mix_kernel): pack_recipes appends
   // to the caller's doubles the coefficient blocks of the slots that hold a mix and their bases
@@ -492,7 +520,7 @@ class EnsembleCore {
   int trk_iy() const {
     return (tracking_year_ > scen_.start && tracking_year_ <= scen_.end) ? tracking_year_ - scen_.start : -1;
   }
-  double *d_derived_ = nullptr, *d_dpart_ = nullptr, *d_gather_ = nullptr, *d_hist_ = nullptr;
+  double *d_derived_ = nullptr, *d_dpart_ = nullptr, *d_hist_ = nullptr;
   unsigned *d_hist_status_ = nullptr;  // [ns][npad] status bits of every year (with d_hist_)
   void remap_biome_outputs(const std::vector<int> &old_of_new);
   bool history_ = false, shared_dirty_ = false;
@@ -501,28 +529,31 @@ class EnsembleCore {
   int hist_valid_to_ = 0;   // history slabs 1..hist_valid_to_ are valid
   int dirty_from_iy_ = -1;  // pending auto-reset target (R wrapper's reset_date)
   int *d_lane_of_member_ = nullptr;
-  size_t gather_cap_ = 0, diag_cap_ = 0;
-  double *d_diag_ = nullptr, *d_slr_ = nullptr;
+  Scratch<double> d_gather_, d_diag_;   // fetchvars: [ny][n_] in member order, [ny][npad_] of a derived diagnostic
+  double *d_slr_ = nullptr;
   int slr_valid_to_ = -1;
   void check_parameters() const;
   bool fetch_host(const std::string &capability, int year0, int year1, double *out_host);
   void compute_derived(const std::string &capability, int iy0, int ny, double *dst);
-  // scratch of member_score / quantiles
-  double *d_score_ = nullptr;                 // [obs n][sigma n][chi2 npad][chi2 in member order n_] + years
-  size_t score_cap_ = 0;
-  // scratch of member_score_whitened: [W in fragment order np^2][obs np][base npad][chi2 npad][chi2 in
-  // member order n_] + rows np
-  double *d_whiten_ = nullptr;
-  size_t whiten_cap_ = 0;
-  // scratch of member_project: [basis in fragment order][center][base npad][out m x npad][out in member
-  // order m x n_] + rows
-  double *d_project_ = nullptr;
-  size_t project_cap_ = 0;
+  // ---- the scratch of the verbs (ensemble_post.cpp).  The three that hold doubles with a list of
+  // ints behind them are sized in bytes.
+  // member_score: [obs n][sigma n][chi2 npad][chi2 in member order n_] doubles + years; shared with the
+  // metric, pair-metric and rank verbs, which bring their block to member order through it
+  Scratch<unsigned char> d_score_;
+  // member_score_whitened: [W in fragment order np^2][obs np][base npad][chi2 npad][chi2 in member order
+  // n_] doubles + rows np
+  Scratch<unsigned char> d_whiten_;
+  // member_project: [basis in fragment order][center][base npad][out m x npad][out in member order
+  // m x n_] doubles + rows
+  Scratch<unsigned char> d_project_;
   unsigned long long *d_q_ = nullptr;         // integer weights in lane order [npad]
-  unsigned long long *d_qstate_ = nullptr;    // per year {HxQYear, lo}, per (year, prob) {prefix, rem}, probs
-  unsigned long long *d_qhist_ = nullptr;     // [ny][nprobs][256]
-  size_t qstate_cap_ = 0, qhist_cap_ = 0;
-  const double *q_src_ = nullptr;             // the block q_begin / mq_begin prepared for q_pass: d_out_[v] or d_met_
+  Scratch<unsigned long long> d_qstate_;      // per year {HxQYear, lo}, per (year, prob) {prefix, rem}, probs
+  Scratch<unsigned long long> d_qhist_;       // [ny][nprobs][256]
+  // The block q_begin / mq_begin prepared for q_pass: d_out_[v], a series, a derived block or d_met_.
+  // It is not owned, and between the two steps it may point into the metric block: a metric or
+  // pair-metric call that regrows d_met_ in between leaves it dangling, as it always has (the fleet
+  // drives q_begin and q_pass back to back).  free_device() resets it.
+  const double *q_src_ = nullptr;
   int q_iy0_ = 0, q_ny_ = 0, q_np_ = 0;
   bool q_weighted_ = false;
   int post_flags_ = 0;                        // HECTOR_AMD_POST_AB (measurements): 1 no prefix skip, 2 with wave aggregation
@@ -537,29 +568,27 @@ class EnsembleCore {
   void bin_block(const double *src, int iy0, int nrows, const unsigned long long *q, const double *edges,
                  int nedges, unsigned long long *sums_host);
   // scratch of the metric kernel: group records + row lists, and the block [nspecs][npad_] (lane order)
-  unsigned char *d_metplan_ = nullptr;
-  double *d_met_ = nullptr;
-  size_t metplan_cap_ = 0, met_cap_ = 0;
-  unsigned long long *d_bin_ = nullptr;       // [32 edges as doubles][rows][nedges + 2]
-  size_t bin_cap_ = 0;
-  unsigned long long *d_mom_ = nullptr;       // scratch of the moment verbs (MomBuf in ensemble_core.cpp)
-  size_t mom_cap_ = 0;
+  Scratch<unsigned char> d_metplan_;
+  Scratch<double> d_met_;
+  Scratch<unsigned long long> d_bin_;         // [32 edges as doubles][rows][nedges + 2]
+  Scratch<unsigned long long> d_mom_;         // scratch of the moment verbs (MomBuf in ensemble_post.cpp)
   const double *mom_src_ = nullptr;           // the block mom_begin prepared for mom_finish
   int mom_iy0_ = 0, mom_ny_ = 0, mom_npred_ = 0;
   // the grouped summaries: labels [npad_] in lane order, then [n_] in member order as uploaded
   int *d_glab_ = nullptr;
   int q_groups_ = 0, mom_groups_ = 0;         // 0: q_pass / the moment scratch belong to an ungrouped call
-  // the rows of a grouped call resolved (and, for metrics, queued on stream_) -> block, first row, rows
+  // the rows of a grouped call checked -> the block they are computed from or read in; grp_source
+  // then resolves them (for metrics: queued on stream_) -> block, first row, rows
+  const double *grp_check(const std::string &capability, int year0, int year1, const hx_metric *specs,
+                          int nspecs, int nprobs, const char *fn);
   const double *grp_source(const std::string &capability, int year0, int year1, const hx_metric *specs,
                            int nspecs, int nprobs, const char *fn, int *iy0, int *nrows);
   void grp_upload_labels(const int *labels);  // member order -> d_glab_ in lane order (padding lanes -1)
-  unsigned long long *d_comom_ = nullptr;     // scratch of hx_ensemble_comoments (CoBuf in ensemble_core.cpp)
-  size_t comom_cap_ = 0;
+  Scratch<unsigned long long> d_comom_;       // scratch of hx_ensemble_comoments (CoBuf in ensemble_post.cpp)
   const double *co_a_ = nullptr, *co_b_ = nullptr;   // the windows comom_begin prepared for comom_finish
   int co_ia0_ = 0, co_ib0_ = 0, co_na_ = 0, co_nb_ = 0;
   bool co_sym_ = false;
-  unsigned long long *d_sobol_ = nullptr;     // scratch of the Sobol verbs (SobBuf in ensemble_core.cpp)
-  size_t sobol_cap_ = 0;
+  Scratch<unsigned long long> d_sobol_;       // scratch of the Sobol verbs (SobBuf in ensemble_post.cpp)
   const double *sob_src_ = nullptr;           // the block sobol_begin prepared for sobol_finish
   int sob_iy0_ = 0, sob_ny_ = 0, sob_k_ = 0, sob_nb_ = 0;
   void mom_begin_block(const double *src, int iy0, int ny, const unsigned long long *q, const double *pred,
@@ -581,6 +610,19 @@ class EnsembleCore {
   // fn: the ABI function on whose behalf it is resolved (named in the messages of the new cases).
   // Derived diagnostics and combinations are computed on stream_ into a block kept in derived_cache_.
   PostSource post_source(const std::string &capability, const char *fn);
+  // ensemble_core.cpp's tables by name, for the resolver: a derived diagnostic (-1: none, 0: computed
+  // into a block by hx_diag_kernel, 1 + i: block i of the slr family in d_slr_), a recorded output
+  static int derived_kind(const std::string &name);
+  static bool recorded_name(const std::string &name);
+  // every check of the whitened score and of the projection -> the variable; both hold years[n] and the
+  // reference period to the variable's range through listed_source (f: the ABI function named)
+  PostSource listed_source(const std::string &f, const std::string &capability, const int *years, int n,
+                           int base_year0, int base_year1);
+  PostSource whitened_check(const std::string &capability, const int *years, const double *obs,
+                            const double *whiten, int n, int base_year0, int base_year1, const double *out_host);
+  PostSource project_check(const std::string &capability, const int *years, const double *center,
+                           const double *basis, int n, int m, int base_year0, int base_year1,
+                           const double *out_host);
   struct Series {
     std::string name;
     double *block = nullptr;             // [ns][npad_], lane order `lane_of_member`
@@ -592,12 +634,11 @@ class EnsembleCore {
   // the rules of hx_series_define for a new or replaced name, fn named in the messages -> the index of
   // the series it replaces, -1 for a new one
   int series_name_check(const std::string &fn, const std::string &name);
-  // scratch of the rank verbs (RankBuf in ensemble_core.cpp) and the sort of `nrows` rows of a block in
+  // scratch of the rank verbs (RankBuf in ensemble_post.cpp) and the sort of `nrows` rows of a block in
   // lane order: rows == nullptr the rows row0.., else rows[i]; mode HX_RANK_* writes dst rows
   // dst_row0.., mode 2 (the CRPS against obs[i]) fills the records it returns (4 words a row:
   // crps, pit, n_part, 0).  Queued on stream_ and waited for.
-  unsigned long long *d_rank_ = nullptr;
-  size_t rank_cap_ = 0;
+  Scratch<unsigned long long> d_rank_;
   std::vector<unsigned long long> rank_rows(const char *fn, const double *src, int row0, const int *rows,
                                             int nrows, const unsigned long long *q, int mode, const double *obs,
                                             double *dst, int dst_row0);
@@ -634,14 +675,5 @@ class EnsembleCore {
   int simds_ = 1024;              // SIMDs of this core's device (4 per compute unit)
   mutable double run_ms_ = 0, spin_ms_ = 0;
 };
-
-// the select state of hx_ensemble_quantiles on the host (the same arithmetic as the device's
-// hx_q_init_kernel / hx_q_pick_kernel): st[4] = {~min key, max key, sum q, count}
-int hxq_host_start(const unsigned long long *st, unsigned long long *pre);
-unsigned long long hxq_host_target(double p, unsigned long long W);
-// one probability of one year: hist[256] -> prefix and remaining rank updated for the digit below lo
-void hxq_host_pick(int lo, const unsigned long long *hist, unsigned long long *prefix,
-                   unsigned long long *rem);
-double hxq_key_to_double(unsigned long long key);
 
 }  // namespace hx

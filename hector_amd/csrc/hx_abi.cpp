@@ -11,12 +11,6 @@
 #include "ensemble_core.hpp"
 #include "hx_fleet.hpp"
 
-hipError_t hx_launch_unit_csys(int n, const double *Tc, const double *carbon, const double *alk,
-                               double inv_vol, double *out, hipStream_t st);
-hipError_t hx_launch_doeclim_kernel(const double *diff_row, double *ker, int ns, int count,
-                                    int stride, hipStream_t st);
-int hx_doeclim_kernel_pad();
-
 #ifndef HX_BACKEND_NAME
 #define HX_BACKEND_NAME "hip"
 #endif

@@ -8,14 +8,17 @@
 // The reference has no counterpart: its
 // hosts aggregate fetchvars() data frames in R.  Compiled for the GPU through hx_post.hip -- a
 // translation unit of its own, so the year-loop kernels' code generation does not see it -- and
-// for the host-emulation build through ensemble_core.cpp (score, metric, pair-metric and series kernels only: the
-// quantile, bin and moment kernels are cooperative -- LDS atomics, cross-lane -- and one lane at a
-// time cannot run them).
+// for the host-emulation build through ensemble_post.cpp, the one file that may include this one
+// there, itself compiled as the tail of ensemble_core.cpp in that build (score, metric, pair-metric, series and mix kernels only: the quantile, bin and
+// moment kernels are cooperative -- LDS atomics, cross-lane -- and one lane at a time cannot run
+// them).  The records and constants the host fills or reads, and the launchers' prototypes, are in
+// hx_post_abi.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/hector_amd.h"   // hx_metric, HX_MET_*
+#include "hx_post_abi.h"
 
 // ===========================================================================
 // Score: chi2[lane] = sum_i r_i^2, r_i = ((x(iy[i], lane) - base) - obs[i]) / sigma[i], evaluated
@@ -76,16 +79,8 @@ hipError_t hx_launch_score(const double *var, int n, int npad, const int *iy, co
 // load of a lane in flight; here a lane takes HXM_BATCH rows into registers, all loads in flight,
 // and the next batch is issued before the current one is consumed in the defined order.  The group
 // record and the row lists are wave-uniform reads of constant memory (scalar loads).
+// HXM_GROUP, HXM_BATCH, HXM_PAD, HxMetSpec and HxMetGroup: hx_post_abi.h.
 // ===========================================================================
-#define HXM_GROUP 4
-#define HXM_BATCH 16
-#define HXM_PAD 0x40000000   // a list is padded to a multiple of HXM_BATCH with (last row | HXM_PAD): loaded, never consumed
-struct HxMetSpec { int op, iy0, iy1, base; double thr, mid; };   // base: which of the group's reference periods, -1 none
-struct HxMetGroup {
-  int nspec, nbase, brow0, nbrow, wrow0, nwrow, pad0, pad1;   // rows[brow0 .. brow0 + nbrow), rows[wrow0 .. wrow0 + nwrow)
-  int b0[HXM_GROUP], b1[HXM_GROUP];
-  HxMetSpec s[HXM_GROUP];
-};
 
 // (the row numbers are read again from the list when the batch is consumed -- scalar loads that hit
 //  the scalar cache -- instead of being held in 2 x HXM_BATCH scalar registers across the loop)
@@ -289,9 +284,7 @@ hipError_t hx_launch_metric(const double *var, int n, int npad, const void *grou
 //                           rows neighbouring years re-read from L2
 //   hx_series_permute_kernel a block into another lane order
 // ===========================================================================
-#define HXS_BATCH 16
-#define HXS_ANOM_APPLY 100   // internal: z = a - base[lane]
-#define HXS_COMBINE 101      // internal: z = (c0 * a) + (c1 * b), the whole-surface combinations
+#define HXS_BATCH 16   // (the internal ops HXS_ANOM_APPLY and HXS_COMBINE: hx_post_abi.h)
 
 template <int OP>
 #if defined(__GNUC__) && !defined(__clang__)
@@ -834,8 +827,7 @@ hipError_t hx_launch_slcf_mix(const double *ser, const double *kon, const int *r
 // that last row and never consumed).  BVEC: b is the caller's per-year vector, bvec[iy - bvec_iy0],
 // the same for every lane -- wave-uniform reads where the value is consumed, no b loads.
 // ===========================================================================
-#define HXP_BATCH 8
-struct HxPairSpec { int op, iy0, iy1, a0, a1, b0, b1, pad; double thr; };   // rows; a0 > a1 / b0 > b1: no reference period
+#define HXP_BATCH 8   // (the specification record HxPairSpec: hx_post_abi.h)
 
 template <bool BVEC>
 __device__ __forceinline__ void hxp_load(const double *colA, const double *colB, int npad, int r, int last,
@@ -1031,10 +1023,7 @@ hipError_t hx_launch_pair_metric(const double *a, const double *b, const double 
 #define HXQ_BLOCK 256
 #define HXQ_PER 32       // keys of a row per lane: in registers during a histogram pass
 #define HXQ_CHUNK (HXQ_BLOCK * HXQ_PER)  // elements of a row per workgroup
-#define HXQ_MAXP 16
-typedef unsigned long long hxq_u64;
-
-struct HxQYear { hxq_u64 nkmin, kmax, W, cnt; };  // ~(min key), max key, sum of q, members taking part
+// (HXQ_MAXP, hxq_u64 and the year record HxQYear: hx_post_abi.h)
 
 __device__ __forceinline__ hxq_u64 hxq_key(double x) {
   const hxq_u64 b = (hxq_u64)__double_as_longlong(x);
@@ -1300,8 +1289,7 @@ hipError_t hx_launch_q_pick(int ny, int *lo, unsigned long long *prefix, unsigne
 #define HXR_CHUNK (HXR_BLOCK * HXR_PER)
 #define HXR_MODE_CRPS 2   // modes 0 and 1 are HX_RANK_PIT and HX_RANK_NUMERATOR
 static_assert(HX_RANK_PIT == 0 && HX_RANK_NUMERATOR == 1, "the header's kinds are the kernel's modes");
-
-struct HxRankOut { double crps, pit; long long npart, pad; };
+// (a row's result record HxRankOut: hx_post_abi.h)
 
 __device__ __forceinline__ double hxr_unkey(hxq_u64 key) {
   const hxq_u64 b = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
@@ -2344,7 +2332,7 @@ hipError_t hx_launch_gmoments(const double *var, int n, int npad, int iy0, int n
 #define HXSB_BLOCK 256
 #define HXSB_PER 4                            // groups of a row per lane
 #define HXSB_CHUNK (HXSB_BLOCK * HXSB_PER)    // groups of a row per workgroup
-struct HxSobRow { hxq_u64 nkmin, cnt; };      // ~(min key of x_A, x_B), groups taking part
+// (a row's record HxSobRow: hx_post_abi.h)
 
 // Workgroups whose linear ids agree modulo 8 share an XCD and its L2 (a speed matter only).  A
 // chunk's gathers touch cache lines all over its row, so the chunks of one row are given ids that

@@ -14,9 +14,6 @@
 #include <rccl/rccl.h>  // types and prototypes only: the library is loaded at first use
 #endif
 
-hipError_t hx_launch_combine_stats(const double *slots, int world, int rows, double *out,
-                                   hipStream_t st);
-
 namespace hx {
 
 namespace {
