@@ -1665,6 +1665,18 @@ class Core:
                                          cap, ctypes.byref(n)))
         return buf[:n.value]
 
+    def wave_epilogue_clock(self, shard=0):
+        """-> int64 array [wavefronts]: ticks of the same clock every wavefront of the last launch
+        spent behind its year loop on its partial statistics (hx_wave_epilogue_clock); empty when
+        the launch wrote none."""
+        cap = 2 * ((self.n_members + 63) // 64)
+        buf = np.zeros(cap, dtype=np.int64)
+        n = ctypes.c_int(0)
+        self._ck(self._lib.hx_wave_epilogue_clock(self._h, int(shard),
+                                                  buf.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
+                                                  cap, ctypes.byref(n)))
+        return buf[:n.value]
+
     def set_two_wave_from(self, min_members):
         """Ensembles of at least min_members members (one biome, no carbon
         tracking) run on the flavour of the kernel built for two resident

@@ -513,6 +513,7 @@ void EnsembleCore::free_device() {
   fr(d_slcf_mix_); d_slcf_mix_ = nullptr;
   fr(d_cost_); d_cost_ = nullptr; cost_from_iy_ = -1;
   fr(d_wave_clk_); d_wave_clk_ = nullptr;
+  fr(d_wpart_); d_wpart_ = nullptr; wpart_on_ = false; wpart_hi_ = -1;
   fr(d_bscratch_); d_bscratch_ = nullptr;
   fr(d_spin_rec_); d_spin_rec_ = nullptr;
   fr(d_q_); d_q_ = nullptr;
@@ -610,6 +611,11 @@ void EnsembleCore::alloc_device() {
   check(hipMalloc(&d_cost_, sizeof(double) * np), "hipMalloc lane cost");
   check(hipMalloc(&d_wave_clk_, sizeof(long long) * 4 * (np / HX_WAVE)), "hipMalloc wave clock");
   check(hipMemsetAsync(d_wave_clk_, 0, sizeof(long long) * 4 * (np / HX_WAVE), stream_), "zero");
+  // (the per-wavefront partial statistics: 32 B per wavefront, year and variable -- 36 MB at 65 536
+  // members x 556 years; only the one-biome run kernels write them)
+  if (B_ == 1 && out_enabled_[HXO_CO2] && out_enabled_[HXO_TGAV] &&
+      hx_run_writes_partials(1, false, false, 0, false))
+    check(hipMalloc(&d_wpart_, sizeof(double) * 2 * ns * (np / HX_WAVE) * 4), "hipMalloc wavefront partials");
   check(hipMalloc(&d_bscratch_, sizeof(double) * np * (size_t)(3 * B_)), "hipMalloc biome scratch");
   check(hipMemsetAsync(d_bscratch_, 0, sizeof(double) * np * (size_t)(3 * B_), stream_), "zero");
   cost_from_iy_ = -1;
@@ -670,6 +676,8 @@ HxBuffers EnsembleCore::buffers() const {
   b.spin_rec = d_spin_rec_;
   b.bscratch = d_bscratch_;
   b.wave_clk = d_wave_clk_;
+  b.wpart = wpart_on_ ? d_wpart_ : nullptr;
+  b.wpart_skip = wpart_skip_; b.wpart_row0 = wpart_row0_; b.wpart_row1 = wpart_row1_;
   return b;
 }
 
@@ -2637,6 +2645,7 @@ void EnsembleCore::prepare() {
   spin_valid_ = uniform;
   need_spinup_ = false;
   ++out_epoch_;
+  wpart_hi_ = -1;   // (row 0 rewritten: the next launch from startDate reduces it again)
   last_iy_ = 0;
   hist_valid_to_ = 0;
   dirty_from_iy_ = -1;
@@ -2762,9 +2771,6 @@ void EnsembleCore::run(double runtodate) {
       upload_args();
     }
   }
-  last_run_prewarmed_ = false;
-  prewarm_end();
-  check(hipEventRecord(ev0_, stream_), "event");
   // one launch for the whole span: wavefronts are independent (each does its own DOECLIM
   // history pass every HX_DBLK years), so there is no global barrier to wait at
   const bool hf = d_out_[HXO_HEATFLUX] || d_out_[HXO_FLUX_MIXED] || d_out_[HXO_FLUX_INTERIOR];
@@ -2829,12 +2835,37 @@ void EnsembleCore::run(double runtodate) {
   last_run_w2_ = w2;
   last_run_con_ = con;
   last_run_faithful_ = kc_.faithful_retries;
+  {  // Per-wavefront partial statistics behind the year loop (hx_wave_partials): the plain one-biome
+    // kernel writes them for the rows of this launch; HECTOR_AMD_STATS_PARTIALS=0: never.  The rows
+    // any other flavour writes have none: the valid range ends in front of them.
+    const char *e = getenv("HECTOR_AMD_STATS_PARTIALS");
+    const bool want = d_wpart_ && !pair && !(e && e[0] == '0') &&
+                      hx_run_writes_partials(B_, hf || con == 2, ker_per_member_, con, w2);
+    const bool extend = want && last_iy_ != 0 && wpart_hi_ >= wpart_lo_ && wpart_hi_ >= last_iy_;
+    const int skip = !want ? wpart_skip_ : extend ? wpart_skip_ : partials_skip_waves();
+    const int row0 = !want ? wpart_row0_ : last_iy_ == 0 ? 0 : last_iy_ + 1;   // (the kernel reads it from its arguments)
+    const int row1 = want ? target : wpart_row1_;
+    if (want != wpart_on_ || skip != wpart_skip_ || row0 != wpart_row0_ || row1 != wpart_row1_) {
+      wpart_on_ = want; wpart_skip_ = skip; wpart_row0_ = row0; wpart_row1_ = row1;
+      upload_args();
+    }
+    if (want) {
+      if (!extend) wpart_lo_ = last_iy_ == 0 ? 0 : last_iy_ + 1;
+      wpart_hi_ = extend ? std::max(wpart_hi_, target) : target;
+    } else if (wpart_hi_ > last_iy_) {
+      wpart_hi_ = last_iy_;
+    }
+    last_run_wpart_ = want;
+  }
+  last_run_prewarmed_ = false;
+  prewarm_end();
+  check(hipEventRecord(ev0_, stream_), "event");
   if (pair)
     check(hx_launch_run_pair(d_args_, npad_, d_out_[HXO_HEATFLUX] != nullptr, ker_per_member_, last_iy_, target,
                              stream_, pair_cons != 0 || pair_forcing, B_), "run kernel (pair)");
   else
   check(hx_launch_run(B_, d_args_, npad_, hf || con == 2, ker_per_member_, con, last_iy_, target,
-                      stream_, w2, simds_ / 4),
+                      stream_, w2, simds_ / 4, last_run_wpart_),
         "run kernel");
   check(hipEventRecord(ev1_, stream_), "event");
   run_timed_ = true;
@@ -2868,6 +2899,20 @@ int EnsembleCore::wave_clock(long long *ticks, int cap) {
   for (int w = 0; w < nw; ++w) t0 = std::min(t0, t[(size_t)2 * w]);
   const int n = std::min(nw, cap);
   for (int w = 0; w < n; ++w) { ticks[2 * w] = t[(size_t)2 * w] - t0; ticks[2 * w + 1] = t[(size_t)2 * w + 1] - t0; }
+  return n;
+}
+
+// What the statistics epilogue of the last launch cost each wavefront: its third stamp (behind
+// hx_wave_partials) minus the end stamp of its year loop; 0 for a wavefront that skipped it.
+int EnsembleCore::wave_epilogue_clock(long long *ticks, int cap) {
+  if (!d_wave_clk_ || last_iy_ == 0 || !last_run_wpart_) return 0;
+  sync();
+  const int nw = npad_ / HX_WAVE;
+  std::vector<long long> t((size_t)nw * 3);
+  check(hipMemcpy(t.data(), d_wave_clk_, sizeof(long long) * t.size(), hipMemcpyDeviceToHost), "wave clock");
+  const int n = std::min(nw, cap);
+  for (int w = 0; w < n; ++w)
+    ticks[w] = w < wpart_skip_ ? 0 : t[(size_t)2 * nw + w] - t[(size_t)2 * w + 1];
   return n;
 }
 
@@ -3431,8 +3476,55 @@ void EnsembleCore::stats_async(const std::string &capability, int year0, int yea
     throw std::runtime_error("variable " + capability + " was not enabled with set_outputs()");
   if (year0 < scen_.start || year1 > scen_.start + ps.last_iy || year1 < year0)
     throw std::runtime_error("stats: dates must lie between startDate and the current date");
-  check(hx_launch_stats(ps.block, n_, npad_, year0 - scen_.start, year1 - year0 + 1, d_stats,
-                        stream_), "stats kernel");
+  const int iy0 = year0 - scen_.start, ny = year1 - year0 + 1;
+  const int pv = stats_partials_var(ps.block, iy0, iy0 + ny - 1);
+  if (pv >= 0) {
+    check(hx_launch_combine_partials(d_wpart_, 1, &pv, &ps.block, &d_stats, n_, npad_, scen_.ns(), iy0, ny,
+                                     wpart_skip_, stream_), "combine wavefront partials");
+    return;
+  }
+  check(hx_launch_stats(ps.block, n_, npad_, iy0, ny, d_stats, stream_), "stats kernel");
+}
+
+void EnsembleCore::stats_async(const std::vector<std::string> &caps, int year0, int year1, double *d_stats) {
+  const size_t ny = (size_t)(year1 - year0 + 1);
+  // two variables with partials (there are no more): one launch
+  if (caps.size() == 2 && year1 >= year0 && year0 >= scen_.start && caps[0] != caps[1]) {
+    const int iy0 = year0 - scen_.start;
+    int var[2]; const double *rows[2]; double *out[2] = {d_stats, d_stats + ny * 5};
+    bool both = true;
+    for (int k = 0; k < 2 && both; ++k) {
+      const PostSource ps = post_source(caps[(size_t)k], "stats");
+      both = ps.v >= 0 && d_out_[ps.v] && year1 <= scen_.start + ps.last_iy;
+      if (both) { rows[k] = ps.block; var[k] = stats_partials_var(ps.block, iy0, iy0 + (int)ny - 1); both = var[k] >= 0; }
+    }
+    if (both) {
+      check(hx_launch_combine_partials(d_wpart_, 2, var, rows, out, n_, npad_, scen_.ns(), iy0, (int)ny,
+                                       wpart_skip_, stream_), "combine wavefront partials");
+      return;
+    }
+  }
+  for (size_t v = 0; v < caps.size(); ++v) stats_async(caps[v], year0, year1, d_stats + v * ny * 5);
+}
+
+// Which variable of the run kernel's per-wavefront partials `block` is (0 CO2_concentration, 1
+// global_tas), if rows iy0 .. iy1 of it were written together with theirs; -1: take hx_stats_kernel
+// (any other variable, a derived block or series, rows of another kernel flavour,
+// HECTOR_AMD_STATS_PARTIALS=0).
+int EnsembleCore::stats_partials_var(const double *block, int iy0, int iy1) const {
+  if (!d_wpart_ || !block || iy0 < wpart_lo_ || iy1 > wpart_hi_) return -1;
+  const int v = block == d_out_[HXO_CO2] ? 0 : block == d_out_[HXO_TGAV] ? 1 : -1;
+  if (v < 0) return -1;
+  const char *e = getenv("HECTOR_AMD_STATS_PARTIALS");
+  return (e && e[0] == '0') ? -1 : v;
+}
+
+// How many of the first wavefronts leave the epilogue out (HxBuffers::wpart_skip).
+// HECTOR_AMD_STATS_SKIP_WAVES=<k> forces it.
+int EnsembleCore::partials_skip_waves() const {
+  const int nw = npad_ / HX_WAVE;
+  if (const char *e = getenv("HECTOR_AMD_STATS_SKIP_WAVES")) return std::max(0, std::min(nw, std::atoi(e)));
+  return 0;
 }
 
 void EnsembleCore::status(unsigned *out_host) {

@@ -195,6 +195,9 @@ class EnsembleCore {
   void stats_device(const std::string &capability, int year0, int year1, double *d_stats);
   // the same, queued on the core's stream without waiting (the fleet's collective follows it)
   void stats_async(const std::string &capability, int year0, int year1, double *d_stats);
+  // ... of several variables, d_stats[v][year][5]: those the run kernel left per-wavefront partials
+  // for (stats_partials_var) share one combine launch, the others take hx_stats_kernel each
+  void stats_async(const std::vector<std::string> &capabilities, int year0, int year1, double *d_stats);
   // ---- post-processing on the device (ensemble_post.cpp, hx_dev_post.h); both read results only: no prepare(), no
   // prewarm loop, no spinup, the core is not dirtied.  Scratch is allocated on first use.
   // chi2[member] of a recorded output against obs (hx_member_score in hector_amd.h): out_host[n_]
@@ -341,6 +344,9 @@ class EnsembleCore {
   // device has SIMDs --, 0 never
   void set_two_wave_from(int min_members) { two_wave_from_ = min_members; }
   int wave_clock(long long *ticks, int cap);   // [wavefront][start, end] of the last launch, 100 MHz ticks
+  // ticks a wavefront of the last launch spent in the statistics epilogue behind its year loop
+  // (hx_wave_partials); -> wavefronts written, 0 if the launch wrote no partials
+  int wave_epilogue_clock(long long *ticks, int cap);
   const char *last_run_kernel() const { return last_run_pair_ ? "pair" : last_run_w2_ ? "run2" : "run"; }
   // which instantiation family the last run() asked for (the CON template argument of
   // hx_run_kernel): 0 plain, -2 plain + diagnostics, -1 extended, 1 extended with the NBP
@@ -402,6 +408,16 @@ class EnsembleCore {
   std::vector<double> lane_cost_;  // [n_] measured cost per member (empty: parameter key)
   double *d_cost_ = nullptr;
   long long *d_wave_clk_ = nullptr;   // HxBuffers::wave_clk
+  // Per-wavefront partial statistics of CO2_concentration and global_tas (HxBuffers::wpart),
+  // allocated with the outputs of a one-biome core.  wpart_on_ / wpart_skip_: what the kernel
+  // arguments on the device say.  Rows wpart_lo_ .. wpart_hi_ of the output blocks were written
+  // together with their partials and by nothing else since (hi < lo: none): a launch of another
+  // kernel flavour cuts the range at its first row, a new layout or spinup empties it.
+  double *d_wpart_ = nullptr;
+  bool wpart_on_ = false, last_run_wpart_ = false;
+  int wpart_skip_ = 0, wpart_row0_ = 0, wpart_row1_ = -1, wpart_lo_ = 0, wpart_hi_ = -1;
+  int stats_partials_var(const double *block, int iy0, int iy1) const;   // 0 / 1, or -1: hx_stats_kernel
+  int partials_skip_waves() const;
   double *d_bscratch_ = nullptr;  // [nbiome][npad] f_new_thaw of the seven- and eight-biome kernels
   int cost_from_iy_ = -1;         // d_cost_ covers the years cost_from_iy_+1..last_iy_ (-1: nothing)
   void maybe_calibrate_lanes();

@@ -619,6 +619,11 @@ int hx_wave_clock(hx_core *core, int shard, long long *ticks, int cap, int *n_wa
   HX_TRY(if (shard < 0 || shard >= core->core->n_shards()) throw std::runtime_error("bad shard index");
          *n_waves = core->core->wave_clock(shard, ticks, cap))
 }
+int hx_wave_epilogue_clock(hx_core *core, int shard, long long *ticks, int cap, int *n_waves) {
+  if (!ticks || !n_waves || cap < 0) return fail("hx_wave_epilogue_clock: bad argument");
+  HX_TRY(if (shard < 0 || shard >= core->core->n_shards()) throw std::runtime_error("bad shard index");
+         *n_waves = core->core->wave_epilogue_clock(shard, ticks, cap))
+}
 int hx_last_run_kernel(hx_core *core, const char **name) { HX_TRY(*name = core->core->last_run_kernel()) }
 int hx_last_run_variant(hx_core *core, int *variant) { HX_TRY(*variant = core->core->last_run_variant()) }
 int hx_last_run_retries(hx_core *core, int *faithful) { HX_TRY(*faithful = core->core->last_run_retries()) }

@@ -20,6 +20,16 @@ __device__ __forceinline__ void hx_wave_stamp(const HxBuffers &buf, int wave, in
 #endif
 }
 
+// A third stamp behind the statistics epilogue of the run kernels (hx_wave_partials): the buffer has
+// four slots a wavefront, the run kernels' start / end pairs fill the first half, this one slot
+// 2 * (npad / 64) + wave.  hx_wave_stamp(.., 1, ..) stays the end of the year loop.
+__device__ __forceinline__ void hx_wave_stamp_epilogue(const HxBuffers &buf, int wave, int lane) {
+#ifndef HX_HOST_EMULATION
+  if (buf.wave_clk && lane == 0)
+    ((long long HX_GLOBAL *)buf.wave_clk)[2 * (buf.npad >> 6) + wave] = (long long)__builtin_amdgcn_s_memrealtime();
+#endif
+}
+
 #ifdef HX_PHASE_CLOCK
 #define HX_NCLK 24
 __shared__ long long hx_s_clk[HX_NCLK + 1];

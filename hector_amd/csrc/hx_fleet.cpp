@@ -1015,6 +1015,11 @@ int Fleet::wave_clock(int shard_index, long long *ticks, int cap) {
   use(s);
   return s.core->wave_clock(ticks, cap);
 }
+int Fleet::wave_epilogue_clock(int shard_index, long long *ticks, int cap) {
+  Shard &s = shards_[(size_t)shard_index];
+  use(s);
+  return s.core->wave_epilogue_clock(ticks, cap);
+}
 double Fleet::last_run_kernel_ms() {
   double ms = 0;
   for (Shard &s : shards_) { use(s); s.core->sync(); ms = std::max(ms, s.core->last_run_kernel_ms()); }
@@ -1144,18 +1149,26 @@ void Fleet::ensemble_stats(const std::vector<std::string> &caps, int year0, int 
   const int world = comm_ready_ ? world_ : 1;
   const size_t nv = caps.size(), rows = nv * (size_t)ny, blk = rows * 5;
   ensure_stats_buffers(blk);
+  // One rank: its own block is the result (folding one slot copies it, bit for bit) -- reduced
+  // straight into the caller's device buffer, no slot copy, no combine, no result copy.
+  if (world == 1) {
+    Shard &s = shards_[0];
+    use(s);
+    double *dst = d_out ? d_out : s.d_local;
+    s.core->stats_async(caps, year0, year1, dst);
+    if (out_host)
+      hip_ck(hipMemcpyAsync(out_host, dst, sizeof(double) * blk, hipMemcpyDeviceToHost, s.core->stream()),
+             "stats result to host");
+    hip_ck(hipStreamSynchronize(s.core->stream()), "stats sync");
+    return;
+  }
   // 1. every shard reduces its own members on its own GPU, on its own stream
   for (Shard &s : shards_) {
     use(s);
-    for (size_t v = 0; v < nv; ++v)
-      s.core->stats_async(caps[v], year0, year1, s.d_local + v * (size_t)ny * 5);
+    s.core->stats_async(caps, year0, year1, s.d_local);
   }
   // 2. the one collective: every rank receives every rank's block
-  if (world == 1) {
-    Shard &s = shards_[0];
-    hip_ck(hipMemcpyAsync(s.d_slots, s.d_local, sizeof(double) * blk, hipMemcpyDeviceToDevice,
-                          s.core->stream()), "stats copy");
-  } else if (duplicates_) {
+  if (duplicates_) {
     for (Shard &s : shards_) { use(s); hip_ck(hipStreamSynchronize(s.core->stream()), "stats sync"); }
     for (Shard &dst : shards_) {
       use(dst);

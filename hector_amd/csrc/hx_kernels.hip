@@ -34,6 +34,9 @@
 // interval (hx_chem_fit.inc); the permafrost curve's erfc as one polynomial range
 // (hx_erfc_fit.inc); LUC ratio via one division; 200-year Q10 window as a running sum; forcing
 // summed in groups.
+// (This file includes itself: the body of the year-loop kernels stands once, at the end, behind
+//  HX_RUN_BODY_PASS, and is included as text by hx_run_kernel and by hx_run_kernel_stats.)
+#ifndef HX_RUN_BODY_PASS
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <math.h>
@@ -539,6 +542,88 @@ __global__ __launch_bounds__(64) void hx_spinup_kernel(const HxArgs *__restrict_
 }
 
 // ===========================================================================
+// Statistics epilogue of a run kernel that owns the [HX_DBLK][64] LDS tile: behind its year loop
+// the wavefront reduces what it wrote itself -- CO2_concentration and global_tas of its 64 members,
+// rows iy_from + 1 .. iy_to (and row 0 when the launch starts there) -- to {sum, sum of squares,
+// min, max} per (variable, year): HxBuffers::wpart[var][iy][wave][4].  hx_combine_partials_kernel
+// folds the wavefronts; the ensemble statistics then need no second pass over the rows.
+// A tile of 32 rows x 64 lanes goes through the LDS (every lane its own value, the next tile's 32
+// loads in flight meanwhile) and is reduced transposed: lane (h, j) walks the 32 entries of half
+// h of row j, the two halves meet in one shuffle.  The entry a lane reads at step k is
+// k ^ (iy & 31): 32 lanes, 32 different banks, and an order that depends on the year alone -- a
+// row's partial has the same bits wherever a launch's first row falls.  No wavefront reads
+// another's data or waits for anything.
+// ===========================================================================
+#ifndef HX_HOST_EMULATION
+// (The first and the last row come from the host, HxBuffers::wpart_row0 / wpart_row1, not from the
+//  launch's iy_from and iy_to: the year loop counts down and keeps neither, a scalar more alive across
+//  it spills one.)
+__device__ __forceinline__ void hx_wave_partials(const HxBuffers &buf, double (*tile)[64], int ns, int mem,
+                                                 int wave) {
+  const int lane = mem & 63, nw = buf.npad >> 6;
+  const int iy_to = buf.wpart_row1 < ns ? buf.wpart_row1 : ns - 1;
+  const int row0 = buf.wpart_row0 > 0 ? buf.wpart_row0 : 0;
+  int live = buf.n - wave * 64;   // lanes 0 .. live - 1 hold members
+  live = live < 0 ? 0 : live > 64 ? 64 : live;
+  const int j = lane & 31, h = lane >> 5;
+#pragma unroll 1
+  for (int var = 0; var < 2; ++var) {
+    const double *rows = buf.out[var ? HXO_TGAV : HXO_CO2];
+    if (!rows) continue;
+    hx_gcd src = HX_GCD(rows) + mem;
+    hx_gd dst = HX_GD(buf.wpart) + ((size_t)var * (size_t)ns * (size_t)nw + (size_t)wave) * 4;
+    double cur[HX_DBLK];
+    // (rows past the last one: that one again, not reduced.  The 32 row indices formed per lane:
+    //  as scalars they are 32 more registers of a file the year loop has filled.)
+    auto load_tile = [&](int t) {
+      int vt = t;
+      asm volatile("" : "+v"(vt));
+#pragma unroll
+      for (int r = 0; r < HX_DBLK; ++r) {
+        const int iy = vt + r < iy_to ? vt + r : iy_to;
+        cur[r] = src[(size_t)iy * buf.npad];
+      }
+    };
+    load_tile(row0);
+#pragma unroll 1
+    for (int t0 = row0; t0 <= iy_to; t0 += HX_DBLK) {
+#pragma unroll
+      for (int r = 0; r < HX_DBLK; ++r) tile[r][lane] = cur[r];
+      if (t0 + HX_DBLK <= iy_to) load_tile(t0 + HX_DBLK);
+      __syncthreads();   // (one wavefront a block: orders the LDS traffic, no barrier to wait at)
+      const int iy = t0 + j;
+      const double *half = &tile[j][32 * h];
+      const int rot = iy & 31;
+      double s = 0.0, q = 0.0, mn = INFINITY, mx = -INFINITY;
+      if (live == 64) {
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+          const double x = half[k ^ rot];
+          s += x; q = fma(x, x, q); mn = fmin(mn, x); mx = fmax(mx, x);
+        }
+      } else {
+#pragma unroll 4
+        for (int k = 0; k < 32; ++k) {
+          const int e = k ^ rot;
+          if (32 * h + e < live) {
+            const double x = half[e];
+            s += x; q = fma(x, x, q); mn = fmin(mn, x); mx = fmax(mx, x);
+          }
+        }
+      }
+      __syncthreads();   // (the tile is free for the next rows)
+      s += __shfl_down(s, 32, 64); q += __shfl_down(q, 32, 64);
+      mn = fmin(mn, __shfl_down(mn, 32, 64)); mx = fmax(mx, __shfl_down(mx, 32, 64));
+      if (h == 0 && iy <= iy_to) {
+        hx_gd o = dst + (size_t)iy * (size_t)nw * 4;
+        o[0] = s; o[1] = q; o[2] = mn; o[3] = mx;
+      }
+    }
+  }
+}
+#endif
+
+// ===========================================================================
 // Main run: years (iy_from, iy_to] (indices relative to startDate).  Each year
 // is three phases separated by compiler fences:
 //   A  gases, ocean year start, slow parameters   (year-level constants from HBM)
@@ -562,6 +647,906 @@ template <int B> constexpr bool hx_rowio() { return hx_tbl<B>(); }
 template <int B, bool HF, bool KERPM, int CON>
 __global__ __launch_bounds__(CON == 3 ? 64 * (1 + trk_waves<(B < 1 || B > 4 ? 1 : B)>()) : 64) HX_WAVES_PER_SIMD(B)
 void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
+  constexpr bool WP = false;
+#define HX_RUN_BODY_PASS
+#include "hx_kernels.hip"
+#undef HX_RUN_BODY_PASS
+}
+// The plain one-biome kernel, hx_run_kernel<1, false, false, 0>, with the statistics epilogue
+// (hx_wave_partials) behind its year loop: a kernel of its own, so that the plain one stays what it
+// is, instruction for instruction, for the launches that want no partials.  (A template, so that
+// the body's `if constexpr` discard what they discard in hx_run_kernel.)
+#ifndef HX_HOST_EMULATION
+#define HX_HAS_RUN_STATS 1
+template <int B, bool WP>
+__global__ __launch_bounds__(64) HX_WAVES_PER_SIMD(B)
+void hx_run_kernel_stats(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
+  static_assert(B == 1 && WP, "the epilogue needs the LDS tile: the plain one-biome kernel");
+  constexpr bool HF = false, KERPM = false;
+  constexpr int CON = 0;
+#define HX_RUN_BODY_PASS
+#include "hx_kernels.hip"
+#undef HX_RUN_BODY_PASS
+}
+#else
+#define HX_HAS_RUN_STATS 0
+#endif
+
+// ===========================================================================
+// Broadcast member 0's state/outputs row to every member (shared spinup).
+// ===========================================================================
+__global__ void hx_broadcast_rows_kernel(double *table, int nrows, int npad) {
+  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
+  if (mem >= npad || mem == 0) return;
+  for (int r = 0; r < nrows; ++r) table[(size_t)r * npad + mem] = table[(size_t)r * npad];
+}
+__global__ void hx_broadcast_u32_kernel(unsigned *v, int npad) {
+  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
+  if (mem >= npad || mem == 0) return;
+  v[mem] = v[0];
+}
+// status |= the member's own derive-time flags (HXD_FLAG row), after the spinup
+__global__ void hx_or_flags_kernel(unsigned *status, const double *flag_row, int npad) {
+  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
+  if (mem >= npad) return;
+  status[mem] |= (unsigned)flag_row[mem];
+}
+
+// ===========================================================================
+// N2OComponent::run (src/n2o_component.cpp:152-191) and HalocarbonComponent::run
+// (src/halocarbon_component.cpp:181-229) per member, for ensembles whose N2O or halocarbon
+// parameters differ between members (otherwise the host runs them once while it builds the
+// per-year table).  Neither depends on the carbon-climate state, so they run ahead of the year
+// loop, one member per thread: N2O[t] and the year's halocarbon + albedo + misc forcing.
+//   par [3 + 3 nh][npad]: N0, TN2O0, UC_N2O, then tau, rho, delta of each gas
+//   ser [4 + 2 nh][ns]:   N2O emissions (anthropogenic + natural), N2O constraint (NaN = none),
+//                         RF_albedo, RF_misc, then per gas the year's concentration increment
+//                         per unit lifetime (emissions / molar mass / 0.18) and its constraint
+//   h0 [nh]: preindustrial concentrations.  Gases in the order their forcings are summed.
+// ===========================================================================
+__global__ __launch_bounds__(64) void hx_gas_kernel(const double *par, const double *ser,
+                                                    const double *h0, int nh, int ns, int npad,
+                                                    double *n2o_out, double *rf_other_out) {
+  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
+  if (mem >= npad) return;
+  const size_t np = (size_t)npad;
+  const double N0 = par[mem], TN2O0 = par[np + mem], UC = par[2 * np + mem];
+  const double *em = ser, *ncon = ser + ns, *alb = ser + 2 * (size_t)ns, *misc = ser + 3 * (size_t)ns;
+  constexpr int MAXH = 40;
+  double conc[MAXH], expfac[MAXH];
+  for (int h = 0; h < nh && h < MAXH; ++h) {
+    conc[h] = h0[h];
+    expfac[h] = exp(-(1 / par[(size_t)(3 + 3 * h) * np + mem]));
+  }
+  const double N0f = isnan(ncon[0]) ? N0 : ncon[0];  // n2o_component.cpp:137-145
+  double n2o = N0f;
+  n2o_out[mem] = n2o;
+  rf_other_out[mem] = (0.0 + alb[0]) + misc[0];
+  for (int iy = 1; iy < ns; ++iy) {
+    const double tau_n = TN2O0 * pow(n2o / N0f, -0.05);
+    n2o = n2o + (em[iy] / UC - n2o / tau_n);
+    if (!isnan(ncon[iy])) n2o = ncon[iy];
+    double rf_h = 0.0;
+    for (int h = 0; h < nh && h < MAXH; ++h) {
+      const double tau = par[(size_t)(3 + 3 * h) * np + mem], rho = par[(size_t)(4 + 3 * h) * np + mem],
+                   delta = par[(size_t)(5 + 3 * h) * np + mem];
+      const double dconc = ser[(size_t)(4 + 2 * h) * ns + iy], hc = ser[(size_t)(5 + 2 * h) * ns + iy];
+      conc[h] = conc[h] * expfac[h] + dconc * tau * (1.0 - expfac[h]);
+      if (!isnan(hc)) conc[h] = hc;
+      const double rf_un = rho * conc[h];
+      rf_h = rf_h + (rf_un + delta * rf_un);
+    }
+    n2o_out[(size_t)iy * np + mem] = n2o;
+    rf_other_out[(size_t)iy * np + mem] = (rf_h + alb[iy]) + misc[iy];
+  }
+}
+
+// ===========================================================================
+// Output gather: members are assigned to lanes in a behaviour-sorted order (see
+// EnsembleCore::upload_params); results go back to the caller in member order.
+// dst[y][member] = src[y][lane_of_member[member]]
+// ===========================================================================
+__global__ __launch_bounds__(256) void hx_gather_kernel(const double *src, const int *lane_of_member,
+                                                        double *dst, int n, int npad, int nyears) {
+  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
+  const int y = blockIdx.y;
+  if (mem >= n || y >= nyears) return;
+  dst[(size_t)y * n + mem] = src[(size_t)y * npad + lane_of_member[mem]];
+}
+
+// ===========================================================================
+// Per-year ensemble statistics of one output variable over members [0, n):
+// count, sum, sum of squares, min, max -> stats[year][5].  One workgroup per
+// year; wave-level DPP/shuffle reduction, then one LDS hop across the waves.
+// ===========================================================================
+__global__ __launch_bounds__(256) void hx_stats_kernel(const double *var, int n, int npad,
+                                                       int iy0, double *stats) {
+  const int iy = iy0 + blockIdx.x;
+  const double *row = var + (size_t)iy * npad;
+  // pure streaming: four 16-byte loads in flight per lane (rows are 512-byte aligned: npad is a
+  // multiple of 64), four independent accumulator sets
+  double sa[4] = {0, 0, 0, 0}, qa[4] = {0, 0, 0, 0};
+  double mn = INFINITY, mx = -INFINITY;
+  const int n2 = n >> 1;                       // number of double2 elements
+  const double2 *row2 = reinterpret_cast<const double2 *>(row);
+  int i = threadIdx.x;
+  for (; i + 3 * (int)blockDim.x < n2; i += 4 * blockDim.x) {
+    double2 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = row2[i + k * (int)blockDim.x];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      sa[k] += v[k].x + v[k].y;
+      qa[k] += v[k].x * v[k].x + v[k].y * v[k].y;
+      mn = fmin(mn, fmin(v[k].x, v[k].y));
+      mx = fmax(mx, fmax(v[k].x, v[k].y));
+    }
+  }
+  for (; i < n2; i += blockDim.x) {
+    const double2 v = row2[i];
+    sa[0] += v.x + v.y; qa[0] += v.x * v.x + v.y * v.y;
+    mn = fmin(mn, fmin(v.x, v.y)); mx = fmax(mx, fmax(v.x, v.y));
+  }
+  if ((n & 1) && threadIdx.x == 0) {
+    const double v = row[n - 1];
+    sa[0] += v; qa[0] += v * v; mn = fmin(mn, v); mx = fmax(mx, v);
+  }
+  double s = (sa[0] + sa[1]) + (sa[2] + sa[3]), s2 = (qa[0] + qa[1]) + (qa[2] + qa[3]);
+  double cnt = (threadIdx.x == 0) ? (double)n : 0.0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    s += __shfl_down(s, off, 64); s2 += __shfl_down(s2, off, 64);
+    cnt += __shfl_down(cnt, off, 64);
+    mn = fmin(mn, __shfl_down(mn, off, 64)); mx = fmax(mx, __shfl_down(mx, off, 64));
+  }
+  __shared__ double red[4][5];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[w][0] = cnt; red[w][1] = s; red[w][2] = s2;
+                                 red[w][3] = mn; red[w][4] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 4; ++k) { red[0][0] += red[k][0]; red[0][1] += red[k][1];
+      red[0][2] += red[k][2]; red[0][3] = fmin(red[0][3], red[k][3]);
+      red[0][4] = fmax(red[0][4], red[k][4]); }
+    double *o = stats + (size_t)blockIdx.x * 5;
+    o[0] = red[0][0]; o[1] = red[0][1]; o[2] = red[0][2]; o[3] = red[0][3]; o[4] = red[0][4];
+  }
+}
+
+// ===========================================================================
+// The last step of the multi-GPU statistics (hx_fleet.cpp): slots[rank][row][5] holds every
+// rank's {count, sum, sum of squares, min, max} of a (variable, year) row, gathered by ONE
+// ncclAllGather; every rank folds them in rank order, so the result is bit-identical everywhere.
+// ===========================================================================
+__global__ __launch_bounds__(256) void hx_combine_stats_kernel(const double *slots, int world,
+                                                               int rows, double *out) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  const double *p = slots + (size_t)r * 5;
+  double cnt = p[0], s = p[1], s2 = p[2], mn = p[3], mx = p[4];
+  for (int k = 1; k < world; ++k) {
+    p += (size_t)rows * 5;
+    cnt += p[0]; s += p[1]; s2 += p[2]; mn = fmin(mn, p[3]); mx = fmax(mx, p[4]);
+  }
+  double *o = out + (size_t)r * 5;
+  o[0] = cnt; o[1] = s; o[2] = s2; o[3] = mn; o[4] = mx;
+}
+
+// ===========================================================================
+// The same statistics from the run kernel's per-wavefront partials (hx_wave_partials): one
+// workgroup per (year, variable) reads the year's [npad / 64][4] partials -- 32 B a wavefront,
+// contiguous -- every thread its wavefronts in ascending order, then the tree of hx_stats_kernel:
+// the same bits from run to run.  The members of wavefronts < skip, which wrote no partials, come
+// straight from the row.
+// ===========================================================================
+__global__ __launch_bounds__(256) void hx_combine_partials_kernel(const double *wpart, int var0, int var1,
+                                                                  const double *rows0, const double *rows1,
+                                                                  double *out0, double *out1, int n, int npad,
+                                                                  int ns, int iy0, int skip) {
+  const int iy = iy0 + blockIdx.x, var = blockIdx.y ? var1 : var0;
+  const int nw = npad >> 6, nlive = (n + 63) >> 6;   // (wavefronts behind nlive hold no member)
+  const double2 *p = reinterpret_cast<const double2 *>(wpart + ((size_t)var * ns + (size_t)iy) * (size_t)nw * 4);
+  double s = 0.0, s2 = 0.0, mn = INFINITY, mx = -INFINITY;
+  for (int w = skip + (int)threadIdx.x; w < nlive; w += blockDim.x) {
+    const double2 a = p[2 * w], b = p[2 * w + 1];
+    s += a.x; s2 += a.y; mn = fmin(mn, b.x); mx = fmax(mx, b.y);
+  }
+  const int nrow = skip * 64 < n ? skip * 64 : n;
+  if (nrow > 0) {
+    const double *row = (blockIdx.y ? rows1 : rows0) + (size_t)iy * npad;
+    for (int i = threadIdx.x; i < nrow; i += blockDim.x) {
+      const double x = row[i];
+      s += x; s2 = fma(x, x, s2); mn = fmin(mn, x); mx = fmax(mx, x);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    s += __shfl_down(s, off, 64); s2 += __shfl_down(s2, off, 64);
+    mn = fmin(mn, __shfl_down(mn, off, 64)); mx = fmax(mx, __shfl_down(mx, off, 64));
+  }
+  __shared__ double red[4][4];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[w][0] = s; red[w][1] = s2; red[w][2] = mn; red[w][3] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 4; ++k) { red[0][0] += red[k][0]; red[0][1] += red[k][1];
+      red[0][2] = fmin(red[0][2], red[k][2]); red[0][3] = fmax(red[0][3], red[k][3]); }
+    double *o = (blockIdx.y ? out1 : out0) + (size_t)blockIdx.x * 5;
+    o[0] = (double)n; o[1] = red[0][0]; o[2] = red[0][1]; o[3] = red[0][2]; o[4] = red[0][3];
+  }
+}
+
+// ===========================================================================
+// DOECLIM convolution kernel table Ker[i] (temperature_component.cpp:303-371)
+// for `count` diffusivities: ker[i * stride + mem].  count = 1, stride = 1 when
+// every member shares the diffusivity.
+// ===========================================================================
+__global__ __launch_bounds__(256) void hx_doeclim_table_kernel(const double *diff_row,
+                                                               double *ker, int ns, int count,
+                                                               int stride) {
+  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = blockIdx.y;
+  if (mem >= count || i >= ns) return;
+  const double keff = (D_secs / 10000) * diff_row[mem];
+  const double tb = (D_zbot * D_zbot) / keff;  // taubot / dt, dt = 1
+  const double sq2 = sqrt(2.0), sqpt = sqrt(M_PI * tb);
+  double KT0, KTA1, KTB1, KTA2, KTB2, KTA3, KTB3;
+  if (i == ns - 1) {
+    KT0 = 4.0 - 2.0 * sq2;
+    KTA1 = -8.0 * exp(-tb) + 4.0 * sq2 * exp(-0.5 * tb);
+    KTB1 = 4.0 * sqpt * (1.0 + erf(sqrt(0.5 * tb)) - 2.0 * erf(sqrt(tb)));
+    KTA2 = 8.0 * exp(-4.0 * tb) - 4.0 * sq2 * exp(-2.0 * tb);
+    KTB2 = -8.0 * sqpt * (1.0 + erf(sqrt(2.0 * tb)) - 2.0 * erf(2.0 * sqrt(tb)));
+    KTA3 = -8.0 * exp(-9.0 * tb) + 4.0 * sq2 * exp(-4.5 * tb);
+    KTB3 = 12.0 * sqpt * (1.0 + erf(sqrt(4.5 * tb)) - 2.0 * erf(3.0 * sqrt(tb)));
+  } else {
+    const double a = (double)(ns - i), b = (double)(ns + 1 - i), c = (double)(ns - 1 - i);
+    const double ra = sqrt(a), rb = sqrt(b), rc = sqrt(c);
+    const double ua = sqrt(tb / a), ub = sqrt(tb / b), uc = sqrt(tb / c);
+    KT0 = 4.0 * ra - 2.0 * rb - 2.0 * rc;
+    KTA1 = -8.0 * ra * exp(-tb / a) + 4.0 * rb * exp(-tb / b) + 4.0 * rc * exp(-tb / c);
+    KTB1 = 4.0 * sqpt * (erf(uc) + erf(ub) - 2.0 * erf(ua));
+    KTA2 = 8.0 * ra * exp(-4.0 * tb / a) - 4.0 * rb * exp(-4.0 * tb / b) -
+           4.0 * rc * exp(-4.0 * tb / c);
+    KTB2 = -8.0 * sqpt * (erf(2.0 * uc) + erf(2.0 * ub) - 2.0 * erf(2.0 * ua));
+    KTA3 = -8.0 * ra * exp(-9.0 * tb / a) + 4.0 * rb * exp(-9.0 * tb / b) +
+           4.0 * rc * exp(-9.0 * tb / c);
+    KTB3 = 12.0 * sqpt * (erf(3.0 * uc) + erf(3.0 * ub) - 2.0 * erf(3.0 * ua));
+  }
+  ker[(size_t)(i + HX_KPAD) * stride + mem] = KT0 + KTA1 + KTB1 + KTA2 + KTB2 + KTA3 + KTB3;
+}
+
+// ===========================================================================
+// oceanbox::chem_equilibrate for both surface boxes (src/oceanbox.cpp:382-445,
+// ocean_component.cpp:392-400): the first post-spinup ocean.run() turns the chemistry on and
+// tunes each box's alkalinity so that it reproduces the spinup flux at the spun-up CO2.  Its
+// inputs are all spinup results (box carbon, atmosphere, SST = 0), so it runs once, directly
+// after the spinup kernel, and the run kernel finds the alkalinities in the state table.
+// ===========================================================================
+__global__ __launch_bounds__(64) void hx_alk_kernel(const HxArgs *__restrict__ args, int nmem) {
+#ifndef HX_HOST_EMULATION
+  __builtin_amdgcn_s_setprio(3);   // (see hx_spinup_kernel)
+#endif
+  const int mem = blockIdx.x * 64 + threadIdx.x;
+  if (mem >= nmem) return;
+  const HxBuffers &buf = args->buf;
+  const double cHL = lds_(buf, HXS_C_HL, mem), cLL = lds_(buf, HXS_C_LL, mem);
+  const double co2 = lds_(buf, HXS_ATMOS, mem) * PGC2PPM;
+  const double sst = lds_(buf, HXS_SST, mem);
+  unsigned status = HX_GU(buf.status)[mem];
+  ChemK kH, kL;
+  chem_constants2(sst + 18 + (-16.4), sst + 18 + 2.9, kH, kL);
+  double hH = 0, hL = 0;
+  const double alkH = equilibrate_alk(kH, cHL, 1.0 / O_vHL, O_AsHL, co2, 1.000, hH, status);
+  const double alkL = equilibrate_alk(kL, cLL, 1.0 / O_vLL, O_AsLL, co2, -1.000, hL, status);
+  sts_(buf, HXS_ALK_HL, mem, alkH); sts_(buf, HXS_ALK_LL, mem, alkL);
+  sts_(buf, HXS_H_HL, mem, hH); sts_(buf, HXS_H_LL, mem, hL);
+  HX_GU(buf.status)[mem] = status;
+}
+
+// ===========================================================================
+// Diagnostics derived from recorded outputs, one (year, member) element per thread.
+// The reference keeps them as members of the carbonate-chemistry object of the last solve
+// (ocean_csys.cpp:328-366) or recomputes them on request (ocean_component.cpp:440-512);
+// here they follow from what the run recorded:
+//   [H+] = 10^-pH and pCO2 of the last solve, the box temperature Tbox = SST(year-1) + 18 +
+//   deltaT (oceanbox.cpp:97-99, 309-323), and the year-end box carbon:
+//   CO2* = pCO2 Kh, CO3 = CO2* K1 K2 / [H+]^2  (identical to DIC / (1 + h/K2 + h^2/(K1 K2)))
+// ===========================================================================
+__device__ __forceinline__ double diag_rf(int kind, const HxDiagArgs &a, int iy, int mem) {
+  hx_ccd sh = HX_CCD(a.shared) + (size_t)iy * HXSH_STRIDE;
+  const size_t o = (size_t)iy * a.npad + mem;
+  const double a2 = -3.4197e-4, b2 = 2.5455e-4, c2 = -2.4357e-4, d2 = 0.12173;
+  const double a3 = -8.9603e-5, b3 = -1.2462e-4, d3 = 0.045194;
+  double sqN = sh[HXSH_SQRT_N2O], sqN0 = a.sqrtN0;
+  if (a.n2o_members) { sqN = sqrt(a.n2o_members[o]); sqN0 = sqrt(a.n2o_members[mem]); }
+  if (kind == HXG_RF_O3) return 0.042 * a.o3[o];
+  const double ch4 = a.ch4[o], sqM = sqrt(ch4);
+  if (kind == HXG_RF_H2O) return 0.0485 * ((ch4 - a.M0f) / (1831 - a.M0f));
+  if (kind == HXG_RF_CH4) {
+    const double sarf = (a3 * sqM + b3 * sqN + d3) * (sqM - a.sqrtM0);
+    const double delta = a.eff_members ? a.eff_members[(size_t)a.npad + mem] : a.delta_ch4;
+    return (delta * sarf) + sarf;
+  }
+  const double sqC = sqrt(a.co2[o]);
+  const double sarf = (a2 * sqC + b2 * sqN + c2 * sqM + d2) * (sqN - sqN0);
+  const double delta = a.eff_members ? a.eff_members[2 * (size_t)a.npad + mem] : a.delta_n2o;
+  return (delta * sarf) + sarf;
+}
+
+__global__ __launch_bounds__(256) void hx_diag_kernel(int kind, HxDiagArgs a, double *out) {
+  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
+  const int iy = a.iy0 + blockIdx.y;
+  if (mem >= a.npad) return;
+  const size_t o = (size_t)iy * a.npad + mem;
+  double r = 0.0;
+  if (kind >= HXG_RF_N2O) {
+    // forcings are reported relative to the base year (forcing_component.cpp:507-527)
+    if (iy >= a.base_idx) r = diag_rf(kind, a, iy, mem) - diag_rf(kind, a, a.base_idx, mem);
+  } else if (kind == HXG_OCEAN_TAS) {
+    const double lo = a.lo_ratio[mem];
+    r = (lo != 0) ? a.tgav[o] / ((lo * D_flnd) + (1 - D_flnd)) : D_bsi * a.sst[o];
+  } else {
+    const double sst_prev = (iy >= 1) ? a.sst[o - a.npad] : 0.0;
+    const double Tc = sst_prev + 18 + a.deltaT;
+    // convertToDIC  ocean_csys.cpp:403-408 (umol/kg)
+    const double dic = ((((a.carbon ? a.carbon[o] : 0.0) * 1e15) * (1.0 / 12.01)) * (1.0 / 1027.0) *
+                        a.inv_vol) * 1e6;
+    if (kind == HXG_TEMP) r = Tc;
+    else if (kind == HXG_DIC) r = dic;
+    else {
+      ChemK k;
+      chem_constants(Tc, k);
+      const double h = exp10(-a.ph[o]);
+      const double co2st = a.pco2[o] * k.Kh;            // umol/kg
+      const double co3 = co2st * ((k.K1 * k.K2) / (h * h));  // umol/kg
+      if (kind == HXG_CO3) r = co3;
+      else if (kind == HXG_REVELLE) r = dic / co3;        // oceanbox.cpp:278-292
+      else {
+        const double S = O_S, Tk = Tc + 273.15, sqrtS = 5.873670062235365,
+                     S15 = 202.64161714712009;
+        double t1, t2, t3;
+        if (kind == HXG_OMEGA_CA) {  // ocean_csys.cpp:266-274
+          t1 = -171.9065 - 0.077993 * Tk + 2839.319 / Tk + 71.595 * log10(Tk);
+          t2 = +(-0.77712 + 0.0028426 * Tk + 178.34 / Tk) * sqrtS;
+          t3 = -0.07711 * S + 0.0041249 * S15;
+        } else {
+          t1 = -171.945 - 0.077993 * Tk + 2903.293 / Tk + 71.595 * log10(Tk);
+          t2 = +(-0.068393 + 0.0017276 * Tk + 88.135 / Tk) * sqrtS;
+          t3 = -0.10018 * S + 0.0059415 * S15;
+        }
+        const double Ksp = exp10(t1 + t2 + t3);
+        const double calcium = 0.02128 / 40.087 * (S / 1.80655);
+        r = (((co3 * 1e-6) * calcium) / Ksp);
+      }
+    }
+  }
+  out[(size_t)blockIdx.y * a.npad + mem] = r;
+}
+
+// slrComponent (slr_component.cpp:116-232, Vermeer & Rahmstorf 2009): sea-level rise from the
+// global tas series of each member; one thread walks one member's years.  Nothing exists
+// before the reference period 1951-1980 has been run; dT/dt is the derivative of the series as
+// known when the date was computed (h_interpolator.cpp:132-167).  out: 4 arrays [ns][npad]
+// (slr, sl_rc, slr_no_ice, sl_rc_no_ice), zero where the reference has no value.
+__global__ __launch_bounds__(64) void hx_slr_kernel(const double *tgav, int npad, int start_year,
+                                                    int iy_to, double *out, size_t var_stride) {
+  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
+  if (mem >= npad) return;
+  const int lo = 1951 - start_year, hi = 1980 - start_year, first = 1;
+  if (lo < first || iy_to < hi) return;
+  auto TG = [&](int iy) { return tgav[(size_t)iy * npad + mem]; };
+  double sum = 0.0;
+  for (int i = lo; i <= hi; ++i) sum += TG(i);
+  const double ref = sum / (hi - lo + 1);
+  double slr = 0.0, slr_ni = 0.0;
+  for (int iy = first; iy <= iy_to; ++iy) {
+    const int last = (iy <= hi) ? hi : iy;  // the series' last date when this date was computed
+    double dTdt = 0.0;
+    if (last - first + 1 > 2) {
+      if (iy == first) dTdt = (TG(first + 1) - TG(first)) / 1.0;
+      else if (iy == last) dTdt = (TG(iy) - TG(iy - 1)) / 1.0;
+      else dTdt = (((TG(iy) - TG(iy - 1)) / 1.0) + ((TG(iy + 1) - TG(iy)) / 1.0)) / 2.0;
+    }
+    const double T = TG(iy) - ref;
+    const double dHdt = 0.56 * (T - (-0.41)) + (-4.9) * dTdt;
+    const double dHdt_ni = 0.08 * (T - (-0.375)) + 2.5 * dTdt;
+    slr = slr + dHdt;
+    slr_ni = slr_ni + dHdt_ni;
+    const size_t o = (size_t)iy * npad + mem;
+    out[o] = slr;
+    out[var_stride + o] = dHdt;
+    out[2 * var_stride + o] = slr_ni;
+    out[3 * var_stride + o] = dHdt_ni;
+  }
+}
+
+// Unit vector of the carbonate chemistry (a7): n independent (T, carbon, alkalinity) triples
+// through chem_constants + chem_solve from a cold start (the Fujiwara bound is not needed: the
+// bracketed Newton accepts any positive start), one per thread.  Test hook for parity at the
+// function level; the run kernel uses the same two functions.
+__global__ void hx_unit_csys_kernel(int n, const double *Tc, const double *carbon,
+                                    const double *alk, double inv_vol, double *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  ChemK k;
+  chem_constants(Tc[i], k);
+  double h = 1e-8;
+  unsigned status = 0;
+  const double pco2 = chem_solve(k, carbon[i], inv_vol, alk[i], h, status);
+  out[4 * i + 0] = pco2;
+  out[4 * i + 1] = -log10(h);
+  out[4 * i + 2] = k.Tr;
+  out[4 * i + 3] = (double)status;
+}
+
+// ---------------------------------------------------------------------------
+// host-callable launchers (the only symbols the host runtime uses)
+// ---------------------------------------------------------------------------
+extern "C++" {
+// dynamic LDS of a looped kernel for nb biomes (hx_dev_member.h: hx_npark_dyn)
+static size_t hx_dyn_lds_bytes(int nb) { return (size_t)hx_npark_dyn(nb) * 64 * sizeof(double); }
+static void hx_allow_dynamic_lds(const void *kernel, size_t bytes) {
+#if HX_HAS_MFMA   // (the host-emulation build has no such attribute)
+  if (bytes > 64 * 1024)   // beyond the default window a kernel has to be told
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+#else
+  (void)kernel; (void)bytes;
+#endif
+}
+
+// experiment builds (tools/prof/build_variant.sh <name> -DHX_ONLY_B=<biomes>, with HX_MINIMAL_BUILD):
+// nothing but that biome count's kernels (0: the looped ones) -- a compile of seconds
+#ifdef HX_ONLY_B
+#define HX_ONLY_B_IS(b) (HX_ONLY_B == (b))
+#else
+#define HX_ONLY_B_IS(b) 1
+#endif
+// biome counts from this one on take the looped kernels (default: 9; HECTOR_AMD_LOOPED_BIOMES_FROM=5
+// sends 5-8 there as well -- the tests hold the unrolled and the looped kernels against each other)
+static int hx_looped_from() {   // (read at every launch: a test switches it between two cores)
+  const char *e = getenv("HECTOR_AMD_LOOPED_BIOMES_FROM");
+  const int x = e ? atoi(e) : 9;
+  return x < 5 ? 5 : x;
+}
+
+hipError_t hx_launch_spinup(int B, const HxArgs *d_args, int nmem_launch, int *d_steps,
+                            hipStream_t st) {
+  const int blocks = (nmem_launch + 63) / 64;
+#ifdef HX_W2_ONLY
+  if (B != 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hx_spinup_kernel<1>, dim3(blocks), dim3(64), 0, st, d_args, d_steps);
+  return hipGetLastError();
+#else
+  switch (B >= hx_looped_from() ? HX_BDYN + 1 : B) {
+#if HX_ONLY_B_IS(1)
+    case 1: hipLaunchKernelGGL(hx_spinup_kernel<1>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
+#endif
+#ifndef HX_MINIMAL_BUILD
+    case 2: hipLaunchKernelGGL(hx_spinup_kernel<2>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
+    case 3: hipLaunchKernelGGL(hx_spinup_kernel<3>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
+#endif
+#if HX_ONLY_B_IS(4)
+    case 4: hipLaunchKernelGGL(hx_spinup_kernel<4>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
+#endif
+#if HX_ONLY_B_IS(5)
+    case 5: hipLaunchKernelGGL(hx_spinup_kernel<5>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
+#endif
+#if HX_ONLY_B_IS(6)
+    case 6: hipLaunchKernelGGL(hx_spinup_kernel<6>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
+#endif
+#if HX_ONLY_B_IS(7)
+    case 7: hipLaunchKernelGGL(hx_spinup_kernel<7>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
+#endif
+#if HX_ONLY_B_IS(8)
+    case 8: hipLaunchKernelGGL(hx_spinup_kernel<8>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
+#endif
+#if HX_ONLY_B_IS(0)
+    default:
+      if (B < 1 || B > HX_BDYN) return hipErrorInvalidValue;
+      {
+        const size_t lds = hx_dyn_lds_bytes(B);
+        hx_allow_dynamic_lds(reinterpret_cast<const void *>(&hx_spinup_kernel<HX_DYN>), lds);
+        hipLaunchKernelGGL(hx_spinup_kernel<HX_DYN>, dim3(blocks), dim3(64), lds, st, d_args, d_steps);
+      }
+#else
+    default: return hipErrorInvalidValue;
+#endif
+  }
+  return hipGetLastError();
+#endif
+}
+
+hipError_t hx_launch_alk(const HxArgs *d_args, int nmem_launch, hipStream_t st) {
+  hipLaunchKernelGGL(hx_alk_kernel, dim3((nmem_launch + 63) / 64), dim3(64), 0, st, d_args,
+                     nmem_launch);
+  return hipGetLastError();
+}
+
+// biome counts whose carbon tracking runs on companion wavefronts (tools/prof/tracking_times.py)
+// (8 192 members tracked 1750-2300: one biome 11.4 ms on companions against 29.9 ms inside the
+//  stash, two biomes 23.5 / 32.1 ms, three 70.9 / 60.3 ms, four 215 / 82 ms -- their 147 and 234
+//  fractions a wavefront spill; a block of four 512-register wavefronts owns a CU, so two biomes
+//  take the companions only while every block gets a CU of its own: 32 768 members 49.8 / 41.3 ms)
+#ifndef HX_TRK_COMPANION_MAXB
+#define HX_TRK_COMPANION_MAXB 2
+#endif
+template <int B>
+static void launch_run_b(const HxArgs *d_args, int npad, bool hf, bool kpm, int con,
+                         int iy_from, int iy_to, hipStream_t st, int nb = B, bool two_wave = false,
+                         int cus = 256) {
+  const int blocks = npad / 64;
+  const size_t lds = (B == HX_DYN) ? hx_dyn_lds_bytes(nb) : 0;
+  if constexpr (B == HX_DYN) {
+    for (const void *k : {reinterpret_cast<const void *>(&hx_run_kernel<B, false, false, 0>),
+#ifndef HX_MINIMAL_BUILD
+                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, false, 0>),
+                          reinterpret_cast<const void *>(&hx_run_kernel<B, false, true, 0>),
+                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, true, 0>),
+                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, false, 1>),
+                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, true, 1>),
+                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, false, -1>),
+                          reinterpret_cast<const void *>(&hx_run_kernel<B, false, false, -1>),
+                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, true, -1>),
+                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, false, 2>),
+                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, true, 2>),
+#endif
+                          static_cast<const void *>(nullptr)})
+      if (k)
+      hx_allow_dynamic_lds(k, lds);
+  }
+  // CON = -2 (the plain kernel + the extended one's diagnostics, hx_dev_solver.h) is built for one
+  // to four biomes and for the two-wavefront flavour; other biome counts take CON = -1 for it
+  if (con == -2 && !(B >= 1 && B <= 4)) con = -1;
+  if constexpr (B == 1) {
+    // the flavour built for two resident wavefronts per SIMD (EnsembleCore::run decides)
+    if (two_wave && con == -2) {
+      if (kpm) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, true, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      else if (hf) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, false, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      else hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, false, false, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      return;
+    }
+    if (two_wave && con == 1) {
+      if (kpm) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, true, 1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      else hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, false, 1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      return;
+    }
+    if (two_wave && con == -1) {   // (extended, no NBP constraint: hx_dev_solver.h, hx_nbp)
+      if (kpm) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, true, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      else if (hf) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, false, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      else hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, false, false, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      return;
+    }
+    if (two_wave && !con) {
+      if (hf && kpm) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, true, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      else if (kpm) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, false, true, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      else if (hf) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, false, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      else hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, false, false, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      return;
+    }
+  }
+#ifdef HX_MINIMAL_BUILD  // experiment builds (tools/prof): the plain kernel only
+  (void)hf; (void)kpm; (void)con;
+#ifdef HX_MINIMAL_TRACK  // ... and the carbon-tracking ones
+  if constexpr (B == 1) {
+    if (con == 2 && !getenv("HECTOR_AMD_TRACK_INLINE")) {
+      hipLaunchKernelGGL((hx_run_kernel<1, true, false, 3>), dim3(blocks), dim3(64 * (1 + trk_waves<1>())), lds, st, d_args, iy_from, iy_to);
+      return;
+    }
+  }
+  if (con == 2) {
+    hipLaunchKernelGGL((hx_run_kernel<B, true, false, 2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+    return;
+  }
+#endif
+#ifdef HX_MINIMAL_EXT    // ... and the extended ones without the NBP machinery / second history sum
+  if constexpr (B >= 1 && B <= 4) {
+    if (con == -2) {
+      hipLaunchKernelGGL((hx_run_kernel<B, false, false, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      return;
+    }
+  }
+  if (con == -1) {
+    hipLaunchKernelGGL((hx_run_kernel<B, false, false, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+    return;
+  }
+#endif
+  hipLaunchKernelGGL((hx_run_kernel<B, false, false, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+  return;
+#endif
+#ifndef HX_W2_ONLY   // (HX_W2_ONLY, with HX_MINIMAL_BUILD: nothing but the plain one-biome kernels)
+#ifndef HX_HOST_EMULATION   // (the host build runs a block's threads one after the other)
+  if constexpr (B >= 1 && B <= HX_TRK_COMPANION_MAXB) {  // the maps live on companion wavefronts
+    // (read at every launch, like hx_looped_from(): a test switches it between two cores; the
+    // CU count is the launching core's device's, handed down by EnsembleCore::run)
+    const bool inline_maps = getenv("HECTOR_AMD_TRACK_INLINE") != nullptr;
+    if (con == 2 && !inline_maps && (B == 1 || blocks <= cus)) {
+      constexpr int threads = 64 * (1 + trk_waves<B>());
+      if (kpm) hipLaunchKernelGGL((hx_run_kernel<B, true, true, 3>), dim3(blocks), dim3(threads), lds, st, d_args, iy_from, iy_to);
+      else hipLaunchKernelGGL((hx_run_kernel<B, true, false, 3>), dim3(blocks), dim3(threads), lds, st, d_args, iy_from, iy_to);
+      return;
+    }
+  }
+#endif
+  if constexpr (B <= 4) {  // (HX_DYN = 0 included; hx_launch_run sends 5 and 6 biomes with tracking there)
+  if (con == 2 && kpm) {
+    hipLaunchKernelGGL((hx_run_kernel<B, true, true, 2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+    return;
+  }
+  if (con == 2) {
+    hipLaunchKernelGGL((hx_run_kernel<B, true, false, 2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+    return;
+  }
+  }
+  if constexpr (B >= 1 && B <= 4) {
+    if (con == -2) {   // diagnostics only: no constraint, warming ratio or per-member series anywhere
+      if (kpm) hipLaunchKernelGGL((hx_run_kernel<B, true, true, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      else if (hf) hipLaunchKernelGGL((hx_run_kernel<B, true, false, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      else hipLaunchKernelGGL((hx_run_kernel<B, false, false, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+      return;
+    }
+  }
+  if (con == -1 && kpm)
+    hipLaunchKernelGGL((hx_run_kernel<B, true, true, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+  else if (con == -1 && hf)
+    hipLaunchKernelGGL((hx_run_kernel<B, true, false, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+  else if (con == -1)   // (shared diffusivity, no heat-flux output: without the second history sum)
+    hipLaunchKernelGGL((hx_run_kernel<B, false, false, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+  else if (con && kpm)
+    hipLaunchKernelGGL((hx_run_kernel<B, true, true, 1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+  else if (con)
+    hipLaunchKernelGGL((hx_run_kernel<B, true, false, 1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+  else if (hf && kpm)
+    hipLaunchKernelGGL((hx_run_kernel<B, true, true, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+  else if (hf)
+    hipLaunchKernelGGL((hx_run_kernel<B, true, false, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+  else if (kpm)
+    hipLaunchKernelGGL((hx_run_kernel<B, false, true, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+  else
+    hipLaunchKernelGGL((hx_run_kernel<B, false, false, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
+#endif
+}
+#if HX_HAS_MFMA && ((!defined(HX_W2_ONLY) && !defined(HX_ONLY_B)) || defined(HX_WITH_PAIR))
+#define HX_HAS_PAIR 1
+#include "hx_dev_pair.h"
+#else
+#define HX_HAS_PAIR 0
+#endif
+// the small-ensemble kernel (two wavefronts per 64 members, hx_dev_pair.h): one biome, no
+// constraints, the outputs listed in EnsembleCore::run; kpm: per-member DOECLIM kernel tables
+int hx_pair_available() { return HX_HAS_PAIR; }
+hipError_t hx_launch_run_pair(const HxArgs *d_args, int npad, bool heatflux, bool kpm, int iy_from,
+                              int iy_to, hipStream_t st, bool cons, int nbiome) {
+#if HX_HAS_PAIR
+  const dim3 g(npad / 64), b(128);
+  // (two to four biomes: shared diffusivity, no heat-flux sum -- plain or with scenario-wide constraints;
+  // the host sends every other split ensemble to the run kernels)
+  if (nbiome > 1) {
+    if (heatflux || kpm || nbiome > 4) return hipErrorInvalidValue;
+    if (cons) {
+      if (nbiome == 2) hipLaunchKernelGGL((hx_pair_kernel<false, false, true, 2>), g, b, 0, st, d_args, iy_from, iy_to);
+      else if (nbiome == 3) hipLaunchKernelGGL((hx_pair_kernel<false, false, true, 3>), g, b, 0, st, d_args, iy_from, iy_to);
+      else hipLaunchKernelGGL((hx_pair_kernel<false, false, true, 4>), g, b, 0, st, d_args, iy_from, iy_to);
+      return hipGetLastError();
+    }
+    if (nbiome == 2) hipLaunchKernelGGL((hx_pair_kernel<false, false, false, 2>), g, b, 0, st, d_args, iy_from, iy_to);
+    else if (nbiome == 3) hipLaunchKernelGGL((hx_pair_kernel<false, false, false, 3>), g, b, 0, st, d_args, iy_from, iy_to);
+    else hipLaunchKernelGGL((hx_pair_kernel<false, false, false, 4>), g, b, 0, st, d_args, iy_from, iy_to);
+    return hipGetLastError();
+  }
+  // (with a CO2 / tas / RF_tot / CH4 constraint: the shared-diffusivity instantiations; the host
+  // sends per-member diffusivity with constraints to the run kernel)
+  if (cons && kpm) return hipErrorInvalidValue;
+  if (cons && heatflux) hipLaunchKernelGGL((hx_pair_kernel<false, true, true>), g, b, 0, st, d_args, iy_from, iy_to);
+  else if (cons) hipLaunchKernelGGL((hx_pair_kernel<false, false, true>), g, b, 0, st, d_args, iy_from, iy_to);
+  else if (kpm && heatflux) hipLaunchKernelGGL((hx_pair_kernel<true, true>), g, b, 0, st, d_args, iy_from, iy_to);
+  else if (kpm) hipLaunchKernelGGL((hx_pair_kernel<true, false>), g, b, 0, st, d_args, iy_from, iy_to);
+  else if (heatflux) hipLaunchKernelGGL((hx_pair_kernel<false, true>), g, b, 0, st, d_args, iy_from, iy_to);
+  else hipLaunchKernelGGL((hx_pair_kernel<false, false>), g, b, 0, st, d_args, iy_from, iy_to);
+  return hipGetLastError();
+#else
+  (void)d_args; (void)npad; (void)heatflux; (void)kpm; (void)iy_from; (void)iy_to; (void)st; (void)cons; (void)nbiome;
+  return hipErrorInvalidValue;
+#endif
+}
+hipError_t hx_launch_run(int B, const HxArgs *d_args, int npad, bool heatflux, bool kpm, int con,
+                         int iy_from, int iy_to, hipStream_t st, bool two_wave, int cus, bool partials) {
+  if (partials) {   // the plain one-biome kernel with the statistics epilogue
+#if HX_HAS_RUN_STATS
+    if (B != 1 || heatflux || kpm || con != 0 || two_wave) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((hx_run_kernel_stats<1, true>), dim3(npad / 64), dim3(64), 0, st, d_args, iy_from, iy_to);
+    return hipGetLastError();
+#else
+    return hipErrorInvalidValue;
+#endif
+  }
+#ifdef HX_W2_ONLY
+  if (B != 1) return hipErrorInvalidValue;
+  launch_run_b<1>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, 1, two_wave, cus);
+  return hipGetLastError();
+#else
+  switch (B >= hx_looped_from() ? HX_BDYN + 1 : B) {
+#if HX_ONLY_B_IS(1)
+    case 1: launch_run_b<1>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, 1, two_wave, cus); break;
+#endif
+#ifndef HX_MINIMAL_BUILD
+    case 2: launch_run_b<2>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, 2, false, cus); break;
+    case 3: launch_run_b<3>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break;
+#endif
+#if HX_ONLY_B_IS(4)
+    case 4: launch_run_b<4>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break;
+#endif
+    // five to eight biomes: unrolled like 1-4 (lean park, hx_dev_member.h); carbon tracking on the
+    // looped kernels' 8-column chunks
+#if HX_ONLY_B_IS(5)
+    case 5: if (con != 2) { launch_run_b<5>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break; }
+#if HX_ONLY_B_IS(0)
+            launch_run_b<HX_DYN>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, B); break;
+#else
+            return hipErrorInvalidValue;
+#endif
+#endif
+#if HX_ONLY_B_IS(6)
+    case 6: if (con != 2) { launch_run_b<6>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break; }
+#if HX_ONLY_B_IS(0)
+            launch_run_b<HX_DYN>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, B); break;
+#else
+            return hipErrorInvalidValue;
+#endif
+#endif
+#if HX_ONLY_B_IS(7)
+    case 7: if (con != 2) { launch_run_b<7>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break; }
+#if HX_ONLY_B_IS(0)
+            launch_run_b<HX_DYN>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, B); break;
+#else
+            return hipErrorInvalidValue;
+#endif
+#endif
+#if HX_ONLY_B_IS(8)
+    case 8: if (con != 2) { launch_run_b<8>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break; }
+#if HX_ONLY_B_IS(0)
+            launch_run_b<HX_DYN>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, B); break;
+#else
+            return hipErrorInvalidValue;
+#endif
+#endif
+    default:
+#if HX_ONLY_B_IS(0)
+      if (B < 1 || B > HX_BDYN) return hipErrorInvalidValue;
+      launch_run_b<HX_DYN>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, B);
+#else
+      return hipErrorInvalidValue;
+#endif
+  }
+  return hipGetLastError();
+#endif
+}
+
+int hx_doeclim_block_years() { return HX_DBLK; }
+void hx_fill_chem_table_host(double *t) { hx_fill_chem_table(t); }
+int hx_track_value_rows(int B) { return hx_trk_vrows(B); }
+int hx_doeclim_kernel_pad() { return HX_KPAD; }
+hipError_t hx_launch_unit_csys(int n, const double *Tc, const double *carbon, const double *alk,
+                               double inv_vol, double *out, hipStream_t st) {
+  hipLaunchKernelGGL(hx_unit_csys_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, Tc, carbon, alk,
+                     inv_vol, out);
+  return hipGetLastError();
+}
+// ---- the chip's clocks ahead of a one-shot run ---------------------------------------------------
+// A run kernel launched after an idle gap -- the first run of a fresh core: the host has just spent
+// 10-15 ms uploading and spinning up -- executes at ramping clocks: +6 % at 65 536 members, +11-15 %
+// on the two-wavefront kernel, and ~12 ms of full-chip work right before it removes most of that
+// (tools/prof/prewarm_curve.py, profiles/r06_prewarm_curve.txt).  This kernel is that work: one
+// small wavefront on some of the SIMDs (never all: a kernel that needs a whole SIMD's registers
+// must find one) multiplies and adds until the host raises `stop` (a memset on the core's stream,
+// right ahead of the run kernel) or its own deadline on the constant 100 MHz clock passes --
+// whichever comes first, so it cannot outlive its budget whatever the host does.
+__global__ __launch_bounds__(64) void hx_prewarm_kernel(const int *stop, long long max_ticks, double *sink,
+                                                         const double *mem, unsigned long long n_mem) {
+#ifndef HX_HOST_EMULATION
+  const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
+  double a = 1.0 + 1e-9 * threadIdx.x, b = 0.999999, c = 1e-7, d = a, e = a + c, f = a - c, acc = 0.0;
+  unsigned long long pos = (unsigned long long)blockIdx.x * 64 + threadIdx.x;
+  const unsigned long long stride = (unsigned long long)gridDim.x * 64;
+  for (;;) {
+#pragma unroll
+    for (int k = 0; k < 32; ++k) { a = fma(a, b, c); d = fma(d, b, c); e = fma(e, b, c); f = fma(f, b, c); }
+    if (n_mem) {   // (... and the memory system: a sweep over the arrays the run will write)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { acc += __builtin_nontemporal_load(mem + pos % n_mem); pos += stride; }
+    }
+    if (__builtin_nontemporal_load(stop) != 0) break;
+    if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > max_ticks) break;
+  }
+  if (((a + d) + (e + f)) + acc == 12345.678) sink[blockIdx.x & 1023] = a;   // (keeps the arithmetic)
+#endif
+}
+hipError_t hx_launch_prewarm(const int *d_stop, long long max_ticks, double *d_sink, int waves,
+                             const double *mem, unsigned long long n_mem, hipStream_t st) {
+  hipLaunchKernelGGL(hx_prewarm_kernel, dim3(waves), dim3(64), 0, st, d_stop, max_ticks, d_sink, mem, n_mem);
+  return hipGetLastError();
+}
+hipError_t hx_launch_diag(int kind, const HxDiagArgs &a, double *out, hipStream_t st) {
+  hipLaunchKernelGGL(hx_diag_kernel, dim3((a.npad + 255) / 256, a.ny), dim3(256), 0, st, kind, a, out);
+  return hipGetLastError();
+}
+hipError_t hx_launch_slr(const double *tgav, int npad, int start_year, int iy_to, double *out,
+                         size_t var_stride, hipStream_t st) {
+  hipLaunchKernelGGL(hx_slr_kernel, dim3((npad + 63) / 64), dim3(64), 0, st, tgav, npad,
+                     start_year, iy_to, out, var_stride);
+  return hipGetLastError();
+}
+hipError_t hx_launch_broadcast(double *table, int nrows, int npad, hipStream_t st) {
+  hipLaunchKernelGGL(hx_broadcast_rows_kernel, dim3((npad + 255) / 256), dim3(256), 0, st,
+                     table, nrows, npad);
+  return hipGetLastError();
+}
+hipError_t hx_launch_broadcast_u32(unsigned *v, int npad, hipStream_t st) {
+  hipLaunchKernelGGL(hx_broadcast_u32_kernel, dim3((npad + 255) / 256), dim3(256), 0, st, v, npad);
+  return hipGetLastError();
+}
+hipError_t hx_launch_gas(const double *par, const double *ser, const double *h0, int nh, int ns,
+                         int npad, double *n2o_out, double *rf_other_out, hipStream_t st) {
+  if (nh > 40) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hx_gas_kernel, dim3((npad + 63) / 64), dim3(64), 0, st, par, ser, h0, nh, ns,
+                     npad, n2o_out, rf_other_out);
+  return hipGetLastError();
+}
+hipError_t hx_launch_or_flags(unsigned *status, const double *flag_row, int npad, hipStream_t st) {
+  hipLaunchKernelGGL(hx_or_flags_kernel, dim3((npad + 255) / 256), dim3(256), 0, st, status,
+                     flag_row, npad);
+  return hipGetLastError();
+}
+hipError_t hx_launch_doeclim_kernel(const double *diff_row, double *ker, int ns, int count,
+                                    int stride, hipStream_t st) {
+  hipLaunchKernelGGL(hx_doeclim_table_kernel, dim3((count + 255) / 256, ns), dim3(256), 0, st,
+                     diff_row, ker, ns, count, stride);
+  return hipGetLastError();
+}
+hipError_t hx_launch_derive(const double *params, double *derived, const double *ker,
+                            int ker_per_member, int ns, int nbiome, int npad, hipStream_t st) {
+  hipLaunchKernelGGL(hx_derive_kernel, dim3((npad + 255) / 256), dim3(256), 0, st, params,
+                     derived, ker, ker_per_member, ns, nbiome, npad);
+  return hipGetLastError();
+}
+hipError_t hx_launch_gather(const double *src, const int *lane_of_member, double *dst, int n,
+                            int npad, int nyears, hipStream_t st) {
+  hipLaunchKernelGGL(hx_gather_kernel, dim3((n + 255) / 256, nyears), dim3(256), 0, st, src,
+                     lane_of_member, dst, n, npad, nyears);
+  return hipGetLastError();
+}
+hipError_t hx_launch_combine_stats(const double *slots, int world, int rows, double *out,
+                                   hipStream_t st) {
+  hipLaunchKernelGGL(hx_combine_stats_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, slots,
+                     world, rows, out);
+  return hipGetLastError();
+}
+hipError_t hx_launch_combine_partials(const double *wpart, int nvar, const int *var,
+                                      const double *const *rows, double *const *out, int n, int npad,
+                                      int ns, int iy0, int nyears, int skip, hipStream_t st) {
+  if (nvar < 1 || nvar > 2 || nyears < 1) return hipErrorInvalidValue;
+  const int k1 = nvar - 1;
+  hipLaunchKernelGGL(hx_combine_partials_kernel, dim3(nyears, nvar), dim3(256), 0, st, wpart, var[0], var[k1],
+                     rows[0], rows[k1], out[0], out[k1], n, npad, ns, iy0, skip);
+  return hipGetLastError();
+}
+bool hx_run_writes_partials(int B, bool heatflux, bool kpm, int con, bool two_wave) {
+  return HX_HAS_RUN_STATS && B == 1 && !two_wave && !heatflux && !kpm && con == 0;
+}
+hipError_t hx_launch_stats(const double *var, int n, int npad, int iy0, int nyears,
+                           double *stats, hipStream_t st) {
+  hipLaunchKernelGGL(hx_stats_kernel, dim3(nyears), dim3(256), 0, st, var, n, npad, iy0, stats);
+  return hipGetLastError();
+}
+}
+#else  // HX_RUN_BODY_PASS
+// ===========================================================================
+// The body of the year-loop kernels, as text: included inside hx_run_kernel<B, HF, KERPM, CON>
+// (WP = false) and inside hx_run_kernel_stats (the plain one-biome kernel with the statistics
+// epilogue, WP = true), so that the first stays what it was, instruction for instruction.  Expects
+// B, HF, KERPM, CON, WP as constants of the enclosing template and the kernel's parameters args,
+// iy_from, iy_to.
+// ===========================================================================
   static_assert(CON != 3 || (B >= 1 && B <= 4), "tracking companions: the unrolled kernels");
   static_assert(!hx_w2<B>() || CON <= 1, "two-wavefront flavour: the plain and the extended kernel");
   // LDS: the SSTs produced inside this launch's block of years (<= HX_DBLK), per lane
@@ -1665,812 +2650,24 @@ void hx_run_kernel(const HxArgs *__restrict__ args, int iy_from, int iy_to) {
   // (a dopri5 pass of the wavefront costs ~2.7k cycles, a stash ~3.4k: tools/prof/phase_clock.py)
   if (args->buf.cost) HX_GD(args->buf.cost)[mem] += (double)(4 * cost_steps + 5 * cost_stash);
   hx_wave_stamp(args->buf, blockIdx.x, 1, lane);
+#ifndef HX_HOST_EMULATION
+  if constexpr (WP) {   // s_tblk is dead from here on
+    // (The member index made opaque, lane and wavefront taken from it: whatever the epilogue
+    //  addresses is formed here, behind the loop.  With the kernel's own `lane` and blockIdx.x an
+    //  address pair stayed alive across the year loop: 334 -> 336 registers, two more v_accvgpr
+    //  moves a year.  The launch's iy_from and iy_to are not used for the same reason, see above.)
+    int emem = mem;
+    asm volatile("" : "+v"(emem));
+    const int ewave = __builtin_amdgcn_readfirstlane(emem >> 6);
+    if (args->buf.wpart && ewave >= args->buf.wpart_skip) {
+      hx_wave_partials(args->buf, s_tblk, args->kc.ns, emem, ewave);
+      hx_wave_stamp_epilogue(args->buf, ewave, emem & 63);
+    }
+  }
+#endif
 #ifdef HX_PHASE_CLOCK
   if (args->buf.out[HXO_TGAV])
     for (int k = 0; k < HX_NCLK; ++k)
       HX_GD(args->buf.out[HXO_TGAV])[(size_t)k * args->buf.npad + mem] = (double)hx_s_clk[k];
 #endif
-}
-
-// ===========================================================================
-// Broadcast member 0's state/outputs row to every member (shared spinup).
-// ===========================================================================
-__global__ void hx_broadcast_rows_kernel(double *table, int nrows, int npad) {
-  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
-  if (mem >= npad || mem == 0) return;
-  for (int r = 0; r < nrows; ++r) table[(size_t)r * npad + mem] = table[(size_t)r * npad];
-}
-__global__ void hx_broadcast_u32_kernel(unsigned *v, int npad) {
-  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
-  if (mem >= npad || mem == 0) return;
-  v[mem] = v[0];
-}
-// status |= the member's own derive-time flags (HXD_FLAG row), after the spinup
-__global__ void hx_or_flags_kernel(unsigned *status, const double *flag_row, int npad) {
-  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
-  if (mem >= npad) return;
-  status[mem] |= (unsigned)flag_row[mem];
-}
-
-// ===========================================================================
-// N2OComponent::run (src/n2o_component.cpp:152-191) and HalocarbonComponent::run
-// (src/halocarbon_component.cpp:181-229) per member, for ensembles whose N2O or halocarbon
-// parameters differ between members (otherwise the host runs them once while it builds the
-// per-year table).  Neither depends on the carbon-climate state, so they run ahead of the year
-// loop, one member per thread: N2O[t] and the year's halocarbon + albedo + misc forcing.
-//   par [3 + 3 nh][npad]: N0, TN2O0, UC_N2O, then tau, rho, delta of each gas
-//   ser [4 + 2 nh][ns]:   N2O emissions (anthropogenic + natural), N2O constraint (NaN = none),
-//                         RF_albedo, RF_misc, then per gas the year's concentration increment
-//                         per unit lifetime (emissions / molar mass / 0.18) and its constraint
-//   h0 [nh]: preindustrial concentrations.  Gases in the order their forcings are summed.
-// ===========================================================================
-__global__ __launch_bounds__(64) void hx_gas_kernel(const double *par, const double *ser,
-                                                    const double *h0, int nh, int ns, int npad,
-                                                    double *n2o_out, double *rf_other_out) {
-  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
-  if (mem >= npad) return;
-  const size_t np = (size_t)npad;
-  const double N0 = par[mem], TN2O0 = par[np + mem], UC = par[2 * np + mem];
-  const double *em = ser, *ncon = ser + ns, *alb = ser + 2 * (size_t)ns, *misc = ser + 3 * (size_t)ns;
-  constexpr int MAXH = 40;
-  double conc[MAXH], expfac[MAXH];
-  for (int h = 0; h < nh && h < MAXH; ++h) {
-    conc[h] = h0[h];
-    expfac[h] = exp(-(1 / par[(size_t)(3 + 3 * h) * np + mem]));
-  }
-  const double N0f = isnan(ncon[0]) ? N0 : ncon[0];  // n2o_component.cpp:137-145
-  double n2o = N0f;
-  n2o_out[mem] = n2o;
-  rf_other_out[mem] = (0.0 + alb[0]) + misc[0];
-  for (int iy = 1; iy < ns; ++iy) {
-    const double tau_n = TN2O0 * pow(n2o / N0f, -0.05);
-    n2o = n2o + (em[iy] / UC - n2o / tau_n);
-    if (!isnan(ncon[iy])) n2o = ncon[iy];
-    double rf_h = 0.0;
-    for (int h = 0; h < nh && h < MAXH; ++h) {
-      const double tau = par[(size_t)(3 + 3 * h) * np + mem], rho = par[(size_t)(4 + 3 * h) * np + mem],
-                   delta = par[(size_t)(5 + 3 * h) * np + mem];
-      const double dconc = ser[(size_t)(4 + 2 * h) * ns + iy], hc = ser[(size_t)(5 + 2 * h) * ns + iy];
-      conc[h] = conc[h] * expfac[h] + dconc * tau * (1.0 - expfac[h]);
-      if (!isnan(hc)) conc[h] = hc;
-      const double rf_un = rho * conc[h];
-      rf_h = rf_h + (rf_un + delta * rf_un);
-    }
-    n2o_out[(size_t)iy * np + mem] = n2o;
-    rf_other_out[(size_t)iy * np + mem] = (rf_h + alb[iy]) + misc[iy];
-  }
-}
-
-// ===========================================================================
-// Output gather: members are assigned to lanes in a behaviour-sorted order (see
-// EnsembleCore::upload_params); results go back to the caller in member order.
-// dst[y][member] = src[y][lane_of_member[member]]
-// ===========================================================================
-__global__ __launch_bounds__(256) void hx_gather_kernel(const double *src, const int *lane_of_member,
-                                                        double *dst, int n, int npad, int nyears) {
-  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
-  const int y = blockIdx.y;
-  if (mem >= n || y >= nyears) return;
-  dst[(size_t)y * n + mem] = src[(size_t)y * npad + lane_of_member[mem]];
-}
-
-// ===========================================================================
-// Per-year ensemble statistics of one output variable over members [0, n):
-// count, sum, sum of squares, min, max -> stats[year][5].  One workgroup per
-// year; wave-level DPP/shuffle reduction, then one LDS hop across the waves.
-// ===========================================================================
-__global__ __launch_bounds__(256) void hx_stats_kernel(const double *var, int n, int npad,
-                                                       int iy0, double *stats) {
-  const int iy = iy0 + blockIdx.x;
-  const double *row = var + (size_t)iy * npad;
-  // pure streaming: four 16-byte loads in flight per lane (rows are 512-byte aligned: npad is a
-  // multiple of 64), four independent accumulator sets
-  double sa[4] = {0, 0, 0, 0}, qa[4] = {0, 0, 0, 0};
-  double mn = INFINITY, mx = -INFINITY;
-  const int n2 = n >> 1;                       // number of double2 elements
-  const double2 *row2 = reinterpret_cast<const double2 *>(row);
-  int i = threadIdx.x;
-  for (; i + 3 * (int)blockDim.x < n2; i += 4 * blockDim.x) {
-    double2 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = row2[i + k * (int)blockDim.x];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      sa[k] += v[k].x + v[k].y;
-      qa[k] += v[k].x * v[k].x + v[k].y * v[k].y;
-      mn = fmin(mn, fmin(v[k].x, v[k].y));
-      mx = fmax(mx, fmax(v[k].x, v[k].y));
-    }
-  }
-  for (; i < n2; i += blockDim.x) {
-    const double2 v = row2[i];
-    sa[0] += v.x + v.y; qa[0] += v.x * v.x + v.y * v.y;
-    mn = fmin(mn, fmin(v.x, v.y)); mx = fmax(mx, fmax(v.x, v.y));
-  }
-  if ((n & 1) && threadIdx.x == 0) {
-    const double v = row[n - 1];
-    sa[0] += v; qa[0] += v * v; mn = fmin(mn, v); mx = fmax(mx, v);
-  }
-  double s = (sa[0] + sa[1]) + (sa[2] + sa[3]), s2 = (qa[0] + qa[1]) + (qa[2] + qa[3]);
-  double cnt = (threadIdx.x == 0) ? (double)n : 0.0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    s += __shfl_down(s, off, 64); s2 += __shfl_down(s2, off, 64);
-    cnt += __shfl_down(cnt, off, 64);
-    mn = fmin(mn, __shfl_down(mn, off, 64)); mx = fmax(mx, __shfl_down(mx, off, 64));
-  }
-  __shared__ double red[4][5];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[w][0] = cnt; red[w][1] = s; red[w][2] = s2;
-                                 red[w][3] = mn; red[w][4] = mx; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < 4; ++k) { red[0][0] += red[k][0]; red[0][1] += red[k][1];
-      red[0][2] += red[k][2]; red[0][3] = fmin(red[0][3], red[k][3]);
-      red[0][4] = fmax(red[0][4], red[k][4]); }
-    double *o = stats + (size_t)blockIdx.x * 5;
-    o[0] = red[0][0]; o[1] = red[0][1]; o[2] = red[0][2]; o[3] = red[0][3]; o[4] = red[0][4];
-  }
-}
-
-// ===========================================================================
-// The last step of the multi-GPU statistics (hx_fleet.cpp): slots[rank][row][5] holds every
-// rank's {count, sum, sum of squares, min, max} of a (variable, year) row, gathered by ONE
-// ncclAllGather; every rank folds them in rank order, so the result is bit-identical everywhere.
-// ===========================================================================
-__global__ __launch_bounds__(256) void hx_combine_stats_kernel(const double *slots, int world,
-                                                               int rows, double *out) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= rows) return;
-  const double *p = slots + (size_t)r * 5;
-  double cnt = p[0], s = p[1], s2 = p[2], mn = p[3], mx = p[4];
-  for (int k = 1; k < world; ++k) {
-    p += (size_t)rows * 5;
-    cnt += p[0]; s += p[1]; s2 += p[2]; mn = fmin(mn, p[3]); mx = fmax(mx, p[4]);
-  }
-  double *o = out + (size_t)r * 5;
-  o[0] = cnt; o[1] = s; o[2] = s2; o[3] = mn; o[4] = mx;
-}
-
-// ===========================================================================
-// DOECLIM convolution kernel table Ker[i] (temperature_component.cpp:303-371)
-// for `count` diffusivities: ker[i * stride + mem].  count = 1, stride = 1 when
-// every member shares the diffusivity.
-// ===========================================================================
-__global__ __launch_bounds__(256) void hx_doeclim_table_kernel(const double *diff_row,
-                                                               double *ker, int ns, int count,
-                                                               int stride) {
-  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
-  const int i = blockIdx.y;
-  if (mem >= count || i >= ns) return;
-  const double keff = (D_secs / 10000) * diff_row[mem];
-  const double tb = (D_zbot * D_zbot) / keff;  // taubot / dt, dt = 1
-  const double sq2 = sqrt(2.0), sqpt = sqrt(M_PI * tb);
-  double KT0, KTA1, KTB1, KTA2, KTB2, KTA3, KTB3;
-  if (i == ns - 1) {
-    KT0 = 4.0 - 2.0 * sq2;
-    KTA1 = -8.0 * exp(-tb) + 4.0 * sq2 * exp(-0.5 * tb);
-    KTB1 = 4.0 * sqpt * (1.0 + erf(sqrt(0.5 * tb)) - 2.0 * erf(sqrt(tb)));
-    KTA2 = 8.0 * exp(-4.0 * tb) - 4.0 * sq2 * exp(-2.0 * tb);
-    KTB2 = -8.0 * sqpt * (1.0 + erf(sqrt(2.0 * tb)) - 2.0 * erf(2.0 * sqrt(tb)));
-    KTA3 = -8.0 * exp(-9.0 * tb) + 4.0 * sq2 * exp(-4.5 * tb);
-    KTB3 = 12.0 * sqpt * (1.0 + erf(sqrt(4.5 * tb)) - 2.0 * erf(3.0 * sqrt(tb)));
-  } else {
-    const double a = (double)(ns - i), b = (double)(ns + 1 - i), c = (double)(ns - 1 - i);
-    const double ra = sqrt(a), rb = sqrt(b), rc = sqrt(c);
-    const double ua = sqrt(tb / a), ub = sqrt(tb / b), uc = sqrt(tb / c);
-    KT0 = 4.0 * ra - 2.0 * rb - 2.0 * rc;
-    KTA1 = -8.0 * ra * exp(-tb / a) + 4.0 * rb * exp(-tb / b) + 4.0 * rc * exp(-tb / c);
-    KTB1 = 4.0 * sqpt * (erf(uc) + erf(ub) - 2.0 * erf(ua));
-    KTA2 = 8.0 * ra * exp(-4.0 * tb / a) - 4.0 * rb * exp(-4.0 * tb / b) -
-           4.0 * rc * exp(-4.0 * tb / c);
-    KTB2 = -8.0 * sqpt * (erf(2.0 * uc) + erf(2.0 * ub) - 2.0 * erf(2.0 * ua));
-    KTA3 = -8.0 * ra * exp(-9.0 * tb / a) + 4.0 * rb * exp(-9.0 * tb / b) +
-           4.0 * rc * exp(-9.0 * tb / c);
-    KTB3 = 12.0 * sqpt * (erf(3.0 * uc) + erf(3.0 * ub) - 2.0 * erf(3.0 * ua));
-  }
-  ker[(size_t)(i + HX_KPAD) * stride + mem] = KT0 + KTA1 + KTB1 + KTA2 + KTB2 + KTA3 + KTB3;
-}
-
-// ===========================================================================
-// oceanbox::chem_equilibrate for both surface boxes (src/oceanbox.cpp:382-445,
-// ocean_component.cpp:392-400): the first post-spinup ocean.run() turns the chemistry on and
-// tunes each box's alkalinity so that it reproduces the spinup flux at the spun-up CO2.  Its
-// inputs are all spinup results (box carbon, atmosphere, SST = 0), so it runs once, directly
-// after the spinup kernel, and the run kernel finds the alkalinities in the state table.
-// ===========================================================================
-__global__ __launch_bounds__(64) void hx_alk_kernel(const HxArgs *__restrict__ args, int nmem) {
-#ifndef HX_HOST_EMULATION
-  __builtin_amdgcn_s_setprio(3);   // (see hx_spinup_kernel)
-#endif
-  const int mem = blockIdx.x * 64 + threadIdx.x;
-  if (mem >= nmem) return;
-  const HxBuffers &buf = args->buf;
-  const double cHL = lds_(buf, HXS_C_HL, mem), cLL = lds_(buf, HXS_C_LL, mem);
-  const double co2 = lds_(buf, HXS_ATMOS, mem) * PGC2PPM;
-  const double sst = lds_(buf, HXS_SST, mem);
-  unsigned status = HX_GU(buf.status)[mem];
-  ChemK kH, kL;
-  chem_constants2(sst + 18 + (-16.4), sst + 18 + 2.9, kH, kL);
-  double hH = 0, hL = 0;
-  const double alkH = equilibrate_alk(kH, cHL, 1.0 / O_vHL, O_AsHL, co2, 1.000, hH, status);
-  const double alkL = equilibrate_alk(kL, cLL, 1.0 / O_vLL, O_AsLL, co2, -1.000, hL, status);
-  sts_(buf, HXS_ALK_HL, mem, alkH); sts_(buf, HXS_ALK_LL, mem, alkL);
-  sts_(buf, HXS_H_HL, mem, hH); sts_(buf, HXS_H_LL, mem, hL);
-  HX_GU(buf.status)[mem] = status;
-}
-
-// ===========================================================================
-// Diagnostics derived from recorded outputs, one (year, member) element per thread.
-// The reference keeps them as members of the carbonate-chemistry object of the last solve
-// (ocean_csys.cpp:328-366) or recomputes them on request (ocean_component.cpp:440-512);
-// here they follow from what the run recorded:
-//   [H+] = 10^-pH and pCO2 of the last solve, the box temperature Tbox = SST(year-1) + 18 +
-//   deltaT (oceanbox.cpp:97-99, 309-323), and the year-end box carbon:
-//   CO2* = pCO2 Kh, CO3 = CO2* K1 K2 / [H+]^2  (identical to DIC / (1 + h/K2 + h^2/(K1 K2)))
-// ===========================================================================
-__device__ __forceinline__ double diag_rf(int kind, const HxDiagArgs &a, int iy, int mem) {
-  hx_ccd sh = HX_CCD(a.shared) + (size_t)iy * HXSH_STRIDE;
-  const size_t o = (size_t)iy * a.npad + mem;
-  const double a2 = -3.4197e-4, b2 = 2.5455e-4, c2 = -2.4357e-4, d2 = 0.12173;
-  const double a3 = -8.9603e-5, b3 = -1.2462e-4, d3 = 0.045194;
-  double sqN = sh[HXSH_SQRT_N2O], sqN0 = a.sqrtN0;
-  if (a.n2o_members) { sqN = sqrt(a.n2o_members[o]); sqN0 = sqrt(a.n2o_members[mem]); }
-  if (kind == HXG_RF_O3) return 0.042 * a.o3[o];
-  const double ch4 = a.ch4[o], sqM = sqrt(ch4);
-  if (kind == HXG_RF_H2O) return 0.0485 * ((ch4 - a.M0f) / (1831 - a.M0f));
-  if (kind == HXG_RF_CH4) {
-    const double sarf = (a3 * sqM + b3 * sqN + d3) * (sqM - a.sqrtM0);
-    const double delta = a.eff_members ? a.eff_members[(size_t)a.npad + mem] : a.delta_ch4;
-    return (delta * sarf) + sarf;
-  }
-  const double sqC = sqrt(a.co2[o]);
-  const double sarf = (a2 * sqC + b2 * sqN + c2 * sqM + d2) * (sqN - sqN0);
-  const double delta = a.eff_members ? a.eff_members[2 * (size_t)a.npad + mem] : a.delta_n2o;
-  return (delta * sarf) + sarf;
-}
-
-__global__ __launch_bounds__(256) void hx_diag_kernel(int kind, HxDiagArgs a, double *out) {
-  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
-  const int iy = a.iy0 + blockIdx.y;
-  if (mem >= a.npad) return;
-  const size_t o = (size_t)iy * a.npad + mem;
-  double r = 0.0;
-  if (kind >= HXG_RF_N2O) {
-    // forcings are reported relative to the base year (forcing_component.cpp:507-527)
-    if (iy >= a.base_idx) r = diag_rf(kind, a, iy, mem) - diag_rf(kind, a, a.base_idx, mem);
-  } else if (kind == HXG_OCEAN_TAS) {
-    const double lo = a.lo_ratio[mem];
-    r = (lo != 0) ? a.tgav[o] / ((lo * D_flnd) + (1 - D_flnd)) : D_bsi * a.sst[o];
-  } else {
-    const double sst_prev = (iy >= 1) ? a.sst[o - a.npad] : 0.0;
-    const double Tc = sst_prev + 18 + a.deltaT;
-    // convertToDIC  ocean_csys.cpp:403-408 (umol/kg)
-    const double dic = ((((a.carbon ? a.carbon[o] : 0.0) * 1e15) * (1.0 / 12.01)) * (1.0 / 1027.0) *
-                        a.inv_vol) * 1e6;
-    if (kind == HXG_TEMP) r = Tc;
-    else if (kind == HXG_DIC) r = dic;
-    else {
-      ChemK k;
-      chem_constants(Tc, k);
-      const double h = exp10(-a.ph[o]);
-      const double co2st = a.pco2[o] * k.Kh;            // umol/kg
-      const double co3 = co2st * ((k.K1 * k.K2) / (h * h));  // umol/kg
-      if (kind == HXG_CO3) r = co3;
-      else if (kind == HXG_REVELLE) r = dic / co3;        // oceanbox.cpp:278-292
-      else {
-        const double S = O_S, Tk = Tc + 273.15, sqrtS = 5.873670062235365,
-                     S15 = 202.64161714712009;
-        double t1, t2, t3;
-        if (kind == HXG_OMEGA_CA) {  // ocean_csys.cpp:266-274
-          t1 = -171.9065 - 0.077993 * Tk + 2839.319 / Tk + 71.595 * log10(Tk);
-          t2 = +(-0.77712 + 0.0028426 * Tk + 178.34 / Tk) * sqrtS;
-          t3 = -0.07711 * S + 0.0041249 * S15;
-        } else {
-          t1 = -171.945 - 0.077993 * Tk + 2903.293 / Tk + 71.595 * log10(Tk);
-          t2 = +(-0.068393 + 0.0017276 * Tk + 88.135 / Tk) * sqrtS;
-          t3 = -0.10018 * S + 0.0059415 * S15;
-        }
-        const double Ksp = exp10(t1 + t2 + t3);
-        const double calcium = 0.02128 / 40.087 * (S / 1.80655);
-        r = (((co3 * 1e-6) * calcium) / Ksp);
-      }
-    }
-  }
-  out[(size_t)blockIdx.y * a.npad + mem] = r;
-}
-
-// slrComponent (slr_component.cpp:116-232, Vermeer & Rahmstorf 2009): sea-level rise from the
-// global tas series of each member; one thread walks one member's years.  Nothing exists
-// before the reference period 1951-1980 has been run; dT/dt is the derivative of the series as
-// known when the date was computed (h_interpolator.cpp:132-167).  out: 4 arrays [ns][npad]
-// (slr, sl_rc, slr_no_ice, sl_rc_no_ice), zero where the reference has no value.
-__global__ __launch_bounds__(64) void hx_slr_kernel(const double *tgav, int npad, int start_year,
-                                                    int iy_to, double *out, size_t var_stride) {
-  const int mem = blockIdx.x * blockDim.x + threadIdx.x;
-  if (mem >= npad) return;
-  const int lo = 1951 - start_year, hi = 1980 - start_year, first = 1;
-  if (lo < first || iy_to < hi) return;
-  auto TG = [&](int iy) { return tgav[(size_t)iy * npad + mem]; };
-  double sum = 0.0;
-  for (int i = lo; i <= hi; ++i) sum += TG(i);
-  const double ref = sum / (hi - lo + 1);
-  double slr = 0.0, slr_ni = 0.0;
-  for (int iy = first; iy <= iy_to; ++iy) {
-    const int last = (iy <= hi) ? hi : iy;  // the series' last date when this date was computed
-    double dTdt = 0.0;
-    if (last - first + 1 > 2) {
-      if (iy == first) dTdt = (TG(first + 1) - TG(first)) / 1.0;
-      else if (iy == last) dTdt = (TG(iy) - TG(iy - 1)) / 1.0;
-      else dTdt = (((TG(iy) - TG(iy - 1)) / 1.0) + ((TG(iy + 1) - TG(iy)) / 1.0)) / 2.0;
-    }
-    const double T = TG(iy) - ref;
-    const double dHdt = 0.56 * (T - (-0.41)) + (-4.9) * dTdt;
-    const double dHdt_ni = 0.08 * (T - (-0.375)) + 2.5 * dTdt;
-    slr = slr + dHdt;
-    slr_ni = slr_ni + dHdt_ni;
-    const size_t o = (size_t)iy * npad + mem;
-    out[o] = slr;
-    out[var_stride + o] = dHdt;
-    out[2 * var_stride + o] = slr_ni;
-    out[3 * var_stride + o] = dHdt_ni;
-  }
-}
-
-// Unit vector of the carbonate chemistry (a7): n independent (T, carbon, alkalinity) triples
-// through chem_constants + chem_solve from a cold start (the Fujiwara bound is not needed: the
-// bracketed Newton accepts any positive start), one per thread.  Test hook for parity at the
-// function level; the run kernel uses the same two functions.
-__global__ void hx_unit_csys_kernel(int n, const double *Tc, const double *carbon,
-                                    const double *alk, double inv_vol, double *out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  ChemK k;
-  chem_constants(Tc[i], k);
-  double h = 1e-8;
-  unsigned status = 0;
-  const double pco2 = chem_solve(k, carbon[i], inv_vol, alk[i], h, status);
-  out[4 * i + 0] = pco2;
-  out[4 * i + 1] = -log10(h);
-  out[4 * i + 2] = k.Tr;
-  out[4 * i + 3] = (double)status;
-}
-
-// ---------------------------------------------------------------------------
-// host-callable launchers (the only symbols the host runtime uses)
-// ---------------------------------------------------------------------------
-extern "C++" {
-// dynamic LDS of a looped kernel for nb biomes (hx_dev_member.h: hx_npark_dyn)
-static size_t hx_dyn_lds_bytes(int nb) { return (size_t)hx_npark_dyn(nb) * 64 * sizeof(double); }
-static void hx_allow_dynamic_lds(const void *kernel, size_t bytes) {
-#if HX_HAS_MFMA   // (the host-emulation build has no such attribute)
-  if (bytes > 64 * 1024)   // beyond the default window a kernel has to be told
-    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-#else
-  (void)kernel; (void)bytes;
-#endif
-}
-
-// experiment builds (tools/prof/build_variant.sh <name> -DHX_ONLY_B=<biomes>, with HX_MINIMAL_BUILD):
-// nothing but that biome count's kernels (0: the looped ones) -- a compile of seconds
-#ifdef HX_ONLY_B
-#define HX_ONLY_B_IS(b) (HX_ONLY_B == (b))
-#else
-#define HX_ONLY_B_IS(b) 1
-#endif
-// biome counts from this one on take the looped kernels (default: 9; HECTOR_AMD_LOOPED_BIOMES_FROM=5
-// sends 5-8 there as well -- the tests hold the unrolled and the looped kernels against each other)
-static int hx_looped_from() {   // (read at every launch: a test switches it between two cores)
-  const char *e = getenv("HECTOR_AMD_LOOPED_BIOMES_FROM");
-  const int x = e ? atoi(e) : 9;
-  return x < 5 ? 5 : x;
-}
-
-hipError_t hx_launch_spinup(int B, const HxArgs *d_args, int nmem_launch, int *d_steps,
-                            hipStream_t st) {
-  const int blocks = (nmem_launch + 63) / 64;
-#ifdef HX_W2_ONLY
-  if (B != 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(hx_spinup_kernel<1>, dim3(blocks), dim3(64), 0, st, d_args, d_steps);
-  return hipGetLastError();
-#else
-  switch (B >= hx_looped_from() ? HX_BDYN + 1 : B) {
-#if HX_ONLY_B_IS(1)
-    case 1: hipLaunchKernelGGL(hx_spinup_kernel<1>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
-#endif
-#ifndef HX_MINIMAL_BUILD
-    case 2: hipLaunchKernelGGL(hx_spinup_kernel<2>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
-    case 3: hipLaunchKernelGGL(hx_spinup_kernel<3>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
-#endif
-#if HX_ONLY_B_IS(4)
-    case 4: hipLaunchKernelGGL(hx_spinup_kernel<4>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
-#endif
-#if HX_ONLY_B_IS(5)
-    case 5: hipLaunchKernelGGL(hx_spinup_kernel<5>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
-#endif
-#if HX_ONLY_B_IS(6)
-    case 6: hipLaunchKernelGGL(hx_spinup_kernel<6>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
-#endif
-#if HX_ONLY_B_IS(7)
-    case 7: hipLaunchKernelGGL(hx_spinup_kernel<7>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
-#endif
-#if HX_ONLY_B_IS(8)
-    case 8: hipLaunchKernelGGL(hx_spinup_kernel<8>, dim3(blocks), dim3(64), 0, st, d_args, d_steps); break;
-#endif
-#if HX_ONLY_B_IS(0)
-    default:
-      if (B < 1 || B > HX_BDYN) return hipErrorInvalidValue;
-      {
-        const size_t lds = hx_dyn_lds_bytes(B);
-        hx_allow_dynamic_lds(reinterpret_cast<const void *>(&hx_spinup_kernel<HX_DYN>), lds);
-        hipLaunchKernelGGL(hx_spinup_kernel<HX_DYN>, dim3(blocks), dim3(64), lds, st, d_args, d_steps);
-      }
-#else
-    default: return hipErrorInvalidValue;
-#endif
-  }
-  return hipGetLastError();
-#endif
-}
-
-hipError_t hx_launch_alk(const HxArgs *d_args, int nmem_launch, hipStream_t st) {
-  hipLaunchKernelGGL(hx_alk_kernel, dim3((nmem_launch + 63) / 64), dim3(64), 0, st, d_args,
-                     nmem_launch);
-  return hipGetLastError();
-}
-
-// biome counts whose carbon tracking runs on companion wavefronts (tools/prof/tracking_times.py)
-// (8 192 members tracked 1750-2300: one biome 11.4 ms on companions against 29.9 ms inside the
-//  stash, two biomes 23.5 / 32.1 ms, three 70.9 / 60.3 ms, four 215 / 82 ms -- their 147 and 234
-//  fractions a wavefront spill; a block of four 512-register wavefronts owns a CU, so two biomes
-//  take the companions only while every block gets a CU of its own: 32 768 members 49.8 / 41.3 ms)
-#ifndef HX_TRK_COMPANION_MAXB
-#define HX_TRK_COMPANION_MAXB 2
-#endif
-template <int B>
-static void launch_run_b(const HxArgs *d_args, int npad, bool hf, bool kpm, int con,
-                         int iy_from, int iy_to, hipStream_t st, int nb = B, bool two_wave = false,
-                         int cus = 256) {
-  const int blocks = npad / 64;
-  const size_t lds = (B == HX_DYN) ? hx_dyn_lds_bytes(nb) : 0;
-  if constexpr (B == HX_DYN) {
-    for (const void *k : {reinterpret_cast<const void *>(&hx_run_kernel<B, false, false, 0>),
-#ifndef HX_MINIMAL_BUILD
-                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, false, 0>),
-                          reinterpret_cast<const void *>(&hx_run_kernel<B, false, true, 0>),
-                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, true, 0>),
-                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, false, 1>),
-                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, true, 1>),
-                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, false, -1>),
-                          reinterpret_cast<const void *>(&hx_run_kernel<B, false, false, -1>),
-                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, true, -1>),
-                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, false, 2>),
-                          reinterpret_cast<const void *>(&hx_run_kernel<B, true, true, 2>),
-#endif
-                          static_cast<const void *>(nullptr)})
-      if (k)
-      hx_allow_dynamic_lds(k, lds);
-  }
-  // CON = -2 (the plain kernel + the extended one's diagnostics, hx_dev_solver.h) is built for one
-  // to four biomes and for the two-wavefront flavour; other biome counts take CON = -1 for it
-  if (con == -2 && !(B >= 1 && B <= 4)) con = -1;
-  if constexpr (B == 1) {
-    // the flavour built for two resident wavefronts per SIMD (EnsembleCore::run decides)
-    if (two_wave && con == -2) {
-      if (kpm) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, true, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      else if (hf) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, false, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      else hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, false, false, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      return;
-    }
-    if (two_wave && con == 1) {
-      if (kpm) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, true, 1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      else hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, false, 1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      return;
-    }
-    if (two_wave && con == -1) {   // (extended, no NBP constraint: hx_dev_solver.h, hx_nbp)
-      if (kpm) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, true, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      else if (hf) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, false, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      else hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, false, false, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      return;
-    }
-    if (two_wave && !con) {
-      if (hf && kpm) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, true, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      else if (kpm) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, false, true, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      else if (hf) hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, true, false, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      else hipLaunchKernelGGL((hx_run_kernel<HX_B1W2, false, false, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      return;
-    }
-  }
-#ifdef HX_MINIMAL_BUILD  // experiment builds (tools/prof): the plain kernel only
-  (void)hf; (void)kpm; (void)con;
-#ifdef HX_MINIMAL_TRACK  // ... and the carbon-tracking ones
-  if constexpr (B == 1) {
-    if (con == 2 && !getenv("HECTOR_AMD_TRACK_INLINE")) {
-      hipLaunchKernelGGL((hx_run_kernel<1, true, false, 3>), dim3(blocks), dim3(64 * (1 + trk_waves<1>())), lds, st, d_args, iy_from, iy_to);
-      return;
-    }
-  }
-  if (con == 2) {
-    hipLaunchKernelGGL((hx_run_kernel<B, true, false, 2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-    return;
-  }
-#endif
-#ifdef HX_MINIMAL_EXT    // ... and the extended ones without the NBP machinery / second history sum
-  if constexpr (B >= 1 && B <= 4) {
-    if (con == -2) {
-      hipLaunchKernelGGL((hx_run_kernel<B, false, false, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      return;
-    }
-  }
-  if (con == -1) {
-    hipLaunchKernelGGL((hx_run_kernel<B, false, false, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-    return;
-  }
-#endif
-  hipLaunchKernelGGL((hx_run_kernel<B, false, false, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-  return;
-#endif
-#ifndef HX_W2_ONLY   // (HX_W2_ONLY, with HX_MINIMAL_BUILD: nothing but the plain one-biome kernels)
-#ifndef HX_HOST_EMULATION   // (the host build runs a block's threads one after the other)
-  if constexpr (B >= 1 && B <= HX_TRK_COMPANION_MAXB) {  // the maps live on companion wavefronts
-    // (read at every launch, like hx_looped_from(): a test switches it between two cores; the
-    // CU count is the launching core's device's, handed down by EnsembleCore::run)
-    const bool inline_maps = getenv("HECTOR_AMD_TRACK_INLINE") != nullptr;
-    if (con == 2 && !inline_maps && (B == 1 || blocks <= cus)) {
-      constexpr int threads = 64 * (1 + trk_waves<B>());
-      if (kpm) hipLaunchKernelGGL((hx_run_kernel<B, true, true, 3>), dim3(blocks), dim3(threads), lds, st, d_args, iy_from, iy_to);
-      else hipLaunchKernelGGL((hx_run_kernel<B, true, false, 3>), dim3(blocks), dim3(threads), lds, st, d_args, iy_from, iy_to);
-      return;
-    }
-  }
-#endif
-  if constexpr (B <= 4) {  // (HX_DYN = 0 included; hx_launch_run sends 5 and 6 biomes with tracking there)
-  if (con == 2 && kpm) {
-    hipLaunchKernelGGL((hx_run_kernel<B, true, true, 2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-    return;
-  }
-  if (con == 2) {
-    hipLaunchKernelGGL((hx_run_kernel<B, true, false, 2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-    return;
-  }
-  }
-  if constexpr (B >= 1 && B <= 4) {
-    if (con == -2) {   // diagnostics only: no constraint, warming ratio or per-member series anywhere
-      if (kpm) hipLaunchKernelGGL((hx_run_kernel<B, true, true, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      else if (hf) hipLaunchKernelGGL((hx_run_kernel<B, true, false, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      else hipLaunchKernelGGL((hx_run_kernel<B, false, false, -2>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-      return;
-    }
-  }
-  if (con == -1 && kpm)
-    hipLaunchKernelGGL((hx_run_kernel<B, true, true, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-  else if (con == -1 && hf)
-    hipLaunchKernelGGL((hx_run_kernel<B, true, false, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-  else if (con == -1)   // (shared diffusivity, no heat-flux output: without the second history sum)
-    hipLaunchKernelGGL((hx_run_kernel<B, false, false, -1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-  else if (con && kpm)
-    hipLaunchKernelGGL((hx_run_kernel<B, true, true, 1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-  else if (con)
-    hipLaunchKernelGGL((hx_run_kernel<B, true, false, 1>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-  else if (hf && kpm)
-    hipLaunchKernelGGL((hx_run_kernel<B, true, true, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-  else if (hf)
-    hipLaunchKernelGGL((hx_run_kernel<B, true, false, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-  else if (kpm)
-    hipLaunchKernelGGL((hx_run_kernel<B, false, true, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-  else
-    hipLaunchKernelGGL((hx_run_kernel<B, false, false, 0>), dim3(blocks), dim3(64), lds, st, d_args, iy_from, iy_to);
-#endif
-}
-#if HX_HAS_MFMA && ((!defined(HX_W2_ONLY) && !defined(HX_ONLY_B)) || defined(HX_WITH_PAIR))
-#define HX_HAS_PAIR 1
-#include "hx_dev_pair.h"
-#else
-#define HX_HAS_PAIR 0
-#endif
-// the small-ensemble kernel (two wavefronts per 64 members, hx_dev_pair.h): one biome, no
-// constraints, the outputs listed in EnsembleCore::run; kpm: per-member DOECLIM kernel tables
-int hx_pair_available() { return HX_HAS_PAIR; }
-hipError_t hx_launch_run_pair(const HxArgs *d_args, int npad, bool heatflux, bool kpm, int iy_from,
-                              int iy_to, hipStream_t st, bool cons, int nbiome) {
-#if HX_HAS_PAIR
-  const dim3 g(npad / 64), b(128);
-  // (two to four biomes: shared diffusivity, no heat-flux sum -- plain or with scenario-wide constraints;
-  // the host sends every other split ensemble to the run kernels)
-  if (nbiome > 1) {
-    if (heatflux || kpm || nbiome > 4) return hipErrorInvalidValue;
-    if (cons) {
-      if (nbiome == 2) hipLaunchKernelGGL((hx_pair_kernel<false, false, true, 2>), g, b, 0, st, d_args, iy_from, iy_to);
-      else if (nbiome == 3) hipLaunchKernelGGL((hx_pair_kernel<false, false, true, 3>), g, b, 0, st, d_args, iy_from, iy_to);
-      else hipLaunchKernelGGL((hx_pair_kernel<false, false, true, 4>), g, b, 0, st, d_args, iy_from, iy_to);
-      return hipGetLastError();
-    }
-    if (nbiome == 2) hipLaunchKernelGGL((hx_pair_kernel<false, false, false, 2>), g, b, 0, st, d_args, iy_from, iy_to);
-    else if (nbiome == 3) hipLaunchKernelGGL((hx_pair_kernel<false, false, false, 3>), g, b, 0, st, d_args, iy_from, iy_to);
-    else hipLaunchKernelGGL((hx_pair_kernel<false, false, false, 4>), g, b, 0, st, d_args, iy_from, iy_to);
-    return hipGetLastError();
-  }
-  // (with a CO2 / tas / RF_tot / CH4 constraint: the shared-diffusivity instantiations; the host
-  // sends per-member diffusivity with constraints to the run kernel)
-  if (cons && kpm) return hipErrorInvalidValue;
-  if (cons && heatflux) hipLaunchKernelGGL((hx_pair_kernel<false, true, true>), g, b, 0, st, d_args, iy_from, iy_to);
-  else if (cons) hipLaunchKernelGGL((hx_pair_kernel<false, false, true>), g, b, 0, st, d_args, iy_from, iy_to);
-  else if (kpm && heatflux) hipLaunchKernelGGL((hx_pair_kernel<true, true>), g, b, 0, st, d_args, iy_from, iy_to);
-  else if (kpm) hipLaunchKernelGGL((hx_pair_kernel<true, false>), g, b, 0, st, d_args, iy_from, iy_to);
-  else if (heatflux) hipLaunchKernelGGL((hx_pair_kernel<false, true>), g, b, 0, st, d_args, iy_from, iy_to);
-  else hipLaunchKernelGGL((hx_pair_kernel<false, false>), g, b, 0, st, d_args, iy_from, iy_to);
-  return hipGetLastError();
-#else
-  (void)d_args; (void)npad; (void)heatflux; (void)kpm; (void)iy_from; (void)iy_to; (void)st; (void)cons; (void)nbiome;
-  return hipErrorInvalidValue;
-#endif
-}
-hipError_t hx_launch_run(int B, const HxArgs *d_args, int npad, bool heatflux, bool kpm, int con,
-                         int iy_from, int iy_to, hipStream_t st, bool two_wave, int cus) {
-#ifdef HX_W2_ONLY
-  if (B != 1) return hipErrorInvalidValue;
-  launch_run_b<1>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, 1, two_wave, cus);
-  return hipGetLastError();
-#else
-  switch (B >= hx_looped_from() ? HX_BDYN + 1 : B) {
-#if HX_ONLY_B_IS(1)
-    case 1: launch_run_b<1>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, 1, two_wave, cus); break;
-#endif
-#ifndef HX_MINIMAL_BUILD
-    case 2: launch_run_b<2>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, 2, false, cus); break;
-    case 3: launch_run_b<3>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break;
-#endif
-#if HX_ONLY_B_IS(4)
-    case 4: launch_run_b<4>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break;
-#endif
-    // five to eight biomes: unrolled like 1-4 (lean park, hx_dev_member.h); carbon tracking on the
-    // looped kernels' 8-column chunks
-#if HX_ONLY_B_IS(5)
-    case 5: if (con != 2) { launch_run_b<5>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break; }
-#if HX_ONLY_B_IS(0)
-            launch_run_b<HX_DYN>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, B); break;
-#else
-            return hipErrorInvalidValue;
-#endif
-#endif
-#if HX_ONLY_B_IS(6)
-    case 6: if (con != 2) { launch_run_b<6>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break; }
-#if HX_ONLY_B_IS(0)
-            launch_run_b<HX_DYN>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, B); break;
-#else
-            return hipErrorInvalidValue;
-#endif
-#endif
-#if HX_ONLY_B_IS(7)
-    case 7: if (con != 2) { launch_run_b<7>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break; }
-#if HX_ONLY_B_IS(0)
-            launch_run_b<HX_DYN>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, B); break;
-#else
-            return hipErrorInvalidValue;
-#endif
-#endif
-#if HX_ONLY_B_IS(8)
-    case 8: if (con != 2) { launch_run_b<8>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st); break; }
-#if HX_ONLY_B_IS(0)
-            launch_run_b<HX_DYN>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, B); break;
-#else
-            return hipErrorInvalidValue;
-#endif
-#endif
-    default:
-#if HX_ONLY_B_IS(0)
-      if (B < 1 || B > HX_BDYN) return hipErrorInvalidValue;
-      launch_run_b<HX_DYN>(d_args, npad, heatflux, kpm, con, iy_from, iy_to, st, B);
-#else
-      return hipErrorInvalidValue;
-#endif
-  }
-  return hipGetLastError();
-#endif
-}
-
-int hx_doeclim_block_years() { return HX_DBLK; }
-void hx_fill_chem_table_host(double *t) { hx_fill_chem_table(t); }
-int hx_track_value_rows(int B) { return hx_trk_vrows(B); }
-int hx_doeclim_kernel_pad() { return HX_KPAD; }
-hipError_t hx_launch_unit_csys(int n, const double *Tc, const double *carbon, const double *alk,
-                               double inv_vol, double *out, hipStream_t st) {
-  hipLaunchKernelGGL(hx_unit_csys_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, Tc, carbon, alk,
-                     inv_vol, out);
-  return hipGetLastError();
-}
-// ---- the chip's clocks ahead of a one-shot run ---------------------------------------------------
-// A run kernel launched after an idle gap -- the first run of a fresh core: the host has just spent
-// 10-15 ms uploading and spinning up -- executes at ramping clocks: +6 % at 65 536 members, +11-15 %
-// on the two-wavefront kernel, and ~12 ms of full-chip work right before it removes most of that
-// (tools/prof/prewarm_curve.py, profiles/r06_prewarm_curve.txt).  This kernel is that work: one
-// small wavefront on some of the SIMDs (never all: a kernel that needs a whole SIMD's registers
-// must find one) multiplies and adds until the host raises `stop` (a memset on the core's stream,
-// right ahead of the run kernel) or its own deadline on the constant 100 MHz clock passes --
-// whichever comes first, so it cannot outlive its budget whatever the host does.
-__global__ __launch_bounds__(64) void hx_prewarm_kernel(const int *stop, long long max_ticks, double *sink,
-                                                         const double *mem, unsigned long long n_mem) {
-#ifndef HX_HOST_EMULATION
-  const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-  double a = 1.0 + 1e-9 * threadIdx.x, b = 0.999999, c = 1e-7, d = a, e = a + c, f = a - c, acc = 0.0;
-  unsigned long long pos = (unsigned long long)blockIdx.x * 64 + threadIdx.x;
-  const unsigned long long stride = (unsigned long long)gridDim.x * 64;
-  for (;;) {
-#pragma unroll
-    for (int k = 0; k < 32; ++k) { a = fma(a, b, c); d = fma(d, b, c); e = fma(e, b, c); f = fma(f, b, c); }
-    if (n_mem) {   // (... and the memory system: a sweep over the arrays the run will write)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { acc += __builtin_nontemporal_load(mem + pos % n_mem); pos += stride; }
-    }
-    if (__builtin_nontemporal_load(stop) != 0) break;
-    if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > max_ticks) break;
-  }
-  if (((a + d) + (e + f)) + acc == 12345.678) sink[blockIdx.x & 1023] = a;   // (keeps the arithmetic)
-#endif
-}
-hipError_t hx_launch_prewarm(const int *d_stop, long long max_ticks, double *d_sink, int waves,
-                             const double *mem, unsigned long long n_mem, hipStream_t st) {
-  hipLaunchKernelGGL(hx_prewarm_kernel, dim3(waves), dim3(64), 0, st, d_stop, max_ticks, d_sink, mem, n_mem);
-  return hipGetLastError();
-}
-hipError_t hx_launch_diag(int kind, const HxDiagArgs &a, double *out, hipStream_t st) {
-  hipLaunchKernelGGL(hx_diag_kernel, dim3((a.npad + 255) / 256, a.ny), dim3(256), 0, st, kind, a, out);
-  return hipGetLastError();
-}
-hipError_t hx_launch_slr(const double *tgav, int npad, int start_year, int iy_to, double *out,
-                         size_t var_stride, hipStream_t st) {
-  hipLaunchKernelGGL(hx_slr_kernel, dim3((npad + 63) / 64), dim3(64), 0, st, tgav, npad,
-                     start_year, iy_to, out, var_stride);
-  return hipGetLastError();
-}
-hipError_t hx_launch_broadcast(double *table, int nrows, int npad, hipStream_t st) {
-  hipLaunchKernelGGL(hx_broadcast_rows_kernel, dim3((npad + 255) / 256), dim3(256), 0, st,
-                     table, nrows, npad);
-  return hipGetLastError();
-}
-hipError_t hx_launch_broadcast_u32(unsigned *v, int npad, hipStream_t st) {
-  hipLaunchKernelGGL(hx_broadcast_u32_kernel, dim3((npad + 255) / 256), dim3(256), 0, st, v, npad);
-  return hipGetLastError();
-}
-hipError_t hx_launch_gas(const double *par, const double *ser, const double *h0, int nh, int ns,
-                         int npad, double *n2o_out, double *rf_other_out, hipStream_t st) {
-  if (nh > 40) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(hx_gas_kernel, dim3((npad + 63) / 64), dim3(64), 0, st, par, ser, h0, nh, ns,
-                     npad, n2o_out, rf_other_out);
-  return hipGetLastError();
-}
-hipError_t hx_launch_or_flags(unsigned *status, const double *flag_row, int npad, hipStream_t st) {
-  hipLaunchKernelGGL(hx_or_flags_kernel, dim3((npad + 255) / 256), dim3(256), 0, st, status,
-                     flag_row, npad);
-  return hipGetLastError();
-}
-hipError_t hx_launch_doeclim_kernel(const double *diff_row, double *ker, int ns, int count,
-                                    int stride, hipStream_t st) {
-  hipLaunchKernelGGL(hx_doeclim_table_kernel, dim3((count + 255) / 256, ns), dim3(256), 0, st,
-                     diff_row, ker, ns, count, stride);
-  return hipGetLastError();
-}
-hipError_t hx_launch_derive(const double *params, double *derived, const double *ker,
-                            int ker_per_member, int ns, int nbiome, int npad, hipStream_t st) {
-  hipLaunchKernelGGL(hx_derive_kernel, dim3((npad + 255) / 256), dim3(256), 0, st, params,
-                     derived, ker, ker_per_member, ns, nbiome, npad);
-  return hipGetLastError();
-}
-hipError_t hx_launch_gather(const double *src, const int *lane_of_member, double *dst, int n,
-                            int npad, int nyears, hipStream_t st) {
-  hipLaunchKernelGGL(hx_gather_kernel, dim3((n + 255) / 256, nyears), dim3(256), 0, st, src,
-                     lane_of_member, dst, n, npad, nyears);
-  return hipGetLastError();
-}
-hipError_t hx_launch_combine_stats(const double *slots, int world, int rows, double *out,
-                                   hipStream_t st) {
-  hipLaunchKernelGGL(hx_combine_stats_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, slots,
-                     world, rows, out);
-  return hipGetLastError();
-}
-hipError_t hx_launch_stats(const double *var, int n, int npad, int iy0, int nyears,
-                           double *stats, hipStream_t st) {
-  hipLaunchKernelGGL(hx_stats_kernel, dim3(nyears), dim3(256), 0, st, var, n, npad, iy0, stats);
-  return hipGetLastError();
-}
-}
+#endif  // HX_RUN_BODY_PASS

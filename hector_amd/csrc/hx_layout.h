@@ -277,6 +277,17 @@ struct HxBuffers {
   // the 4 KB mark (see HxArgs) and every "plain + diagnostics" kernel gained 6 instructions and 2
   // spilled scalars.  Here no other field moves; these are read behind their ms_mask bit only.
   const double *mseries_slcf[HXM_N - HXM_OH_B];
+  // Per-wavefront partial statistics of CO2_concentration (var 0) and global_tas (var 1),
+  // [2][ns][npad / 64][4] = {sum, sum of squares, min, max} over the wavefront's live lanes: written
+  // behind the year loop by the run kernels that own the LDS tile (hx_wave_partials, hx_kernels.hip)
+  // for the rows the launch wrote, folded by hx_combine_partials_kernel.  Null: no partials.
+  // Wavefronts < wpart_skip leave theirs out (the costliest ones, dispatched first: the launch
+  // lasts as long as they do); the combine reads their members from the rows.  Behind everything
+  // else for the reason above.
+  // wpart_row0 .. wpart_row1: the rows the launch reduces -- iy_from + 1 (0 for a launch from
+  // startDate) .. iy_to.
+  double *wpart;
+  int wpart_skip, wpart_row0, wpart_row1;
 };
 #define HXM_SLCF(buf, k) ((buf).mseries_slcf[(k) - HXM_OH_B])
 // rows of HxBuffers::spin_rec: the carbon-cycle variables of the stream, which are the ones that

@@ -48,7 +48,8 @@ hipError_t hx_launch_run_pair(const HxArgs *d_args, int npad, bool heatflux, boo
 hipError_t hx_launch_prewarm(const int *d_stop, long long max_ticks, double *d_sink, int waves,
                              const double *mem, unsigned long long n_mem, hipStream_t st);
 hipError_t hx_launch_run(int B, const HxArgs *d_args, int npad, bool heatflux, bool kpm, int con,
-                         int iy_from, int iy_to, hipStream_t st, bool two_wave, int cus);
+                         int iy_from, int iy_to, hipStream_t st, bool two_wave, int cus,
+                         bool partials = false);
 int hx_doeclim_block_years();
 int hx_doeclim_kernel_pad();
 void hx_fill_chem_table_host(double *t);
@@ -67,6 +68,16 @@ hipError_t hx_launch_stats(const double *var, int n, int npad, int iy0, int nyea
                            double *stats, hipStream_t st);
 hipError_t hx_launch_combine_stats(const double *slots, int world, int rows, double *out,
                                    hipStream_t st);
+// {n, sum, sum of squares, min, max} of rows iy0 .. iy0 + nyears - 1 from the run kernel's
+// per-wavefront partials (HxBuffers::wpart), for one or two of its variables in one launch:
+// var[k] 0 = CO2_concentration, 1 = global_tas; rows[k] the variable's output block (the members of
+// the first `skip` wavefronts, which wrote no partials, are read from it); out[k] [nyears][5]
+hipError_t hx_launch_combine_partials(const double *wpart, int nvar, const int *var,
+                                      const double *const *rows, double *const *out, int n, int npad,
+                                      int ns, int iy0, int nyears, int skip, hipStream_t st);
+// can hx_launch_run(B, .., heatflux, kpm, con, .., two_wave, .., partials = true) be asked for them?
+// (hx_run_kernel_stats: the plain one-biome kernel's flavour with the epilogue)
+bool hx_run_writes_partials(int B, bool heatflux, bool kpm, int con, bool two_wave);
 hipError_t hx_launch_derive(const double *params, double *derived, const double *ker,
                             int ker_per_member, int ns, int nbiome, int npad, hipStream_t st);
 hipError_t hx_launch_doeclim_kernel(const double *diff_row, double *ker, int ns, int count,

@@ -1151,6 +1151,12 @@ int hx_last_run_retries(hx_core *core, int *faithful);
  * order or more resident wavefronts can shorten a launch.  No counterpart in the reference
  * (src/core.cpp:483-504 runs one member). */
 int hx_wave_clock(hx_core *core, int shard, long long *ticks, int cap, int *n_waves);
+/* ticks[w]: what wavefront w of shard `shard`'s last year-loop launch spent behind its year loop
+ * reducing its own CO2_concentration and global_tas rows to per-wavefront partial statistics (what
+ * hx_stats_device and hx_ensemble_stats fold instead of reading the rows again), same clock;
+ * 0 for a wavefront that left it out.  *n_waves = 0 when the launch wrote no partials (any kernel
+ * but the plain one-biome run kernel, or HECTOR_AMD_STATS_PARTIALS=0). */
+int hx_wave_epilogue_clock(hx_core *core, int shard, long long *ticks, int cap, int *n_waves);
 
 #define HX_ERR_MASS 1u     /* mass not conserved        simpleNbox-runtime.cpp:553-563 */
 #define HX_ERR_RETRIES 2u  /* solver retries exhausted  carbon-cycle-solver.cpp:242-294 */
