@@ -35,6 +35,27 @@ struct PairCall {
   int nspecs;
 };
 
+// The rows a summary verb works on.  fn is the ABI function named in every message.  specs and pair
+// null: the years year0..year1 of capability; else its nspecs metrics, or the pair->nspecs pair
+// metrics with capability as operand a.
+struct RowSource {
+  const char *fn;
+  std::string capability;
+  int year0, year1;
+  const hx_metric *specs;
+  int nspecs;
+  const PairCall *pair;
+};
+
+// The groups of a grouped summary (hx_group_* in hector_amd.h): labels[n_] in member order,
+// -1 .. ngroups-1 (checked by the fleet, whose shards take labels + offset); ngroups == 0: ungrouped.
+// Every state and result array of a grouped call is group-major, (group, row) at g * nrows + row, so
+// that hx_fleet.cpp combines shards over ngroups * nrows rows exactly as it does over rows.
+struct Groups {
+  const int *labels;
+  int ngroups;
+};
+
 // How a mix of a dated input is evaluated: not at all, into the variable's table
 // (hx_mseries_mix_kernel), by the gas pre-pass (hx_gas_mix_kernel) or by the aerosol / precursor
 // pre-pass (hx_slcf_mix_kernel; taken only behind hx_enable_slcf_mixes)
@@ -213,84 +234,47 @@ class EnsembleCore {
   void member_project(const std::string &capability, const int *years, const double *center,
                       const double *basis, int n, int m, int base_year0, int base_year1, double *out_host,
                       size_t row_pitch = 0);
-  // weighted quantiles (hx_ensemble_quantiles): q[n_] integer weights in member order (nullptr:
-  // every member 1), out_host[(year - year0) * nprobs + j], n_part[year - year0] (may be nullptr)
-  void quantiles(const std::string &capability, int year0, int year1, const unsigned long long *q,
-                 const double *probs, int nprobs, double *out_host, long long *n_part);
-  // ... and its steps for a core of several shards (hx_fleet.cpp adds the shards' integer
-  // histograms): q_begin validates, uploads q and reduces {~min key, max key, sum q, count} of
-  // every year into st_host[ny][4]; q_pass fills hist_host[ny][nprobs][256] for the select state
-  // lo[ny], prefix[ny][nprobs] (hxq_* below)
-  void q_begin(const std::string &capability, int year0, int year1, const unsigned long long *q,
-               int nprobs, unsigned long long *st_host);
-  void q_pass(const int *lo, const unsigned long long *prefix, unsigned long long *hist_host);
   // per-member metrics (hx_member_metrics): out_host[nspecs][n_] in member order.  fn: the ABI
   // function on whose behalf the specifications are checked (it is named in every message)
   void member_metrics(const std::string &capability, const hx_metric *specs, int nspecs,
                       double *out_host, const char *fn = "hx_member_metrics");
-  // hx_metric_quantiles: the metric block [nspecs][npad] is computed in lane order on the device and
-  // handed to the same select as a block of year rows; mq_begin is q_begin for it (q_pass follows)
-  void metric_quantiles(const std::string &capability, const hx_metric *specs, int nspecs,
-                        const unsigned long long *q, const double *probs, int nprobs, double *out_host,
-                        long long *n_part);
-  void mq_begin(const std::string &capability, const hx_metric *specs, int nspecs,
-                const unsigned long long *q, int nprobs, unsigned long long *st_host);
-  // weighted bin sums (hx_ensemble_probabilities / hx_metric_probabilities): this core's integer
-  // sums_host[row][nedges + 2] = the nedges + 1 bins, then the members that took part
-  void bin_sums(const std::string &capability, int year0, int year1, const unsigned long long *q,
-                const double *edges, int nedges, unsigned long long *sums_host);
-  void metric_bin_sums(const std::string &capability, const hx_metric *specs, int nspecs,
-                       const unsigned long long *q, const double *edges, int nedges,
-                       unsigned long long *sums_host);
-  // weighted moments (hx_ensemble_moments; specs != nullptr: hx_metric_moments over the metric
-  // block), in the two steps hx_fleet.cpp drives for one shard or several.  mom_begin validates,
-  // brings q[n_] (effective integer weights: 0 where a predictor is not finite) and pred[npred][n_]
-  // (member order) to lane order with the predictor shifts c[8] subtracted, and reduces {~min key,
-  // max key, sum q, count} of every row into st_host[rows][4]; mom_finish takes the rows' shifts over
-  // ALL shards and returns this core's sums_host[rows][2 + 3 npred]
-  void mom_begin(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                 const unsigned long long *q, const double *pred, int npred, const double *c,
-                 unsigned long long *st_host, const char *fn);
-  void mom_finish(const double *shift_host, double *sums_host);
-  // ---- the grouped summaries (hx_group_quantiles / _probabilities / _moments in hector_amd.h) -------
-  // labels[n_] in member order, -1 .. ngroups-1 (checked by the fleet); rows are specs == nullptr ? the
-  // years year0..year1 : the nspecs metrics; every state and result array is group-major, (group, row)
-  // at g * nrows + row, so that hx_fleet.cpp combines shards over ngroups * nrows rows exactly as it
-  // does over rows.  fn: the ABI function named in every message; the host-emulation build refuses
-  // by that name after the checks.
-  // grp_quantiles: the whole select on this core's GPU -> out_host[ngroups * nrows][nprobs], n_part
-  void grp_quantiles(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                     const int *labels, int ngroups, const unsigned long long *q, const double *probs,
-                     int nprobs, double *out_host, long long *n_part, const char *fn);
-  // grp_q_begin is q_begin over (group, row): st_host[ngroups * nrows][4]; q_pass follows, with lo,
-  // prefix and hist_host over ngroups * nrows rows
-  void grp_q_begin(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                   const int *labels, int ngroups, const unsigned long long *q, int nprobs,
-                   unsigned long long *st_host, const char *fn);
-  // sums_host[ngroups * nrows][nedges + 2]
-  void grp_bin_sums(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                    const int *labels, int ngroups, const unsigned long long *q, const double *edges,
-                    int nedges, unsigned long long *sums_host, const char *fn);
-  // mom_begin / mom_finish over (group, row): q[n_] effective weights (0 where the label is -1 or a
-  // predictor is not finite), c[ngroups][8] the groups' predictor shifts; st_host[ngroups * nrows][4];
-  // shift_host[ngroups * nrows] -> sums_host[ngroups * nrows][2 + 3 npred]
-  void grp_mom_begin(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                     const int *labels, int ngroups, const unsigned long long *q, const double *pred,
-                     int npred, const double *c, unsigned long long *st_host, const char *fn);
-  void grp_mom_finish(const double *shift_host, double *sums_host);
   // per-member pair metrics (hx_member_pair_metrics): two operands of a member, PairCall above;
-  // out_host row s at out_host + s * row_pitch (0: n_), member order.  The three block verbs are the
-  // metric verbs above with the pair block in place of the metric block (fn: the ABI function named
-  // in every message); mom_begin takes the pair call instead of specs.
+  // out_host row s at out_host + s * row_pitch (0: n_), member order
   void member_pair_metrics(const std::string &cap_a, const PairCall &pc, double *out_host, size_t row_pitch = 0);
-  void pair_metric_quantiles(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
-                             const double *probs, int nprobs, double *out_host, long long *n_part);
-  void pmq_begin(const std::string &cap_a, const PairCall &pc, const unsigned long long *q, int nprobs,
-                 unsigned long long *st_host);
-  void pair_metric_bin_sums(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
-                            const double *edges, int nedges, unsigned long long *sums_host);
-  void pair_mom_begin(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
-                      const double *pred, int npred, const double *c, unsigned long long *st_host);
+  // ---- the summary verbs over a RowSource, per group if Groups says so.  rows below counts
+  // max(ngroups, 1) * nrows, group-major; q[n_] are integer weights in member order.
+  // Every check of a source, and nothing else: capability, dates or specifications, nprobs (1 for a
+  // verb without probabilities), a core that has not run -> the block the rows are read in or computed
+  // from (*src_b: operand b of a pair call).  A year window tests nprobs before it resolves the
+  // capability, the metric and pair sources after their specifications.  The host-emulation build
+  // refuses by rs.fn here: at once, or for a pair or grouped call behind the checks.
+  const double *rows_check(const RowSource &rs, const Groups &g, int nprobs, const double **src_b = nullptr);
+  // weighted quantiles (hx_ensemble_quantiles, hx_metric_quantiles, hx_pair_metric_quantiles,
+  // hx_group_quantiles): the whole select on this core's GPU.  q nullptr: every member 1;
+  // out_host[rows][nprobs], n_part[rows] (may be nullptr)
+  void quantiles(const RowSource &rs, const Groups &g, const unsigned long long *q, const double *probs,
+                 int nprobs, double *out_host, long long *n_part);
+  // ... and its steps for a core of several shards (hx_fleet.cpp adds the shards' integer
+  // histograms): q_begin validates, uploads q and reduces {~min key, max key, sum q, count} of
+  // every row into st_host[rows][4]; q_pass fills hist_host[rows][nprobs][256] for the select state
+  // lo[rows], prefix[rows][nprobs] (hxq_* below)
+  void q_begin(const RowSource &rs, const Groups &g, const unsigned long long *q, int nprobs,
+               unsigned long long *st_host);
+  void q_pass(const int *lo, const unsigned long long *prefix, unsigned long long *hist_host);
+  // weighted bin sums (hx_ensemble_probabilities and its metric, pair and group forms): this core's
+  // integer sums_host[rows][nedges + 2] = the nedges + 1 bins, then the members that took part.  The
+  // edges are checked by the fleet (1..31, finite, strictly ascending)
+  void bin_sums(const RowSource &rs, const Groups &g, const unsigned long long *q, const double *edges,
+                int nedges, unsigned long long *sums_host);
+  // weighted moments (hx_ensemble_moments and its forms), in the two steps hx_fleet.cpp drives for
+  // one shard or several.  mom_begin validates, brings q[n_] (effective integer weights: 0 where a
+  // predictor is not finite or the label is -1) and pred[npred][n_] (member order) to lane order with
+  // the predictor shifts c[max(ngroups, 1)][8] subtracted, and reduces {~min key, max key, sum q,
+  // count} of every row into st_host[rows][4]; mom_finish takes the rows' shifts over ALL shards,
+  // shift_host[rows], and returns this core's sums_host[rows][2 + 3 npred]
+  void mom_begin(const RowSource &rs, const Groups &g, const unsigned long long *q, const double *pred,
+                 int npred, const double *c, unsigned long long *st_host);
+  void mom_finish(const double *shift_host, double *sums_host);
   // year-by-year co-moments (hx_ensemble_comoments), in the same two steps.  comom_begin validates
   // both windows (cap_b == nullptr: the symmetric call, B is A), brings q[n_] to lane order, zeroes
   // it where any value of either window is NaN (complete cases) and reduces the rows' records into
@@ -301,17 +285,14 @@ class EnsembleCore {
   void comom_begin(const std::string &cap_a, int a0, int a1, const std::string *cap_b, int b0, int b1,
                    const unsigned long long *q, unsigned long long *st_host);
   void comom_finish(const double *shift_host, double *sums_host, double *cross_host);
-  // Sobol sums of a Saltelli design (hx_ensemble_sobol; specs != nullptr: hx_metric_sobol over the
+  // Sobol sums of a Saltelli design (hx_ensemble_sobol; rs.specs != nullptr: hx_metric_sobol over the
   // metric block), one shard only: a group's k + 2 consecutive members must all live on this core.
-  // sobol_check is the validation alone (fn is named in every message; the host-emulation build
-  // refuses here); sobol_begin validates, turns the lane order into the group-major lane table with
-  // use[n_base] (nullptr: every group) and reduces every row's participation, min key and count on
-  // the device; sobol_finish runs the sum pass and returns shift_host[rows], sums_host[rows][4 + 4 k]
-  // and n_part_host[rows].  No prepare(), no spinup, not dirtied.
-  void sobol_check(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                   const char *fn);
-  void sobol_begin(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                   int k, int n_base, const unsigned char *use, const char *fn);
+  // rows_check is the validation alone; sobol_begin validates, turns the lane order into the
+  // group-major lane table with use[n_base] (nullptr: every group) and reduces every row's
+  // participation, min key and count on the device; sobol_finish runs the sum pass and returns
+  // shift_host[rows], sums_host[rows][4 + 4 k] and n_part_host[rows].  No prepare(), no spinup, not
+  // dirtied.
+  void sobol_begin(const RowSource &rs, int k, int n_base, const unsigned char *use);
   void sobol_finish(double *shift_host, double *sums_host, long long *n_part_host);
   // ---- held and derived per-member series (hx_series_define in hector_amd.h) ----------------------
   void series_define(const std::string &name, const std::string &a, const hx_series_op &op);
@@ -319,11 +300,8 @@ class EnsembleCore {
   void series_list(std::vector<std::string> *names, std::vector<int> *valid_to) const;
   // ---- member ranks and the CRPS (hx_series_rank / hx_metric_ranks / hx_ensemble_crps) ------------
   // One shard only: the sort needs the whole row on this core.  q[n_] integer weights in member order
-  // (nullptr: every member 1); kind: HX_RANK_*.  rank_check is the validation of capability and dates
-  // (specs != nullptr: of the specifications) alone, fn named in every message; the host-emulation
-  // build refuses there.  No prepare(), no spinup, not dirtied.
-  void rank_check(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                  const char *fn);
+  // (nullptr: every member 1); kind: HX_RANK_*.  rows_check is the validation of capability and
+  // dates or specifications alone.  No prepare(), no spinup, not dirtied.
   void series_rank(const std::string &name, const std::string &capability, int year0, int year1,
                    const unsigned long long *q, int kind);
   void metric_ranks(const std::string &capability, const hx_metric *specs, int nspecs,
@@ -565,24 +543,30 @@ class EnsembleCore {
   unsigned long long *d_q_ = nullptr;         // integer weights in lane order [npad]
   Scratch<unsigned long long> d_qstate_;      // per year {HxQYear, lo}, per (year, prob) {prefix, rem}, probs
   Scratch<unsigned long long> d_qhist_;       // [ny][nprobs][256]
-  // The block q_begin / mq_begin prepared for q_pass: d_out_[v], a series, a derived block or d_met_.
-  // It is not owned, and between the two steps it may point into the metric block: a metric or
-  // pair-metric call that regrows d_met_ in between leaves it dangling, as it always has (the fleet
-  // drives q_begin and q_pass back to back).  free_device() resets it.
+  // The block the select's first step (q_begin, or quantiles itself) prepared for its histogram
+  // passes: d_out_[v], a series, a derived block or d_met_.  It is not owned, and between q_begin and
+  // q_pass it may point into the metric block: a metric or pair-metric call that regrows d_met_ in
+  // between leaves it dangling, as it always has (the fleet drives q_begin and q_pass back to back).
+  // free_device() resets it.
   const double *q_src_ = nullptr;
   int q_iy0_ = 0, q_ny_ = 0, q_np_ = 0;
   bool q_weighted_ = false;
   int post_flags_ = 0;                        // HECTOR_AMD_POST_AB (measurements): 1 no prefix skip, 2 with wave aggregation
   const double *q_check(const std::string &capability, int year0, int year1, int nprobs,
-                        const char *fn = "hx_ensemble_quantiles");   // -> the source block
-  void q_upload(const unsigned long long *q, int ny, int np);
-  // the select over the rows iy0 .. iy0 + ny - 1 of a [rows][npad_] block in lane order
-  void q_select(const double *src, int iy0, int ny, const unsigned long long *q, const double *probs,
-                int np, double *out_host, long long *n_part);
-  void q_begin_block(const double *src, int iy0, int ny, const unsigned long long *q, int np,
-                     unsigned long long *st_host);
-  void bin_block(const double *src, int iy0, int nrows, const unsigned long long *q, const double *edges,
-                 int nedges, unsigned long long *sums_host);
+                        const char *fn);      // -> the source block
+  // rows_check, then sync(), then the metric or pair kernel queued on stream_ -> the rows iy0 ..
+  // iy0 + nrows - 1 of a [rows][npad_] block in lane order
+  struct Rows { const double *block; int iy0, nrows; };
+  Rows rows(const RowSource &rs, const Groups &g, int nprobs);
+  // q[n_] in member order -> d_q_ in lane order (padding lanes 0), which it returns; nullptr stays
+  const unsigned long long *lane_weights(const unsigned long long *q);
+  int *group_labels();                        // d_glab_ allocated, its lane part set to -1 on stream_
+  void upload_labels(const int *labels);      // member order -> d_glab_ in lane order
+  // {~min key, max key, sum q, count} of every row of r, per group if ngroups, into st (zeroed here)
+  void minmax(const Rows &r, int ngroups, const unsigned long long *dq, unsigned long long *st);
+  // the select's scratch, q and the rows' records for rs; q_src_ and its companions set -> rows
+  int q_start(const RowSource &rs, const Groups &g, const unsigned long long *q, int np);
+  void q_hist(const int *lo, const unsigned long long *prefix);   // one histogram pass over q_src_
   // scratch of the metric kernel: group records + row lists, and the block [nspecs][npad_] (lane order)
   Scratch<unsigned char> d_metplan_;
   Scratch<double> d_met_;
@@ -593,13 +577,6 @@ class EnsembleCore {
   // the grouped summaries: labels [npad_] in lane order, then [n_] in member order as uploaded
   int *d_glab_ = nullptr;
   int q_groups_ = 0, mom_groups_ = 0;         // 0: q_pass / the moment scratch belong to an ungrouped call
-  // the rows of a grouped call checked -> the block they are computed from or read in; grp_source
-  // then resolves them (for metrics: queued on stream_) -> block, first row, rows
-  const double *grp_check(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                          int nspecs, int nprobs, const char *fn);
-  const double *grp_source(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                           int nspecs, int nprobs, const char *fn, int *iy0, int *nrows);
-  void grp_upload_labels(const int *labels);  // member order -> d_glab_ in lane order (padding lanes -1)
   Scratch<unsigned long long> d_comom_;       // scratch of hx_ensemble_comoments (CoBuf in ensemble_post.cpp)
   const double *co_a_ = nullptr, *co_b_ = nullptr;   // the windows comom_begin prepared for comom_finish
   int co_ia0_ = 0, co_ib0_ = 0, co_na_ = 0, co_nb_ = 0;
@@ -607,8 +584,6 @@ class EnsembleCore {
   Scratch<unsigned long long> d_sobol_;       // scratch of the Sobol verbs (SobBuf in ensemble_post.cpp)
   const double *sob_src_ = nullptr;           // the block sobol_begin prepared for sobol_finish
   int sob_iy0_ = 0, sob_ny_ = 0, sob_k_ = 0, sob_nb_ = 0;
-  void mom_begin_block(const double *src, int iy0, int ny, const unsigned long long *q, const double *pred,
-                       int npred, const double *c, unsigned long long *st_host);
   int metric_check(const std::string &capability, const hx_metric *specs, int nspecs, const char *fn,
                    const double **src);
   const double *metric_block(const double *src, const hx_metric *specs, int nspecs);   // -> d_met_, queued on stream_

@@ -26,6 +26,12 @@ namespace {
 void check_nprobs(const char *fn, int nprobs) {
   if (nprobs < 1 || nprobs > HXQ_MAXP) throw std::runtime_error(std::string(fn) + ": nprobs must lie in 1..16");
 }
+#ifdef HX_HOST_EMULATION
+[[noreturn]] void refuse(const char *fn, bool why = true) {
+  throw std::runtime_error(std::string(fn) + " is not available in the host-emulation build" +
+                           (why ? " (its kernels are cooperative: LDS atomics and cross-lane operations)" : ""));
+}
+#endif
 }  // namespace
 
 // ---- member scores (hx_dev_post.h) ---------------------------------------------------------------
@@ -324,15 +330,23 @@ void EnsembleCore::member_pair_metrics(const std::string &cap_a, const PairCall 
 // ---- the checks of the cooperative verbs that check before they run (or, in the host-emulation
 // build, before they refuse) ----------------------------------------------------------------------
 
-// the rows of a grouped call: the nspecs metrics (specs != nullptr) or the years year0..year1 -> the
-// block they are computed from or read in
-const double *EnsembleCore::grp_check(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                                      int nspecs, int nprobs, const char *fn) {
-  if (!specs) return q_check(capability, year0, year1, nprobs, fn);
-  const double *src = nullptr;
-  metric_check(capability, specs, nspecs, fn, &src);
-  check_nprobs(fn, nprobs);
-  if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
+const double *EnsembleCore::rows_check(const RowSource &rs, const Groups &g, int nprobs, const double **src_b) {
+#ifdef HX_HOST_EMULATION
+  if (!rs.pair && !g.ngroups) refuse(rs.fn);
+#endif
+  const double *src = nullptr, *sb = nullptr;
+  if (!rs.specs && !rs.pair) {
+    src = q_check(rs.capability, rs.year0, rs.year1, nprobs, rs.fn);
+  } else {
+    if (rs.pair) pair_metric_check(rs.capability, *rs.pair, rs.fn, &src, &sb);
+    else metric_check(rs.capability, rs.specs, rs.nspecs, rs.fn, &src);
+    check_nprobs(rs.fn, nprobs);
+    if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
+  }
+#ifdef HX_HOST_EMULATION
+  refuse(rs.fn);
+#endif
+  if (src_b) *src_b = sb;
   return src;
 }
 
@@ -676,10 +690,50 @@ void EnsembleCore::series_define(const std::string &name, const std::string &a_n
 // host-emulation build, one lane at a time, cannot run: it has the refusals at the end instead.
 #ifndef HX_HOST_EMULATION
 
+// ---- what the summary verbs share: the rows of a source, weights and labels in lane order, the
+// rows' records ------------------------------------------------------------------------------------
+
+EnsembleCore::Rows EnsembleCore::rows(const RowSource &rs, const Groups &g, int nprobs) {
+  const double *sb = nullptr, *src = rows_check(rs, g, nprobs, &sb);
+  sync();
+  if (rs.pair) return {pair_metric_block(src, sb, *rs.pair), 0, rs.pair->nspecs};
+  if (rs.specs) return {metric_block(src, rs.specs, rs.nspecs), 0, rs.nspecs};
+  return {src, rs.year0 - scen_.start, rs.year1 - rs.year0 + 1};
+}
+
+const unsigned long long *EnsembleCore::lane_weights(const unsigned long long *q) {
+  if (!q) return nullptr;
+  if (!d_q_) check(hipMalloc(&d_q_, 8 * (size_t)npad_), "hipMalloc weights");
+  std::vector<unsigned long long> ql((size_t)npad_, 0ull);
+  for (int m = 0; m < n_; ++m) ql[(size_t)lane_of_member_[(size_t)m]] = q[m];
+  check(hipMemcpy(d_q_, ql.data(), 8 * (size_t)npad_, hipMemcpyHostToDevice), "weights");
+  return d_q_;
+}
+
+int *EnsembleCore::group_labels() {
+  if (!d_glab_) check(hipMalloc(&d_glab_, sizeof(int) * ((size_t)npad_ + (size_t)n_)), "hipMalloc group labels");
+  check(hipMemsetAsync(d_glab_, 0xff, sizeof(int) * (size_t)npad_, stream_), "group labels");   // -1: in no group
+  return d_glab_;
+}
+
+void EnsembleCore::upload_labels(const int *labels) {
+  int *d_mem = group_labels() + npad_;
+  check(hipMemcpyAsync(d_mem, labels, sizeof(int) * (size_t)n_, hipMemcpyHostToDevice, stream_), "group labels");
+  check(hx_launch_grp_prepare(d_mem, n_, npad_, d_lane_of_member_, d_glab_, stream_), "group label kernel");
+}
+
+// The grouped kernels fill the (group, row) records and sums from one read of every row; the init,
+// pick and reduce kernels run over them unchanged.
+void EnsembleCore::minmax(const Rows &r, int ngroups, const unsigned long long *dq, unsigned long long *st) {
+  check(hipMemsetAsync(st, 0, 8 * 4 * (size_t)std::max(ngroups, 1) * (size_t)r.nrows, stream_), "row records");
+  check(ngroups ? hx_launch_gq_minmax(r.block, n_, npad_, r.iy0, r.nrows, dq, d_glab_, ngroups, st, stream_)
+                : hx_launch_q_minmax(r.block, n_, npad_, r.iy0, r.nrows, dq, st, stream_), "min/max kernel");
+}
+
 // ---- weighted quantiles (hx_ensemble_quantiles) ---------------------------------------------------
 
 namespace {
-// d_qstate_ in 8-byte words: [ny][4] year records, [ny][np] prefix, [ny][np] rem, [HXQ_MAXP] probs, [ny] lo (int)
+// d_qstate_ in 8-byte words: [ny][4] row records, [ny][np] prefix, [ny][np] rem, [HXQ_MAXP] probs, [ny] lo (int)
 struct QState {
   unsigned long long *st, *prefix, *rem;
   double *probs;
@@ -695,37 +749,42 @@ struct QState {
 };
 }  // namespace
 
-// scratch for ny years x np probabilities; the weights into lane order (padding lanes: 0)
-void EnsembleCore::q_upload(const unsigned long long *q, int ny, int np) {
-  const size_t words = QState(nullptr, ny, np).words, hwords = (size_t)ny * (size_t)np * 256;
-  d_qstate_.reserve(words, *this, "hipMalloc quantile state");
-  d_qhist_.reserve(hwords, *this, "hipMalloc quantile histograms");
-  if (!q) return;
-  if (!d_q_) check(hipMalloc(&d_q_, 8 * (size_t)npad_), "hipMalloc quantile weights");
-  std::vector<unsigned long long> ql((size_t)npad_, 0ull);
-  for (int m = 0; m < n_; ++m) ql[(size_t)lane_of_member_[(size_t)m]] = q[m];
-  check(hipMemcpy(d_q_, ql.data(), 8 * (size_t)npad_, hipMemcpyHostToDevice), "quantile weights");
+int EnsembleCore::q_start(const RowSource &rs, const Groups &g, const unsigned long long *q, int np) {
+  const Rows r = rows(rs, g, np);
+  const int nrows = std::max(g.ngroups, 1) * r.nrows;
+  if (g.ngroups) upload_labels(g.labels);
+  d_qstate_.reserve(QState(nullptr, nrows, np).words, *this, "hipMalloc quantile state");
+  d_qhist_.reserve((size_t)nrows * (size_t)np * 256, *this, "hipMalloc quantile histograms");
+  minmax(r, g.ngroups, lane_weights(q), QState(d_qstate_.get(), nrows, np).st);
+  q_src_ = r.block; q_iy0_ = r.iy0; q_ny_ = r.nrows; q_np_ = np; q_weighted_ = q != nullptr; q_groups_ = g.ngroups;
+  return nrows;
 }
 
-void EnsembleCore::q_select(const double *src, int iy0, int ny, const unsigned long long *q,
-                            const double *probs, int np, double *out_host, long long *n_part) {
-  q_upload(q, ny, np);
+void EnsembleCore::q_hist(const int *lo, const unsigned long long *prefix) {
+  const unsigned long long *dq = q_weighted_ ? d_q_ : nullptr;
+  check(q_groups_ ? hx_launch_gq_hist(q_src_, n_, npad_, q_iy0_, q_ny_, dq, d_glab_, q_groups_, lo, prefix, q_np_,
+                                      d_qhist_.get(), stream_)
+                  : hx_launch_q_hist(q_src_, n_, npad_, q_iy0_, q_ny_, dq, lo, prefix, q_np_,
+                                     (post_flags_ & 2) ? 1 : 0, d_qhist_.get(), stream_),
+        "quantile histogram kernel");
+}
+
+void EnsembleCore::quantiles(const RowSource &rs, const Groups &g, const unsigned long long *q,
+                             const double *probs, int nprobs, double *out_host, long long *n_part) {
+  const int ny = q_start(rs, g, q, nprobs), np = nprobs;
   QState s(d_qstate_.get(), ny, np);
   const size_t yp = (size_t)ny * (size_t)np;
-  check(hipMemsetAsync(s.st, 0, 8 * 4 * (size_t)ny, stream_), "quantile state");
   check(hipMemsetAsync(d_qhist_.get(), 0, 8 * yp * 256, stream_), "quantile histograms");
   check(hipMemcpyAsync(s.probs, probs, sizeof(double) * (size_t)np, hipMemcpyHostToDevice, stream_), "quantile probs");
-  const unsigned long long *dq = q ? d_q_ : nullptr;
-  check(hx_launch_q_minmax(src, n_, npad_, iy0, ny, dq, s.st, stream_), "quantile min/max kernel");
   check(hx_launch_q_init(s.st, ny, s.probs, np, (post_flags_ & 1) ? 0 : 1, s.lo, s.prefix, s.rem, stream_),
         "quantile init kernel");
-  // eight 8-bit digits at most; a year whose select has finished makes its workgroups return at once
+  // eight 8-bit digits at most; a row whose select has finished makes its workgroups return at once
+  // (grouped: when every group of its row has finished)
   for (int pass = 0; pass < 8; ++pass) {
-    check(hx_launch_q_hist(src, n_, npad_, iy0, ny, dq, s.lo, s.prefix, np, (post_flags_ & 2) ? 1 : 0,
-                           d_qhist_.get(), stream_), "quantile histogram kernel");
+    q_hist(s.lo, s.prefix);
     check(hx_launch_q_pick(ny, s.lo, s.prefix, s.rem, np, d_qhist_.get(), stream_), "quantile pick kernel");
   }
-  std::vector<unsigned long long> h((size_t)4 * ny + yp);   // year records, then prefixes: adjacent
+  std::vector<unsigned long long> h((size_t)4 * ny + yp);   // row records, then prefixes: adjacent
   check(hipMemcpyAsync(h.data(), s.st, 8 * h.size(), hipMemcpyDeviceToHost, stream_), "quantile fetch");
   check(hipStreamSynchronize(stream_), "quantile sync");
   for (int y = 0; y < ny; ++y) {
@@ -736,393 +795,123 @@ void EnsembleCore::q_select(const double *src, int iy0, int ny, const unsigned l
   }
 }
 
-void EnsembleCore::q_begin_block(const double *src, int iy0, int ny, const unsigned long long *q, int np,
-                                 unsigned long long *st_host) {
-  q_upload(q, ny, np);
-  QState s(d_qstate_.get(), ny, np);
-  check(hipMemsetAsync(s.st, 0, 8 * 4 * (size_t)ny, stream_), "quantile state");
-  check(hx_launch_q_minmax(src, n_, npad_, iy0, ny, q ? d_q_ : nullptr, s.st, stream_), "quantile min/max kernel");
-  check(hipMemcpyAsync(st_host, s.st, 8 * 4 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "quantile fetch");
+void EnsembleCore::q_begin(const RowSource &rs, const Groups &g, const unsigned long long *q, int nprobs,
+                           unsigned long long *st_host) {
+  const int ny = q_start(rs, g, q, nprobs);
+  check(hipMemcpyAsync(st_host, QState(d_qstate_.get(), ny, nprobs).st, 8 * 4 * (size_t)ny, hipMemcpyDeviceToHost,
+                       stream_), "quantile fetch");
   check(hipStreamSynchronize(stream_), "quantile sync");
-  q_src_ = src; q_iy0_ = iy0; q_ny_ = ny; q_np_ = np; q_weighted_ = q != nullptr; q_groups_ = 0;
-}
-
-void EnsembleCore::quantiles(const std::string &capability, int year0, int year1,
-                             const unsigned long long *q, const double *probs, int nprobs,
-                             double *out_host, long long *n_part) {
-  const double *src = q_check(capability, year0, year1, nprobs);
-  sync();
-  q_select(src, year0 - scen_.start, year1 - year0 + 1, q, probs, nprobs, out_host, n_part);
-}
-
-void EnsembleCore::q_begin(const std::string &capability, int year0, int year1,
-                           const unsigned long long *q, int nprobs, unsigned long long *st_host) {
-  const double *src = q_check(capability, year0, year1, nprobs);
-  sync();
-  q_begin_block(src, year0 - scen_.start, year1 - year0 + 1, q, nprobs, st_host);
 }
 
 void EnsembleCore::q_pass(const int *lo, const unsigned long long *prefix, unsigned long long *hist_host) {
   if (!q_src_) throw std::runtime_error("quantile pass without q_begin");
-  const int rows = q_groups_ ? q_groups_ * q_ny_ : q_ny_;   // a grouped call: (group, row) pairs
+  const int rows = std::max(q_groups_, 1) * q_ny_;
   QState s(d_qstate_.get(), rows, q_np_);
   const size_t yp = (size_t)rows * (size_t)q_np_;
   check(hipMemcpyAsync(s.lo, lo, sizeof(int) * (size_t)rows, hipMemcpyHostToDevice, stream_), "quantile lo");
   check(hipMemcpyAsync(s.prefix, prefix, 8 * yp, hipMemcpyHostToDevice, stream_), "quantile prefix");
   check(hipMemsetAsync(d_qhist_.get(), 0, 8 * yp * 256, stream_), "quantile histograms");
-  if (q_groups_)
-    check(hx_launch_gq_hist(q_src_, n_, npad_, q_iy0_, q_ny_, q_weighted_ ? d_q_ : nullptr, d_glab_, q_groups_,
-                            s.lo, s.prefix, q_np_, d_qhist_.get(), stream_), "grouped quantile histogram kernel");
-  else
-    check(hx_launch_q_hist(q_src_, n_, npad_, q_iy0_, q_ny_, q_weighted_ ? d_q_ : nullptr, s.lo, s.prefix,
-                           q_np_, (post_flags_ & 2) ? 1 : 0, d_qhist_.get(), stream_), "quantile histogram kernel");
+  q_hist(s.lo, s.prefix);
   check(hipMemcpyAsync(hist_host, d_qhist_.get(), 8 * yp * 256, hipMemcpyDeviceToHost, stream_), "quantile fetch");
   check(hipStreamSynchronize(stream_), "quantile sync");
 }
 
-// ---- quantiles and bin probabilities of the metrics and of a recorded output ---------------------
+// ---- weighted bin probabilities (hx_ensemble_probabilities) ----------------------------------------
 
-void EnsembleCore::metric_quantiles(const std::string &capability, const hx_metric *specs, int nspecs,
-                                    const unsigned long long *q, const double *probs, int nprobs,
-                                    double *out_host, long long *n_part) {
-  const double *src = nullptr;
-  metric_check(capability, specs, nspecs, "hx_metric_quantiles", &src);
-  check_nprobs("hx_metric_quantiles", nprobs);
-  if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
-  sync();
-  q_select(metric_block(src, specs, nspecs), 0, nspecs, q, probs, nprobs, out_host, n_part);
-}
-
-void EnsembleCore::mq_begin(const std::string &capability, const hx_metric *specs, int nspecs,
-                            const unsigned long long *q, int nprobs, unsigned long long *st_host) {
-  const double *src = nullptr;
-  metric_check(capability, specs, nspecs, "hx_metric_quantiles", &src);
-  check_nprobs("hx_metric_quantiles", nprobs);
-  if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
-  sync();
-  q_begin_block(metric_block(src, specs, nspecs), 0, nspecs, q, nprobs, st_host);
-}
-
-// edges checked by the fleet (1..31, finite, strictly ascending)
-void EnsembleCore::bin_block(const double *src, int iy0, int nrows, const unsigned long long *q,
-                             const double *edges, int nedges, unsigned long long *sums_host) {
-  q_upload(q, 1, 1);   // (the weights into lane order; the select's scratch at its smallest)
-  const size_t words = 32 + (size_t)nrows * (size_t)(nedges + 2);
+void EnsembleCore::bin_sums(const RowSource &rs, const Groups &g, const unsigned long long *q, const double *edges,
+                            int nedges, unsigned long long *sums_host) {
+  const Rows r = rows(rs, g, 1);
+  if (g.ngroups) upload_labels(g.labels);
+  const unsigned long long *dq = lane_weights(q);
+  const size_t words = 32 + (size_t)std::max(g.ngroups, 1) * (size_t)r.nrows * (size_t)(nedges + 2);
   d_bin_.reserve(words, *this, "hipMalloc bin sums");
   double *d_edges = reinterpret_cast<double *>(d_bin_.get());
   unsigned long long *d_sums = d_bin_.get() + 32;
   check(hipMemcpyAsync(d_edges, edges, sizeof(double) * (size_t)nedges, hipMemcpyHostToDevice, stream_), "bin edges");
   check(hipMemsetAsync(d_sums, 0, 8 * (words - 32), stream_), "bin sums");
-  check(hx_launch_bin(src, n_, npad_, iy0, nrows, q ? d_q_ : nullptr, d_edges, nedges, d_sums, stream_),
+  check(g.ngroups ? hx_launch_gbin(r.block, n_, npad_, r.iy0, r.nrows, dq, d_glab_, g.ngroups, d_edges, nedges,
+                                   d_sums, stream_)
+                  : hx_launch_bin(r.block, n_, npad_, r.iy0, r.nrows, dq, d_edges, nedges, d_sums, stream_),
         "bin kernel");
   check(hipMemcpyAsync(sums_host, d_sums, 8 * (words - 32), hipMemcpyDeviceToHost, stream_), "bin fetch");
   check(hipStreamSynchronize(stream_), "bin sync");
 }
 
-void EnsembleCore::bin_sums(const std::string &capability, int year0, int year1, const unsigned long long *q,
-                            const double *edges, int nedges, unsigned long long *sums_host) {
-  const double *src = q_check(capability, year0, year1, 1, "hx_ensemble_probabilities");
-  sync();
-  bin_block(src, year0 - scen_.start, year1 - year0 + 1, q, edges, nedges, sums_host);
-}
-
-void EnsembleCore::metric_bin_sums(const std::string &capability, const hx_metric *specs, int nspecs,
-                                   const unsigned long long *q, const double *edges, int nedges,
-                                   unsigned long long *sums_host) {
-  const double *src = nullptr;
-  metric_check(capability, specs, nspecs, "hx_metric_probabilities", &src);
-  sync();
-  bin_block(metric_block(src, specs, nspecs), 0, nspecs, q, edges, nedges, sums_host);
-}
-
-// ---- quantiles, bin probabilities and moments of the pair metrics --------------------------------
-
-void EnsembleCore::pair_metric_quantiles(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
-                                         const double *probs, int nprobs, double *out_host, long long *n_part) {
-  const char *fn = "hx_pair_metric_quantiles";
-  const double *sa = nullptr, *sb = nullptr;
-  pair_metric_check(cap_a, pc, fn, &sa, &sb);
-  check_nprobs(fn, nprobs);
-  if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
-  sync();
-  q_select(pair_metric_block(sa, sb, pc), 0, pc.nspecs, q, probs, nprobs, out_host, n_part);
-}
-
-void EnsembleCore::pmq_begin(const std::string &cap_a, const PairCall &pc, const unsigned long long *q, int nprobs,
-                             unsigned long long *st_host) {
-  const char *fn = "hx_pair_metric_quantiles";
-  const double *sa = nullptr, *sb = nullptr;
-  pair_metric_check(cap_a, pc, fn, &sa, &sb);
-  check_nprobs(fn, nprobs);
-  if (const char *e = std::getenv("HECTOR_AMD_POST_AB")) post_flags_ = std::atoi(e);
-  sync();
-  q_begin_block(pair_metric_block(sa, sb, pc), 0, pc.nspecs, q, nprobs, st_host);
-}
-
-void EnsembleCore::pair_metric_bin_sums(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
-                                        const double *edges, int nedges, unsigned long long *sums_host) {
-  const char *fn = "hx_pair_metric_probabilities";
-  const double *sa = nullptr, *sb = nullptr;
-  pair_metric_check(cap_a, pc, fn, &sa, &sb);
-  sync();
-  bin_block(pair_metric_block(sa, sb, pc), 0, pc.nspecs, q, edges, nedges, sums_host);
-}
-
-void EnsembleCore::pair_mom_begin(const std::string &cap_a, const PairCall &pc, const unsigned long long *q,
-                                  const double *pred, int npred, const double *c, unsigned long long *st_host) {
-  const char *fn = "hx_pair_metric_moments";
-  const double *sa = nullptr, *sb = nullptr;
-  pair_metric_check(cap_a, pc, fn, &sa, &sb);
-  sync();
-  mom_begin_block(pair_metric_block(sa, sb, pc), 0, pc.nspecs, q, pred, npred, c, st_host);
-}
-
-// ---- weighted moments and cross moments with predictors (hx_ensemble_moments, hx_metric_moments) ---
+// ---- weighted moments and cross moments with predictors (hx_ensemble_moments) ----------------------
 
 namespace {
 // d_mom_ in 8-byte words: the call's weights and predictors in member order and in lane order, the
-// predictor shifts, the rows' records and shifts, the chunks' partial sums and the sums
+// groups' predictor shifts, the rows' records and shifts, the chunks' partial sums and the sums; for
+// a grouped call (ngroups > 0, ny = ngroups * nrows) the labels in member order behind them, two to
+// a word
 struct MomBuf {
-  unsigned long long *q_mem, *q_lane, *st;
-  double *pred_mem, *c, *qd_lane, *e_lane, *shift, *part, *out;
-  size_t words, lane_words;
-  MomBuf(unsigned long long *base, int n, int npad, int npred, int ny, int nchunks) {
-    const size_t N = (size_t)n, P = (size_t)npad, K = (size_t)npred, Y = (size_t)ny;
-    const size_t nc = 2 + 3 * K;
-    q_lane = base;                                             // [npad]  } zeroed before the prepare
-    qd_lane = reinterpret_cast<double *>(q_lane + P);          // [npad]  } kernel: padding lanes
-    e_lane = qd_lane + P;                                      // [npred][npad] } take no part
-    lane_words = (2 + K) * P;
-    q_mem = base + lane_words;                                 // [n]
-    pred_mem = reinterpret_cast<double *>(q_mem + N);          // [npred][n]
-    c = pred_mem + K * N;                                      // [8]
-    st = reinterpret_cast<unsigned long long *>(c + 8);        // [ny][4]
-    shift = reinterpret_cast<double *>(st + 4 * Y);            // [ny]
-    part = shift + Y;                                          // [ny][nchunks][nc]
-    out = part + Y * (size_t)nchunks * nc;                     // [ny][nc]
-    words = lane_words + N + K * N + 8 + 5 * Y + Y * (size_t)nchunks * nc + Y * nc;
-  }
-};
-}  // namespace
-
-// the minimum pass over the rows iy0 .. iy0 + ny - 1 of a [rows][npad_] block in lane order, with
-// the call's effective weights; st_host[ny][4] as q_begin_block returns it
-void EnsembleCore::mom_begin_block(const double *src, int iy0, int ny, const unsigned long long *q,
-                                   const double *pred, int npred, const double *c,
-                                   unsigned long long *st_host) {
-  const int nchunks = hx_mom_chunks(n_);
-  const size_t words = MomBuf(nullptr, n_, npad_, npred, ny, nchunks).words;
-  d_mom_.reserve(words, *this, "hipMalloc moments");
-  MomBuf b(d_mom_.get(), n_, npad_, npred, ny, nchunks);
-  const size_t N = (size_t)n_;
-  check(hipMemsetAsync(b.q_lane, 0, 8 * b.lane_words, stream_), "moments lanes");
-  check(hipMemsetAsync(b.st, 0, 8 * 4 * (size_t)ny, stream_), "moments state");
-  check(hipMemcpyAsync(b.q_mem, q, 8 * N, hipMemcpyHostToDevice, stream_), "moments weights");
-  if (npred)
-    check(hipMemcpyAsync(b.pred_mem, pred, 8 * N * (size_t)npred, hipMemcpyHostToDevice, stream_),
-          "moments predictors");
-  check(hipMemcpyAsync(b.c, c, 8 * 8, hipMemcpyHostToDevice, stream_), "moments predictor shifts");
-  check(hx_launch_mom_prepare(b.q_mem, b.pred_mem, npred, n_, npad_, d_lane_of_member_, b.c, b.q_lane,
-                              b.qd_lane, b.e_lane, stream_), "moments prepare kernel");
-  check(hx_launch_q_minmax(src, n_, npad_, iy0, ny, b.q_lane, b.st, stream_), "moments min kernel");
-  check(hipMemcpyAsync(st_host, b.st, 8 * 4 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "moments fetch");
-  check(hipStreamSynchronize(stream_), "moments sync");   // (q, pred and c are the caller's until here)
-  mom_src_ = src; mom_iy0_ = iy0; mom_ny_ = ny; mom_npred_ = npred; mom_groups_ = 0;
-}
-
-void EnsembleCore::mom_begin(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                             int nspecs, const unsigned long long *q, const double *pred, int npred,
-                             const double *c, unsigned long long *st_host, const char *fn) {
-  const double *src = nullptr;
-  if (specs) {
-    metric_check(capability, specs, nspecs, fn, &src);
-    sync();
-    mom_begin_block(metric_block(src, specs, nspecs), 0, nspecs, q, pred, npred, c, st_host);
-  } else {
-    src = q_check(capability, year0, year1, 1, fn);
-    sync();
-    mom_begin_block(src, year0 - scen_.start, year1 - year0 + 1, q, pred, npred, c, st_host);
-  }
-}
-
-// the sum pass over the block mom_begin prepared: shift_host[ny] (the smallest participating value
-// of every row over ALL shards) -> sums_host[ny][2 + 3 npred] of this core's members
-void EnsembleCore::mom_finish(const double *shift_host, double *sums_host) {
-  if (!mom_src_) throw std::runtime_error("moment sums without mom_begin");
-  const int ny = mom_ny_, npred = mom_npred_;
-  MomBuf b(d_mom_.get(), n_, npad_, npred, ny, hx_mom_chunks(n_));
-  const size_t nc = 2 + 3 * (size_t)npred;
-  check(hipMemcpyAsync(b.shift, shift_host, 8 * (size_t)ny, hipMemcpyHostToDevice, stream_), "moments shifts");
-  check(hx_launch_moments(mom_src_, n_, npad_, mom_iy0_, ny, b.qd_lane, b.e_lane, npred, b.shift, b.part,
-                          b.out, stream_), "moments kernel");
-  check(hipMemcpyAsync(sums_host, b.out, 8 * (size_t)ny * nc, hipMemcpyDeviceToHost, stream_), "moments fetch");
-  check(hipStreamSynchronize(stream_), "moments sync");
-  mom_src_ = nullptr;
-}
-
-// ---- grouped summaries (hx_group_quantiles, hx_group_probabilities, hx_group_moments) --------------
-// The ungrouped steps above over (group, row) pairs: the state arrays hold ngroups * nrows rows in
-// group-major order, the grouped kernels fill them from one read of every row, and the init, pick
-// and reduce kernels run over them unchanged.
-
-const double *EnsembleCore::grp_source(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                                       int nspecs, int nprobs, const char *fn, int *iy0, int *nrows) {
-  const double *src = grp_check(capability, year0, year1, specs, nspecs, nprobs, fn);
-  sync();
-  if (specs) { *iy0 = 0; *nrows = nspecs; return metric_block(src, specs, nspecs); }
-  *iy0 = year0 - scen_.start; *nrows = year1 - year0 + 1;
-  return src;
-}
-
-void EnsembleCore::grp_upload_labels(const int *labels) {
-  if (!d_glab_) check(hipMalloc(&d_glab_, sizeof(int) * ((size_t)npad_ + (size_t)n_)), "hipMalloc group labels");
-  int *d_mem = d_glab_ + npad_;
-  check(hipMemsetAsync(d_glab_, 0xff, sizeof(int) * (size_t)npad_, stream_), "group labels");   // -1: in no group
-  check(hipMemcpyAsync(d_mem, labels, sizeof(int) * (size_t)n_, hipMemcpyHostToDevice, stream_), "group labels");
-  check(hx_launch_grp_prepare(d_mem, n_, npad_, d_lane_of_member_, d_glab_, stream_), "group label kernel");
-}
-
-void EnsembleCore::grp_quantiles(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                                 int nspecs, const int *labels, int ngroups, const unsigned long long *q,
-                                 const double *probs, int nprobs, double *out_host, long long *n_part,
-                                 const char *fn) {
-  int iy0 = 0, ny = 0;
-  const double *src = grp_source(capability, year0, year1, specs, nspecs, nprobs, fn, &iy0, &ny);
-  const int np = nprobs, rows = ngroups * ny;
-  grp_upload_labels(labels);
-  q_upload(q, rows, np);
-  QState s(d_qstate_.get(), rows, np);
-  const size_t yp = (size_t)rows * (size_t)np;
-  check(hipMemsetAsync(s.st, 0, 8 * 4 * (size_t)rows, stream_), "quantile state");
-  check(hipMemsetAsync(d_qhist_.get(), 0, 8 * yp * 256, stream_), "quantile histograms");
-  check(hipMemcpyAsync(s.probs, probs, sizeof(double) * (size_t)np, hipMemcpyHostToDevice, stream_), "quantile probs");
-  const unsigned long long *dq = q ? d_q_ : nullptr;
-  check(hx_launch_gq_minmax(src, n_, npad_, iy0, ny, dq, d_glab_, ngroups, s.st, stream_),
-        "grouped quantile min/max kernel");
-  check(hx_launch_q_init(s.st, rows, s.probs, np, (post_flags_ & 1) ? 0 : 1, s.lo, s.prefix, s.rem, stream_),
-        "quantile init kernel");
-  // eight digits at most; a workgroup returns at once when every group of its year has finished
-  for (int pass = 0; pass < 8; ++pass) {
-    check(hx_launch_gq_hist(src, n_, npad_, iy0, ny, dq, d_glab_, ngroups, s.lo, s.prefix, np, d_qhist_.get(), stream_),
-          "grouped quantile histogram kernel");
-    check(hx_launch_q_pick(rows, s.lo, s.prefix, s.rem, np, d_qhist_.get(), stream_), "quantile pick kernel");
-  }
-  std::vector<unsigned long long> h((size_t)4 * rows + yp);   // records, then prefixes: adjacent
-  check(hipMemcpyAsync(h.data(), s.st, 8 * h.size(), hipMemcpyDeviceToHost, stream_), "quantile fetch");
-  check(hipStreamSynchronize(stream_), "quantile sync");
-  for (int r = 0; r < rows; ++r) {
-    const unsigned long long cnt = h[(size_t)4 * r + 3];
-    if (n_part) n_part[r] = (long long)cnt;
-    for (int j = 0; j < np; ++j)
-      out_host[(size_t)r * np + j] = cnt ? hxq_key_to_double(h[(size_t)4 * rows + (size_t)r * np + j]) : std::nan("");
-  }
-}
-
-void EnsembleCore::grp_q_begin(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                               int nspecs, const int *labels, int ngroups, const unsigned long long *q,
-                               int nprobs, unsigned long long *st_host, const char *fn) {
-  int iy0 = 0, ny = 0;
-  const double *src = grp_source(capability, year0, year1, specs, nspecs, nprobs, fn, &iy0, &ny);
-  const int rows = ngroups * ny;
-  grp_upload_labels(labels);
-  q_upload(q, rows, nprobs);
-  QState s(d_qstate_.get(), rows, nprobs);
-  check(hipMemsetAsync(s.st, 0, 8 * 4 * (size_t)rows, stream_), "quantile state");
-  check(hx_launch_gq_minmax(src, n_, npad_, iy0, ny, q ? d_q_ : nullptr, d_glab_, ngroups, s.st, stream_),
-        "grouped quantile min/max kernel");
-  check(hipMemcpyAsync(st_host, s.st, 8 * 4 * (size_t)rows, hipMemcpyDeviceToHost, stream_), "quantile fetch");
-  check(hipStreamSynchronize(stream_), "quantile sync");
-  q_src_ = src; q_iy0_ = iy0; q_ny_ = ny; q_np_ = nprobs; q_weighted_ = q != nullptr; q_groups_ = ngroups;
-}
-
-void EnsembleCore::grp_bin_sums(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                                int nspecs, const int *labels, int ngroups, const unsigned long long *q,
-                                const double *edges, int nedges, unsigned long long *sums_host, const char *fn) {
-  int iy0 = 0, ny = 0;
-  const double *src = grp_source(capability, year0, year1, specs, nspecs, 1, fn, &iy0, &ny);
-  grp_upload_labels(labels);
-  q_upload(q, 1, 1);   // (the weights into lane order; the select's scratch at its smallest)
-  const size_t words = 32 + (size_t)ngroups * (size_t)ny * (size_t)(nedges + 2);
-  d_bin_.reserve(words, *this, "hipMalloc bin sums");
-  double *d_edges = reinterpret_cast<double *>(d_bin_.get());
-  unsigned long long *d_sums = d_bin_.get() + 32;
-  check(hipMemcpyAsync(d_edges, edges, sizeof(double) * (size_t)nedges, hipMemcpyHostToDevice, stream_), "bin edges");
-  check(hipMemsetAsync(d_sums, 0, 8 * (words - 32), stream_), "bin sums");
-  check(hx_launch_gbin(src, n_, npad_, iy0, ny, q ? d_q_ : nullptr, d_glab_, ngroups, d_edges, nedges, d_sums,
-                       stream_), "grouped bin kernel");
-  check(hipMemcpyAsync(sums_host, d_sums, 8 * (words - 32), hipMemcpyDeviceToHost, stream_), "bin fetch");
-  check(hipStreamSynchronize(stream_), "bin sync");
-}
-
-namespace {
-// d_mom_ of a grouped call, in 8-byte words: MomBuf over ngroups * ny rows, with ngroups x 8 predictor
-// shifts and the labels in member order (two to a word) behind it
-struct GrpMomBuf {
   unsigned long long *q_mem, *q_lane, *st;
   double *pred_mem, *c, *qd_lane, *e_lane, *shift, *part, *out;
   int *lab_mem;
   size_t words, lane_words;
-  GrpMomBuf(unsigned long long *base, int n, int npad, int npred, int rows, int nchunks, int ngroups) {
-    const size_t N = (size_t)n, P = (size_t)npad, K = (size_t)npred, Y = (size_t)rows, G = (size_t)ngroups;
-    const size_t nc = 2 + 3 * K;
+  MomBuf(unsigned long long *base, int n, int npad, int npred, int ny, int nchunks, int ngroups) {
+    const size_t N = (size_t)n, P = (size_t)npad, K = (size_t)npred, Y = (size_t)ny;
+    const size_t nc = 2 + 3 * K, G = (size_t)std::max(ngroups, 1);
     q_lane = base;                                             // [npad]  } zeroed before the prepare
     qd_lane = reinterpret_cast<double *>(q_lane + P);          // [npad]  } kernel: padding lanes
     e_lane = qd_lane + P;                                      // [npred][npad] } take no part
     lane_words = (2 + K) * P;
     q_mem = base + lane_words;                                 // [n]
     pred_mem = reinterpret_cast<double *>(q_mem + N);          // [npred][n]
-    c = pred_mem + K * N;                                      // [ngroups][8]
-    st = reinterpret_cast<unsigned long long *>(c + 8 * G);    // [rows][4]
-    shift = reinterpret_cast<double *>(st + 4 * Y);            // [rows]
-    part = shift + Y;                                          // [rows][nchunks][nc]
-    out = part + Y * (size_t)nchunks * nc;                     // [rows][nc]
-    lab_mem = reinterpret_cast<int *>(out + Y * nc);           // [n]
-    words = lane_words + N + K * N + 8 * G + 5 * Y + Y * (size_t)nchunks * nc + Y * nc + (N + 1) / 2;
+    c = pred_mem + K * N;                                      // [G][8]
+    st = reinterpret_cast<unsigned long long *>(c + 8 * G);    // [ny][4]
+    shift = reinterpret_cast<double *>(st + 4 * Y);            // [ny]
+    part = shift + Y;                                          // [ny][nchunks][nc]
+    out = part + Y * (size_t)nchunks * nc;                     // [ny][nc]
+    lab_mem = reinterpret_cast<int *>(out + Y * nc);           // [n], grouped only
+    words = lane_words + N + K * N + 8 * G + 5 * Y + Y * (size_t)nchunks * nc + Y * nc + (ngroups ? (N + 1) / 2 : 0);
   }
 };
 }  // namespace
 
-void EnsembleCore::grp_mom_begin(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                                 int nspecs, const int *labels, int ngroups, const unsigned long long *q,
-                                 const double *pred, int npred, const double *c, unsigned long long *st_host,
-                                 const char *fn) {
-  int iy0 = 0, ny = 0;
-  const double *src = grp_source(capability, year0, year1, specs, nspecs, 1, fn, &iy0, &ny);
-  const int nchunks = hx_mom_chunks(n_), rows = ngroups * ny;
-  const size_t words = GrpMomBuf(nullptr, n_, npad_, npred, rows, nchunks, ngroups).words;
-  d_mom_.reserve(words, *this, "hipMalloc moments");
-  GrpMomBuf b(d_mom_.get(), n_, npad_, npred, rows, nchunks, ngroups);
+void EnsembleCore::mom_begin(const RowSource &rs, const Groups &g, const unsigned long long *q, const double *pred,
+                             int npred, const double *c, unsigned long long *st_host) {
+  const Rows r = rows(rs, g, 1);
+  const int G = g.ngroups, ny = std::max(G, 1) * r.nrows, nchunks = hx_mom_chunks(n_);
+  d_mom_.reserve(MomBuf(nullptr, n_, npad_, npred, ny, nchunks, G).words, *this, "hipMalloc moments");
+  MomBuf b(d_mom_.get(), n_, npad_, npred, ny, nchunks, G);
   const size_t N = (size_t)n_;
-  if (!d_glab_) check(hipMalloc(&d_glab_, sizeof(int) * ((size_t)npad_ + N)), "hipMalloc group labels");
   check(hipMemsetAsync(b.q_lane, 0, 8 * b.lane_words, stream_), "moments lanes");
-  check(hipMemsetAsync(d_glab_, 0xff, sizeof(int) * (size_t)npad_, stream_), "group labels");
-  check(hipMemsetAsync(b.st, 0, 8 * 4 * (size_t)rows, stream_), "moments state");
   check(hipMemcpyAsync(b.q_mem, q, 8 * N, hipMemcpyHostToDevice, stream_), "moments weights");
-  check(hipMemcpyAsync(b.lab_mem, labels, sizeof(int) * N, hipMemcpyHostToDevice, stream_), "group labels");
   if (npred)
     check(hipMemcpyAsync(b.pred_mem, pred, 8 * N * (size_t)npred, hipMemcpyHostToDevice, stream_),
           "moments predictors");
-  check(hipMemcpyAsync(b.c, c, 8 * 8 * (size_t)ngroups, hipMemcpyHostToDevice, stream_), "moments predictor shifts");
-  check(hx_launch_gmom_prepare(b.q_mem, b.pred_mem, b.lab_mem, npred, n_, npad_, d_lane_of_member_, b.c, b.q_lane,
-                               b.qd_lane, b.e_lane, d_glab_, stream_), "grouped moments prepare kernel");
-  check(hx_launch_gq_minmax(src, n_, npad_, iy0, ny, b.q_lane, d_glab_, ngroups, b.st, stream_),
-        "grouped moments min kernel");
-  check(hipMemcpyAsync(st_host, b.st, 8 * 4 * (size_t)rows, hipMemcpyDeviceToHost, stream_), "moments fetch");
-  check(hipStreamSynchronize(stream_), "moments sync");   // (q, pred, c and labels are the caller's until here)
-  mom_src_ = src; mom_iy0_ = iy0; mom_ny_ = ny; mom_npred_ = npred; mom_groups_ = ngroups;
+  check(hipMemcpyAsync(b.c, c, 8 * 8 * (size_t)std::max(G, 1), hipMemcpyHostToDevice, stream_),
+        "moments predictor shifts");
+  if (G) {   // (the prepare kernel brings the labels to lane order with the weights)
+    check(hipMemcpyAsync(b.lab_mem, g.labels, sizeof(int) * N, hipMemcpyHostToDevice, stream_), "group labels");
+    check(hx_launch_gmom_prepare(b.q_mem, b.pred_mem, b.lab_mem, npred, n_, npad_, d_lane_of_member_, b.c, b.q_lane,
+                                 b.qd_lane, b.e_lane, group_labels(), stream_), "grouped moments prepare kernel");
+  } else {
+    check(hx_launch_mom_prepare(b.q_mem, b.pred_mem, npred, n_, npad_, d_lane_of_member_, b.c, b.q_lane,
+                                b.qd_lane, b.e_lane, stream_), "moments prepare kernel");
+  }
+  minmax(r, G, b.q_lane, b.st);
+  check(hipMemcpyAsync(st_host, b.st, 8 * 4 * (size_t)ny, hipMemcpyDeviceToHost, stream_), "moments fetch");
+  check(hipStreamSynchronize(stream_), "moments sync");   // (q, pred, c and the labels are the caller's until here)
+  mom_src_ = r.block; mom_iy0_ = r.iy0; mom_ny_ = r.nrows; mom_npred_ = npred; mom_groups_ = G;
 }
 
-void EnsembleCore::grp_mom_finish(const double *shift_host, double *sums_host) {
-  if (!mom_src_ || !mom_groups_) throw std::runtime_error("grouped moment sums without grp_mom_begin");
-  const int ny = mom_ny_, npred = mom_npred_, G = mom_groups_, rows = G * ny;
-  GrpMomBuf b(d_mom_.get(), n_, npad_, npred, rows, hx_mom_chunks(n_), G);
+// the sum pass over the block mom_begin prepared: shift_host[rows] (the smallest participating value
+// of every row over ALL shards) -> sums_host[rows][2 + 3 npred] of this core's members
+void EnsembleCore::mom_finish(const double *shift_host, double *sums_host) {
+  if (!mom_src_) throw std::runtime_error("moment sums without mom_begin");
+  const int nrows = mom_ny_, npred = mom_npred_, G = mom_groups_, ny = std::max(G, 1) * nrows;
+  MomBuf b(d_mom_.get(), n_, npad_, npred, ny, hx_mom_chunks(n_), G);
   const size_t nc = 2 + 3 * (size_t)npred;
-  check(hipMemcpyAsync(b.shift, shift_host, 8 * (size_t)rows, hipMemcpyHostToDevice, stream_), "moments shifts");
-  check(hx_launch_gmoments(mom_src_, n_, npad_, mom_iy0_, ny, b.qd_lane, b.e_lane, d_glab_, G, npred, b.shift,
-                           b.part, b.out, stream_), "grouped moments kernel");
-  check(hipMemcpyAsync(sums_host, b.out, 8 * (size_t)rows * nc, hipMemcpyDeviceToHost, stream_), "moments fetch");
+  check(hipMemcpyAsync(b.shift, shift_host, 8 * (size_t)ny, hipMemcpyHostToDevice, stream_), "moments shifts");
+  check(G ? hx_launch_gmoments(mom_src_, n_, npad_, mom_iy0_, nrows, b.qd_lane, b.e_lane, d_glab_, G, npred, b.shift,
+                               b.part, b.out, stream_)
+          : hx_launch_moments(mom_src_, n_, npad_, mom_iy0_, nrows, b.qd_lane, b.e_lane, npred, b.shift, b.part,
+                              b.out, stream_), "moments kernel");
+  check(hipMemcpyAsync(sums_host, b.out, 8 * (size_t)ny * nc, hipMemcpyDeviceToHost, stream_), "moments fetch");
   check(hipStreamSynchronize(stream_), "moments sync");
-  mom_src_ = nullptr; mom_groups_ = 0;
+  mom_src_ = nullptr;
 }
 
 // ---- Sobol sums from a Saltelli design (hx_ensemble_sobol, hx_metric_sobol) -----------------------
@@ -1157,30 +946,14 @@ struct SobBuf {
 };
 }  // namespace
 
-void EnsembleCore::sobol_check(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                               int nspecs, const char *fn) {
-  const double *src = nullptr;
-  if (specs) metric_check(capability, specs, nspecs, fn, &src);
-  else (void)q_check(capability, year0, year1, 1, fn);
-}
-
-void EnsembleCore::sobol_begin(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                               int nspecs, int k, int n_base, const unsigned char *use, const char *fn) {
-  const std::string f(fn);
+void EnsembleCore::sobol_begin(const RowSource &rs, int k, int n_base, const unsigned char *use) {
+  const std::string f(rs.fn);
   if (k < 1 || k > HX_SOBOL_MAX_FACTORS) throw std::runtime_error(f + ": k must lie in 1..16");
   if (n_base < 1 || (long long)n_base * (long long)(k + 2) > (long long)n_)
     throw std::runtime_error(f + ": n_base * (k + 2) must lie in 1..n_members");
-  const double *src = nullptr;
-  int iy0 = 0, ny = nspecs;
-  if (specs) {
-    metric_check(capability, specs, nspecs, fn, &src);
-    sync();
-    src = metric_block(src, specs, nspecs);
-  } else {
-    src = q_check(capability, year0, year1, 1, fn);
-    sync();
-    iy0 = year0 - scen_.start; ny = year1 - year0 + 1;
-  }
+  const Rows r = rows(rs, Groups{nullptr, 0}, 1);
+  const double *src = r.block;
+  const int iy0 = r.iy0, ny = r.nrows;
   const int nchunks = hx_sobol_chunks(n_base);
   const size_t words = SobBuf(nullptr, k, n_base, ny, nchunks).words;
   d_sobol_.reserve(words, *this, "hipMalloc sobol");
@@ -1412,13 +1185,6 @@ struct RankBuf {
 };
 }  // namespace
 
-void EnsembleCore::rank_check(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                              int nspecs, const char *fn) {
-  const double *src = nullptr;
-  if (specs) metric_check(capability, specs, nspecs, fn, &src);
-  else (void)q_check(capability, year0, year1, 1, fn);
-}
-
 std::vector<unsigned long long> EnsembleCore::rank_rows(const char *fn, const double *src, int row0,
                                                         const int *rows, int nrows, const unsigned long long *q,
                                                         int mode, const double *obs, double *dst, int dst_row0) {
@@ -1430,14 +1196,7 @@ std::vector<unsigned long long> EnsembleCore::rank_rows(const char *fn, const do
                              std::to_string((8 * words) >> 20) + " MiB)");
   }
   RankBuf b(d_rank_.get(), n_, nrows);
-  const unsigned long long *dq = nullptr;
-  if (q) {   // member order -> lane order (padding lanes: 0; the sort never reads them)
-    if (!d_q_) check(hipMalloc(&d_q_, 8 * (size_t)npad_), "hipMalloc quantile weights");
-    std::vector<unsigned long long> ql((size_t)npad_, 0ull);
-    for (int m = 0; m < n_; ++m) ql[(size_t)lane_of_member_[(size_t)m]] = q[m];
-    check(hipMemcpy(d_q_, ql.data(), 8 * (size_t)npad_, hipMemcpyHostToDevice), "rank weights");
-    dq = d_q_;
-  }
+  const unsigned long long *dq = lane_weights(q);   // (the sort never reads the padding lanes)
   if (rows) check(hipMemcpy(b.rows, rows, sizeof(int) * (size_t)nrows, hipMemcpyHostToDevice), "rank rows");
   if (obs) check(hipMemcpy(b.obs, obs, sizeof(double) * (size_t)nrows, hipMemcpyHostToDevice), "rank observations");
   for (int r0 = 0; r0 < nrows; r0 += b.per) {   // (stream order: a batch has finished with the buffers before the next)
@@ -1529,80 +1288,32 @@ void EnsembleCore::crps(const std::string &capability, const int *years, const d
 }
 
 
-#else   // HX_HOST_EMULATION: the same entry points refuse, each where it refused before -- most at once,
-        // some behind their argument checks.  The helpers only they reach (q_select, q_begin_block,
-        // bin_block, mom_begin_block, grp_source, rank_rows and their like) are not built.
+#else   // HX_HOST_EMULATION: the same entry points refuse, each where it refused before.  The summary
+        // verbs over a RowSource refuse in rows_check: at once, or behind the checks of a pair or grouped
+        // call.  The helpers only the verbs reach (rows, q_start, minmax, rank_rows and their like) are
+        // not built.
 
 namespace {
-[[noreturn]] void refuse(const char *fn, bool why = true) {
-  throw std::runtime_error(std::string(fn) + " is not available in the host-emulation build" +
-                           (why ? " (its kernels are cooperative: LDS atomics and cross-lane operations)" : ""));
-}
 using Str = const std::string &;
 using U64 = unsigned long long;
 }  // namespace
 
-void EnsembleCore::quantiles(Str, int, int, const U64 *, const double *, int, double *, long long *) { refuse("hx_ensemble_quantiles"); }
-void EnsembleCore::q_begin(Str, int, int, const U64 *, int, U64 *) { refuse("hx_ensemble_quantiles"); }
+void EnsembleCore::quantiles(const RowSource &rs, const Groups &g, const U64 *, const double *, int nprobs, double *, long long *) { rows_check(rs, g, nprobs); }
+void EnsembleCore::q_begin(const RowSource &rs, const Groups &g, const U64 *, int nprobs, U64 *) { rows_check(rs, g, nprobs); }
 void EnsembleCore::q_pass(const int *, const U64 *, U64 *) { refuse("hx_ensemble_quantiles", false); }
-void EnsembleCore::metric_quantiles(Str, const hx_metric *, int, const U64 *, const double *, int, double *, long long *) { refuse("hx_metric_quantiles"); }
-void EnsembleCore::mq_begin(Str, const hx_metric *, int, const U64 *, int, U64 *) { refuse("hx_metric_quantiles"); }
-void EnsembleCore::bin_sums(Str, int, int, const U64 *, const double *, int, U64 *) { refuse("hx_ensemble_probabilities"); }
-void EnsembleCore::metric_bin_sums(Str, const hx_metric *, int, const U64 *, const double *, int, U64 *) { refuse("hx_metric_probabilities"); }
-void EnsembleCore::mom_begin(Str, int, int, const hx_metric *, int, const U64 *, const double *, int, const double *, U64 *, const char *fn) { refuse(fn); }
+void EnsembleCore::bin_sums(const RowSource &rs, const Groups &g, const U64 *, const double *, int, U64 *) { rows_check(rs, g, 1); }
+void EnsembleCore::mom_begin(const RowSource &rs, const Groups &g, const U64 *, const double *, int, const double *, U64 *) { rows_check(rs, g, 1); }
 void EnsembleCore::mom_finish(const double *, double *) { refuse("hx_ensemble_moments"); }
-void EnsembleCore::grp_mom_finish(const double *, double *) { refuse("hx_group_moments"); }
-void EnsembleCore::sobol_check(Str, int, int, const hx_metric *, int, const char *fn) { refuse(fn); }
-void EnsembleCore::sobol_begin(Str, int, int, const hx_metric *, int, int, int, const unsigned char *, const char *fn) { refuse(fn); }
+void EnsembleCore::sobol_begin(const RowSource &rs, int, int, const unsigned char *) { refuse(rs.fn); }
 void EnsembleCore::sobol_finish(double *, double *, long long *) { refuse("hx_ensemble_sobol"); }
 void EnsembleCore::comom_check(Str, int, int, const std::string *, int, int) { refuse("hx_ensemble_comoments"); }
 void EnsembleCore::comom_begin(Str, int, int, const std::string *, int, int, const U64 *, U64 *) { refuse("hx_ensemble_comoments"); }
 void EnsembleCore::comom_finish(const double *, double *, double *) { refuse("hx_ensemble_comoments"); }
-void EnsembleCore::rank_check(Str, int, int, const hx_metric *, int, const char *fn) { refuse(fn); }
 void EnsembleCore::series_rank(Str, Str, int, int, const U64 *, int) { refuse("hx_series_rank"); }
 void EnsembleCore::metric_ranks(Str, const hx_metric *, int, const U64 *, int, double *) { refuse("hx_metric_ranks"); }
 void EnsembleCore::crps(Str, const int *, const double *, int, const U64 *, double *, double *, long long *) { refuse("hx_ensemble_crps"); }
 
 // ... and those that check their arguments first
-void EnsembleCore::pair_metric_quantiles(Str cap_a, const PairCall &pc, const U64 *, const double *, int nprobs, double *, long long *) {
-  const double *sa = nullptr, *sb = nullptr;
-  pair_metric_check(cap_a, pc, "hx_pair_metric_quantiles", &sa, &sb);
-  check_nprobs("hx_pair_metric_quantiles", nprobs);
-  refuse("hx_pair_metric_quantiles");
-}
-void EnsembleCore::pmq_begin(Str cap_a, const PairCall &pc, const U64 *q, int nprobs, U64 *) {
-  pair_metric_quantiles(cap_a, pc, q, nullptr, nprobs, nullptr, nullptr);
-}
-void EnsembleCore::pair_metric_bin_sums(Str cap_a, const PairCall &pc, const U64 *, const double *, int, U64 *) {
-  const double *sa = nullptr, *sb = nullptr;
-  pair_metric_check(cap_a, pc, "hx_pair_metric_probabilities", &sa, &sb);
-  refuse("hx_pair_metric_probabilities");
-}
-void EnsembleCore::pair_mom_begin(Str cap_a, const PairCall &pc, const U64 *, const double *, int, const double *, U64 *) {
-  const double *sa = nullptr, *sb = nullptr;
-  pair_metric_check(cap_a, pc, "hx_pair_metric_moments", &sa, &sb);
-  refuse("hx_pair_metric_moments");
-}
-void EnsembleCore::grp_quantiles(Str capability, int year0, int year1, const hx_metric *specs, int nspecs, const int *, int,
-                                 const U64 *, const double *, int nprobs, double *, long long *, const char *fn) {
-  grp_check(capability, year0, year1, specs, nspecs, nprobs, fn);
-  refuse(fn);
-}
-void EnsembleCore::grp_q_begin(Str capability, int year0, int year1, const hx_metric *specs, int nspecs, const int *, int,
-                               const U64 *, int nprobs, U64 *, const char *fn) {
-  grp_check(capability, year0, year1, specs, nspecs, nprobs, fn);
-  refuse(fn);
-}
-void EnsembleCore::grp_bin_sums(Str capability, int year0, int year1, const hx_metric *specs, int nspecs, const int *, int,
-                                const U64 *, const double *, int, U64 *, const char *fn) {
-  grp_check(capability, year0, year1, specs, nspecs, 1, fn);
-  refuse(fn);
-}
-void EnsembleCore::grp_mom_begin(Str capability, int year0, int year1, const hx_metric *specs, int nspecs, const int *, int,
-                                 const U64 *, const double *, int, const double *, U64 *, const char *fn) {
-  grp_check(capability, year0, year1, specs, nspecs, 1, fn);
-  refuse(fn);
-}
 void EnsembleCore::member_score_whitened(Str capability, const int *years, const double *obs, const double *whiten, int n,
                                          int base_year0, int base_year1, double *out_host) {
   whitened_check(capability, years, obs, whiten, n, base_year0, base_year1, out_host);

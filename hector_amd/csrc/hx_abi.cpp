@@ -23,6 +23,15 @@ namespace {
 thread_local std::string g_err;
 int fail(const std::exception &e) { g_err = e.what(); return 1; }
 int fail(const char *msg) { g_err = msg; return 1; }
+
+// The rows of a summary call and its groups (ensemble_core.hpp), as the hx_* functions name them.
+hx::RowSource rows_of(const char *fn, const char *capability, int year0, int year1, const hx_metric *specs,
+                      int nspecs, const hx::PairCall *pair = nullptr) {
+  return {fn, capability, year0, year1, specs, nspecs, pair};
+}
+const hx::Groups kUngrouped{nullptr, 0};
+// A grouped call stays one whatever it passes: (NULL, 0) is refused for its labels, not read as ungrouped.
+hx::Groups groups_of(const int *labels, int ngroups) { return {labels, (labels || ngroups) ? ngroups : -1}; }
 }  // namespace
 
 #define HX_TRY(body)                                                           \
@@ -425,7 +434,8 @@ int hx_ensemble_quantiles(hx_core *core, const char *capability, int year0, int 
                           const double *weights, const double *probs, int nprobs, double *out,
                           long long *n_part) {
   if (!capability || !probs || !out) return fail("hx_ensemble_quantiles: null argument");
-  HX_TRY(core->core->quantiles(capability, year0, year1, weights, probs, nprobs, out, n_part))
+  HX_TRY(core->core->quantiles(rows_of("hx_ensemble_quantiles", capability, year0, year1, nullptr, 0), kUngrouped,
+                               weights, probs, nprobs, out, n_part))
 }
 int hx_member_metrics(hx_core *core, const char *capability, const hx_metric *specs, int nspecs,
                       double *out) {
@@ -436,58 +446,59 @@ int hx_metric_quantiles(hx_core *core, const char *capability, const hx_metric *
                         const double *weights, const double *probs, int nprobs, double *out,
                         long long *n_part) {
   if (!capability || !specs || !probs || !out) return fail("hx_metric_quantiles: null argument");
-  HX_TRY(core->core->metric_quantiles(capability, specs, nspecs, weights, probs, nprobs, out, n_part))
+  HX_TRY(core->core->quantiles(rows_of("hx_metric_quantiles", capability, 0, 0, specs, nspecs), kUngrouped, weights,
+                               probs, nprobs, out, n_part))
 }
 int hx_ensemble_probabilities(hx_core *core, const char *capability, int year0, int year1,
                               const double *weights, const double *edges, int nedges, double *prob,
                               unsigned long long *sums, long long *n_part) {
   if (!capability || !prob) return fail("hx_ensemble_probabilities: null argument");
-  HX_TRY(core->core->probabilities(capability, year0, year1, nullptr, 0, weights, edges, nedges, prob,
-                                   sums, n_part))
+  HX_TRY(core->core->probabilities(rows_of("hx_ensemble_probabilities", capability, year0, year1, nullptr, 0),
+                                   kUngrouped, weights, edges, nedges, prob, sums, n_part))
 }
 int hx_metric_probabilities(hx_core *core, const char *capability, const hx_metric *specs,
                             int nspecs, const double *weights, const double *edges, int nedges,
                             double *prob, unsigned long long *sums, long long *n_part) {
   if (!capability || !specs || !prob) return fail("hx_metric_probabilities: null argument");
-  HX_TRY(core->core->probabilities(capability, 0, 0, specs, nspecs, weights, edges, nedges, prob, sums,
-                                   n_part))
+  HX_TRY(core->core->probabilities(rows_of("hx_metric_probabilities", capability, 0, 0, specs, nspecs), kUngrouped,
+                                   weights, edges, nedges, prob, sums, n_part))
 }
 int hx_ensemble_moments(hx_core *core, const char *capability, int year0, int year1,
                         const double *weights, const double *predictors, int npred, double *shift,
                         double *sums, unsigned long long *wsum, long long *n_part) {
   if (!capability || !shift || !sums) return fail("hx_ensemble_moments: null argument");
-  HX_TRY(core->core->moments(capability, year0, year1, nullptr, 0, weights, predictors, npred, shift, sums,
-                             wsum, n_part))
+  HX_TRY(core->core->moments(rows_of("hx_ensemble_moments", capability, year0, year1, nullptr, 0), kUngrouped,
+                             weights, predictors, npred, shift, nullptr, sums, wsum, n_part))
 }
 int hx_metric_moments(hx_core *core, const char *capability, const hx_metric *specs, int nspecs,
                       const double *weights, const double *predictors, int npred, double *shift,
                       double *sums, unsigned long long *wsum, long long *n_part) {
   if (!capability || !specs || !shift || !sums) return fail("hx_metric_moments: null argument");
-  HX_TRY(core->core->moments(capability, 0, 0, specs, nspecs, weights, predictors, npred, shift, sums, wsum,
-                             n_part))
+  HX_TRY(core->core->moments(rows_of("hx_metric_moments", capability, 0, 0, specs, nspecs), kUngrouped, weights,
+                             predictors, npred, shift, nullptr, sums, wsum, n_part))
 }
 int hx_group_quantiles(hx_core *core, const char *capability, int year0, int year1, const hx_metric *specs,
                        int nspecs, const int *labels, int ngroups, const double *weights, const double *probs,
                        int nprobs, double *out, long long *n_part) {
   if (!capability || !probs || !out) return fail("hx_group_quantiles: null argument");
-  HX_TRY(core->core->group_quantiles(capability, year0, year1, specs, nspecs, labels, ngroups, weights, probs,
-                                     nprobs, out, n_part))
+  HX_TRY(core->core->quantiles(rows_of("hx_group_quantiles", capability, year0, year1, specs, nspecs),
+                               groups_of(labels, ngroups), weights, probs, nprobs, out, n_part))
 }
 int hx_group_probabilities(hx_core *core, const char *capability, int year0, int year1, const hx_metric *specs,
                            int nspecs, const int *labels, int ngroups, const double *weights,
                            const double *edges, int nedges, double *prob, unsigned long long *sums,
                            long long *n_part) {
   if (!capability || !prob) return fail("hx_group_probabilities: null argument");
-  HX_TRY(core->core->group_probabilities(capability, year0, year1, specs, nspecs, labels, ngroups, weights,
-                                         edges, nedges, prob, sums, n_part))
+  HX_TRY(core->core->probabilities(rows_of("hx_group_probabilities", capability, year0, year1, specs, nspecs),
+                                   groups_of(labels, ngroups), weights, edges, nedges, prob, sums, n_part))
 }
 int hx_group_moments(hx_core *core, const char *capability, int year0, int year1, const hx_metric *specs,
                      int nspecs, const int *labels, int ngroups, const double *weights,
                      const double *predictors, int npred, double *shift, double *pshift, double *sums,
                      unsigned long long *wsum, long long *n_part) {
   if (!capability || !shift || !sums) return fail("hx_group_moments: null argument");
-  HX_TRY(core->core->group_moments(capability, year0, year1, specs, nspecs, labels, ngroups, weights,
-                                   predictors, npred, shift, pshift, sums, wsum, n_part))
+  HX_TRY(core->core->moments(rows_of("hx_group_moments", capability, year0, year1, specs, nspecs),
+                             groups_of(labels, ngroups), weights, predictors, npred, shift, pshift, sums, wsum, n_part))
 }
 int hx_member_pair_metrics(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
                            int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs, double *out) {
@@ -501,7 +512,8 @@ int hx_pair_metric_quantiles(hx_core *core, const char *cap_a, const char *cap_b
                              long long *n_part) {
   if (!cap_a || !specs || !probs || !out) return fail("hx_pair_metric_quantiles: null argument");
   const hx::PairCall pc{cap_b, b_vec, b_year0, b_year1, specs, nspecs};
-  HX_TRY(core->core->metric_quantiles(cap_a, nullptr, 0, weights, probs, nprobs, out, n_part, &pc))
+  HX_TRY(core->core->quantiles(rows_of("hx_pair_metric_quantiles", cap_a, 0, 0, nullptr, 0, &pc), kUngrouped, weights,
+                               probs, nprobs, out, n_part))
 }
 int hx_pair_metric_probabilities(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
                                  int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs,
@@ -509,7 +521,8 @@ int hx_pair_metric_probabilities(hx_core *core, const char *cap_a, const char *c
                                  unsigned long long *sums, long long *n_part) {
   if (!cap_a || !specs || !prob) return fail("hx_pair_metric_probabilities: null argument");
   const hx::PairCall pc{cap_b, b_vec, b_year0, b_year1, specs, nspecs};
-  HX_TRY(core->core->probabilities(cap_a, 0, 0, nullptr, 0, weights, edges, nedges, prob, sums, n_part, &pc))
+  HX_TRY(core->core->probabilities(rows_of("hx_pair_metric_probabilities", cap_a, 0, 0, nullptr, 0, &pc), kUngrouped,
+                                   weights, edges, nedges, prob, sums, n_part))
 }
 int hx_pair_metric_moments(hx_core *core, const char *cap_a, const char *cap_b, const double *b_vec,
                            int b_year0, int b_year1, const hx_pair_metric *specs, int nspecs,
@@ -517,8 +530,8 @@ int hx_pair_metric_moments(hx_core *core, const char *cap_a, const char *cap_b, 
                            double *sums, unsigned long long *wsum, long long *n_part) {
   if (!cap_a || !specs || !shift || !sums) return fail("hx_pair_metric_moments: null argument");
   const hx::PairCall pc{cap_b, b_vec, b_year0, b_year1, specs, nspecs};
-  HX_TRY(core->core->moments(cap_a, 0, 0, nullptr, 0, weights, predictors, npred, shift, sums, wsum, n_part,
-                             &pc))
+  HX_TRY(core->core->moments(rows_of("hx_pair_metric_moments", cap_a, 0, 0, nullptr, 0, &pc), kUngrouped, weights,
+                             predictors, npred, shift, nullptr, sums, wsum, n_part))
 }
 int hx_ensemble_comoments(hx_core *core, const char *cap_a, int a_year0, int a_year1, const char *cap_b,
                           int b_year0, int b_year1, const double *weights, double *shift_a, double *sums_a,

@@ -463,50 +463,62 @@ static void check_probs(const double *probs, int nprobs, const char *fn) {
       throw std::runtime_error(f + ": a probability outside [0, 1]");
 }
 
-void Fleet::quantiles(const std::string &cap, int year0, int year1, const double *weights,
-                      const double *probs, int nprobs, double *out, long long *n_part) {
-  check_poison();
-  check_probs(probs, nprobs, "hx_ensemble_quantiles");
-  refuse_processes("hx_ensemble_quantiles", "quantiles");
-  std::vector<unsigned long long> q;
-  quantise_weights(weights, "hx_ensemble_quantiles", q);
-  const unsigned long long *qp = weights ? q.data() : nullptr;
-  if (shards_.size() == 1) {
-    use(shards_[0]);
-    shards_[0].core->quantiles(cap, year0, year1, qp, probs, nprobs, out, n_part);
-    return;
-  }
-  const int ny = year1 - year0 + 1;
-  if (ny < 1) throw std::runtime_error("hx_ensemble_quantiles: year1 < year0");
-  select_rows(ny, qp, probs, nprobs, out, n_part,
-              [&](Shard &s, const unsigned long long *qs, unsigned long long *part) {
-                s.core->q_begin(cap, year0, year1, qs, nprobs, part);
-              });
+// nspecs of a metric or pair source held to its range -> the rows of the source.  A year window may
+// still be empty: "year1 < year0" is refused behind the weights.
+static int source_rows(const RowSource &rs) {
+  if (!rs.specs && !rs.pair) return rs.year1 - rs.year0 + 1;
+  const int nspecs = rs.pair ? rs.pair->nspecs : rs.nspecs;
+  if (nspecs < 1 || nspecs > HX_MET_MAX_SPECS || (rs.pair && !rs.pair->specs))
+    throw std::runtime_error(std::string(rs.fn) + ": nspecs must lie in 1..32");
+  return nspecs;
 }
 
-void Fleet::metric_quantiles(const std::string &cap, const hx_metric *specs, int nspecs,
-                             const double *weights, const double *probs, int nprobs, double *out,
-                             long long *n_part, const PairCall *pair) {
+// a shard's four-word row records {~min key, max key, sum q, count} into the totals
+static void fold_records(std::vector<unsigned long long> &st, const std::vector<unsigned long long> &part) {
+  for (size_t y = 0; y < st.size() / 4; ++y) {
+    if (!part[4 * y + 3]) continue;
+    st[4 * y] = std::max(st[4 * y], part[4 * y]);
+    st[4 * y + 1] = std::max(st[4 * y + 1], part[4 * y + 1]);
+    st[4 * y + 2] += part[4 * y + 2];
+    st[4 * y + 3] += part[4 * y + 3];
+  }
+}
+
+// the labels of a grouped call: -1 .. ngroups-1, one of them >= 0 (an ungrouped call passes)
+void Fleet::check_groups(const char *fn, const Groups &g) const {
+  if (!g.labels && !g.ngroups) return;
+  const std::string f(fn);
+  if (!g.labels) throw std::runtime_error(f + ": labels is NULL");
+  if (g.ngroups < 1 || g.ngroups > HX_GROUP_MAX) throw std::runtime_error(f + ": ngroups must lie in 1..16");
+  bool any = false;
+  for (int m = 0; m < n_; ++m) {
+    if (g.labels[m] < -1 || g.labels[m] >= g.ngroups)
+      throw std::runtime_error(f + ": label " + std::to_string(g.labels[m]) + " of member " + std::to_string(m) +
+                               " lies outside -1.." + std::to_string(g.ngroups - 1));
+    any = any || g.labels[m] >= 0;
+  }
+  if (!any) throw std::runtime_error(f + ": no member has a label >= 0");
+}
+
+void Fleet::quantiles(const RowSource &rs, const Groups &g, const double *weights, const double *probs,
+                      int nprobs, double *out, long long *n_part) {
   check_poison();
-  const char *fn = pair ? "hx_pair_metric_quantiles" : "hx_metric_quantiles";
-  if (pair) nspecs = pair->nspecs;
-  if (nspecs < 1 || nspecs > HX_MET_MAX_SPECS || !(pair ? (const void *)pair->specs : (const void *)specs))
-    throw std::runtime_error(std::string(fn) + ": nspecs must lie in 1..32");
-  check_probs(probs, nprobs, fn);
-  refuse_processes(fn, "quantiles");
+  const int nrows = source_rows(rs);
+  check_probs(probs, nprobs, rs.fn);
+  check_groups(rs.fn, g);
+  refuse_processes(rs.fn, "quantiles");
   std::vector<unsigned long long> q;
-  quantise_weights(weights, fn, q);
+  quantise_weights(weights, rs.fn, q);
   const unsigned long long *qp = weights ? q.data() : nullptr;
-  if (shards_.size() == 1) {
+  if (shards_.size() == 1) {   // (an empty year window: the core's own date check speaks)
     use(shards_[0]);
-    if (pair) shards_[0].core->pair_metric_quantiles(cap, *pair, qp, probs, nprobs, out, n_part);
-    else shards_[0].core->metric_quantiles(cap, specs, nspecs, qp, probs, nprobs, out, n_part);
+    shards_[0].core->quantiles(rs, g, qp, probs, nprobs, out, n_part);
     return;
   }
-  select_rows(nspecs, qp, probs, nprobs, out, n_part,
+  if (nrows < 1) throw std::runtime_error(std::string(rs.fn) + ": year1 < year0");
+  select_rows(std::max(g.ngroups, 1) * nrows, qp, probs, nprobs, out, n_part,
               [&](Shard &s, const unsigned long long *qs, unsigned long long *part) {
-                if (pair) s.core->pmq_begin(cap, *pair, qs, nprobs, part);
-                else s.core->mq_begin(cap, specs, nspecs, qs, nprobs, part);
+                s.core->q_begin(rs, of_shard(g, s), qs, nprobs, part);
               });
 }
 
@@ -526,13 +538,7 @@ void Fleet::select_rows(int ny, const unsigned long long *qp, const double *prob
   for (Shard &s : shards_) {
     use(s);
     begin(s, qp ? qp + s.offset : nullptr, part.data());
-    for (size_t y = 0; y < Y; ++y) {
-      if (!part[4 * y + 3]) continue;
-      st[4 * y] = std::max(st[4 * y], part[4 * y]);
-      st[4 * y + 1] = std::max(st[4 * y + 1], part[4 * y + 1]);
-      st[4 * y + 2] += part[4 * y + 2];
-      st[4 * y + 3] += part[4 * y + 3];
-    }
+    fold_records(st, part);
   }
   std::vector<int> lo(Y);
   std::vector<unsigned long long> prefix(YP), rem(YP), hist(YP * 256), hpart(YP * 256);
@@ -594,35 +600,29 @@ void Fleet::member_metrics(const std::string &cap, const hx_metric *specs, int n
   }
 }
 
-void Fleet::probabilities(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
-                          const double *weights, const double *edges, int nedges, double *prob,
-                          unsigned long long *sums, long long *n_part, const PairCall *pair) {
+void Fleet::probabilities(const RowSource &rs, const Groups &g, const double *weights, const double *edges,
+                          int nedges, double *prob, unsigned long long *sums, long long *n_part) {
   check_poison();
-  const char *fn = pair ? "hx_pair_metric_probabilities" : specs ? "hx_metric_probabilities" : "hx_ensemble_probabilities";
+  const char *fn = rs.fn;
   const std::string f(fn);
-  if (pair) nspecs = pair->nspecs;
-  if ((specs || pair) && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
-    throw std::runtime_error(f + ": nspecs must lie in 1..32");
+  const int nrows = source_rows(rs);
   if (nedges < 1 || nedges > HX_BIN_MAX_EDGES || !edges)
     throw std::runtime_error(f + ": nedges must lie in 1..31");
   for (int k = 0; k < nedges; ++k) {
     if (!std::isfinite(edges[k])) throw std::runtime_error(f + ": an edge is not finite");
     if (k && !(edges[k] > edges[k - 1])) throw std::runtime_error(f + ": the edges are not strictly ascending");
   }
+  check_groups(fn, g);
   refuse_processes(fn, "probabilities");
   std::vector<unsigned long long> q;
   quantise_weights(weights, fn, q);
   const unsigned long long *qp = weights ? q.data() : nullptr;
-  const int nrows = (specs || pair) ? nspecs : year1 - year0 + 1;
   if (nrows < 1) throw std::runtime_error(f + ": year1 < year0");
-  const size_t stride = (size_t)nedges + 2, R = (size_t)nrows;
+  const size_t stride = (size_t)nedges + 2, R = (size_t)std::max(g.ngroups, 1) * (size_t)nrows;
   std::vector<unsigned long long> tot(R * stride, 0ull), part(R * stride);
   for (Shard &s : shards_) {
     use(s);
-    const unsigned long long *qs = qp ? qp + s.offset : nullptr;
-    if (pair) s.core->pair_metric_bin_sums(cap, *pair, qs, edges, nedges, part.data());
-    else if (specs) s.core->metric_bin_sums(cap, specs, nspecs, qs, edges, nedges, part.data());
-    else s.core->bin_sums(cap, year0, year1, qs, edges, nedges, part.data());
+    s.core->bin_sums(rs, of_shard(g, s), qp ? qp + s.offset : nullptr, edges, nedges, part.data());
     for (size_t i = 0; i < tot.size(); ++i) tot[i] += part[i];
   }
   const size_t B = (size_t)nedges + 1;
@@ -638,37 +638,41 @@ void Fleet::probabilities(const std::string &cap, int year0, int year1, const hx
   }
 }
 
-void Fleet::moments(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
-                    const double *weights, const double *predictors, int npred, double *shift, double *sums,
-                    unsigned long long *wsum, long long *n_part, const PairCall *pair) {
+void Fleet::moments(const RowSource &rs, const Groups &g, const double *weights, const double *predictors,
+                    int npred, double *shift, double *pshift, double *sums, unsigned long long *wsum,
+                    long long *n_part) {
   check_poison();
-  const char *fn = pair ? "hx_pair_metric_moments" : specs ? "hx_metric_moments" : "hx_ensemble_moments";
+  const char *fn = rs.fn;
   const std::string f(fn);
-  if (pair) nspecs = pair->nspecs;
-  if ((specs || pair) && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
-    throw std::runtime_error(f + ": nspecs must lie in 1..32");
+  const int nrows = source_rows(rs);
   if (npred < 0 || npred > HX_MOM_MAX_PRED)
     throw std::runtime_error(f + ": npred must lie in 0..8");
   if (npred > 0 && !predictors)
     throw std::runtime_error(f + ": predictors is NULL with npred > 0");
+  check_groups(fn, g);
   refuse_processes(fn, "moments");
   std::vector<unsigned long long> q;
   quantise_weights(weights, fn, q);
   if (!weights) q.assign((size_t)n_, 1ull);
-  const int nrows = (specs || pair) ? nspecs : year1 - year0 + 1;
   if (nrows < 1) throw std::runtime_error(f + ": year1 < year0");
-  // the call's effective weights, and the predictor shifts over the members they leave
-  const size_t N = (size_t)n_, K = (size_t)npred, R = (size_t)nrows, nc = 2 + 3 * K;
+  // the call's effective weights, and every group's predictor shifts over the members they leave it
+  // (an ungrouped call: one group of every member)
+  const size_t N = (size_t)n_, K = (size_t)npred, G = (size_t)std::max(g.ngroups, 1), R = G * (size_t)nrows;
+  const size_t nc = 2 + 3 * K;
+  // (predictor by predictor: the loops stream through one array each)
   for (size_t k = 0; k < K; ++k)
     for (size_t m = 0; m < N; ++m)
       if (!std::isfinite(predictors[k * N + m])) q[m] = 0;
-  double c[HX_MOM_MAX_PRED];
-  for (size_t k = 0; k < HX_MOM_MAX_PRED; ++k) {
-    c[k] = std::nan("");
-    if (k >= K) continue;
+  if (g.ngroups)
     for (size_t m = 0; m < N; ++m)
-      if (q[m] && !(c[k] <= predictors[k * N + m])) c[k] = predictors[k * N + m];
-  }
+      if (g.labels[m] < 0) q[m] = 0;
+  std::vector<double> c(G * HX_MOM_MAX_PRED, std::nan(""));
+  for (size_t k = 0; k < K; ++k)
+    for (size_t m = 0; m < N; ++m) {
+      if (!q[m]) continue;   // (among them every label -1)
+      double &ck = c[(g.ngroups ? (size_t)g.labels[m] : 0) * HX_MOM_MAX_PRED + k];
+      if (!(ck <= predictors[k * N + m])) ck = predictors[k * N + m];
+    }
   // 1. every shard's minimum, W and count of every row; the minimum over the shards is the shift
   std::vector<unsigned long long> st(4 * R, 0ull), part(4 * R);
   std::vector<double> pred;
@@ -678,168 +682,8 @@ void Fleet::moments(const std::string &cap, int year0, int year1, const hx_metri
     for (size_t k = 0; k < K; ++k)
       std::copy(predictors + k * N + (size_t)s.offset, predictors + k * N + (size_t)(s.offset + s.count),
                 pred.begin() + k * (size_t)s.count);
-    if (pair) s.core->pair_mom_begin(cap, *pair, q.data() + s.offset, pred.data(), npred, c, part.data());
-    else s.core->mom_begin(cap, year0, year1, specs, nspecs, q.data() + s.offset, pred.data(), npred, c,
-                           part.data(), fn);
-    for (size_t y = 0; y < R; ++y) {
-      if (!part[4 * y + 3]) continue;
-      st[4 * y] = std::max(st[4 * y], part[4 * y]);
-      st[4 * y + 2] += part[4 * y + 2];
-      st[4 * y + 3] += part[4 * y + 3];
-    }
-  }
-  for (size_t y = 0; y < R; ++y) {
-    shift[y] = st[4 * y + 3] ? hxq_key_to_double(~st[4 * y]) : std::nan("");
-    if (wsum) wsum[y] = st[4 * y + 2];
-    if (n_part) n_part[y] = (long long)st[4 * y + 3];
-  }
-  // 2. every shard's sums about that shift, added in ascending shard order
-  std::fill(sums, sums + R * nc, 0.0);
-  std::vector<double> sp(R * nc);
-  for (Shard &s : shards_) {
-    use(s);
-    s.core->mom_finish(shift, sp.data());
-    for (size_t i = 0; i < R * nc; ++i) sums[i] += sp[i];
-  }
-}
-
-// ---- grouped summaries: the routines above over (group, row) pairs ---------------------------------
-
-void Fleet::check_groups(const char *fn, const int *labels, int ngroups) const {
-  const std::string f(fn);
-  if (!labels) throw std::runtime_error(f + ": labels is NULL");
-  if (ngroups < 1 || ngroups > HX_GROUP_MAX) throw std::runtime_error(f + ": ngroups must lie in 1..16");
-  bool any = false;
-  for (int m = 0; m < n_; ++m) {
-    if (labels[m] < -1 || labels[m] >= ngroups)
-      throw std::runtime_error(f + ": label " + std::to_string(labels[m]) + " of member " + std::to_string(m) +
-                               " lies outside -1.." + std::to_string(ngroups - 1));
-    any = any || labels[m] >= 0;
-  }
-  if (!any) throw std::runtime_error(f + ": no member has a label >= 0");
-}
-
-void Fleet::group_quantiles(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
-                            const int *labels, int ngroups, const double *weights, const double *probs,
-                            int nprobs, double *out, long long *n_part) {
-  check_poison();
-  const char *fn = "hx_group_quantiles";
-  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
-    throw std::runtime_error(std::string(fn) + ": nspecs must lie in 1..32");
-  check_probs(probs, nprobs, fn);
-  check_groups(fn, labels, ngroups);
-  refuse_processes(fn, "quantiles");
-  std::vector<unsigned long long> q;
-  quantise_weights(weights, fn, q);
-  const unsigned long long *qp = weights ? q.data() : nullptr;
-  if (shards_.size() == 1) {
-    use(shards_[0]);
-    shards_[0].core->grp_quantiles(cap, year0, year1, specs, nspecs, labels, ngroups, qp, probs, nprobs, out,
-                                   n_part, fn);
-    return;
-  }
-  const int nrows = specs ? nspecs : year1 - year0 + 1;
-  if (nrows < 1) throw std::runtime_error(std::string(fn) + ": year1 < year0");
-  select_rows(ngroups * nrows, qp, probs, nprobs, out, n_part,
-              [&](Shard &s, const unsigned long long *qs, unsigned long long *part) {
-                s.core->grp_q_begin(cap, year0, year1, specs, nspecs, labels + s.offset, ngroups, qs, nprobs,
-                                    part, fn);
-              });
-}
-
-void Fleet::group_probabilities(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
-                                const int *labels, int ngroups, const double *weights, const double *edges,
-                                int nedges, double *prob, unsigned long long *sums, long long *n_part) {
-  check_poison();
-  const char *fn = "hx_group_probabilities";
-  const std::string f(fn);
-  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
-    throw std::runtime_error(f + ": nspecs must lie in 1..32");
-  if (nedges < 1 || nedges > HX_BIN_MAX_EDGES || !edges)
-    throw std::runtime_error(f + ": nedges must lie in 1..31");
-  for (int k = 0; k < nedges; ++k) {
-    if (!std::isfinite(edges[k])) throw std::runtime_error(f + ": an edge is not finite");
-    if (k && !(edges[k] > edges[k - 1])) throw std::runtime_error(f + ": the edges are not strictly ascending");
-  }
-  check_groups(fn, labels, ngroups);
-  refuse_processes(fn, "probabilities");
-  std::vector<unsigned long long> q;
-  quantise_weights(weights, fn, q);
-  const unsigned long long *qp = weights ? q.data() : nullptr;
-  const int nrows = specs ? nspecs : year1 - year0 + 1;
-  if (nrows < 1) throw std::runtime_error(f + ": year1 < year0");
-  const size_t stride = (size_t)nedges + 2, R = (size_t)ngroups * (size_t)nrows;
-  std::vector<unsigned long long> tot(R * stride, 0ull), part(R * stride);
-  for (Shard &s : shards_) {
-    use(s);
-    s.core->grp_bin_sums(cap, year0, year1, specs, nspecs, labels + s.offset, ngroups,
-                         qp ? qp + s.offset : nullptr, edges, nedges, part.data(), fn);
-    for (size_t i = 0; i < tot.size(); ++i) tot[i] += part[i];
-  }
-  const size_t B = (size_t)nedges + 1;
-  for (size_t r = 0; r < R; ++r) {
-    const unsigned long long *t = &tot[r * stride];
-    unsigned long long W = 0;
-    for (size_t b = 0; b < B; ++b) W += t[b];
-    if (n_part) n_part[r] = (long long)t[B];
-    for (size_t b = 0; b < B; ++b) {
-      if (sums) sums[r * B + b] = t[b];
-      prob[r * B + b] = t[B] ? (double)t[b] / (double)W : std::nan("");
-    }
-  }
-}
-
-void Fleet::group_moments(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs,
-                          const int *labels, int ngroups, const double *weights, const double *predictors,
-                          int npred, double *shift, double *pshift, double *sums, unsigned long long *wsum,
-                          long long *n_part) {
-  check_poison();
-  const char *fn = "hx_group_moments";
-  const std::string f(fn);
-  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
-    throw std::runtime_error(f + ": nspecs must lie in 1..32");
-  if (npred < 0 || npred > HX_MOM_MAX_PRED)
-    throw std::runtime_error(f + ": npred must lie in 0..8");
-  if (npred > 0 && !predictors)
-    throw std::runtime_error(f + ": predictors is NULL with npred > 0");
-  check_groups(fn, labels, ngroups);
-  refuse_processes(fn, "moments");
-  std::vector<unsigned long long> q;
-  quantise_weights(weights, fn, q);
-  if (!weights) q.assign((size_t)n_, 1ull);
-  const int nrows = specs ? nspecs : year1 - year0 + 1;
-  if (nrows < 1) throw std::runtime_error(f + ": year1 < year0");
-  // the call's effective weights, and every group's predictor shifts over the members they leave it
-  const size_t N = (size_t)n_, K = (size_t)npred, G = (size_t)ngroups, R = G * (size_t)nrows, nc = 2 + 3 * K;
-  for (size_t m = 0; m < N; ++m) {
-    if (labels[m] < 0) q[m] = 0;
-    for (size_t k = 0; k < K; ++k)
-      if (!std::isfinite(predictors[k * N + m])) q[m] = 0;
-  }
-  std::vector<double> c(G * HX_MOM_MAX_PRED, std::nan(""));
-  for (size_t m = 0; m < N; ++m) {
-    if (!q[m]) continue;
-    double *cg = &c[(size_t)labels[m] * HX_MOM_MAX_PRED];
-    for (size_t k = 0; k < K; ++k)
-      if (!(cg[k] <= predictors[k * N + m])) cg[k] = predictors[k * N + m];
-  }
-  // 1. every shard's minimum, W and count of every (group, row); the minimum over the shards is the shift
-  std::vector<unsigned long long> st(4 * R, 0ull), part(4 * R);
-  std::vector<double> pred;
-  for (Shard &s : shards_) {
-    use(s);
-    pred.resize(K * (size_t)s.count);
-    for (size_t k = 0; k < K; ++k)
-      std::copy(predictors + k * N + (size_t)s.offset, predictors + k * N + (size_t)(s.offset + s.count),
-                pred.begin() + k * (size_t)s.count);
-    s.core->grp_mom_begin(cap, year0, year1, specs, nspecs, labels + s.offset, ngroups, q.data() + s.offset,
-                          pred.data(), npred, c.data(), part.data(), fn);
-    for (size_t y = 0; y < R; ++y) {
-      if (!part[4 * y + 3]) continue;
-      st[4 * y] = std::max(st[4 * y], part[4 * y]);
-      st[4 * y + 2] += part[4 * y + 2];
-      st[4 * y + 3] += part[4 * y + 3];
-    }
+    s.core->mom_begin(rs, of_shard(g, s), q.data() + s.offset, pred.data(), npred, c.data(), part.data());
+    fold_records(st, part);
   }
   for (size_t y = 0; y < R; ++y) {
     shift[y] = st[4 * y + 3] ? hxq_key_to_double(~st[4 * y]) : std::nan("");
@@ -847,14 +691,14 @@ void Fleet::group_moments(const std::string &cap, int year0, int year1, const hx
     if (n_part) n_part[y] = (long long)st[4 * y + 3];
   }
   if (pshift)
-    for (size_t g = 0; g < G; ++g)
-      for (size_t k = 0; k < K; ++k) pshift[g * K + k] = c[g * HX_MOM_MAX_PRED + k];
+    for (size_t gi = 0; gi < G; ++gi)
+      for (size_t k = 0; k < K; ++k) pshift[gi * K + k] = c[gi * HX_MOM_MAX_PRED + k];
   // 2. every shard's sums about those shifts, added in ascending shard order
   std::fill(sums, sums + R * nc, 0.0);
   std::vector<double> sp(R * nc);
   for (Shard &s : shards_) {
     use(s);
-    s.core->grp_mom_finish(shift, sp.data());
+    s.core->mom_finish(shift, sp.data());
     for (size_t i = 0; i < R * nc; ++i) sums[i] += sp[i];
   }
 }
@@ -877,12 +721,13 @@ void Fleet::sobol(const std::string &cap, int year0, int year1, const hx_metric 
   // build refuses by name there); k and n_base were held to the whole core above
   Shard &s = shards_.front();
   use(s);
-  s.core->sobol_check(cap, year0, year1, specs, nspecs, fn);
+  const RowSource rs{fn, cap, year0, year1, specs, nspecs, nullptr};
+  s.core->rows_check(rs, Groups{nullptr, 0}, 1);
   if (shards_.size() > 1)
     throw std::runtime_error(f + ": this core has several shards (" + std::to_string(shards_.size()) +
                              "): the members of a group lie on different GPUs under the fleet's split, "
                              "which the Sobol verbs do not serve");
-  s.core->sobol_begin(cap, year0, year1, specs, nspecs, k, n_base, use_group, fn);
+  s.core->sobol_begin(rs, k, n_base, use_group);
   s.core->sobol_finish(shift, sums, n_part);
 }
 
@@ -907,12 +752,7 @@ void Fleet::comoments(const std::string &cap_a, int a0, int a1, const char *cap_
   for (Shard &s : shards_) {
     use(s);
     s.core->comom_begin(cap_a, a0, a1, sym ? nullptr : &sb, b0, b1, q.data() + s.offset, part.data());
-    for (size_t y = 0; y < R; ++y) {
-      if (!part[4 * y + 3]) continue;
-      st[4 * y] = std::max(st[4 * y], part[4 * y]);
-      st[4 * y + 2] += part[4 * y + 2];
-      st[4 * y + 3] += part[4 * y + 3];
-    }
+    fold_records(st, part);
   }
   std::vector<double> shift(R);
   for (size_t y = 0; y < R; ++y) shift[y] = st[4 * y + 3] ? hxq_key_to_double(~st[4 * y]) : std::nan("");
@@ -947,7 +787,7 @@ EnsembleCore &Fleet::rank_shard(const char *fn, const std::string &cap, int year
   refuse_processes(fn, "ranks");
   Shard &s = shards_.front();
   use(s);
-  s.core->rank_check(cap, year0, year1, specs, nspecs, fn);
+  s.core->rows_check(RowSource{fn, cap, year0, year1, specs, nspecs, nullptr}, Groups{nullptr, 0}, 1);
   if (shards_.size() > 1)
     throw std::runtime_error(std::string(fn) + ": this core has several shards (" +
                              std::to_string(shards_.size()) + "): a rank needs the whole row of members on "

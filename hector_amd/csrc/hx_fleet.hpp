@@ -106,49 +106,30 @@ class Fleet {
   // hx_member_project: shard by shard like member_score_whitened; out_host[m][n_], a shard fills its columns
   void member_project(const std::string &capability, const int *years, const double *center,
                       const double *basis, int n, int m, int base_year0, int base_year1, double *out_host);
-  // hx_ensemble_quantiles: weights checked and quantised against the largest of the WHOLE ensemble;
-  // one shard runs the select on its GPU, several shards fill integer histograms that are added
-  // and searched here, pass by pass (exact: the same bits as one core)
-  void quantiles(const std::string &capability, int year0, int year1, const double *weights,
-                 const double *probs, int nprobs, double *out_host, long long *n_part);
   // hx_member_metrics: routed per shard like member_score
   void member_metrics(const std::string &capability, const hx_metric *specs, int nspecs, double *out_host);
-  // hx_metric_quantiles: quantiles() over the metric block every shard computes on its GPU
-  // (pair != nullptr: hx_pair_metric_quantiles -- capability is operand a, the rows are the pair
-  //  metrics of *pair, specs / nspecs are not read; likewise in probabilities and moments below)
-  void metric_quantiles(const std::string &capability, const hx_metric *specs, int nspecs,
-                        const double *weights, const double *probs, int nprobs, double *out_host,
-                        long long *n_part, const PairCall *pair = nullptr);
   // hx_member_pair_metrics: shard by shard, every shard into its columns of out_host[nspecs][n_]
   void member_pair_metrics(const std::string &cap_a, const PairCall &pc, double *out_host);
-  // hx_ensemble_probabilities (specs == nullptr: the rows year0..year1) and hx_metric_probabilities
-  // (the rows are the nspecs metrics): the shards' integer bin sums added here
-  void probabilities(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                     const double *weights, const double *edges, int nedges, double *prob,
-                     unsigned long long *sums, long long *n_part, const PairCall *pair = nullptr);
-  // hx_ensemble_moments (specs == nullptr: the rows year0..year1) and hx_metric_moments: the weights
-  // quantised as for quantiles, zeroed where a predictor is not finite, the predictor shifts taken
-  // here; then two steps over the shards -- the rows' minima (their minimum is the shift), the sums
-  // about it -- with the predictor arrays split by shard offsets and the sums added in shard order
-  void moments(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-               const double *weights, const double *predictors, int npred, double *shift, double *sums,
-               unsigned long long *wsum, long long *n_part, const PairCall *pair = nullptr);
-  // hx_group_quantiles / hx_group_probabilities / hx_group_moments: the three routines above over
-  // (group, row) pairs in group-major order.  labels[n_] checked here (-1 .. ngroups-1, one >= 0),
-  // the weights quantised against the largest of the WHOLE ensemble whatever the labels; every shard
-  // takes its members' labels, and its histograms, bin sums, minima and sums are combined over
-  // ngroups * nrows rows as they are over rows
-  void group_quantiles(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                       const int *labels, int ngroups, const double *weights, const double *probs, int nprobs,
-                       double *out_host, long long *n_part);
-  void group_probabilities(const std::string &capability, int year0, int year1, const hx_metric *specs,
-                           int nspecs, const int *labels, int ngroups, const double *weights,
-                           const double *edges, int nedges, double *prob, unsigned long long *sums,
-                           long long *n_part);
-  void group_moments(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs,
-                     const int *labels, int ngroups, const double *weights, const double *predictors,
-                     int npred, double *shift, double *pshift, double *sums, unsigned long long *wsum,
-                     long long *n_part);
+  // ---- the summaries of a RowSource (ensemble_core.hpp: a window of years, the metrics or the pair
+  // metrics every shard computes on its GPU), per group if g says so: labels[n_] are checked here
+  // (-1 .. ngroups-1, one >= 0), every shard takes its members' labels, and its histograms, bin sums,
+  // minima and sums are combined over ngroups * nrows rows in group-major order as they are over rows.
+  // hx_ensemble_quantiles and its metric, pair and group forms: weights checked and quantised against
+  // the largest of the WHOLE ensemble, whatever the labels; one shard runs the select on its GPU,
+  // several shards fill integer histograms that are added and searched here, pass by pass (exact: the
+  // same bits as one core)
+  void quantiles(const RowSource &rs, const Groups &g, const double *weights, const double *probs, int nprobs,
+                 double *out_host, long long *n_part);
+  // hx_ensemble_probabilities and its forms: the shards' integer bin sums added here
+  void probabilities(const RowSource &rs, const Groups &g, const double *weights, const double *edges,
+                     int nedges, double *prob, unsigned long long *sums, long long *n_part);
+  // hx_ensemble_moments and its forms: the weights quantised as for quantiles, zeroed where a predictor
+  // is not finite or the label is -1, the predictor shifts taken here per group (pshift[ngroups][npred],
+  // may be nullptr); then two steps over the shards -- the rows' minima (their minimum is the shift),
+  // the sums about it -- with the predictor arrays split by shard offsets and the sums added in shard
+  // order
+  void moments(const RowSource &rs, const Groups &g, const double *weights, const double *predictors, int npred,
+               double *shift, double *pshift, double *sums, unsigned long long *wsum, long long *n_part);
   // hx_ensemble_comoments (cap_b == nullptr: the symmetric call): the weights quantised once; the
   // shards' masks and row minima, then their minimum, W and count; then the shards' sums and cross
   // sums about the common shifts, added in ascending shard order
@@ -224,7 +205,10 @@ class Fleet {
   EnsembleCore &rank_shard(const char *fn, const std::string &capability, int year0, int year1,
                            const hx_metric *specs, int nspecs);
   void refuse_processes(const char *fn, const char *what) const;
-  void check_groups(const char *fn, const int *labels, int ngroups) const;
+  void check_groups(const char *fn, const Groups &g) const;
+  static Groups of_shard(const Groups &g, const Shard &s) {   // the shard's members' labels
+    return {g.labels ? g.labels + s.offset : nullptr, g.ngroups};
+  }
   // the select over ny rows, one shard on its GPU or the shards' histograms added per pass; begin /
   // one: what to call on a shard
   void select_rows(int ny, const unsigned long long *qp, const double *probs, int np, double *out,
