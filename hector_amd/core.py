@@ -520,6 +520,105 @@ class CoMoments:
                                                                      self.symmetric, self.n_part)
 
 
+# The hx_* function of include/hector_amd.h that serves (verb, kind of rows, grouped).  A grouped call
+# has one function per verb, for a window of years and for metrics; pair rows have no grouped form.
+_SUMMARY_FN = {
+    ("quantiles", "window", False): "hx_ensemble_quantiles",
+    ("quantiles", "metric", False): "hx_metric_quantiles",
+    ("quantiles", "pair", False): "hx_pair_metric_quantiles",
+    ("quantiles", "window", True): "hx_group_quantiles",
+    ("quantiles", "metric", True): "hx_group_quantiles",
+    ("probabilities", "window", False): "hx_ensemble_probabilities",
+    ("probabilities", "metric", False): "hx_metric_probabilities",
+    ("probabilities", "pair", False): "hx_pair_metric_probabilities",
+    ("probabilities", "window", True): "hx_group_probabilities",
+    ("probabilities", "metric", True): "hx_group_probabilities",
+    ("moments", "window", False): "hx_ensemble_moments",
+    ("moments", "metric", False): "hx_metric_moments",
+    ("moments", "pair", False): "hx_pair_metric_moments",
+    ("moments", "window", True): "hx_group_moments",
+    ("moments", "metric", True): "hx_group_moments",
+    ("sobol", "window", False): "hx_ensemble_sobol",
+    ("sobol", "metric", False): "hx_metric_sobol",
+    ("members", "metric", False): "hx_member_metrics",
+    ("members", "pair", False): "hx_member_pair_metrics",
+    ("ranks", "metric", False): "hx_metric_ranks",
+}
+
+_PTR_OF = {np.dtype(t).num: ctypes.POINTER(c) for t, c in (   # the C pointer an array goes as, by dtype.num
+    (np.float64, ctypes.c_double), (np.int64, ctypes.c_longlong), (np.uint64, ctypes.c_ulonglong),
+    (np.int32, ctypes.c_int), (np.uint8, ctypes.c_ubyte))}
+
+
+class _Rows:
+    """The rows a summary verb runs over -- the RowSource of csrc/ensemble_core.hpp on this side: a
+    window of years, metrics or pair metrics.  what: the public verb, the prefix of every message;
+    nrows; lead / group_lead: the arguments of the ungrouped / grouped ABI function between the
+    handle and the labels or the verb's own arguments; keep: what they point into (alive as long as
+    the rows are, and the verb holds the rows until its call has returned)."""
+    __slots__ = ("core", "what", "kind", "nrows", "lead", "group_lead", "keep")
+
+    def __init__(self, core, what, kind, nrows, lead, group_lead=None, keep=None):
+        self.core, self.what, self.kind, self.nrows = core, what, kind, nrows
+        self.lead, self.group_lead, self.keep = lead, group_lead, keep
+
+    @classmethod
+    def window(cls, core, what, var, dates):
+        y0, y1, ny = core._window(dates)
+        cap = var.encode()
+        return cls(core, what, "window", ny, (cap, y0, y1), (cap, y0, y1, None, 0))
+
+    @staticmethod
+    def _specs(specs, of, ctype, what):
+        if isinstance(specs, of):
+            specs = [specs]
+        specs = list(specs)
+        if not all(isinstance(m, of) for m in specs):
+            raise HectorAmdError("%s: specs must be hector_amd.%s objects" % (what, of.__name__))
+        return (ctype * max(len(specs), 1))(*[m._c() for m in specs]), len(specs)
+
+    @classmethod
+    def metrics(cls, core, what, var, specs):
+        arr, ns = cls._specs(specs, Metric, _HxMetric, what)
+        sp = ctypes.byref(arr)
+        return cls(core, what, "metric", ns, (var.encode(), sp, ns), (var.encode(), 0, 0, sp, ns), arr)
+
+    @classmethod
+    def pair_metrics(cls, core, what, var_a, b, specs):
+        """b: a variable name, or (years, values) -- a per-year vector, the same for every member."""
+        arr, ns = cls._specs(specs, PairMetric, _HxPairMetric, what)
+        if isinstance(b, str):
+            side, v = (b.encode(), None, 0, 0), None
+        else:
+            try:
+                years, values = b
+            except (TypeError, ValueError):
+                raise HectorAmdError("%s: b is a variable name or a (years, values) pair" % what)
+            yr = np.atleast_1d(np.asarray(years)).astype(np.int64)
+            v = np.ascontiguousarray(np.atleast_1d(np.asarray(values, dtype=np.float64)))
+            if yr.ndim != 1 or yr.size < 1 or v.shape != yr.shape:
+                raise HectorAmdError("%s: the vector b needs one value per year" % what)
+            if yr.size > 1 and not (np.diff(yr) == 1).all():
+                raise HectorAmdError("%s: the years of the vector b must be consecutive and ascending" % what)
+            side = (None, v.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(yr[0]), int(yr[-1]))
+        return cls(core, what, "pair", ns, (var_a.encode(),) + side + (ctypes.byref(arr), ns), keep=(arr, v))
+
+    def shape(self, grp, *tail):
+        """The shape of an output with `tail` entries per row: a grouped call has a leading group axis."""
+        return (() if grp is None else (grp[1],)) + (self.nrows,) + tail
+
+    def call(self, verb, grp, *args):
+        """The one call of a verb: the function of _SUMMARY_FN over these rows, grp = None or what
+        Core._groups returned, then the verb's own arguments (an array goes as a pointer to its
+        elements, None as NULL)."""
+        core = self.core
+        lead = self.lead
+        if grp is not None:
+            lead = self.group_lead + (grp[0].ctypes.data_as(ctypes.POINTER(ctypes.c_int)), grp[1])
+        args = [a.ctypes.data_as(_PTR_OF[a.dtype.num]) if isinstance(a, np.ndarray) else a for a in args]
+        core._ck(getattr(core._lib, _SUMMARY_FN[verb, self.kind, grp is not None])(core._h, *lead, *args))
+
+
 class Core:
     """An N-member ensemble core bound to one GPU (device=) or sharded over a list of GPUs
     (devices=[...]: contiguous member blocks, hx_newcore_devices)."""
@@ -842,8 +941,7 @@ class Core:
         """-> ndarray [n_years, n_members] for dates = (year0, year1) inclusive.  `out`: a
         C-contiguous float64 array of that shape to reuse (a buffer the host has already touched
         takes the device-to-host copy ~3x faster than a fresh allocation)."""
-        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
-            (int(min(dates)), int(max(dates)))
+        y0, y1, _ = self._window(dates)
         shape = (y1 - y0 + 1, self.n_members)
         if out is None:
             out = np.empty(shape)
@@ -895,8 +993,7 @@ class Core:
         d_out (an integer address on the first shard's GPU)."""
         if isinstance(variables, str):
             variables = [variables]
-        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
-            (int(min(dates)), int(max(dates)))
+        y0, y1, _ = self._window(dates)
         arr = (ctypes.c_char_p * len(variables))(*[v.encode() for v in variables])
         out = np.empty((len(variables), y1 - y0 + 1, 5)) if host else None
         self._ck(self._lib.hx_ensemble_stats(
@@ -1070,21 +1167,78 @@ class Core:
             raise HectorAmdError("%s: label %d lies outside -1..%d" % (what, bad, g - 1))
         return np.ascontiguousarray(lab.astype(np.int32)), g
 
-    def _group_quantiles(self, what, var, y0, y1, arr, ns, nrows, groups, probs, weights, counts):
-        dp = ctypes.POINTER(ctypes.c_double)
-        lab, g = self._groups(groups, what)
+    def _window(self, dates):
+        """dates= of the verbs over years (None: every year run so far) -> (year0, year1, n_years)."""
+        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
+            (int(min(dates)), int(max(dates)))
+        return y0, y1, max(y1 - y0 + 1, 0)
+
+    def _weights(self, weights, what):
+        if weights is None:
+            return None
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+        if w.shape != (self.n_members,):
+            raise HectorAmdError("%s: weights must have n_members entries" % what)
+        return w
+
+    # The summary verbs, once each: rows is a _Rows, groups what the caller gave (None: ungrouped).
+
+    def _quantiles(self, rows, groups, probs, weights, counts):
+        grp = None if groups is None else self._groups(groups, rows.what)
         pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
         if pr.ndim != 1:
-            raise HectorAmdError("%s: probs must be one-dimensional" % what)
-        w = self._weights(weights, what)
-        out = np.empty((g, nrows, pr.size))
-        npart = np.zeros((g, nrows), dtype=np.int64)
-        self._ck(self._lib.hx_group_quantiles(
-            self._h, var.encode(), y0, y1, ctypes.byref(arr) if arr is not None else None, ns,
-            lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), g, w.ctypes.data_as(dp) if w is not None else None,
-            pr.ctypes.data_as(dp), int(pr.size), out.ctypes.data_as(dp),
-            npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+            raise HectorAmdError("%s: probs must be one-dimensional" % rows.what)
+        w = self._weights(weights, rows.what)
+        out = np.empty(rows.shape(grp, pr.size))
+        npart = np.zeros(rows.shape(grp), dtype=np.int64)
+        rows.call("quantiles", grp, w, pr, int(pr.size), out, npart)
         return (out, npart) if counts else out
+
+    def _probabilities(self, rows, groups, edges, weights, counts, sums):
+        grp = None if groups is None else self._groups(groups, rows.what)
+        ed = np.ascontiguousarray(np.atleast_1d(np.asarray(edges, dtype=np.float64)))
+        if ed.ndim != 1:
+            raise HectorAmdError("%s: edges must be one-dimensional" % rows.what)
+        w = self._weights(weights, rows.what)
+        prob = np.empty(rows.shape(grp, ed.size + 1))
+        qs = np.zeros(rows.shape(grp, ed.size + 1), dtype=np.uint64)
+        npart = np.zeros(rows.shape(grp), dtype=np.int64)
+        rows.call("probabilities", grp, w, ed, int(ed.size), prob, qs, npart)
+        res = (prob,) + ((npart,) if counts else ()) + ((qs,) if sums else ())
+        return res if len(res) > 1 else prob
+
+    def _moments(self, rows, groups, weights, against):
+        grp = None if groups is None else self._groups(groups, rows.what)
+        names, pred, w, q, pshift = self._against(against, weights, rows.what)
+        k = len(names)
+        shift = np.empty(rows.shape(grp))
+        sums = np.zeros(rows.shape(grp, 2 + 3 * k))
+        wsum = np.zeros(rows.shape(grp), dtype=np.uint64)
+        npart = np.zeros(rows.shape(grp), dtype=np.int64)
+        if grp is None:
+            rows.call("moments", None, w, pred, k, shift, sums, wsum, npart)
+            return Moments(shift, sums, wsum, npart, names, pshift, q, pred)
+        pshift = np.full((grp[1], k), np.nan)   # (a grouped call returns every group's shifts itself)
+        rows.call("moments", grp, w, pred, k, shift, pshift, sums, wsum, npart)
+        return GroupedMoments(shift, sums, wsum, npart, names, pshift, q, pred, grp[0])
+
+    def _sobol(self, rows, factors, n_base, use):
+        names = ["factor[%d]" % i for i in range(int(factors))] if isinstance(factors, (int, np.integer)) \
+            else [str(f) for f in factors]
+        k = len(names)
+        if k > SOBOL_MAX_FACTORS:
+            raise HectorAmdError("%s: at most %d factors" % (rows.what, SOBOL_MAX_FACTORS))
+        nb = self.n_members // (k + 2) if n_base is None else int(n_base)
+        u = None
+        if use is not None:
+            u = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
+            if u.shape != (nb,):
+                raise HectorAmdError("%s: use must have n_base entries" % rows.what)
+        shift = np.empty(rows.nrows)
+        sums = np.zeros((rows.nrows, 4 + 4 * k))
+        npart = np.zeros(rows.nrows, dtype=np.int64)
+        rows.call("sobol", None, k, nb, u, shift, sums, npart)
+        return Sobol(names, shift, sums, npart)
 
     def quantiles(self, var, probs, dates=None, weights=None, counts=False, groups=None):
         """Per-year weighted quantiles over every member, on the device (hx_ensemble_quantiles:
@@ -1096,44 +1250,7 @@ class Core:
         (profiles/post_summaries.md, 65 536 members, 556 years, 5 probabilities): 0.46 of the time of
         the G masked calls at G = 8 and 0.40 at G = 16, but 1.57 times the two masked calls at G = 2,
         where the grouped select's fixed cost is not yet repaid."""
-        dp = ctypes.POINTER(ctypes.c_double)
-        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
-            (int(min(dates)), int(max(dates)))
-        if groups is not None:
-            return self._group_quantiles("quantiles", var, y0, y1, None, 0, max(y1 - y0 + 1, 0), groups, probs,
-                                         weights, counts)
-        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
-        w = None
-        if weights is not None:
-            w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
-            if w.shape != (self.n_members,):
-                raise HectorAmdError("quantiles: weights must have n_members entries")
-        ny = max(y1 - y0 + 1, 0)
-        out = np.empty((ny, pr.size))
-        npart = np.zeros(ny, dtype=np.int64)
-        self._ck(self._lib.hx_ensemble_quantiles(
-            self._h, var.encode(), y0, y1, w.ctypes.data_as(dp) if w is not None else None,
-            pr.ctypes.data_as(dp), int(pr.size), out.ctypes.data_as(dp),
-            npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
-        return (out, npart) if counts else out
-
-    @staticmethod
-    def _metric_array(specs, what):
-        if isinstance(specs, Metric):
-            specs = [specs]
-        specs = list(specs)
-        if not all(isinstance(m, Metric) for m in specs):
-            raise HectorAmdError("%s: specs must be hector_amd.Metric objects" % what)
-        arr = (_HxMetric * max(len(specs), 1))(*[m._c() for m in specs])
-        return arr, len(specs)
-
-    def _weights(self, weights, what):
-        if weights is None:
-            return None
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
-        if w.shape != (self.n_members,):
-            raise HectorAmdError("%s: weights must have n_members entries" % what)
-        return w
+        return self._quantiles(_Rows.window(self, "quantiles", var, dates), groups, probs, weights, counts)
 
     def metrics(self, var, specs):
         """One number per member and specification, on the device (hx_member_metrics): windowed
@@ -1141,10 +1258,9 @@ class Core:
         above it / least-squares trend of a recorded output, optionally relative to the member's
         own reference-period mean -> ndarray [n_specs, n_members].  The evaluation order is fixed
         (include/hector_amd.h): numpy reproduces the result bit for bit."""
-        arr, ns = self._metric_array(specs, "metrics")
-        out = np.empty((ns, self.n_members))
-        self._ck(self._lib.hx_member_metrics(self._h, var.encode(), ctypes.byref(arr), ns,
-                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        rows = _Rows.metrics(self, "metrics", var, specs)
+        out = np.empty((rows.nrows, self.n_members))
+        rows.call("members", None, out)
         return out
 
     def metric_quantiles(self, var, specs, probs, weights=None, counts=False, groups=None):
@@ -1152,47 +1268,7 @@ class Core:
         are computed and selected on the device, definition as quantiles()) -> ndarray
         [n_specs, n_probs]; counts=True: also the members that took part [n_specs].  groups: as in
         quantiles() -> [G, n_specs, n_probs], counts [G, n_specs]."""
-        dp = ctypes.POINTER(ctypes.c_double)
-        arr, ns = self._metric_array(specs, "metric_quantiles")
-        if groups is not None:
-            return self._group_quantiles("metric_quantiles", var, 0, 0, arr, ns, ns, groups, probs, weights, counts)
-        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
-        if pr.ndim != 1:
-            raise HectorAmdError("metric_quantiles: probs must be one-dimensional")
-        w = self._weights(weights, "metric_quantiles")
-        out = np.empty((ns, pr.size))
-        npart = np.zeros(ns, dtype=np.int64)
-        self._ck(self._lib.hx_metric_quantiles(
-            self._h, var.encode(), ctypes.byref(arr), ns, w.ctypes.data_as(dp) if w is not None else None,
-            pr.ctypes.data_as(dp), int(pr.size), out.ctypes.data_as(dp),
-            npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
-        return (out, npart) if counts else out
-
-    def _probabilities(self, what, call, nrows, edges, weights, counts, sums, ngroups=0):
-        dp = ctypes.POINTER(ctypes.c_double)
-        ed = np.ascontiguousarray(np.atleast_1d(np.asarray(edges, dtype=np.float64)))
-        if ed.ndim != 1:
-            raise HectorAmdError("%s: edges must be one-dimensional" % what)
-        w = self._weights(weights, what)
-        lead = (ngroups,) if ngroups else ()   # a grouped call: a leading group axis
-        prob = np.empty(lead + (nrows, ed.size + 1))
-        qs = np.zeros(lead + (nrows, ed.size + 1), dtype=np.uint64)
-        npart = np.zeros(lead + (nrows,), dtype=np.int64)
-        self._ck(call(w.ctypes.data_as(dp) if w is not None else None, ed.ctypes.data_as(dp), int(ed.size),
-                      prob.ctypes.data_as(dp), qs.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
-                      npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
-        res = (prob,) + ((npart,) if counts else ()) + ((qs,) if sums else ())
-        return res if len(res) > 1 else prob
-
-    def _group_call(self, fn, var, y0, y1, arr, ns, groups, what):
-        """-> (a call of the grouped ABI function fn with its leading arguments bound, G)."""
-        lab, g = self._groups(groups, what)
-        lp = lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-        sp = ctypes.byref(arr) if arr is not None else None
-
-        def call(*a, _keep=(lab, arr)):
-            return fn(self._h, var.encode(), y0, y1, sp, ns, lp, g, *a)
-        return call, g
+        return self._quantiles(_Rows.metrics(self, "metric_quantiles", var, specs), groups, probs, weights, counts)
 
     def probabilities(self, var, edges, dates=None, weights=None, counts=False, sums=False, groups=None):
         """Per-year weighted probabilities of the classes x < edges[0], edges[0] <= x < edges[1],
@@ -1202,56 +1278,15 @@ class Core:
         groups: as in quantiles() -- the classes of every group from ONE pass
         (hx_group_probabilities) -> [G, n_years, n_edges + 1], counts [G, n_years], sums likewise:
         for one year, the contingency table of (group x class)."""
-        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
-            (int(min(dates)), int(max(dates)))
-        if groups is not None:
-            call, g = self._group_call(self._lib.hx_group_probabilities, var, y0, y1, None, 0, groups,
-                                       "probabilities")
-            return self._probabilities("probabilities", call, max(y1 - y0 + 1, 0), edges, weights, counts, sums, g)
-        return self._probabilities(
-            "probabilities",
-            lambda *a: self._lib.hx_ensemble_probabilities(self._h, var.encode(), y0, y1, *a),
-            max(y1 - y0 + 1, 0), edges, weights, counts, sums)
+        return self._probabilities(_Rows.window(self, "probabilities", var, dates), groups, edges, weights, counts,
+                                   sums)
 
     def metric_probabilities(self, var, specs, edges, weights=None, counts=False, sums=False, groups=None):
         """The same classes over metrics (hx_metric_probabilities) -> ndarray
         [n_specs, n_edges + 1] (+ counts [n_specs], + sums).  groups: as in probabilities() ->
         [G, n_specs, n_edges + 1]."""
-        arr, ns = self._metric_array(specs, "metric_probabilities")
-        if groups is not None:
-            call, g = self._group_call(self._lib.hx_group_probabilities, var, 0, 0, arr, ns, groups,
-                                       "metric_probabilities")
-            return self._probabilities("metric_probabilities", call, ns, edges, weights, counts, sums, g)
-        return self._probabilities(
-            "metric_probabilities",
-            lambda *a: self._lib.hx_metric_probabilities(self._h, var.encode(), ctypes.byref(arr), ns, *a),
-            ns, edges, weights, counts, sums)
-
-    def _pair_args(self, b, specs, what):
-        """-> (the leading arguments of the hx_*pair_metric* functions after cap_a, n_specs, what
-        must stay alive during the call)."""
-        if isinstance(specs, PairMetric):
-            specs = [specs]
-        specs = list(specs)
-        if not all(isinstance(m, PairMetric) for m in specs):
-            raise HectorAmdError("%s: specs must be hector_amd.PairMetric objects" % what)
-        arr = (_HxPairMetric * max(len(specs), 1))(*[m._c() for m in specs])
-        if isinstance(b, str):
-            lead, keep = (b.encode(), None, 0, 0), arr
-        else:
-            try:
-                years, values = b
-            except (TypeError, ValueError):
-                raise HectorAmdError("%s: b is a variable name or a (years, values) pair" % what)
-            yr = np.atleast_1d(np.asarray(years)).astype(np.int64)
-            v = np.ascontiguousarray(np.atleast_1d(np.asarray(values, dtype=np.float64)))
-            if yr.ndim != 1 or yr.size < 1 or v.shape != yr.shape:
-                raise HectorAmdError("%s: the vector b needs one value per year" % what)
-            if yr.size > 1 and not (np.diff(yr) == 1).all():
-                raise HectorAmdError("%s: the years of the vector b must be consecutive and ascending" % what)
-            lead = (None, v.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(yr[0]), int(yr[-1]))
-            keep = (arr, v)
-        return lead + (ctypes.byref(arr), len(specs)), len(specs), keep
+        return self._probabilities(_Rows.metrics(self, "metric_probabilities", var, specs), groups, edges, weights,
+                                   counts, sums)
 
     def pair_metrics(self, var_a, b, specs):
         """One number per member and specification from TWO series of that member, on the device
@@ -1261,51 +1296,27 @@ class Core:
         b: a variable name, or (years, values) -- a per-year vector that is the same for every member
         (cumulative emissions, the year itself).  The evaluation order is fixed
         (include/hector_amd.h): numpy reproduces the result bit for bit."""
-        lead, ns, keep = self._pair_args(b, specs, "pair_metrics")
-        out = np.empty((ns, self.n_members))
-        self._ck(self._lib.hx_member_pair_metrics(self._h, var_a.encode(), *lead,
-                                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
-        del keep
+        rows = _Rows.pair_metrics(self, "pair_metrics", var_a, b, specs)
+        out = np.empty((rows.nrows, self.n_members))
+        rows.call("members", None, out)
         return out
 
     def pair_metric_quantiles(self, var_a, b, specs, probs, weights=None, counts=False):
         """Weighted quantiles of every pair metric over the ensemble (hx_pair_metric_quantiles;
         definition as metric_quantiles()) -> ndarray [n_specs, n_probs] (+ counts [n_specs])."""
-        dp = ctypes.POINTER(ctypes.c_double)
-        lead, ns, keep = self._pair_args(b, specs, "pair_metric_quantiles")
-        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
-        if pr.ndim != 1:
-            raise HectorAmdError("pair_metric_quantiles: probs must be one-dimensional")
-        w = self._weights(weights, "pair_metric_quantiles")
-        out = np.empty((ns, pr.size))
-        npart = np.zeros(ns, dtype=np.int64)
-        self._ck(self._lib.hx_pair_metric_quantiles(
-            self._h, var_a.encode(), *lead, w.ctypes.data_as(dp) if w is not None else None,
-            pr.ctypes.data_as(dp), int(pr.size), out.ctypes.data_as(dp),
-            npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
-        del keep
-        return (out, npart) if counts else out
+        return self._quantiles(_Rows.pair_metrics(self, "pair_metric_quantiles", var_a, b, specs), None, probs,
+                               weights, counts)
 
     def pair_metric_probabilities(self, var_a, b, specs, edges, weights=None, counts=False, sums=False):
         """The classes of probabilities() over pair metrics (hx_pair_metric_probabilities) -> ndarray
         [n_specs, n_edges + 1] (+ counts [n_specs], + sums)."""
-        lead, ns, keep = self._pair_args(b, specs, "pair_metric_probabilities")
-        res = self._probabilities(
-            "pair_metric_probabilities",
-            lambda *a: self._lib.hx_pair_metric_probabilities(self._h, var_a.encode(), *(lead + a)),
-            ns, edges, weights, counts, sums)
-        del keep
-        return res
+        return self._probabilities(_Rows.pair_metrics(self, "pair_metric_probabilities", var_a, b, specs), None,
+                                   edges, weights, counts, sums)
 
     def pair_metric_moments(self, var_a, b, specs, weights=None, against=None):
         """moments() over pair metrics (hx_pair_metric_moments): one row per specification -> Moments."""
-        lead, ns, keep = self._pair_args(b, specs, "pair_metric_moments")
-        res = self._moments(
-            "pair_metric_moments",
-            lambda *a: self._lib.hx_pair_metric_moments(self._h, var_a.encode(), *(lead + a)),
-            ns, weights, against)
-        del keep
-        return res
+        return self._moments(_Rows.pair_metrics(self, "pair_metric_moments", var_a, b, specs), None, weights,
+                             against)
 
     def _against(self, against, weights, what):
         """-> (names, predictors [K, n_members] or None, weights or None, q [n_members] uint64,
@@ -1353,39 +1364,6 @@ class Core:
                 pshift = pred[:, on].min(axis=1)
         return names, pred, w, q, pshift
 
-    def _group_moments(self, what, var, y0, y1, arr, ns, nrows, groups, weights, against):
-        dp = ctypes.POINTER(ctypes.c_double)
-        call, g = self._group_call(self._lib.hx_group_moments, var, y0, y1, arr, ns, groups, what)
-        lab = self._groups(groups, what)[0]
-        names, pred, w, q, _ = self._against(against, weights, what)
-        k = len(names)
-        shift = np.empty((g, nrows))
-        pshift = np.full((g, k), np.nan)
-        sums = np.zeros((g, nrows, 2 + 3 * k))
-        wsum = np.zeros((g, nrows), dtype=np.uint64)
-        npart = np.zeros((g, nrows), dtype=np.int64)
-        self._ck(call(w.ctypes.data_as(dp) if w is not None else None,
-                      pred.ctypes.data_as(dp) if pred is not None else None, k,
-                      shift.ctypes.data_as(dp), pshift.ctypes.data_as(dp), sums.ctypes.data_as(dp),
-                      wsum.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
-                      npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
-        return GroupedMoments(shift, sums, wsum, npart, names, pshift, q, pred, lab)
-
-    def _moments(self, what, call, nrows, weights, against):
-        dp = ctypes.POINTER(ctypes.c_double)
-        names, pred, w, q, pshift = self._against(against, weights, what)
-        k = len(names)
-        shift = np.empty(nrows)
-        sums = np.zeros((nrows, 2 + 3 * k))
-        wsum = np.zeros(nrows, dtype=np.uint64)
-        npart = np.zeros(nrows, dtype=np.int64)
-        self._ck(call(w.ctypes.data_as(dp) if w is not None else None,
-                      pred.ctypes.data_as(dp) if pred is not None else None, k,
-                      shift.ctypes.data_as(dp), sums.ctypes.data_as(dp),
-                      wsum.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
-                      npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
-        return Moments(shift, sums, wsum, npart, names, pshift, q, pred)
-
     def moments(self, var, dates=None, weights=None, against=None, groups=None):
         """Per-year weighted mean and variance of `var` over the ensemble and its covariance,
         correlation and regression slope against per-member quantities, on the device
@@ -1397,46 +1375,12 @@ class Core:
         GroupedMoments: gm[g] is the Moments of group g, and gm.between / gm.within / gm.eta2
         partition every year's variance into the spread of the group means and the spread inside
         the groups."""
-        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
-            (int(min(dates)), int(max(dates)))
-        if groups is not None:
-            return self._group_moments("moments", var, y0, y1, None, 0, max(y1 - y0 + 1, 0), groups, weights,
-                                       against)
-        return self._moments(
-            "moments", lambda *a: self._lib.hx_ensemble_moments(self._h, var.encode(), y0, y1, *a),
-            max(y1 - y0 + 1, 0), weights, against)
+        return self._moments(_Rows.window(self, "moments", var, dates), groups, weights, against)
 
     def metric_moments(self, var, specs, weights=None, against=None, groups=None):
         """The same over metrics (hx_metric_moments): one row per specification -> Moments
         (groups: -> GroupedMoments, as in moments())."""
-        arr, ns = self._metric_array(specs, "metric_moments")
-        if groups is not None:
-            return self._group_moments("metric_moments", var, 0, 0, arr, ns, ns, groups, weights, against)
-        return self._moments(
-            "metric_moments",
-            lambda *a: self._lib.hx_metric_moments(self._h, var.encode(), ctypes.byref(arr), ns, *a),
-            ns, weights, against)
-
-    def _sobol(self, what, call, nrows, factors, n_base, use):
-        names = ["factor[%d]" % i for i in range(int(factors))] if isinstance(factors, (int, np.integer)) \
-            else [str(f) for f in factors]
-        k = len(names)
-        if k > SOBOL_MAX_FACTORS:
-            raise HectorAmdError("%s: at most %d factors" % (what, SOBOL_MAX_FACTORS))
-        nb = self.n_members // (k + 2) if n_base is None else int(n_base)
-        u = None
-        if use is not None:
-            u = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
-            if u.shape != (nb,):
-                raise HectorAmdError("%s: use must have n_base entries" % what)
-        shift = np.empty(nrows)
-        sums = np.zeros((nrows, 4 + 4 * k))
-        npart = np.zeros(nrows, dtype=np.int64)
-        self._ck(call(k, nb, u.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if u is not None else None,
-                      shift.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                      sums.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                      npart.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
-        return Sobol(names, shift, sums, npart)
+        return self._moments(_Rows.metrics(self, "metric_moments", var, specs), groups, weights, against)
 
     def sobol(self, var, factors, dates=None, n_base=None, use=None):
         """Per-year first-order and total Sobol indices of `var` with respect to the factors of a
@@ -1446,19 +1390,11 @@ class Core:
         (labels only), at most 16; n_base defaults to n_members // (k + 2), members past
         n_base * (k + 2) are ignored; use[n_base]: groups with a zero entry take no part.  A group
         takes part in a year if none of its k + 2 values is NaN."""
-        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
-            (int(min(dates)), int(max(dates)))
-        return self._sobol(
-            "sobol", lambda *a: self._lib.hx_ensemble_sobol(self._h, var.encode(), y0, y1, *a),
-            max(y1 - y0 + 1, 0), factors, n_base, use)
+        return self._sobol(_Rows.window(self, "sobol", var, dates), factors, n_base, use)
 
     def metric_sobol(self, var, specs, factors, n_base=None, use=None):
         """The same over metrics (hx_metric_sobol): one row per specification -> Sobol."""
-        arr, ns = self._metric_array(specs, "metric_sobol")
-        return self._sobol(
-            "metric_sobol",
-            lambda *a: self._lib.hx_metric_sobol(self._h, var.encode(), ctypes.byref(arr), ns, *a),
-            ns, factors, n_base, use)
+        return self._sobol(_Rows.metrics(self, "metric_sobol", var, specs), factors, n_base, use)
 
     def comoments(self, var_a, dates_a=None, var_b=None, dates_b=None, weights=None):
         """Year-by-year weighted co-moments of two windows over the ensemble, on the device
@@ -1562,8 +1498,7 @@ class Core:
         if kind not in RANK_KINDS:
             raise HectorAmdError("rank_series: kind must be 'pit' or 'numerator'")
         w = self._weights(weights, "rank_series")
-        y0, y1 = (self.strtdate, self.current_date) if dates is None else \
-            (int(min(dates)), int(max(dates)))
+        y0, y1, _ = self._window(dates)
         self._ck(self._lib.hx_series_rank(
             self._h, name.encode(), var.encode(), y0, y1,
             w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if w is not None else None, RANK_KINDS[kind]))
@@ -1575,13 +1510,10 @@ class Core:
         [n_specs, n_members]; NaN where a member's metric is NaN.  kind as in rank_series()."""
         if kind not in RANK_KINDS:
             raise HectorAmdError("metric_ranks: kind must be 'pit' or 'numerator'")
-        arr, ns = self._metric_array(specs, "metric_ranks")
+        rows = _Rows.metrics(self, "metric_ranks", var, specs)
         w = self._weights(weights, "metric_ranks")
-        dp = ctypes.POINTER(ctypes.c_double)
-        out = np.empty((ns, self.n_members))
-        self._ck(self._lib.hx_metric_ranks(self._h, var.encode(), ctypes.byref(arr), ns,
-                                           w.ctypes.data_as(dp) if w is not None else None, RANK_KINDS[kind],
-                                           out.ctypes.data_as(dp)))
+        out = np.empty((rows.nrows, self.n_members))
+        rows.call("ranks", None, w, RANK_KINDS[kind], out)
         return out
 
     def crps(self, var, years, obs, weights=None, return_pit=False, counts=False):

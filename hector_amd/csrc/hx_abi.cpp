@@ -545,12 +545,14 @@ int hx_ensemble_comoments(hx_core *core, const char *cap_a, int a_year0, int a_y
 int hx_ensemble_sobol(hx_core *core, const char *capability, int year0, int year1, int k, int n_base,
                       const unsigned char *use, double *shift, double *sums, long long *n_part) {
   if (!capability || !shift || !sums || !n_part) return fail("hx_ensemble_sobol: null argument");
-  HX_TRY(core->core->sobol(capability, year0, year1, nullptr, 0, k, n_base, use, shift, sums, n_part))
+  HX_TRY(core->core->sobol(rows_of("hx_ensemble_sobol", capability, year0, year1, nullptr, 0), k, n_base, use, shift,
+                           sums, n_part))
 }
 int hx_metric_sobol(hx_core *core, const char *capability, const hx_metric *specs, int nspecs, int k,
                     int n_base, const unsigned char *use, double *shift, double *sums, long long *n_part) {
   if (!capability || !specs || !shift || !sums || !n_part) return fail("hx_metric_sobol: null argument");
-  HX_TRY(core->core->sobol(capability, 0, 0, specs, nspecs, k, n_base, use, shift, sums, n_part))
+  HX_TRY(core->core->sobol(rows_of("hx_metric_sobol", capability, 0, 0, specs, nspecs), k, n_base, use, shift, sums,
+                           n_part))
 }
 int hx_series_define(hx_core *core, const char *name, const char *a, const hx_series_op *op) {
   if (!name || !a || !op) return fail("hx_series_define: null argument");

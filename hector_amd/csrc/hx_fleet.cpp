@@ -703,13 +703,12 @@ void Fleet::moments(const RowSource &rs, const Groups &g, const double *weights,
   }
 }
 
-void Fleet::sobol(const std::string &cap, int year0, int year1, const hx_metric *specs, int nspecs, int k,
-                  int n_base, const unsigned char *use_group, double *shift, double *sums, long long *n_part) {
+void Fleet::sobol(const RowSource &rs, int k, int n_base, const unsigned char *use_group, double *shift,
+                  double *sums, long long *n_part) {
   check_poison();
-  const char *fn = specs ? "hx_metric_sobol" : "hx_ensemble_sobol";
+  const char *fn = rs.fn;
   const std::string f(fn);
-  if (specs && (nspecs < 1 || nspecs > HX_MET_MAX_SPECS))
-    throw std::runtime_error(f + ": nspecs must lie in 1..32");
+  source_rows(rs);   // (nspecs held to its range; a window's years are held by rows_check below)
   if (k < 1 || k > HX_SOBOL_MAX_FACTORS)
     throw std::runtime_error(f + ": k must lie in 1..16");
   if (n_base < 1) throw std::runtime_error(f + ": n_base must be at least 1");
@@ -721,7 +720,6 @@ void Fleet::sobol(const std::string &cap, int year0, int year1, const hx_metric 
   // build refuses by name there); k and n_base were held to the whole core above
   Shard &s = shards_.front();
   use(s);
-  const RowSource rs{fn, cap, year0, year1, specs, nspecs, nullptr};
   s.core->rows_check(rs, Groups{nullptr, 0}, 1);
   if (shards_.size() > 1)
     throw std::runtime_error(f + ": this core has several shards (" + std::to_string(shards_.size()) +

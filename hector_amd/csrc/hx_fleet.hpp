@@ -136,12 +136,12 @@ class Fleet {
   void comoments(const std::string &cap_a, int a0, int a1, const char *cap_b, int b0, int b1,
                  const double *weights, double *shift_a, double *sums_a, double *shift_b, double *sums_b,
                  double *cross, unsigned long long *wsum, long long *n_part);
-  // hx_ensemble_sobol (specs == nullptr: the rows year0..year1) and hx_metric_sobol: k, n_base and
+  // hx_ensemble_sobol and hx_metric_sobol (rs: a window of years or metrics): k, n_base and
   // nspecs held to their ranges, a communicator of several processes and a core of several shards
   // refused (a group's k + 2 members lie on different GPUs under the split), then the one shard's
   // two steps
-  void sobol(const std::string &capability, int year0, int year1, const hx_metric *specs, int nspecs, int k,
-             int n_base, const unsigned char *use_group, double *shift, double *sums, long long *n_part);
+  void sobol(const RowSource &rs, int k, int n_base, const unsigned char *use_group, double *shift, double *sums,
+             long long *n_part);
   // hx_series_define / hx_series_drop: forwarded to every shard (the kernels are lane-local: nothing
   // crosses shards); hx_series_list: the first shard's list (all shards hold the same names)
   void series_define(const std::string &name, const std::string &a, const hx_series_op &op);

@@ -204,7 +204,7 @@ def test_argument_errors_are_raised_before_the_call(emul_lib):
     out = np.zeros(8)
     rc = c._lib.hx_series_rank(c._h, b"r", b"global_tas", 1750, 1760, None, 7)
     assert rc != 0 and "hx_series_rank: unknown kind 7" in c._lib.hx_last_error().decode()
-    arr, ns = c._metric_array(spec, "t")
+    arr, ns = spec[0]._c(), 1   # (one hx_metric)
     rc = c._lib.hx_metric_ranks(c._h, b"global_tas", ctypes.byref(arr), ns, None, -1, out.ctypes.data_as(dp))
     assert rc != 0 and "hx_metric_ranks: unknown kind -1" in c._lib.hx_last_error().decode()
     rc = c._lib.hx_ensemble_crps(c._h, b"global_tas", (ctypes.c_int * 1)(1750), out.ctypes.data_as(dp), 0, None,

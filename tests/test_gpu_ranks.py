@@ -395,7 +395,7 @@ def test_refusals_change_nothing(hip_lib, monkeypatch):
     rc = core._lib.hx_series_rank(core._h, b"r", b"global_tas", 1750, 1760, None, 2)
     assert rc != 0 and "hx_series_rank: unknown kind 2" in core._lib.hx_last_error().decode()
     out = np.zeros(n)
-    arr, ns = core._metric_array([Metric("mean", (1750, 1760))], "t")
+    arr, ns = Metric("mean", (1750, 1760))._c(), 1   # (one hx_metric)
     rc = core._lib.hx_metric_ranks(core._h, b"global_tas", ctypes.byref(arr), ns, None, 5,
                                    out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
     assert rc != 0 and "hx_metric_ranks: unknown kind 5" in core._lib.hx_last_error().decode()
