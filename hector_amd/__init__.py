@@ -7,6 +7,7 @@ from .core import (Core, Metric, PairMetric, Moments, GroupedMoments, CoMoments,
                    get_biome_inits, sendmessage, GETDATA, SETDATA, isactive, startdate,
                    enddate, getdate, getname, get_biome_list, getunits, getfxn, runscenario)
 from . import capabilities  # noqa: F401
+from . import expr  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -211,6 +211,7 @@ def _declare(lib):
         "hx_metric_sobol": [P, c.c_char_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_ubyte), dp, dp,
                             c.POINTER(c.c_longlong)],
         "hx_series_define": [P, c.c_char_p, c.c_char_p, c.c_void_p],
+        "hx_series_eval": [P, c.c_char_p, c.c_void_p],
         "hx_series_drop": [P, c.c_char_p],
         "hx_series_list": [P, c.POINTER(c.POINTER(c.c_char_p)), c.POINTER(c.POINTER(c.c_int)),
                            c.POINTER(c.c_int)],
@@ -258,5 +259,5 @@ ABI_SYMBOLS = ["hx_backend", "hx_build_info", "hx_last_error", "hx_newcore", "hx
                "hx_group_quantiles", "hx_group_probabilities", "hx_group_moments",
                "hx_member_pair_metrics", "hx_pair_metric_quantiles", "hx_pair_metric_probabilities",
                "hx_pair_metric_moments", "hx_ensemble_sobol", "hx_metric_sobol",
-               "hx_series_define", "hx_series_drop", "hx_series_list",
+               "hx_series_define", "hx_series_eval", "hx_series_drop", "hx_series_list",
                "hx_series_rank", "hx_metric_ranks", "hx_ensemble_crps"]

@@ -1474,6 +1474,28 @@ class Core:
         self._ck(self._lib.hx_series_define(self._h, name.encode(), a.encode(), ctypes.byref(o)))
         return self
 
+    def derive_expr(self, name, expr, bind=None):
+        """Define the series `name` from a whole expression over per-member variables, evaluated on
+        the device in one launch (hx_series_eval in include/hector_amd.h: every distinct operand row
+        is read once, the result written once, nothing reaches the host).  expr: text -- the grammar
+        is hector_amd.expr's: + - * /, comparisons, & | ~ on indicators, ** 2..4, abs sqrt log exp
+        minimum maximum where ifnan lag(x, k), var("name"), param("S"), year -- or a compiled
+        hector_amd.expr.Program; bind: names of the text -> a variable name (an alias), an n_members
+        array, expr.param("S") (the members' parameter, through getvar as `against=` does),
+        (first_year, values) or a number.  Everything but log and exp is what Program.numpy gives,
+        bit for bit.  Defining an existing series replaces it; the expression may name it."""
+        from . import expr as _expr
+        if isinstance(expr, _expr.Program):
+            if bind is not None:
+                raise HectorAmdError("hx_series_eval: bind goes with text; a Program is compiled already")
+            prog = expr
+        else:
+            prog = _expr.compile(expr, bind)
+        ex, keep = prog._c(self.n_members, self.getvar)
+        self._ck(self._lib.hx_series_eval(self._h, name.encode(), ctypes.byref(ex)))
+        del keep
+        return self
+
     def drop_series(self, name):
         self._ck(self._lib.hx_series_drop(self._h, name.encode()))
         return self

@@ -296,6 +296,9 @@ class EnsembleCore {
   void sobol_finish(double *shift_host, double *sums_host, long long *n_part_host);
   // ---- held and derived per-member series (hx_series_define in hector_amd.h) ----------------------
   void series_define(const std::string &name, const std::string &a, const hx_series_op &op);
+  // hx_series_eval: a series from a whole postfix expression in one launch; ex.members point at THIS
+  // core's n_members() doubles (the fleet hands every shard its slice)
+  void series_eval(const std::string &name, const hx_expr &ex);
   void series_drop(const std::string &name);
   void series_list(std::vector<std::string> *names, std::vector<int> *valid_to) const;
   // ---- member ranks and the CRPS (hx_series_rank / hx_metric_ranks / hx_ensemble_crps) ------------
@@ -642,6 +645,8 @@ class EnsembleCore {
   double *d_ps_tmp_ = nullptr;               // [ns][npad_]: the high-latitude part of a combination
   double *d_ser_vec_ = nullptr;              // [ns] a per-year operand + [npad_] ANOMALY's bases
   int *d_ser_perm_ = nullptr;                // [npad_] source lanes of a permutation
+  double *d_expr_ = nullptr;                 // hx_series_eval: HxExprProg, member vectors [npad_], year vectors [ns]
+  size_t d_expr_words_ = 0;
   void free_derived_cache();
   const double *derived_block(const std::string &capability);
   hipStream_t stream_ = nullptr;

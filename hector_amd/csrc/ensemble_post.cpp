@@ -422,7 +422,8 @@ void EnsembleCore::free_series() {
   series_.clear();
   if (d_ser_vec_) (void)hipFree(d_ser_vec_);
   if (d_ser_perm_) (void)hipFree(d_ser_perm_);
-  d_ser_vec_ = nullptr; d_ser_perm_ = nullptr;
+  if (d_expr_) (void)hipFree(d_expr_);
+  d_ser_vec_ = nullptr; d_ser_perm_ = nullptr; d_expr_ = nullptr; d_expr_words_ = 0;
 }
 
 void EnsembleCore::free_derived_cache() {
@@ -674,6 +675,171 @@ void EnsembleCore::series_define(const std::string &name, const std::string &a_n
         break;
     }
     check(hipStreamSynchronize(stream_), "series sync");   // (the old block of a replaced series is freed below)
+  } catch (...) { (void)hipFree(z); throw; }
+  Series s;
+  s.name = name; s.block = z; s.valid_iy = valid; s.lane_of_member = lane_of_member_;
+  if (existing >= 0) {
+    (void)hipFree(series_[(size_t)existing].block);
+    series_[(size_t)existing] = std::move(s);
+  } else {
+    series_.push_back(std::move(s));
+  }
+}
+
+// hx_series_eval: the program is checked and translated before anything is resolved or allocated (a
+// refused call changes nothing); the distinct (name, lag) operands the VAR instructions use become
+// the kernel's operand table, and every instruction carries the stack depth in front of it.
+void EnsembleCore::series_eval(const std::string &name, const hx_expr &ex) {
+  const std::string f = "hx_series_eval";
+  const int existing = series_name_check(f, name);
+  const int ns = scen_.ns();
+  auto refuse = [&](const std::string &what) { throw std::runtime_error(f + ": " + what); };
+  if (ex.reserved[0] || ex.reserved[1]) refuse("a reserved field of hx_expr is not 0");
+  if (ex.nins < 1 || ex.nins > HX_EX_MAX_INS)
+    refuse("nins must lie in 1.." + std::to_string(HX_EX_MAX_INS) + " (HX_EX_MAX_INS)");
+  if (!ex.ins || (ex.nvars > 0 && !ex.vars) || (ex.nmem > 0 && !ex.members) || (ex.nvec > 0 && !ex.yearvecs))
+    refuse("null argument");
+  if (ex.nvars < 0 || ex.nvars > HX_EX_MAX_INS || ex.nmem < 0 || ex.nvec < 0) refuse("a negative or oversized table count");
+  if (ex.nmem > HX_EX_MAX_MEMBERS)
+    refuse("more than " + std::to_string(HX_EX_MAX_MEMBERS) + " member vectors (HX_EX_MAX_MEMBERS)");
+  if (ex.nvec > HX_EX_MAX_YEARVECS)
+    refuse("more than " + std::to_string(HX_EX_MAX_YEARVECS) + " year vectors (HX_EX_MAX_YEARVECS)");
+  for (int k = 0; k < ex.nvars; ++k) {
+    if (!ex.vars[k].name) refuse("null argument (the name of vars[" + std::to_string(k) + "])");
+    if (ex.vars[k].reserved) refuse("a reserved field of vars[" + std::to_string(k) + "] is not 0");
+    if (ex.vars[k].lag < 0 || ex.vars[k].lag >= ns)
+      refuse("the lag of " + std::string(ex.vars[k].name) + " must lie in 0.." + std::to_string(ns - 1) +
+             ", the years of the core");
+  }
+  for (int k = 0; k < ex.nmem; ++k)
+    if (!ex.members[k]) refuse("member vector " + std::to_string(k) + " is a null pointer");
+  for (int k = 0; k < ex.nvec; ++k)
+    if (!ex.yearvecs[k].values || ex.yearvecs[k].n < 1) refuse("year vector " + std::to_string(k) + " is empty");
+  HxExprProg prog;
+  std::memset(&prog, 0, sizeof prog);
+  std::vector<int> distinct;   // indices into ex.vars, one per distinct (name, lag) a VAR instruction uses
+  int depth = 0, top = 0;
+  for (int i = 0; i < ex.nins; ++i) {
+    const hx_expr_ins &in = ex.ins[i];
+    const std::string at = "instruction " + std::to_string(i);
+    if (in.op < 0 || in.op >= HX_EX_NOPS) refuse(at + ": unknown op " + std::to_string(in.op));
+    int arg = 0;
+    const int pops = in.op <= HX_EX_YEAR ? 0 : in.op <= HX_EX_EXP ? 1 : in.op == HX_EX_WHERE ? 3 : 2;
+    if (in.op <= HX_EX_YEARVEC) {
+      const int count = in.op == HX_EX_VAR ? ex.nvars : in.op == HX_EX_MEMBER ? ex.nmem : ex.nvec;
+      const char *table = in.op == HX_EX_VAR ? "vars" : in.op == HX_EX_MEMBER ? "members" : "yearvecs";
+      if (in.arg < 0 || in.arg >= count)
+        refuse(at + ": arg " + std::to_string(in.arg) + " is outside the table " + table + " of " +
+               std::to_string(count));
+      arg = in.arg;
+      if (in.op == HX_EX_VAR) {
+        size_t k = 0;
+        for (; k < distinct.size(); ++k) {
+          const hx_expr_var &v = ex.vars[distinct[k]];
+          if (v.lag == ex.vars[in.arg].lag && std::strcmp(v.name, ex.vars[in.arg].name) == 0) break;
+        }
+        if (k == distinct.size()) {
+          if ((int)distinct.size() == HX_EX_MAX_VARS)
+            refuse("more than " + std::to_string(HX_EX_MAX_VARS) + " distinct (name, lag) operands (HX_EX_MAX_VARS)");
+          distinct.push_back(in.arg);
+        }
+        arg = (int)k;
+      }
+    }
+    if (depth < pops) refuse(at + ": stack underflow (the op takes " + std::to_string(pops) + " values, the stack holds " +
+                             std::to_string(depth) + ")");
+    prog.ins[i] = (unsigned)in.op | (unsigned)arg << 8 | (unsigned)depth << 16;
+    prog.cval[i] = in.op == HX_EX_CONST ? in.value : 0.0;
+    depth += 1 - pops;
+    if (depth > HX_EX_MAX_STACK)
+      refuse(at + ": the stack would hold more than " + std::to_string(HX_EX_MAX_STACK) + " values (HX_EX_MAX_STACK)");
+    top = std::max(top, depth);
+  }
+  if (depth != 1)
+    refuse("the program ends with " + std::to_string(depth) + " values on the stack; it must end with exactly one");
+  if (distinct.empty()) refuse("the program has no VAR: a series needs a per-member variable");
+  // the core keeps two blocks of derived diagnostics / combinations, the one used longest ago is given
+  // up for a third: an expression that names more than two has each copied into a block of its own
+  // as it is resolved, freed when the call returns
+  std::vector<std::string> kept;
+  for (int k : distinct) {
+    const std::string cap = ex.vars[k].name;
+    if (find_series(cap) >= 0 || !(derived_kind(cap) == 0 || combo_of(cap))) continue;
+    if (std::find(kept.begin(), kept.end(), cap) == kept.end()) kept.push_back(cap);
+  }
+  struct Temps {
+    std::vector<std::pair<std::string, double *>> blocks;
+    ~Temps() { for (auto &b : blocks) (void)hipFree(b.second); }
+  } temps;
+  if (!d_lane_of_member_ || lane_of_member_.empty()) refuse("run the core first");
+  sync();
+  int valid = ns - 1;
+  for (size_t k = 0; k < distinct.size(); ++k) {
+    const std::string cap = ex.vars[distinct[k]].name;
+    const PostSource ps = post_source(cap, "hx_series_eval");
+    if (ps.v >= 0 && !out_enabled_[ps.v]) refuse("variable " + cap + " was not enabled with set_outputs()");
+    if (!ps.block) refuse("run the core first");
+    prog.var[k] = ps.block;
+    if (kept.size() > 2 && std::find(kept.begin(), kept.end(), cap) != kept.end()) {
+      const double *own = nullptr;
+      for (auto &b : temps.blocks) if (b.first == cap) own = b.second;
+      if (!own) {
+        double *t = nullptr;
+        if (hipMalloc(&t, sizeof(double) * (size_t)ns * (size_t)npad_) != hipSuccess || !t) {
+          (void)hipGetLastError();
+          refuse("no device memory for a copy of " + cap + " (" +
+                 std::to_string((sizeof(double) * (size_t)ns * (size_t)npad_) >> 20) + " MiB)");
+        }
+        temps.blocks.emplace_back(cap, t);
+        check(hx_launch_series_ew(HX_SER_COPY, ps.block, nullptr, nullptr, nullptr, npad_, ns, 0, ps.last_iy, 0.0, 0.0,
+                                  t, stream_), "series kernel");
+        check(hipStreamSynchronize(stream_), "series sync");
+        own = t;
+      }
+      prog.var[k] = own;
+    }
+    prog.lag[k] = ex.vars[distinct[k]].lag;
+    valid = std::min(valid, ps.last_iy);
+  }
+  // (a series among the operands is permuted at most once per lane order and the derived ones keep
+  //  their two cache slots: resolving one operand does not move another's block)
+  prog.nins = ex.nins; prog.nvar = (int)distinct.size(); prog.nmem = ex.nmem;
+  // the record, the member vectors in lane order and the year vectors over the core's years: one copy
+  const size_t np = (size_t)npad_, head = (sizeof(HxExprProg) + 7) / 8;
+  const size_t words = head + (size_t)ex.nmem * np + (size_t)ex.nvec * (size_t)ns;
+  if (words > d_expr_words_) {
+    if (d_expr_) (void)hipFree(d_expr_);
+    d_expr_ = nullptr; d_expr_words_ = 0;
+    check(hipMalloc(&d_expr_, sizeof(double) * words), "hipMalloc expression operands");
+    d_expr_words_ = words;
+  }
+  std::vector<double> stage(words, 0.0);
+  for (int k = 0; k < ex.nmem; ++k) {
+    double *row = stage.data() + head + (size_t)k * np;
+    for (int m = 0; m < n_; ++m) row[(size_t)lane_of_member_[(size_t)m]] = ex.members[k][m];
+    prog.mem[k] = d_expr_ + head + (size_t)k * np;
+  }
+  for (int k = 0; k < ex.nvec; ++k) {
+    double *row = stage.data() + head + (size_t)ex.nmem * np + (size_t)k * (size_t)ns;
+    for (int y = 0; y < ns; ++y) row[y] = std::nan("");
+    for (int i = 0; i < ex.yearvecs[k].n; ++i) {
+      const long long iy = (long long)ex.yearvecs[k].first_year + i - scen_.start;
+      if (iy >= 0 && iy < ns) row[(size_t)iy] = ex.yearvecs[k].values[i];
+    }
+    prog.vec[k] = d_expr_ + head + (size_t)ex.nmem * np + (size_t)k * (size_t)ns;
+  }
+  std::memcpy(stage.data(), &prog, sizeof prog);
+  check(hipMemcpy(d_expr_, stage.data(), sizeof(double) * words, hipMemcpyHostToDevice), "expression operands");
+  double *z = nullptr;
+  if (hipMalloc(&z, sizeof(double) * (size_t)ns * np) != hipSuccess || !z) {
+    (void)hipGetLastError();
+    throw std::runtime_error(f + ": no device memory for the block of series " + name + " (" +
+                             std::to_string((sizeof(double) * (size_t)ns * np) >> 20) + " MiB)");
+  }
+  try {
+    check(hx_launch_series_expr((const HxExprProg *)d_expr_, prog.nvar, prog.nmem, top, npad_, ns, scen_.start,
+                                valid, z, stream_), "series expression kernel");
+    check(hipStreamSynchronize(stream_), "series sync");
   } catch (...) { (void)hipFree(z); throw; }
   Series s;
   s.name = name; s.block = z; s.valid_iy = valid; s.lane_of_member = lane_of_member_;

@@ -558,6 +558,10 @@ int hx_series_define(hx_core *core, const char *name, const char *a, const hx_se
   if (!name || !a || !op) return fail("hx_series_define: null argument");
   HX_TRY(core->core->series_define(name, a, *op))
 }
+int hx_series_eval(hx_core *core, const char *name, const hx_expr *expr) {
+  if (!name || !expr) return fail("hx_series_eval: null argument");
+  HX_TRY(core->core->series_eval(name, *expr))
+}
 int hx_series_drop(hx_core *core, const char *name) {
   if (!name) return fail("hx_series_drop: null argument");
   HX_TRY(core->core->series_drop(name))

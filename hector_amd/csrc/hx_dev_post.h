@@ -483,6 +483,8 @@ hipError_t hx_launch_series_permute(const double *src, const int *src_lane, int 
   return hipGetLastError();
 }
 
+#include "hx_dev_expr.h"   // hx_series_eval: a series from a whole expression in one launch
+
 // ===========================================================================
 // Per-member input series as a mix of shared year-vectors (hx_setvar_dated_mix in hector_amd.h
 // defines the value and its order; contraction is off as in the score kernel): the [row][npad]

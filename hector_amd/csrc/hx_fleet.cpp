@@ -174,18 +174,21 @@ void Fleet::poison(size_t shard, const char *call, const char *why) {
               "shards before it; shut the core down and create it again";
 }
 
-// a routed call, shard after shard; a failure after the first shard leaves the shards different
-#define HX_EACH(call)                                                              \
+// a routed call, shard after shard; a failure after the first shard leaves the shards different.
+// HX_EACH_DO(label, statements on Shard &s): the one place that holds the poison protocol; HX_EACH(call)
+// is the common case, the same call on every shard's core.
+#define HX_EACH_DO(label_, ...)                                                     \
   {                                                                                \
     check_poison();                                                                \
     size_t k_ = 0;                                                                 \
     try {                                                                          \
-      for (; k_ < shards_.size(); ++k_) { Shard &s = shards_[k_]; use(s); s.core->call; } \
+      for (; k_ < shards_.size(); ++k_) { Shard &s = shards_[k_]; use(s); __VA_ARGS__; } \
     } catch (const std::exception &e_) {                                           \
-      if (k_ > 0) poison(k_, #call, e_.what());                                    \
+      if (k_ > 0) poison(k_, label_, e_.what());                                   \
       throw;                                                                       \
     }                                                                              \
   }
+#define HX_EACH(call) HX_EACH_DO(#call, s.core->call)
 
 // The verbs that do real host work or wait for a device -- run() (lane order, parameter upload,
 // spinup), reset(), sync(), fetchvars() -- take the shards side by side, one host thread per
@@ -774,6 +777,20 @@ void Fleet::comoments(const std::string &cap_a, int a0, int a1, const char *cap_
 
 void Fleet::series_define(const std::string &name, const std::string &a, const hx_series_op &op) {
   HX_EACH(series_define(name, a, op))
+}
+void Fleet::series_eval(const std::string &name, const hx_expr &ex) {
+  // every shard takes its slice of the member vectors (a table the program cannot use is the shard's
+  // to refuse: nothing is read from it here)
+  const bool sliced = ex.members && ex.nmem > 0 && ex.nmem <= HX_EX_MAX_MEMBERS;
+  const double *mem[HX_EX_MAX_MEMBERS];
+  hx_expr part = ex;
+  HX_EACH_DO("series_eval(name, expr)", {
+    if (sliced) {
+      for (int i = 0; i < ex.nmem; ++i) mem[i] = ex.members[i] ? ex.members[i] + s.offset : nullptr;
+      part.members = mem;
+    }
+    s.core->series_eval(name, part);
+  })
 }
 void Fleet::series_drop(const std::string &name) { HX_EACH(series_drop(name)) }
 

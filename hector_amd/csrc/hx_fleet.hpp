@@ -145,6 +145,8 @@ class Fleet {
   // hx_series_define / hx_series_drop: forwarded to every shard (the kernels are lane-local: nothing
   // crosses shards); hx_series_list: the first shard's list (all shards hold the same names)
   void series_define(const std::string &name, const std::string &a, const hx_series_op &op);
+  // hx_series_eval: forwarded likewise, every shard with its slice of the member vectors
+  void series_eval(const std::string &name, const hx_expr &ex);
   void series_drop(const std::string &name);
   void series_list(std::vector<std::string> *names, std::vector<int> *valid_to) const {
     shards_[0].core->series_list(names, valid_to);

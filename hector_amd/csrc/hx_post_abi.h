@@ -27,6 +27,19 @@ struct HxPairSpec { int op, iy0, iy1, a0, a1, b0, b1, pad; double thr; };   // r
 // series: ops of hx_launch_series_ew beside the public HX_SER_*
 #define HXS_ANOM_APPLY 100   // internal: z = a - base[lane]
 #define HXS_COMBINE 101      // internal: z = (c0 * a) + (c1 * b), the whole-surface combinations
+// series from an expression (hx_series_eval): EnsembleCore::series_eval fills the record, the kernel of
+// hx_dev_expr.h reads it through scalar loads.  The tables are sized by the limits of hx_series_eval.
+#define HXE_MAX_INS 64
+#define HXE_MAX_TAB 8
+struct HxExprProg {
+  const double *var[HXE_MAX_TAB];   // the block of distinct operand k, rows of the current lane order
+  const double *mem[HXE_MAX_TAB];   // [npad] a member vector in lane order
+  const double *vec[HXE_MAX_TAB];   // [ns] a year vector, NaN outside its span
+  double cval[HXE_MAX_INS];         // CONST: the value of instruction i
+  unsigned ins[HXE_MAX_INS];        // op | arg << 8 | (stack depth before the instruction) << 16
+  int lag[HXE_MAX_TAB];             // operand k is read lag[k] rows earlier
+  int nins, nvar, nmem, pad;
+};
 // quantiles, moments, co-moments: the host (ensemble_post.cpp, hx_fleet.cpp) reads a row's record back
 // as four 8-byte words, Sobol's as two, a rank record as four
 #define HXQ_MAXP 16
@@ -105,6 +118,8 @@ hipError_t hx_launch_series_runmean(const double *a, int npad, int ns, int w, in
                                     hipStream_t st);
 hipError_t hx_launch_series_permute(const double *src, const int *src_lane, int npad, int ns, double *dst,
                                     hipStream_t st);
+hipError_t hx_launch_series_expr(const HxExprProg *prog, int nvar, int nmem, int depth, int npad, int ns,
+                                 int year_start, int y_hi, double *z, hipStream_t st);
 hipError_t hx_launch_mseries_fill(const double *row, int ns, int npad, double *table, hipStream_t st);
 hipError_t hx_launch_mseries_mix(const double *coeff, const int *member_of_lane, int n, int npad, const int *rows,
                                  const double *basis, int nrows, int nbasis, double *table, hipStream_t st);

@@ -958,6 +958,106 @@ int hx_series_drop(hx_core *core, const char *name);
  * that holds values); either may be NULL.  The arrays stay valid until the next call on this thread. */
 int hx_series_list(hx_core *core, const char *const **names, const int **valid_to, int *count);
 
+/* ---- A series from a whole expression, in one pass ------------------------------------------------
+ * hx_series_eval defines the series `name` from a postfix program over per-member variables, evaluated
+ * per element (member, year) in ONE kernel: every distinct operand row is read once, the result is
+ * written once, nothing reaches the host.  All rules of hx_series_define hold unchanged, through the
+ * same checks and the same store: names, "a name the core already answers", the 17th series, replacing
+ * a series that its own expression names, lane reordering, "run the core first", forwarding to every
+ * shard, the no-device-memory message.  An element depends on its own lane's operands only, so the
+ * block is bit-identical across lane orders, kernel flavours and shard splits.
+ *
+ * The operand tables of hx_expr:
+ *   vars[nvars]      capability names as for every verb (recorded, derived diagnostic, combination,
+ *                    series), each with a lag >= 0 in years.  A (name, lag) pair that occurs twice is ONE
+ *                    operand; at most HX_EX_MAX_VARS distinct pairs (nvars itself may reach
+ *                    HX_EX_MAX_INS).  The core keeps two blocks of derived diagnostics outside the slr
+ *                    family or combinations: an expression that names more than two has each copied
+ *                    into a block of its own for the call (a block of memory and a copy apiece).
+ *   members[nmem]    pointers to n_members doubles in MEMBER order (a parameter, a weight): the library
+ *                    permutes them to lane order, a shard takes its slice.  At most HX_EX_MAX_MEMBERS.
+ *   yearvecs[nvec]   first_year, n, values: one value a year for every member, NaN outside the span (as
+ *                    HX_SER_B_VECTOR).  At most HX_EX_MAX_YEARVECS.
+ *   ins[nins]        {op, arg, value}, 1..HX_EX_MAX_INS instructions; the evaluation stack holds at most
+ *                    HX_EX_MAX_STACK values and the program must end with exactly one.
+ * Instructions, in program order, in IEEE double with contraction off (no fused multiply-add anywhere),
+ * so that numpy reproduces every result but LOG and EXP bit for bit (pops -> pushes):
+ *   VAR k              -> the value of operand vars[arg] in year y - lag; NaN if that year is before
+ *                      startDate (such a row is not loaded)
+ *   MEMBER k           -> members[arg][member]
+ *   YEARVEC k          -> yearvecs[arg] in year y, NaN outside the span
+ *   CONST              -> value
+ *   YEAR               -> (double) calendar year
+ *   NEG ABS            a -> -a, fabs(a): sign-bit operations (-0.0 and NaN payloads as numpy)
+ *   ADD SUB MUL DIV    a b -> a op b, correctly rounded
+ *   SQRT               a -> sqrt(a), correctly rounded
+ *   LOG EXP            a -> natural log / exp of the device's math library (the host-emulation build:
+ *                      libm): within 1 ulp on the host; measured 0.80 (exp) and 0.50 (log) ulp on the
+ *                      MI355X (the bound a conforming device library must keep is 3); log(0) = -inf, log(<0) = NaN,
+ *                      exp(-inf) = 0, inf / NaN as libm -- exact on both
+ *   MIN MAX            a b -> (a < b || a != a) ? a : b  and  (a > b || a != a) ? a : b: numpy's scalar
+ *                      definition -- NaN from either side propagates, at +-0 ties the second operand
+ *   LT LE GT GE EQ NE  a b -> NaN if either operand is NaN, else 1.0 or 0.0
+ *   WHERE              c a b -> NaN if c is NaN; a if c != 0; otherwise b.  The branch not taken does not
+ *                      matter, NaN included.
+ *   IFNAN              a b -> b if a is NaN, else a
+ * At least one VAR is required.  The series is valid to the smallest valid end over its VAR operands;
+ * rows behind that are NaN.
+ * Cost: one kernel, one lane per member, rows read coalesced; a lane takes a batch of rows of every
+ * operand into registers, all loads in flight, and runs the program once over the batch -- the program
+ * is read through scalar loads and decoded once per batch, its stack lives in registers.  One host to
+ * device copy of the program record, the member vectors and the year vectors.  A core of several shards
+ * forwards the call to every shard.
+ * Errors (every message names hx_series_eval; a refused call changes nothing): a null argument, nins
+ * outside 1..HX_EX_MAX_INS, an unknown op, an arg outside its table, stack underflow, a depth above
+ * HX_EX_MAX_STACK, a program that does not end with exactly one value, more than HX_EX_MAX_VARS distinct
+ * (name, lag) pairs, more than HX_EX_MAX_MEMBERS / HX_EX_MAX_YEARVECS of the other tables, no VAR,
+ * lag < 0 or >= the core's years, an empty year vector, a null member pointer, a reserved field that is
+ * not 0, and every refusal of hx_series_define for a name, an operand (unknown, not recorded, answered
+ * on the host, not enabled), a core that has not run and device memory. */
+#define HX_EX_VAR 0
+#define HX_EX_MEMBER 1
+#define HX_EX_YEARVEC 2
+#define HX_EX_CONST 3
+#define HX_EX_YEAR 4
+#define HX_EX_NEG 5
+#define HX_EX_ABS 6
+#define HX_EX_SQRT 7
+#define HX_EX_LOG 8
+#define HX_EX_EXP 9
+#define HX_EX_ADD 10
+#define HX_EX_SUB 11
+#define HX_EX_MUL 12
+#define HX_EX_DIV 13
+#define HX_EX_MIN 14
+#define HX_EX_MAX 15
+#define HX_EX_LT 16
+#define HX_EX_LE 17
+#define HX_EX_GT 18
+#define HX_EX_GE 19
+#define HX_EX_EQ 20
+#define HX_EX_NE 21
+#define HX_EX_WHERE 22
+#define HX_EX_IFNAN 23
+#define HX_EX_NOPS 24
+#define HX_EX_MAX_INS 64
+#define HX_EX_MAX_VARS 8
+#define HX_EX_MAX_MEMBERS 8
+#define HX_EX_MAX_YEARVECS 8
+#define HX_EX_MAX_STACK 8
+typedef struct { const char *name; int lag; int reserved; } hx_expr_var;
+typedef struct { int first_year, n; const double *values; } hx_expr_yearvec;
+typedef struct { int op, arg; double value; } hx_expr_ins;   /* arg: VAR MEMBER YEARVEC; value: CONST */
+typedef struct {
+  int nvars, nmem, nvec, nins;
+  const hx_expr_var *vars;
+  const double *const *members;
+  const hx_expr_yearvec *yearvecs;
+  const hx_expr_ins *ins;
+  int reserved[2];
+} hx_expr;
+int hx_series_eval(hx_core *core, const char *name, const hx_expr *expr);
+
 /* ---- Member ranks within a year's row, and the CRPS of a row against an observation --------------
  * Every member's weighted mid-rank within its year (its mid-PIT), and the continuous ranked
  * probability score of the ensemble against an observed record, by a sort of every row on the
